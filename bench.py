@@ -26,6 +26,8 @@ Rank 0 prints ONE JSON line with the driver's contract plus
                  gradients are comparable with the oracle's run on those utterances.  Gate: loss 1e-4 relative, gradients 2e-4 of
                  the tensor's maximum — the fixture tests' bound, no widening.  The same comparison on the weights the timed steps
                  left is reported under "parity_after_training" (informational: conditioning, not a gate).
+`--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (see dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -54,6 +56,7 @@ GRAD_PROBES = ("fc.weight", "encoder.rnn.weight_hh_l0", "decoder.embedding.weigh
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32-input MFMA, dense
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA, dense
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: payload bound, under the 64 MB the dump may take in all
 
 
 def build_model(cfg, dropout, total_steps):
@@ -194,6 +197,32 @@ def grad_within_tolerance(v):
     return v["max_abs_dev"] <= 2e-4 * max(v["ref_max_abs"], 1e-3)
 
 
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the timed path handed its caller in its last step, so that two builds can be compared output for output.
+    loss.npy: the step's loss (float32, 0-d); per parameter grad.<name>.npy: the gradient the AdamW update consumed, and
+    param.<name>.npy: the weights that update left (float32, flattened).  When the gradients and weights together exceed
+    DUMP_BUDGET_BYTES, every tensor is cut to the same fraction of its elements, taken at fixed indices (a permutation seeded by the
+    tensor's position in named_parameters(), first k entries, ascending), so the sample is the same from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    total_bytes = sum(2 * p.numel() * 4 for _, p in params)
+    frac = min(1.0, DUMP_BUDGET_BYTES / total_bytes)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    for i, (name, p) in enumerate(params):
+        n = p.numel()
+        k = max(1, int(n * frac))
+        idx = None
+        if k < n:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(i))[:k].sort().values.to(p.device)
+        for kind, t in (("grad", p.grad), ("param", p.detach())):
+            flat = t.reshape(-1)
+            if idx is not None:
+                flat = flat.index_select(0, idx)
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"), flat.float().cpu().numpy())
+    progress(f"dumped the last timed step's outputs to {out_dir} ({len(params)} parameters, {100 * frac:.1f} % of their elements)")
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -306,10 +335,15 @@ def main():
                     help="rehearsal only: every rank uses cuda:0 (with --backend gloo), so the N > 1 code path — model step, flat all-reduce "
                          "with the status slot, barrier, max-over-ranks timing — runs end to end on a one-GPU box; the line says so and is "
                          "not a measurement of N GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, gradients, updated weights; a fixed "
+                         "sample of them above 60 MB) to DIR/<name>.npy, for comparing two builds on identical inputs")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(a, sys.argv[1:])   # never returns
     rank = int(os.environ.get("RANK", "0"))
@@ -407,6 +441,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     last_loss = float(loss.detach())
+    if a.dump_outputs and rank == 0:   # before anything else runs a step or clears the gradients
+        dump_outputs(a.dump_outputs, model, loss)
     dt_unprof = None
     if a.unprofiled_steps > 0:
         fence()

@@ -4,15 +4,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_emits_one_contract_line_with_roofline_and_cpu_baseline():
+def test_bench_emits_one_contract_line_with_roofline_and_cpu_baseline(tmp_path):
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "3", "--warmup", "1",
-                          "--cpu-sample", "2", "--cpu-threads", "4"], capture_output=True, text=True, timeout=600)
+                          "--cpu-sample", "2", "--cpu-threads", "4", "--dump-outputs", str(dump)], capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -38,6 +41,13 @@ def test_bench_emits_one_contract_line_with_roofline_and_cpu_baseline():
     assert j["cpu_baseline"]["cpu_model"] and j["cpu_baseline"]["host_logical_cpus"] >= 4
     assert "1 warm-up" in j["cpu_baseline"]["sample"] and "3 timed" in j["cpu_baseline"]["sample"]
     assert j["memory"]["peak_allocated_bytes"] > 0
+    # --dump-outputs: the last timed step's loss, gradients and updated weights (c1 is small enough to be dumped whole)
+    files = sorted(os.listdir(dump))
+    assert "loss.npy" in files and "grad.jointnet.fc.weight.npy" in files and "param.jointnet.fc.weight.npy" in files
+    assert all(np.load(dump / f).dtype in (np.float32, np.float64) for f in files)
+    assert sum((dump / f).stat().st_size for f in files) <= 64 << 20
+    assert abs(float(np.load(dump / "loss.npy")) - j["last_loss"]) < 1e-3
+    assert np.isfinite(np.load(dump / "grad.jointnet.fc.weight.npy")).all()
 
 
 def test_smoke_entry_point():
