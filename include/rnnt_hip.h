@@ -394,6 +394,57 @@ typedef struct rnnt_prednet_step_desc {
 } rnnt_prednet_step_desc;
 int rnnt_hip_prednet_step(const rnnt_prednet_step_desc* d, void* stream);
 
+/* On-device beam search (networks/transducer.py:215-361 with lm=None, hotwords=None: compare_key = asr_score, so the
+ * _get_lm_beams bookkeeping (:147-213) never affects the result).  One workgroup per utterance walks all its frames
+ * t < t_lens[b] (t_lens NULL: all T).  Per frame A = B_prev, B = []; while A is non-empty: the improved early-out
+ * (:298-302, b_best = -9999.0 while B is empty), pop the max-asr_score hypothesis (first in insertion order on ties,
+ * Python's max: :288,304), one prediction-net step on y_star[-1] from its state (:307-312), logp = log_softmax of the 1-D
+ * joint (:313-315), best_prob = max(logp[1:]) (:317, index 0 skipped even when blank != 0), children k = 0..V-1 with fp64
+ * scores (:319-350: blank -> B with the OLD state; others -> A with the new state, k appended to y_star unless it equals
+ * y_star[-1]; improved prunes logp[k] < best_prob - expand_beam in fp32), then the stop check len(B) >= beam and
+ * max B > max A (:355-358).  Divergence: where the reference's max(A) raises ValueError on an empty A (improved mode only)
+ * the frame ends.  Result (:360-361): the last frame's B stable-sorted by asr_score / len(y_star) descending, first `beam`,
+ * y_star with the leading blank.
+ * A prediction-net step is a pure function of (state, token), so each pop's (h', C) is kept with its blank child and
+ * reused when that child is popped in a later frame (memo).  y_star is a prefix tree of (parent, token) nodes.
+ * Every structure is bounded by a cap; on overflow status[b] = RNNT_BEAM_ST_* and the utterance returns nothing. */
+#define RNNT_BEAM_ST_OK 0
+#define RNNT_BEAM_ST_CANDIDATES 1 /* A entries in one frame > max_candidates  */
+#define RNNT_BEAM_ST_POPS 2       /* pops in one frame > max_pops             */
+#define RNNT_BEAM_ST_STATES 3     /* live prediction-net states > max_states  */
+#define RNNT_BEAM_ST_NODES 4      /* prefix-tree nodes > max_nodes            */
+#define RNNT_BEAM_ST_LEN 5        /* a returned y_star longer than max_len    */
+#define RNNT_BEAM_NSTATS 6        /* per utterance: pops, steps run, max pops/frame, max A entries/frame, max live states, nodes */
+typedef struct rnnt_beam_desc {
+  int32_t T, B, V;       /* frames, utterances, vocabulary (V >= 2) */
+  int32_t Hp, O, L;      /* as rnnt_decode_desc */
+  int32_t cell, blank;
+  int32_t beam, improved; /* beam_widths, improved (0/1) */
+  double state_beam, expand_beam;
+  int32_t max_candidates, max_pops, max_states, max_nodes, max_len;  /* caps (see RNNT_BEAM_ST_*) */
+  const float* A;        /* (T,B,V) gelu(enc) W_e^T + bias */
+  const int32_t* t_lens; /* (B) device, or NULL */
+  const float* emb;
+  const float* w_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* w_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* b_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* b_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* w_o;
+  const float* b_o;
+  const float* w_d;      /* fc.weight[:, O_enc:], row stride ld_d floats */
+  int64_t ld_d;
+  void* workspace;       /* rnnt_hip_beam_workspace_bytes(d) bytes, 256-byte aligned */
+  size_t workspace_bytes;
+  int32_t* tokens;       /* (B, beam, max_len) y_star of rank r, leading blank included */
+  int32_t* lens;         /* (B, beam) y_star lengths, 0 past count[b] */
+  double* scores;        /* (B, beam) asr_score */
+  int32_t* count;        /* (B) hypotheses returned: min(beam, len(B)) */
+  int32_t* status;       /* (B) RNNT_BEAM_ST_* */
+  int32_t* stats;        /* (B, RNNT_BEAM_NSTATS) or NULL */
+} rnnt_beam_desc;
+size_t rnnt_hip_beam_workspace_bytes(const rnnt_beam_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance

@@ -13,13 +13,10 @@
 // caller) and C = gelu(dec) W_d^T, which only changes when a symbol is emitted.  ONE workgroup (1024 threads) per
 // utterance keeps the prediction-net state in LDS and streams the weights (L2 / Infinity-Cache resident, shared by
 // all utterances) for each emitted symbol; the per-frame work is a V-wide argmax.  No inter-workgroup communication.
-#include "common.hpp"
+#include "decode_shared.hpp"
 
 namespace rnnt {
 namespace {
-
-constexpr int DEC_THREADS = 1024;
-constexpr int DEC_MAX_LAYERS = RNNT_DECODE_MAX_LAYERS;
 
 struct DecodeK {
   int T, B, V, Hp, O, L, cell, blank, max_iters, max_out;
@@ -38,42 +35,6 @@ struct DecodeK {
   int* ntok;          // (B)
 };
 
-// y[r] = dot(W[r, :cols], x) (+ bias[r]) for r in [0, rows): one wave per group of RU rows (lanes along the contiguous k),
-// 16 waves per pass.  All RU rows' loads are issued before any is consumed: a single row per wave keeps only 2 KB in
-// flight per wave and the step becomes latency-bound (measured 308 us per prediction-net step at H=512).
-constexpr int RU = 8;
-__device__ __forceinline__ void matvec(const float* __restrict__ W, long ld, int rows, int cols, const float* __restrict__ x,
-                                       float* __restrict__ y, const float* __restrict__ bias) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = DEC_THREADS / 64;
-  for (int r0 = wave * RU; r0 < rows; r0 += nw * RU) {
-    float s[RU];
-#pragma unroll
-    for (int i = 0; i < RU; ++i) s[i] = 0.f;
-    for (int k = 4 * lane; k < cols; k += 256) {
-      f32x4 w[RU];
-#pragma unroll
-      for (int i = 0; i < RU; ++i) {
-        const int r = r0 + i < rows ? r0 + i : rows - 1;  // clamp: tail rows re-read the last row, result discarded
-        w[i] = *reinterpret_cast<const f32x4*>(W + (long)r * ld + k);
-      }
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + k);
-#pragma unroll
-      for (int i = 0; i < RU; ++i) s[i] += w[i][0] * xv[0] + w[i][1] * xv[1] + w[i][2] * xv[2] + w[i][3] * xv[3];
-    }
-#pragma unroll
-    for (int i = 0; i < RU; ++i) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
-    }
-    if (lane < RU && r0 + lane < rows) {
-      float v = s[0];
-#pragma unroll
-      for (int i = 1; i < RU; ++i) v = lane == i ? s[i] : v;
-      y[r0 + lane] = v + (bias ? bias[r0 + lane] : 0.f);
-    }
-  }
-}
-
 // dynamic LDS: h[L][Hp] | c[L][Hp] | gi[4Hp] | gh[4Hp] | x[Hp] | dec[O] | Cv[V] | red (2 * 16 floats/ints) | ctl[4]
 __global__ void __launch_bounds__(DEC_THREADS) greedy_decode_kernel(const DecodeK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -91,7 +52,6 @@ __global__ void __launch_bounds__(DEC_THREADS) greedy_decode_kernel(const Decode
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
-  const int NG = p.cell == RNNT_CELL_LSTM ? 4 : (p.cell == RNNT_CELL_GRU ? 3 : 1);
 
   for (int i = tid; i < 2 * L * Hp; i += DEC_THREADS) h[i] = 0.f;  // h and c (hidden_state = None -> zeros)
   __syncthreads();
@@ -100,37 +60,8 @@ __global__ void __launch_bounds__(DEC_THREADS) greedy_decode_kernel(const Decode
   auto prednet_step = [&](int tok) {
     for (int i = tid; i < Hp; i += DEC_THREADS) x[i] = p.emb[(long)tok * Hp + i];
     __syncthreads();
-    for (int l = 0; l < L; ++l) {
-      matvec(p.w_ih[l], Hp, NG * Hp, Hp, x, gi, p.b_ih[l]);
-      matvec(p.w_hh[l], Hp, NG * Hp, Hp, h + l * Hp, gh, p.b_hh[l]);
-      __syncthreads();
-      for (int j = tid; j < Hp; j += DEC_THREADS) {
-        float hv;
-        if (p.cell == RNNT_CELL_LSTM) {
-          const float ig = sigmoidf_(gi[j] + gh[j]), fg = sigmoidf_(gi[Hp + j] + gh[Hp + j]);
-          const float gg = tanhf(gi[2 * Hp + j] + gh[2 * Hp + j]), og = sigmoidf_(gi[3 * Hp + j] + gh[3 * Hp + j]);
-          const float cv = fg * c[l * Hp + j] + ig * gg;
-          c[l * Hp + j] = cv;
-          hv = og * tanhf(cv);
-        } else if (p.cell == RNNT_CELL_GRU) {
-          const float rg = sigmoidf_(gi[j] + gh[j]), zg = sigmoidf_(gi[Hp + j] + gh[Hp + j]);
-          const float ng = tanhf(gi[2 * Hp + j] + rg * gh[2 * Hp + j]);
-          hv = (1.f - zg) * ng + zg * h[l * Hp + j];
-        } else {
-          const float pre = gi[j] + gh[j];
-          hv = p.cell == RNNT_CELL_RNN_RELU ? fmaxf(pre, 0.f) : tanhf(pre);
-        }
-        h[l * Hp + j] = hv;
-        x[j] = hv;  // input of the next layer (no dropout at inference)
-      }
-      __syncthreads();
-    }
-    matvec(p.w_o, Hp, O, Hp, h + (L - 1) * Hp, dec, p.b_o);
-    __syncthreads();
-    for (int i = tid; i < O; i += DEC_THREADS) dec[i] = gelu_tanh(dec[i]);
-    __syncthreads();
-    matvec(p.w_d, p.ld_d, V, O, dec, Cv, nullptr);
-    __syncthreads();
+    prednet_cells(p, h, c, gi, gh, x, nullptr);
+    prednet_joint_half(p, h + (L - 1) * Hp, dec, Cv);
   };
 
   // tok = argmax_v (A[t,b,v] + Cv[v]); lowest index among equal maxima (torch.argmax on a 1-D CPU/GPU tensor)
@@ -207,7 +138,6 @@ __global__ void __launch_bounds__(DEC_THREADS) prednet_step_kernel(const StepK p
   float* gh = gi + 4 * Hp;
   float* x = gh + 4 * Hp;
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int NG = p.cell == RNNT_CELL_LSTM ? 4 : (p.cell == RNNT_CELL_GRU ? 3 : 1);
   for (int i = tid; i < L * Hp; i += DEC_THREADS) {
     const int l = i / Hp, j = i % Hp;
     h[i] = p.h_in ? p.h_in[((long)l * p.B + b) * Hp + j] : 0.f;
@@ -216,31 +146,7 @@ __global__ void __launch_bounds__(DEC_THREADS) prednet_step_kernel(const StepK p
   const long long tok = p.tokens[b];
   for (int i = tid; i < Hp; i += DEC_THREADS) x[i] = p.emb[tok * Hp + i];
   __syncthreads();
-  for (int l = 0; l < L; ++l) {
-    matvec(p.w_ih[l], Hp, NG * Hp, Hp, x, gi, p.b_ih[l]);
-    matvec(p.w_hh[l], Hp, NG * Hp, Hp, h + l * Hp, gh, p.b_hh[l]);
-    __syncthreads();
-    for (int j = tid; j < Hp; j += DEC_THREADS) {
-      float hv;
-      if (p.cell == RNNT_CELL_LSTM) {
-        const float ig = sigmoidf_(gi[j] + gh[j]), fg = sigmoidf_(gi[Hp + j] + gh[Hp + j]);
-        const float gg = tanhf(gi[2 * Hp + j] + gh[2 * Hp + j]), og = sigmoidf_(gi[3 * Hp + j] + gh[3 * Hp + j]);
-        const float cv = fg * c[l * Hp + j] + ig * gg;
-        c[l * Hp + j] = cv;
-        hv = og * tanhf(cv);
-      } else if (p.cell == RNNT_CELL_GRU) {
-        const float rg = sigmoidf_(gi[j] + gh[j]), zg = sigmoidf_(gi[Hp + j] + gh[Hp + j]);
-        const float ng = tanhf(gi[2 * Hp + j] + rg * gh[2 * Hp + j]);
-        hv = (1.f - zg) * ng + zg * h[l * Hp + j];
-      } else {
-        const float pre = gi[j] + gh[j];
-        hv = p.cell == RNNT_CELL_RNN_RELU ? fmaxf(pre, 0.f) : tanhf(pre);
-      }
-      h[l * Hp + j] = hv;
-      x[j] = hv;
-    }
-    __syncthreads();
-  }
+  prednet_cells(p, h, c, gi, gh, x, nullptr);
   for (int i = tid; i < L * Hp; i += DEC_THREADS) {
     const int l = i / Hp, j = i % Hp;
     p.h_out[((long)l * p.B + b) * Hp + j] = h[i];

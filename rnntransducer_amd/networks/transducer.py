@@ -8,12 +8,14 @@ with A = gelu(enc) W_e^T, C = gelu(dec) W_d^T (GELU is element-wise, fc is linea
   * `loss(...)`  — fused joint + log-softmax + alpha/beta + gradient; (B,T,U+1,V) is never built;
   * `joint()/forward()` — still return the full logits tensor for callers that ask for it.
 `recognize_greedy` (transducer.py:95-145) runs as ONE kernel launch (a workgroup per utterance, csrc/decode.hip) instead of
-a host loop with a device sync per symbol; beam search (transducer.py:147-361) stays out of scope.
+a host loop with a device sync per symbol.  `recognize_beams` (transducer.py:215-361, lm=None / hotwords=None) is one persistent
+launch too (csrc/beam.hip): the reference's pop / expand / prune / stop decisions, with memoised prediction-net steps and a
+prefix tree for y_star; LM and hotword rescoring (pyctcdecode / KenLM) stay out of scope.
 """
 import torch
 import torch.nn as nn
 
-from ..ops import JointLogitsFn, JointLossFn, greedy_decode
+from ..ops import JointLogitsFn, JointLossFn, beam_search, greedy_decode
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 
@@ -100,3 +102,33 @@ class JointNet(nn.Module):
         n = ntok.tolist()  # the only host sync of the decode
         outs = [tokens[b, :n[b]] for b in range(tokens.shape[0])]
         return outs[0].unsqueeze(0) if len(outs) == 1 else outs
+
+    @torch.no_grad()
+    def recognize_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 100,
+                        improved: bool = False, state_beam: float = 4.6, expand_beam: float = 2.3, lm=None, tokenizer=None,
+                        hotwords=None, hotword_weight: float = 10.0, *, visit_padded_frames: bool = False,
+                        return_scores: bool = False, **caps):
+        """Beam search, same result as transducer.py:215-361 with lm=None and hotwords=None: a list of up to `beam_widths`
+        y_star token lists (leading blank included), best first by asr_score / len(y_star), duplicates kept.  `tokenizer` is
+        accepted and ignored: without an LM or hotwords the reference only uses it for lm_score, which never decides anything.
+        `lm` / `hotwords` raise NotImplementedError (rescoring needs pyctcdecode and KenLM; out of scope).
+        For a single utterance the list itself, as the reference returns.  For B > 1 (the reference decodes only the first
+        utterance of a batch) one such list per utterance, each equal to decoding that utterance alone; `visit_padded_frames=True`
+        walks all max(lengths) frames for every utterance.  return_scores=True returns (y_star, asr_score) pairs instead
+        (fp64 scores).  `caps`: max_pops / max_candidates / max_states / max_nodes / max_len of ops.beam_search; a search that
+        outgrows one raises RnntHipError naming it (the reference's loop is unbounded there).
+        Divergence: where the reference's max() over an empty A raises ValueError (improved mode) the frame ends instead."""
+        if lm is not None or hotwords is not None:
+            raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
+                                      "lm=None and hotwords=None")
+        if self.training:
+            raise RuntimeError("recognize_beams expects eval() mode (dropout inactive), like the reference's inference script")
+        dev = inputs.device
+        t_lens = lengths_to_device(inputs_lengths, dev)
+        enc = self.encoder.forward_time_major(inputs, t_lens)
+        dec = self.decoder
+        res = beam_search(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                          dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
+                          expand_beam, None if visit_padded_frames else t_lens, **caps)
+        outs = [hyps if return_scores else [y for y, _ in hyps] for hyps in res]
+        return outs[0] if len(outs) == 1 else outs

@@ -780,3 +780,80 @@ def prednet_step(tokens: torch.Tensor, emb_w: torch.Tensor, rnn_weights, cell: i
     d.h_in, d.c_in, d.h_out, d.c_out = _addr(h_in), _addr(c_in), _addr(h_out), _addr(c_out)
     check(_lib.lib().rnnt_hip_prednet_step(C.byref(d), _stream()), "rnnt_hip_prednet_step")
     return h_out, c_out
+
+
+# --------------------------------------------------------------------------------------------------
+# beam search (replaces the host loop of transducer.py:215-361 with lm=None, hotwords=None)
+# --------------------------------------------------------------------------------------------------
+def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
+                cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam: int, improved: bool = False,
+                state_beam: float = 4.6, expand_beam: float = 2.3, t_lens: Optional[torch.Tensor] = None, *,
+                max_pops: int = 1024, max_candidates: Optional[int] = None, max_states: Optional[int] = None,
+                max_nodes: int = 1 << 18, max_len: Optional[int] = None, stats: bool = False):
+    """enc_tm (T,B,Oe) encoder outputs (time-major) -> per utterance the n-best list [(y_star, asr_score), ...] of
+    transducer.py:215-361 (lm=None), one kernel launch for the batch (csrc/beam.hip) and one host sync.
+    t_lens (B) int32 on device = frames visited per utterance (None: all T).  Caps (each raises RnntHipError naming it):
+    max_pops = pops per frame, max_candidates = A entries per frame (default max_pops * V), max_states = live prediction-net
+    states (default 3 * max_pops: a frame carries at most 2 per B entry and adds 1 per pop), max_nodes = y_star prefix nodes
+    per utterance, max_len = tokens of a returned y_star (default 4 T + 64).  stats=True also returns a (B, 6) int tensor:
+    pops, prediction-net steps run, max pops in a frame, max A entries in a frame, max live states, prefix nodes."""
+    _need_gpu(enc_tm, fc_w, emb_w)
+    enc_tm = _f32c(enc_tm, "encoder outputs")
+    T, B, Oe = enc_tm.shape
+    V, Ocat = fc_w.shape
+    Od = Ocat - Oe
+    Hp = emb_w.shape[1]
+    L = len(rnn_weights) // 4
+    if L > _lib.DECODE_MAX_LAYERS:
+        raise ValueError(f"beam search supports at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
+    _check_prednet_weights(rnn_weights, cell, Hp)
+    if Od < 1 or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or tuple(fc_b.shape) != (V,) or emb_w.shape[0] < V:
+        raise ValueError(f"beam search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding {tuple(emb_w.shape)} "
+                         f"do not fit encoder width {Oe}")
+    if not 0 <= blank < V or V < 2 or beam < 1:
+        raise ValueError(f"beam search: blank {blank} outside [0,{V}), V {V} < 2 or beam {beam} < 1")
+    max_candidates = max_pops * V if max_candidates is None else max_candidates
+    max_states = 3 * max_pops if max_states is None else max_states
+    max_len = 4 * T + 64 if max_len is None else max_len
+    dev = enc_tm.device
+    A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
+    gemm(T * B, V, Oe, enc_tm, fc_w, A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    tokens = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
+    lens = torch.empty(B, beam, device=dev, dtype=torch.int32)
+    scores = torch.empty(B, beam, device=dev, dtype=torch.float64)
+    small = torch.empty(B, 2 + _lib.BEAM_NSTATS, device=dev, dtype=torch.int32)   # count | status | stats: one transfer
+    d = _lib.BeamDesc()
+    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = T, B, V, Hp, Od, L, cell, blank
+    d.beam, d.improved, d.state_beam, d.expand_beam = beam, int(bool(improved)), float(state_beam), float(expand_beam)
+    d.max_candidates, d.max_pops, d.max_states, d.max_nodes, d.max_len = max_candidates, max_pops, max_states, max_nodes, max_len
+    ws_bytes = _lib.lib().rnnt_hip_beam_workspace_bytes(C.byref(d))
+    if ws_bytes == 0:
+        raise ValueError("beam search: invalid sizes or caps (all caps must be >= 1)")
+    ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
+    d.workspace, d.workspace_bytes = (_addr(ws) + 255) // 256 * 256, ws_bytes
+    d.A, d.t_lens, d.emb = _addr(A), _addr(t_lens), _addr(emb_w)
+    keep = []
+    for l in range(L):
+        w = [_f32c(t, "prediction-net weight") for t in rnn_weights[4 * l:4 * l + 4]]
+        keep.append(w)
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in w)
+    d.w_o, d.b_o = _addr(out_w), _addr(out_b)
+    d.w_d, d.ld_d = _addr(fc_w, Oe), Ocat
+    d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
+    d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
+    check(_lib.lib().rnnt_hip_beam_search(C.byref(d), _stream()), "rnnt_hip_beam_search")
+    host = small.cpu()   # the only host sync of the search
+    count, status = host.reshape(-1)[:B].tolist(), host.reshape(-1)[B:2 * B].tolist()
+    for b, st in enumerate(status):
+        if st != 0:
+            what, kw = _lib.BEAM_STATUS.get(st, ("unknown", "?"))
+            cap = {"max_candidates": max_candidates, "max_pops": max_pops, "max_states": max_states, "max_nodes": max_nodes,
+                   "max_len": max_len}.get(kw)
+            raise RnntHipError(f"beam search: utterance {b} exceeded the cap on {what} ({kw}={cap}); raise it with the {kw}= "
+                               "keyword (the reference's search is unbounded here)")
+    lens_h, scores_h = lens.cpu().tolist(), scores.cpu().tolist()
+    tok_h = tokens[:, :, :max(1, max(max(r) for r in lens_h))].cpu()
+    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if stats:
+        return out, host.reshape(-1)[2 * B:].reshape(B, _lib.BEAM_NSTATS)
+    return out
