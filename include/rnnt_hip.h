@@ -84,6 +84,9 @@ int rnnt_hip_prof_collect(double* ms, double* work, int64_t* count, int nkinds);
 #define RNNT_GEMM_MUL_DGELU 8u   /* C = result * gelu_tanh'(aux(m,n)), aux laid out like C          */
 #define RNNT_GEMM_EXACT_F32 16u  /* multiply on v_mfma_f32_32x32x2_f32 (bit-exact fp32 fma chains) even when the
                                   * library default is the split-bf16 form (see below)                      */
+#define RNNT_GEMM_HP_F16 32u     /* rnnt_hip_gemm_hp / rnnt_hp_problem only: ONE product hi.hi per fp32 product (the lo
+                                  * halves of both operands are not read) — f16 operand rounding, fp32 accumulation; see
+                                  * RNNT_PRECISION_F16.  The opt-in 3-stage kernel (RNNT_GEMM_HP_3STAGE) declines it. */
 
 typedef struct rnnt_gemm_desc {
   int64_t M, N, K;
@@ -119,7 +122,9 @@ int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream);
  *   [0, src_rows)) — the transposed operands of the weight-gradient products, time-shifted for dW_hh; amax[r] = maximum of source
  *   column r, computed here unless amax_given.
  * rnnt_hip_gemm_hp: C (M x N, row stride ldc) [+]= A (M x K) . B (N x K)^T + bias, both operands hp planes (NT form), fp32 out.
- *   flags: RNNT_GEMM_ACCUM.  workspace (optional, rnnt_hip_gemm_hp_workspace_bytes): deterministic split-K slabs.
+ *   flags: RNNT_GEMM_ACCUM, RNNT_GEMM_HP_F16 (one product hi.hi: the planes are the same, only their hi halves are multiplied —
+ *   each operand element is rounded to 11 significant bits of its row-scaled value, products accumulate in fp32).
+ *   workspace (optional, rnnt_hip_gemm_hp_workspace_bytes): deterministic split-K slabs.
  * ---------------------------------------------------------------------------------------------- */
 size_t rnnt_hip_hp_bytes(int64_t rows, int64_t K);
 int rnnt_hip_hp_split(const float* x, int64_t rows, int64_t K, int64_t ld, int32_t transpose, int64_t src_rows, int64_t shift,
@@ -147,7 +152,7 @@ typedef struct rnnt_hp_problem {
   const void* B; const uint32_t* b_amax;   /* (N x K) */
   int64_t M, N, K;
   float* C; int64_t ldc;
-  uint32_t flags;                          /* RNNT_GEMM_ACCUM */
+  uint32_t flags;                          /* RNNT_GEMM_ACCUM, RNNT_GEMM_HP_F16 (the same for every problem of one launch) */
 } rnnt_hp_problem;
 size_t rnnt_hip_gemm_hp_grouped_workspace_bytes(const rnnt_hp_problem* problems, int32_t n);
 int rnnt_hip_gemm_hp_grouped(const rnnt_hp_problem* problems, int32_t n, uint32_t xcd_skip, void* workspace, size_t workspace_bytes,
@@ -225,6 +230,26 @@ int32_t rnnt_hip_lstm_free_xcds(int32_t T, int32_t B, int32_t H, int32_t D, int3
 int32_t rnnt_hip_lstm_takes_row_idx(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell);
 int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream);
 
+/* Compute precision of a layer (opt-in; rnnt_hip_lstm_fwd / _bwd are RNNT_PRECISION_FP32).  The reference trains with
+ * `--precision 16` (model.py:28-31 hands it to Lightning's AMP), under which nn.LSTM (networks/encoder.py:67-75,99) multiplies f16
+ * operands with fp32 accumulation.  RNNT_PRECISION_F16 is that trade on this library's forms: the recurrences (h . W_hh^T, dG . W_hh)
+ * and the big products each call issues inside itself (input projection; dX, dW_ih, dW_hh, also as the grouped phase-2 launch) run
+ * ONE product hi.hi of the half-pair operands instead of three (RNNT_GEMM_HP_F16).  Every row keeps its own power-of-two scale, so
+ * nothing overflows and no loss scaling is needed; an operand element carries about 2^-11 relative error.  Cell math, gate
+ * pre-activations, the stash, parameters and gradients stay fp32.
+ *   precision: RNNT_PRECISION_FP32 = bitwise rnnt_hip_lstm_fwd / _bwd;  RNNT_PRECISION_F16 = the one-product forms where the layer
+ *   has them (rnnt_hip_lstm_takes_f16), bitwise fp32 elsewhere.  Any other value: RNNT_ERR_INVALID.
+ *   The forward and the backward call of one layer must pass the same precision (the backward is the derivative of the
+ *   arithmetic its forward ran; the library does not check it). */
+#define RNNT_PRECISION_FP32 0
+#define RNNT_PRECISION_F16 1
+int rnnt_hip_lstm_fwd_ex(const rnnt_lstm_desc* d, uint32_t precision, void* stream);
+/* 1 if a layer of this shape really runs the one-product forms under RNNT_PRECISION_F16 (v5 recurrences in both directions of time
+ * and the half-pair products), 0 if it computes in fp32 whatever it is asked (lstm.hip's v3 / v4 forms: H > 640 unless opted in,
+ * RNNT_LSTM_NO_V5, the ReLU cell; products below the half-pair limits; RNNT_GEMM_HP_3STAGE).  Products that stay on
+ * rnnt_hip_gemm_f32 inside an f16 layer (an input narrower than 32 / 128 features) are fp32 either way. */
+int32_t rnnt_hip_lstm_takes_f16(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell);
+
 typedef struct rnnt_lstm_bwd_desc {
   rnnt_lstm_desc f;   /* same description as the forward call (x, weights, y, stash, workspace) */
   const float* dy;    /* (T,B,D*H) gradient w.r.t. y (w.r.t. y_drop when dropout_p > 0) */
@@ -252,6 +277,8 @@ typedef struct rnnt_lstm_bwd_desc {
 #define RNNT_LSTM_BWD_WEIGHTS 2
 
 int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* d, void* stream);
+/* rnnt_hip_lstm_bwd with a compute precision: the one of the layer's forward call (see rnnt_hip_lstm_fwd_ex) */
+int rnnt_hip_lstm_bwd_ex(const rnnt_lstm_bwd_desc* d, uint32_t precision, void* stream);
 /* reads back the persistent kernels' status word from a workspace (synchronises `stream`);
  * 0 = ok, RNNT_ERR_TIMEOUT if an inter-CU wait gave up.  For tests and the bench, not for hot loops. */
 int rnnt_hip_lstm_check(const void* workspace, void* stream);

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("RNNT_HIP_LIB") or os.path.join(_HERE, "csrc", "librnn
 ABI_VERSION = 4   # RNNT_HIP_ABI_VERSION of include/rnnt_hip.h
 
 GEMM_GELU_A, GEMM_GELU_B, GEMM_ACCUM, GEMM_MUL_DGELU, GEMM_EXACT_F32 = 1, 2, 4, 8, 16
+GEMM_HP_F16 = 32   # rnnt_hip_gemm_hp / rnnt_hp_problem: the one-product (hi.hi) form
+PRECISION_FP32, PRECISION_F16 = 0, 1   # rnnt_hip_lstm_fwd_ex / _bwd_ex
 CELL_LSTM, CELL_GRU, CELL_RNN_TANH, CELL_RNN_RELU = 0, 1, 2, 3
 
 c_f32p = C.c_void_p
@@ -109,7 +111,10 @@ SYMBOLS = {
     "rnnt_hip_lstm_free_xcds": (c_i32, [c_i32] * 5),
     "rnnt_hip_lstm_takes_row_idx": (c_i32, [c_i32] * 6),
     "rnnt_hip_lstm_fwd": (C.c_int, [C.POINTER(LstmDesc), C.c_void_p]),
+    "rnnt_hip_lstm_fwd_ex": (C.c_int, [C.POINTER(LstmDesc), C.c_uint32, C.c_void_p]),
+    "rnnt_hip_lstm_takes_f16": (c_i32, [c_i32] * 6),
     "rnnt_hip_lstm_bwd": (C.c_int, [C.POINTER(LstmBwdDesc), C.c_void_p]),
+    "rnnt_hip_lstm_bwd_ex": (C.c_int, [C.POINTER(LstmBwdDesc), C.c_uint32, C.c_void_p]),
     "rnnt_hip_lstm_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rnnt_hip_lstm_debug_read": (C.c_int, [C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_void_p, c_i32, C.c_void_p]),
     "rnnt_hip_joint_loss_workspace_bytes": (C.c_size_t, [c_i32] * 4),

@@ -261,7 +261,10 @@ __device__ __forceinline__ int hp_xcd_remap(int bid, int n) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
-// one 256 x 256 output tile (`bid` = column-major tile index) over K-tiles [z * kt_per_split, ...) of problem p
+// one 256 x 256 output tile (`bid` = column-major tile index) over K-tiles [z * kt_per_split, ...) of problem p.
+// F16 (RNNT_GEMM_HP_F16): the one-product form — only hi.hi is multiplied and the lo fragments are never read from LDS (the planes
+// keep their hi | lo lines: the LDS-DMA still moves both halves)
+template <bool F16>
 __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, const int z, char* lds) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -329,19 +332,19 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
   f16x8 a[4][2], bs[2][2][2];
   auto ld_a = [&](const char* sb, int mq, int i) {
     a[i][0] = *reinterpret_cast<const f16x8*>(sb + (a_base + (4 * mq + i) * 2048));
-    a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + (4 * mq + i) * 2048));
+    if constexpr (!F16) a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + (4 * mq + i) * 2048));
   };
   auto ld_b = [&](int set, const char* sb, int nq) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       bs[set][j][0] = *reinterpret_cast<const f16x8*>(sb + (b_base + (2 * nq + j) * 2048));
-      bs[set][j][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + (2 * nq + j) * 2048));
+      if constexpr (!F16) bs[set][j][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + (2 * nq + j) * 2048));
     }
   };
   // blocks i0, i0 + 1 of A half mq against B half nq (register set `set`): 12 MFMAs, four independent accumulators between dependent ones
   auto mma2 = [&](int mq, int nq, int set, int i0) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+    for (int t = F16 ? 2 : 0; t < 3; ++t)
 #pragma unroll
       for (int i = i0; i < i0 + 2; ++i)
 #pragma unroll
@@ -440,14 +443,14 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         a[i][0] = *reinterpret_cast<const f16x8*>(sb + (a_base + (4 * mq + i) * 2048));
-        a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + (4 * mq + i) * 2048));
+        if constexpr (!F16) a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + (4 * mq + i) * 2048));
       }
     };
     auto load_b = [&](int nq) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         b[j][0] = *reinterpret_cast<const f16x8*>(sb + (b_base + (2 * nq + j) * 2048));
-        b[j][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + (2 * nq + j) * 2048));
+        if constexpr (!F16) b[j][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + (2 * nq + j) * 2048));
       }
     };
 #endif
@@ -457,8 +460,10 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           f32x4 c = acc[4 * mq + i][2 * nq + j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][1], b[j][0], c, 0, 0, 0);  // smallest terms first
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][1], c, 0, 0, 0);
+          if constexpr (!F16) {
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][1], b[j][0], c, 0, 0, 0);  // smallest terms first
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][1], c, 0, 0, 0);
+          }
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][0], c, 0, 0, 0);
           acc[4 * mq + i][2 * nq + j] = c;
         }
@@ -526,11 +531,12 @@ __device__ __forceinline__ int hp_grouped_tile(int idx, int tiles_m, int tiles_n
   return n * tiles_m + m;
 }
 
+template <bool F16>
 __global__ void __launch_bounds__(512, 1) gemm_hp_kernel(const HpGemmK p) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int bid = hp_xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   if (p.group_m > 0) bid = hp_grouped_tile(bid, p.tiles_m, p.tiles_n, p.group_m);
-  hp_tile256(p, bid, blockIdx.y, lds);
+  hp_tile256<F16>(p, bid, blockIdx.y, lds);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -554,7 +560,8 @@ struct HpGemmQ {
 // K range) and, every tiles_n units, the B panels.  Every participating XCD owns one contiguous share of the units (its 32
 // workgroups walk it front to back: what they have in flight at any time re-uses a handful of panels through that XCD's L2;
 // drawing from ONE queue across XCDs measured 2.95 ms against a 2.0 ms estimate for a c2 layer: every tile fetched both panels
-// from HBM); an XCD that runs dry takes units from the others' shares.
+// from HBM); an XCD that runs dry takes units from the others' shares.  F16: every problem of the launch is a one-product one.
+template <bool F16>
 __global__ void __launch_bounds__(512, 1) gemm_hpq_kernel(const HpGemmQ q) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   unsigned xcc;
@@ -587,7 +594,7 @@ __global__ void __launch_bounds__(512, 1) gemm_hpq_kernel(const HpGemmQ q) {
       const HpGemmK& p = q.prob[pi];
       const int local = u - (pi ? q.unit_end[pi - 1] : 0);
       const int tn = local % p.tiles_n, z = (local / p.tiles_n) % p.splits, tm = local / (p.tiles_n * p.splits);
-      hp_tile256(p, tn * p.tiles_m + tm, z, lds);
+      hp_tile256<F16>(p, tn * p.tiles_m + tm, z, lds);
     }
   }
 }
@@ -607,6 +614,8 @@ __global__ void hpq_check_kernel(unsigned* counter, unsigned total, unsigned* st
 // 256 x 128 x 32 tile, 8 waves as 4 (M) x 2 (N), 64 x 64 of C per wave (4 x 4 blocks, 48 MFMAs per K-tile), THREE 48 KB LDS stages:
 // the LDS-DMA of K-tile t+2 is issued before tile t is multiplied and is only waited for (counted vmcnt, raw s_barrier: a
 // __syncthreads() would drain it) at the end of tile t+1 — two tiles of MFMA time to land instead of one.
+// (Opt-in variant, RNNT_GEMM_HP_3STAGE: it has no one-product form and declines RNNT_GEMM_HP_F16 — three products always; while it
+// is selected rnnt_hip_lstm_takes_f16 reports 0 and the LSTM entries run fp32.)
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HP3_BM = 256, HP3_BN = 128, HP3_STAGE = (HP3_BM + HP3_BN) * 128, HP3_NST = 3;
 
@@ -743,6 +752,8 @@ __global__ void __launch_bounds__(256) hp_splitk_reduce_kernel(const HpGemmK p) 
 }  // namespace
 
 // internal entry points shared with lstm.hip -------------------------------------------------------------------------
+bool hp_gemm_3stage() { return getenv("RNNT_GEMM_HP_3STAGE") != nullptr; }
+
 size_t hp_plane_bytes(int64_t rows, int64_t K) { return (size_t)rows * (size_t)ceil_div(K, 32) * 128; }
 
 int hp_colmax(const float* x, int64_t rows, int64_t C, int64_t ld, uint32_t* amax, hipStream_t s) {
@@ -817,7 +828,8 @@ int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t
   k.C = C; k.c_div = (int)(c_div > 0x7fffffff ? 0x7fffffff : c_div); k.c_so = c_so; k.c_si = c_si;
   k.bias = bias; k.flags = flags;
   k.a_rowidx = a_rowidx; k.c_rowidx = c_rowidx;
-  const bool k3 = getenv("RNNT_GEMM_HP_3STAGE") != nullptr && !a_rowidx && !c_rowidx;   // opt-in: 256x128 tiles / 3-stage LDS ring (measured 10-14 % slower than 256x256 / 2 stages)
+  const bool k3 = hp_gemm_3stage() && !a_rowidx && !c_rowidx;   // opt-in: 256x128 tiles / 3-stage LDS ring (measured 10-14 % slower than 256x256 / 2 stages)
+  const bool f16 = (flags & RNNT_GEMM_HP_F16) != 0u && !k3;   // (the 3-stage variant declines the one-product form)
   k.tiles_m = (int)ceil_div(M, HP_BM); k.tiles_n = (int)ceil_div(N, k3 ? HP3_BN : HP_BN);
   const int tiles = k.tiles_m * k.tiles_n;
   {  // band height of the tile walk: 8 x 4 tiles in flight per XCD when an XCD's share is >= 32 tiles, 4 x 2 for the small outputs
@@ -839,11 +851,13 @@ int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t
   k.splits = splits;
   k.slab = (float*)workspace;
   if (k3) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HP3_NST * HP3_STAGE));
-  else RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
+  else if (f16) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
+  else RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
   {
     ProfScope prof(RNNT_K_GEMM_HP, 2.0 * (double)M * (double)N * (double)K, s);
     if (k3) hipLaunchKernelGGL(gemm_hp3_kernel, dim3(tiles, splits), dim3(512), HP3_NST * HP3_STAGE, s, k);
-    else hipLaunchKernelGGL(gemm_hp_kernel, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
+    else if (f16) hipLaunchKernelGGL(gemm_hp_kernel<true>, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
+    else hipLaunchKernelGGL(gemm_hp_kernel<false>, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
     RNNT_CHECK_LAUNCH();
     if (splits > 1) {
       const long blocks = ceil_div((long)M * N, 256);
@@ -865,6 +879,9 @@ int hp_gemm_grouped(const HpProblem* pr, int n, unsigned xcd_skip, unsigned* cou
                     hipStream_t s, unsigned* status) {
   RNNT_CHECK_ARG(pr && n >= 1 && n <= HPQ_MAX && counter, "gemm_hp grouped: 1..%d problems and a counter word", HPQ_MAX);
   RNNT_CHECK_ARG((xcd_skip & 0xffu) != 0xffu, "gemm_hp grouped: xcd_skip leaves no XCD");
+  const bool f16 = (pr[0].flags & RNNT_GEMM_HP_F16) != 0u;
+  for (int i = 1; i < n; ++i)
+    RNNT_CHECK_ARG(((pr[i].flags & RNNT_GEMM_HP_F16) != 0u) == f16, "gemm_hp grouped: the problems of one launch share RNNT_GEMM_HP_F16");
   HpGemmQ q = {};
   q.nprob = n; q.xcd_skip = xcd_skip; q.counter = counter;
   int xcds = 0;
@@ -912,12 +929,15 @@ int hp_gemm_grouped(const HpProblem* pr, int n, unsigned xcd_skip, unsigned* cou
   }
   RNNT_CHECK_HIP(hipMemsetAsync(counter, 0, 64, s));
   const int lds = 2 * HP_STAGE + 16;
-  RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hpq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  const void* qk = f16 ? (const void*)gemm_hpq_kernel<true> : (const void*)gemm_hpq_kernel<false>;
+  RNNT_CHECK_HIP(hipFuncSetAttribute(qk, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   {
     ProfScope prof(RNNT_K_GEMM_HP, flops, s);
     int cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-    hipLaunchKernelGGL(gemm_hpq_kernel, dim3(!xcd_skip && units < cus ? units : cus), dim3(512), lds, s, q);   // with skipped XCDs: one per CU, an eighth lands on each XCD
+    const dim3 grid(!xcd_skip && units < cus ? units : cus);   // with skipped XCDs: one per CU, an eighth lands on each XCD
+    if (f16) hipLaunchKernelGGL(gemm_hpq_kernel<true>, grid, dim3(512), lds, s, q);
+    else hipLaunchKernelGGL(gemm_hpq_kernel<false>, grid, dim3(512), lds, s, q);
     RNNT_CHECK_LAUNCH();
     hipLaunchKernelGGL(hpq_check_kernel, dim3(1), dim3(1), 0, s, counter, (unsigned)units, status);
     RNNT_CHECK_LAUNCH();

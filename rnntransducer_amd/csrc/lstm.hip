@@ -1713,6 +1713,14 @@ bool shape_takes_row_idx(int T, int B, int I, int H, int D, int cell, int cus) {
   Plan2 p2;
   return use_hp(T, B, I, H, D) && I >= 32 && T > 1 && make_plan3(B, H, D, cus, true, &p2) && lstm5_supported(T, B, H, D, cell);
 }
+// RNNT_PRECISION_F16 is honoured where the WHOLE layer runs the forms that have a one-product variant: v5 recurrences in both
+// directions of time and the half-pair products (gemm_hp.hip's default kernel).  Everywhere else the layer computes in fp32, bitwise
+// what RNNT_PRECISION_FP32 computes.  Same answer in the forward and the backward call of a layer (it depends on the shape only).
+bool shape_takes_f16(int T, int B, int I, int H, int D, int cell, int cus) {
+  Plan2 pf, pb;
+  return use_hp(T, B, I, H, D) && make_plan3(B, H, D, cus, false, &pf) && make_plan3(B, H, D, cus, true, &pb) &&
+         lstm5_supported(T, B, H, D, cell) && !hp_gemm_3stage();
+}
 bool ragged_plan(const rnnt_lstm_desc* d, const LstmWs& w, int cus) {
   return d->row_idx && d->n_rows > 0 && d->n_rows < (int64_t)d->T * d->B && w.hp && d->x_sb == d->I && d->x_st == (int64_t)d->B * d->I &&
          shape_takes_row_idx(d->T, d->B, d->I, d->H, d->D, d->cell, cus);
@@ -1753,6 +1761,13 @@ extern "C" int32_t rnnt_hip_lstm_takes_row_idx(int32_t T, int32_t B, int32_t I, 
   return shape_takes_row_idx(T, B, I, H, D, cell, cus) ? 1 : 0;
 }
 
+extern "C" int32_t rnnt_hip_lstm_takes_f16(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell) {
+  int cus = device_cus();
+  if (cus <= 0) cus = 256;
+  if (T < 1 || B < 1 || I < 1 || H < 4 || D < 1 || D > 2) return 0;
+  return shape_takes_f16(T, B, I, H, D, cell, cus) ? 1 : 0;
+}
+
 extern "C" int32_t rnnt_hip_lstm_free_xcds(int32_t T, int32_t B, int32_t H, int32_t D, int32_t cell) {
   int cus = device_cus();
   if (cus <= 0) cus = 256;
@@ -1785,12 +1800,15 @@ extern "C" size_t rnnt_hip_lstm_workspace_bytes(int32_t T, int32_t B, int32_t I,
     }                                                                                       \
   } while (0)
 
-extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) {
+static int lstm_fwd_impl(const rnnt_lstm_desc* d, uint32_t precision, void* stream) {
   Plan pl;
   LstmWs w;
   if (int rc = check_desc(d, &pl, &w)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int H = d->H, D = d->D, I = d->I;
+  // one-product forms (RNNT_PRECISION_F16) where the whole layer has them, fp32 otherwise
+  const bool f16 = precision == RNNT_PRECISION_F16 && shape_takes_f16(d->T, d->B, I, H, D, d->cell, device_cus());
+  const unsigned hpf = f16 ? RNNT_GEMM_HP_F16 : 0u;
   const int ngate = d->cell == RNNT_CELL_LSTM ? 4 : (d->cell == RNNT_CELL_GRU ? 3 : 1);
   // 1. gate-adjacent copy of W_ih (both directions stacked) and of b_ih + b_hh
   {
@@ -1813,7 +1831,7 @@ extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) {
     uint32_t* ax = w.hp_amax, *aw = w.hp_amax + M;
     if (int rc = hp_split(d->x, Mv, I, I, ax, w.hp_x, s, ridx)) return rc;   // planes / maxima of the valid rows, in place
     if (int rc = hp_split(w.wp, N4, I, I, aw, w.hp_w, s)) return rc;
-    if (int rc = hp_gemm(w.hp_x, ax, w.hp_w, aw, Mv, N4, I, d->gates, 1, N4, 0, w.bp, 0, nullptr, 0, s, ridx, M, ridx)) return rc;
+    if (int rc = hp_gemm(w.hp_x, ax, w.hp_w, aw, Mv, N4, I, d->gates, 1, N4, 0, w.bp, hpf, nullptr, 0, s, ridx, M, ridx)) return rc;
   } else {
     rnnt_gemm_desc g = {};
     g.M = (int64_t)d->T * d->B; g.N = (int64_t)D * 4 * H; g.K = I;
@@ -1845,7 +1863,7 @@ extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) {
       else rc = launch_persistent2(lstm_fwd3_kernel<N, 2>, k, p2, p2.lds_fwd, s, "lstm_fwd3");                     \
     } while (0)
     if (lstm5_supported(d->T, d->B, d->H, d->D, d->cell)) {  // v5: tagged-payload exchange, f16 matrix cores (lstm5.hip)
-      rc = lstm5_fwd_launch(k, p2, d->cell, s);
+      rc = lstm5_fwd_launch(k, p2, d->cell, s, f16);
     } else if (p2.MB == 5) {  // H = 640: 5 blocks, 8 waves x 3 k-steps over K padded to 768
       const size_t lds5 = p2.lds_fwd + 8 * 1 * 3 * 3 * 1024;  // one of the five blocks' pieces in LDS
       if (d->cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd3_kernel<3, 0, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
@@ -1886,7 +1904,15 @@ extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) {
   return rc;
 }
 
-extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
+extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) { return lstm_fwd_impl(d, RNNT_PRECISION_FP32, stream); }
+
+extern "C" int rnnt_hip_lstm_fwd_ex(const rnnt_lstm_desc* d, uint32_t precision, void* stream) {
+  RNNT_CHECK_ARG(precision == RNNT_PRECISION_FP32 || precision == RNNT_PRECISION_F16, "lstm_fwd_ex: precision must be 0 (fp32) or 1 (f16), got %u",
+                 precision);
+  return lstm_fwd_impl(d, precision, stream);
+}
+
+static int lstm_bwd_impl(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void* stream) {
   RNNT_CHECK_ARG(bd != nullptr, "lstm_bwd: null descriptor");
   const rnnt_lstm_desc* d = &bd->f;
   Plan pl;
@@ -1894,6 +1920,9 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
   if (int rc = check_desc(d, &pl, &w)) return rc;
   RNNT_CHECK_ARG(bd->dy, "lstm_bwd: null dy");
   const int T = d->T, B = d->B, H = d->H, D = d->D, I = d->I;
+  // same decision as the forward call of the layer (shape only)
+  const bool f16 = precision == RNNT_PRECISION_F16 && shape_takes_f16(T, B, I, H, D, d->cell, device_cus());
+  const unsigned hpf = f16 ? RNNT_GEMM_HP_F16 : 0u;
   const bool gru = d->cell == RNNT_CELL_GRU;
   const int ngate = d->cell == RNNT_CELL_LSTM ? 4 : (gru ? 3 : 1);
   RNNT_CHECK_ARG(!gru || d->aux, "lstm_bwd: GRU needs the aux buffer (T,B,D*4H)");
@@ -1965,7 +1994,7 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
           RNNT_CHECK_HIP(hipMemsetAsync(fill_from, 0, (size_t)(k.colmax_h + N4r - fill_from) * 4, s));
         colmax_done = true;
       }
-      if (do_recur) rc = lstm5_bwd_launch(k, p2, d->cell, s);
+      if (do_recur) rc = lstm5_bwd_launch(k, p2, d->cell, s, f16);
       // the weight-gradient products of THIS layer may run beside the recurrence of the next one (same shape): that one sits on
       // XCDs 0 .. D*G-1 (launch_persistent2's stride-8 placement), the products keep to the others
       if (bd->beside_recurrence) {
@@ -2058,7 +2087,7 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
     if (hp_in) {
       if ((rc = hp_colmax(w.wp, N4, I, I, a_w, s))) return rc;
       if ((rc = hp_split_t(w.wp, I, N4, I, N4, 0, a_w, w.hp_w, s))) return rc;   // W_ih'^T: (I, contraction N4)
-      if ((rc = hp_gemm(w.hp_dg, a_dgr, w.hp_w, a_w, Mv, I, N4, bd->dx, 1, I, 0, nullptr, 0, nullptr, 0, s, ridx, M, ridx))) return rc;
+      if ((rc = hp_gemm(w.hp_dg, a_dgr, w.hp_w, a_w, Mv, I, N4, bd->dx, 1, I, 0, nullptr, hpf, nullptr, 0, s, ridx, M, ridx))) return rc;
     } else {
       rnnt_gemm_desc g = {};
       g.M = M; g.N = I; g.K = N4;
@@ -2086,7 +2115,7 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
       } else if ((rc = hp_colmax(d->x, M, I, I, a_x, s))) return rc;
       if ((rc = hp_split_t(d->x, I, Mv, I, M, 0, a_x, w.hp_x, s, ridx))) return rc;     // X^T: (I, contraction over the (valid) frames)
       if (!grouped)
-        if ((rc = hp_gemm(w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, 1, I, 0, nullptr, 0, w.scratch, w.scratch_bytes, s))) return rc;
+        if ((rc = hp_gemm(w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, 1, I, 0, nullptr, hpf, w.scratch, w.scratch_bytes, s))) return rc;
     } else {
       rnnt_gemm_desc g = {};
       g.M = N4; g.N = I; g.K = M;
@@ -2115,7 +2144,7 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
     }
     HpProblem pr[HP_GROUP_MAX];
     int npr = 0;
-    if (grouped) pr[npr++] = HpProblem{w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, I, 0u};
+    if (grouped) pr[npr++] = HpProblem{w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, I, hpf};
     for (int dir = 0; dir < D; ++dir) {
       // h_prev of frame t is y[t-1] (forward direction) / y[t+1] (reverse): plane row j, index k = y[k -/+ B][dir*H + j], zero outside
       char* yt = w.hp_yt + (size_t)dir * hp_plane_bytes(H, M);
@@ -2123,11 +2152,11 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
       if ((rc = hp_split_t(d->y + (int64_t)dir * H, H, Mv, (int64_t)D * H, M, dir == 0 ? -B : B, a_y + (int64_t)dir * H, yt, s, ridx))) return rc;
       const char* ag = w.hp_dgt + (size_t)dir * 4 * H * (size_t)ceil_div(Mv, 32) * 128;
       if (grouped) {
-        pr[npr++] = HpProblem{ag, a_dgc + (int64_t)dir * 4 * H, yt, a_y + (int64_t)dir * H, 4 * H, H, Mv, w.dwhh + (int64_t)dir * 4 * H * H, H, 0u};
+        pr[npr++] = HpProblem{ag, a_dgc + (int64_t)dir * 4 * H, yt, a_y + (int64_t)dir * H, 4 * H, H, Mv, w.dwhh + (int64_t)dir * 4 * H * H, H, hpf};
         continue;
       }
       if ((rc = hp_gemm(ag, a_dgc + (int64_t)dir * 4 * H, yt, a_y + (int64_t)dir * H, 4 * H, H, Mv, w.dwhh + (int64_t)dir * 4 * H * H, 1, H, 0,
-                        nullptr, 0, w.scratch, w.scratch_bytes, s)))
+                        nullptr, hpf, w.scratch, w.scratch_bytes, s)))
         return rc;
     }
     if (grouped) {
@@ -2184,6 +2213,14 @@ extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) {
     }
   }
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) { return lstm_bwd_impl(bd, RNNT_PRECISION_FP32, stream); }
+
+extern "C" int rnnt_hip_lstm_bwd_ex(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void* stream) {
+  RNNT_CHECK_ARG(precision == RNNT_PRECISION_FP32 || precision == RNNT_PRECISION_F16, "lstm_bwd_ex: precision must be 0 (fp32) or 1 (f16), got %u",
+                 precision);
+  return lstm_bwd_impl(bd, precision, stream);
 }
 
 extern "C" int rnnt_hip_lstm_check(const void* workspace, void* stream) {

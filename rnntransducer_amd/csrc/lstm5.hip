@@ -21,6 +21,9 @@
 //      hand-off costs: c2 forward 8.6 -> 8.0 ms, backward 10.0 -> 9.5 ms per training step).
 //   4. A step's stash stores and the next step's stash loads are issued AFTER the arrival of this step's operands, not behind the
 //      publication: between a publication and the arrival of the next operands a CU's memory queue holds the polls only.
+//   5. One-product forms (template argument F16, RNNT_PRECISION_F16): W_hh keeps its hi halves only (no wlo registers) and every
+//      k-step issues the hi.hi product alone.  The exchange is untouched: the published dword is still hi | lo << 16 with the tag in
+//      lo, the backward's LDS image still holds both planes; the consumer simply does not multiply the lo half.
 //
 // Correctness never depends on placement: stores are sc1 write-through unless the group is VERIFIED to sit on one XCD (then
 // plain stores stay in that L2), loads are always sc1 (bypass L1).  All spins are bounded and raise the status word.
@@ -51,6 +54,11 @@ __device__ __forceinline__ void split8h(const f32x4& a, const f32x4& b, float sc
     hi[e] = h;
     lo[e] = (_Float16)(v - (float)h);
   }
+}
+// the hi fragment alone (one-product forms): the same hi as split8h
+__device__ __forceinline__ void split8h(const f32x4& a, const f32x4& b, float scale, f16x8& hi) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) hi[e] = (_Float16)((e < 4 ? a[e] : b[e - 4]) * scale);
 }
 
 // Steps a sync group runs: T, or — ragged batches, p.gbound — the longest of its rows (uniform over the group's workgroups: every
@@ -89,8 +97,9 @@ __device__ __forceinline__ bool poll_tagged(F&& load_and_check, unsigned* status
 // NKS: 32-deep k-steps per wave (Kp = NWV * 32 * NKS >= H, zero padded).  CELL: 0 LSTM, 1 GRU, 2 tanh Elman RNN.
 // NWV x MB: 4 x 4 (H = 128..512: 16 units per workgroup), 8 x 5 (H = 640: 20 units per workgroup so that a sync group has 32
 // members and fits one XCD; K padded to 768) or 8 x 4 (H = 768 / 1024: NKS = 3 / 4, 48 / 64 workgroups per group).  Wave w < MB owns gate-column block w (one cell per lane).
+// F16: one-product form (whi . h_hi only).
 // ================================================================================================
-template <int NKS, int CELL, int NWV = 4, int MB = 4>
+template <int NKS, int CELL, int NWV = 4, int MB = 4, bool F16 = false>
 __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
   constexpr int NGATE = CELL == 0 ? 4 : (CELL == 1 ? 3 : 1);
   constexpr int HS = 4 * MB, Kw = 32 * NKS;
@@ -114,7 +123,7 @@ __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
   const int T = group_steps(p, b0);         // steps this sync group runs (ragged batches: the longest of its rows)
 
   // W_hh slice: lane -> gate column 16*mb + lrow (gate lrow&3 of unit 4*mb + (lrow>>2)), k = wave*Kw + 32*ks + 8*lq + e
-  f16x8 whi[MB][NKS], wlo[MB][NKS];
+  f16x8 whi[MB][NKS], wlo[F16 ? 1 : MB][F16 ? 1 : NKS];   // (one-product form: no lo registers)
   float out_scale;
   {
     const float* W = p.w_hh[d];
@@ -154,7 +163,10 @@ __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      for (int ks = 0; ks < NKS; ++ks) {
+        if constexpr (F16) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks]);
+        else split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      }
   }
 
   const int NBR = 4 * ((p.Bg + 3) / 4);  // exchange rows of the group (host allocation)
@@ -270,8 +282,10 @@ __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
         //  wave already fills the dependent-issue gaps)
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
-          acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb][ks], hh, acc[mb], 0, 0, 0);
-          acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb][ks], hl, acc[mb], 0, 0, 0);
+          if constexpr (!F16) {
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb][ks], hh, acc[mb], 0, 0, 0);
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb][ks], hl, acc[mb], 0, 0, 0);
+          }
           acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb][ks], hh, acc[mb], 0, 0, 0);
         }
       }
@@ -393,8 +407,9 @@ __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
 // dynamic LDS: red[NT] f32x4 | dgs[16][DGS_LD] float | rowexp[2][16] | wmax[8] | abort
 // NMB: 16-unit output blocks per wave (Kp / 16 / NWV).  NWV x MB: 4 x 4 (H = 128..512), 8 x 5 (H = 640, K padded to 768) or 8 x 4
 // (H = 768 / 1024: 48 / 64 producers per group, NCMAX = 64; such a group spans XCDs and runs the write-through exchange).
+// F16: one-product form (whi . dG_hi only).
 // ================================================================================================
-template <int NMB, int BQ, int CELL, int NWV = 4, int MB = 4, int NCMAX = 32>
+template <int NMB, int BQ, int CELL, int NWV = 4, int MB = 4, int NCMAX = 32, bool F16 = false>
 __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
   constexpr int NGATE = CELL == 0 ? 4 : (CELL == 1 ? 3 : 1);
   constexpr int HS = 4 * MB, UQ = MB, NT = 64 * NWV;
@@ -423,7 +438,7 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
 
   // W_hh slice as the A operand: lane -> output unit u = 16*(wave*NMB + mb) + lrow (a COLUMN of W_hh),
   // k = 32*ks + 8*lq + e = own gate column 4*unit + gate  ->  W_hh[gate*H + j0 + (k>>2)][u]
-  f16x8 whi[NMB][KSB], wlo[NMB][KSB];
+  f16x8 whi[NMB][KSB], wlo[F16 ? 1 : NMB][F16 ? 1 : KSB];   // (one-product form: no lo registers)
   float w_inv;
   {
     const float* W = p.w_hh[d];
@@ -468,7 +483,10 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
-      for (int ks = 0; ks < KSB; ++ks) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      for (int ks = 0; ks < KSB; ++ks) {
+        if constexpr (F16) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks]);
+        else split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      }
   }
 
   const long px_bytes = (long)p.NC * NBR * Kp * 4;  // one (parity, group) image: [producer][row][Kp] fp32
@@ -653,7 +671,8 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
 #pragma unroll
       for (int ks = 0; ks < KSB; ++ks) {
         const float* src = dgs + lrow * DGS_LD + 32 * ks + 8 * lq;
-        split8h(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), gscale, ghi[ks], glo[ks]);
+        if constexpr (F16) split8h(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), gscale, ghi[ks]);
+        else split8h(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), gscale, ghi[ks], glo[ks]);
       }
       const unsigned tag = (((unsigned)s >> 1) & 1u) ^ 1u;
       // groups of 4 output blocks: 4 independent accumulators between dependent MFMAs
@@ -665,10 +684,12 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
         for (int j = 0; j < GB; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KSB; ++ks) {
+          if constexpr (!F16) {
 #pragma unroll
-          for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
+            for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
 #pragma unroll
-          for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], glo[ks], acc[j], 0, 0, 0);
+            for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], glo[ks], acc[j], 0, 0, 0);
+          }
 #pragma unroll
           for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
         }
@@ -787,7 +808,8 @@ __device__ __forceinline__ unsigned xmax32(unsigned u) {
 __device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
 __device__ __forceinline__ float radd(float x, unsigned rot) { return x + __builtin_bit_cast(float, rot); }
 
-template <int NMB, int BQ, int CELL, int NWV = 4>
+// F16: one-product form (whi . dG_hi only; the LDS image keeps both planes, the lo plane is not read).
+template <int NMB, int BQ, int CELL, int NWV = 4, bool F16 = false>
 __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
   constexpr int NGATE = CELL == 0 ? 4 : (CELL == 1 ? 3 : 1);
   constexpr int HS = 16, NT = 64 * NWV, KSB = 2, NCMAX = 32;
@@ -819,7 +841,7 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
 
   // W_hh slice as the A operand (as lstm_bwd5_kernel): lane -> output unit u = 16*(wave*NMB + mb) + lrow,
   // k = 32*ks + 8*lq + e = own gate column 4*unit + gate  ->  W_hh[gate*H + j0 + (k>>2)][u]
-  f16x8 whi[NMB][KSB], wlo[NMB][KSB];
+  f16x8 whi[NMB][KSB], wlo[F16 ? 1 : NMB][F16 ? 1 : KSB];   // (one-product form: no lo registers)
   float w_inv;
   {
     const float* W = p.w_hh[d];
@@ -864,7 +886,10 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
 #pragma unroll
     for (int mb = 0; mb < NMB; ++mb)
 #pragma unroll
-      for (int ks = 0; ks < KSB; ++ks) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      for (int ks = 0; ks < KSB; ++ks) {
+        if constexpr (F16) split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks]);
+        else split8h(raw[mb][ks][0], raw[mb][ks][1], wscale, whi[mb][ks], wlo[mb][ks]);
+      }
   }
 
   const long px_bytes = (long)p.NC * NBR * Kp * 4;  // one (parity, group) image: [producer][Kp / 16 blocks][4 * NBR granules]
@@ -1080,7 +1105,7 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
 #pragma unroll
       for (int ks = 0; ks < KSB; ++ks) {
         ghi[ks] = *reinterpret_cast<const f16x8*>(src + 32 * ks);
-        glo[ks] = *reinterpret_cast<const f16x8*>(src + 16 * GLD + 32 * ks);
+        if constexpr (!F16) glo[ks] = *reinterpret_cast<const f16x8*>(src + 16 * GLD + 32 * ks);
       }
       const unsigned tag = (((unsigned)s >> 1) & 1u) ^ 1u;
       constexpr int GB = (NMB % 4 == 0 && NMB > 4) ? 4 : 2;
@@ -1091,10 +1116,12 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
         for (int j = 0; j < GB; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KSB; ++ks) {
+          if constexpr (!F16) {
 #pragma unroll
-          for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
+            for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
 #pragma unroll
-          for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], glo[ks], acc[j], 0, 0, 0);
+            for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], glo[ks], acc[j], 0, 0, 0);
+          }
 #pragma unroll
           for (int j = 0; j < GB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi[mb0 + j][ks], ghi[ks], acc[j], 0, 0, 0);
         }
@@ -1188,7 +1215,8 @@ static int env_pause(const char* name) {   // "e" or "e,l"
   return (e & 255) | ((l & 255) << 8);
 }
 
-int lstm5_fwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s) {
+template <bool F16>
+static int fwd_launch_t(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s) {
   LstmK k = k_in;
   // A pause between a step's publication and its first poll round: the round issued right behind the publication never finds the
   // operands (they are one L2 hand-off away) and its requests queue in front of the round that would.  Measured (paired bench runs,
@@ -1199,9 +1227,9 @@ int lstm5_fwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
   int rc = RNNT_ERR_UNSUPPORTED;
   if (pl.MB == 5) {   // H = 640
     const size_t lds = (size_t)2 * 8 * 5 * 64 * 16 + 32 + 16 + 16 * 20 * 4;
-    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<3, 0, 8, 5>, k, pl, lds, s, "lstm_fwd5", 512);
-    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<3, 1, 8, 5>, k, pl, lds, s, "lstm_fwd5", 512);
-    else rc = launch_persistent2(lstm_fwd5_kernel<3, 2, 8, 5>, k, pl, lds, s, "lstm_fwd5", 512);
+    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<3, 0, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
+    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<3, 1, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
+    else rc = launch_persistent2(lstm_fwd5_kernel<3, 2, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
     return rc;
   }
   // H = 512: 8 waves x 2 k-steps instead of 4 x 4.  The MFMA phase is pipe-bound either way (192 MFMAs per workgroup and step on 4
@@ -1212,9 +1240,9 @@ int lstm5_fwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
     const size_t lds = (size_t)2 * 8 * 4 * 64 * 16 + 32 + 16 + 16 * 16 * 4;
 #define L58(N)                                                                                                       \
     do {                                                                                                             \
-      if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0, 8, 4>, k, pl, lds, s, "lstm_fwd5", 512);      \
-      else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1, 8, 4>, k, pl, lds, s, "lstm_fwd5", 512);  \
-      else rc = launch_persistent2(lstm_fwd5_kernel<N, 2, 8, 4>, k, pl, lds, s, "lstm_fwd5", 512);                   \
+      if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);      \
+      else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);  \
+      else rc = launch_persistent2(lstm_fwd5_kernel<N, 2, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);                   \
     } while (0)
     if (k.Kp == 768) L58(3);
     else if (k.Kp == 1024) L58(4);
@@ -1226,9 +1254,9 @@ int lstm5_fwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
   const size_t lds = (size_t)2 * 4 * 4 * 64 * 16 + 32 + 16 + 16 * 16 * 4;
 #define L5(N)                                                                                              \
   do {                                                                                                     \
-    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0>, k, pl, lds, s, "lstm_fwd5");      \
-    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1>, k, pl, lds, s, "lstm_fwd5");  \
-    else rc = launch_persistent2(lstm_fwd5_kernel<N, 2>, k, pl, lds, s, "lstm_fwd5");                      \
+    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");      \
+    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");  \
+    else rc = launch_persistent2(lstm_fwd5_kernel<N, 2, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");                      \
   } while (0)
   if (nks == 1) L5(1);
   else if (nks == 2) L5(2);
@@ -1239,7 +1267,8 @@ int lstm5_fwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
   return rc;
 }
 
-int lstm5_bwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s) {
+template <bool F16>
+static int bwd_launch_t(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s) {
   LstmK k = k_in;
   // one-barrier form: c2 7.83 -> 7.55 ms of backward recurrences per step with 8 x 64 cycles, c3 13.4 -> 13.1; 12 and more lose again
   const int env_p = env_pause("RNNT_LSTM_BWD_PAUSE");
@@ -1248,16 +1277,16 @@ int lstm5_bwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
   int rc = RNNT_ERR_UNSUPPORTED;
 #define B5Q(NM, C, ...)                                                                               \
   do {                                                                                                \
-    if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5_kernel<NM, 1, C, ##__VA_ARGS__>, k, pl, lds, s, "lstm_bwd5", threads);       \
-    else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5_kernel<NM, 2, C, ##__VA_ARGS__>, k, pl, lds, s, "lstm_bwd5", threads);  \
-    else rc = launch_persistent2(lstm_bwd5_kernel<NM, 4, C, ##__VA_ARGS__>, k, pl, lds, s, "lstm_bwd5", threads);                  \
+    if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5_kernel<NM, 1, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);       \
+    else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5_kernel<NM, 2, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);  \
+    else rc = launch_persistent2(lstm_bwd5_kernel<NM, 4, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);                  \
   } while (0)
   if (pl.MB == 5) {   // H = 640: 80 own gate columns (3 k-steps), 48 output blocks over 8 waves
     const int threads = 512;
     const size_t lds = (size_t)512 * 16 + 16 * (32 * 3 + 4) * 4 + 32 * 4 + 32 + 16;
-    if (cell == RNNT_CELL_LSTM) B5Q(6, 0, 8, 5);
-    else if (cell == RNNT_CELL_GRU) B5Q(6, 1, 8, 5);
-    else B5Q(6, 2, 8, 5);
+    if (cell == RNNT_CELL_LSTM) B5Q(6, 0, 8, 5, 32);
+    else if (cell == RNNT_CELL_GRU) B5Q(6, 1, 8, 5, 32);
+    else B5Q(6, 2, 8, 5, 32);
     return rc;
   }
   // (H = 512 with 8 waves x 4 output blocks: the MFMA + publication phase drops from 1 961 to 1 432 cycles but the wait for the
@@ -1291,19 +1320,19 @@ int lstm5_bwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
     const size_t lds = (size_t)2 * 2 * 16 * (32 * 2 + 8) * 2 + 32 * 4 + 32 + 16;
 #define B5F(NM)                                                                                                   \
     do {                                                                                                          \
-      if (cell == RNNT_CELL_LSTM) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 0>, k, pl, lds, s, "lstm_bwd5f", threads);       \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 0>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 0>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
-      else if (cell == RNNT_CELL_GRU) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 1>, k, pl, lds, s, "lstm_bwd5f", threads);  \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 1>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 1>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
-      else { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 2>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 2>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 2>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
+      if (cell == RNNT_CELL_LSTM) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);       \
+        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
+        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
+      else if (cell == RNNT_CELL_GRU) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);  \
+        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
+        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
+      else { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
+        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
+        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
     } while (0)
     if (nks == 4 && !getenv("RNNT_LSTM_BWD5F_4W")) {   // H = 512: 8 waves x 4 output blocks (two waves per SIMD keep the MFMA pipe busy; one wave issues a
       const int threads8 = 512;                         // v_mfma_f32_16x16x32_f16 only every 20-25 cycles), waves 4..7 share the MFMA + publication phase only
-#define B5F8(BQV, C) rc = launch_persistent2(lstm_bwd5f_kernel<4, BQV, C, 8>, k, pl, lds, s, "lstm_bwd5f", threads8)
+#define B5F8(BQV, C) rc = launch_persistent2(lstm_bwd5f_kernel<4, BQV, C, 8, F16>, k, pl, lds, s, "lstm_bwd5f", threads8)
       if (cell == RNNT_CELL_LSTM) { if (pl.BQ == 1) B5F8(1, 0); else if (pl.BQ == 2) B5F8(2, 0); else B5F8(4, 0); }
       else if (cell == RNNT_CELL_GRU) { if (pl.BQ == 1) B5F8(1, 1); else if (pl.BQ == 2) B5F8(2, 1); else B5F8(4, 1); }
       else { if (pl.BQ == 1) B5F8(1, 2); else if (pl.BQ == 2) B5F8(2, 2); else B5F8(4, 2); }
@@ -1322,9 +1351,9 @@ int lstm5_bwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
   const size_t lds = (size_t)256 * 16 + 16 * (32 * 2 + 4) * 4 + 32 * 4 + 32 + 16;
 #define B5(NM)                                       \
   do {                                               \
-    if (cell == RNNT_CELL_LSTM) B5Q(NM, 0);          \
-    else if (cell == RNNT_CELL_GRU) B5Q(NM, 1);      \
-    else B5Q(NM, 2);                                 \
+    if (cell == RNNT_CELL_LSTM) B5Q(NM, 0, 4, 4, 32);          \
+    else if (cell == RNNT_CELL_GRU) B5Q(NM, 1, 4, 4, 32);      \
+    else B5Q(NM, 2, 4, 4, 32);                                 \
   } while (0)
   if (nks == 1) B5(2);
   else if (nks == 2) B5(4);
@@ -1334,6 +1363,14 @@ int lstm5_bwd_launch(const LstmK& k_in, const Plan2& pl, int cell, hipStream_t s
 #undef B5
 #undef B5Q
   return rc;
+}
+
+int lstm5_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s, bool f16) {
+  return f16 ? fwd_launch_t<true>(k, pl, cell, s) : fwd_launch_t<false>(k, pl, cell, s);
+}
+
+int lstm5_bwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s, bool f16) {
+  return f16 ? bwd_launch_t<true>(k, pl, cell, s) : bwd_launch_t<false>(k, pl, cell, s);
 }
 
 }  // namespace rnnt

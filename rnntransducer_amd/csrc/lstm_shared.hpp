@@ -53,8 +53,9 @@ struct Plan2 {
 
 // v5 recurrences (lstm5.hip)
 bool lstm5_supported(int T, int B, int H, int D, int cell);
-int lstm5_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
-int lstm5_bwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
+// f16: the one-product forms (hi.hi only, RNNT_PRECISION_F16); the exchange protocol is the same in both modes
+int lstm5_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s, bool f16 = false);
+int lstm5_bwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s, bool f16 = false);
 
 namespace {
 

@@ -45,6 +45,12 @@ class RNNTransducer(_Base):
         self.blank_token_id = int(blank)
         prednet_params["pad_token_id"] = self.blank_token_id  # model.py:26
         self.jointnet = JointNet(dict(transnet_params), prednet_params, **jointnet_params)
+        # Opt-in compute mode of the recurrent layers (include/rnnt_hip.h, RNNT_PRECISION_F16).  An explicit choice: NOT derived from
+        # args.precision (reference checkpoints carry precision=16 in their saved args) nor from autocast, which changes nothing here.
+        cp = getattr(args, "compute_precision", "fp32")
+        if cp not in ("fp32", "fp16"):
+            raise ValueError(f"args.compute_precision must be 'fp32' or 'fp16', got {cp!r}")
+        self.jointnet.set_compute_precision(cp)
         # model.py:28-39 picks torchaudio (precision 16) or warp-transducer; both are this one HIP module here
         self.rnnt_loss = RNNTLoss(blank=self.blank_token_id, reduction="mean")
 

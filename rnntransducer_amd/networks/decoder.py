@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from ..ops import EmbeddingFn, LinearFn, prednet_step
 from .encoder import HipLinear, lengths_to_device
-from .rnn import RNN_CELLS
+from .rnn import RNN_CELLS, HipLSTM
 
 
 class HipEmbedding(nn.Embedding):
@@ -40,6 +40,13 @@ class TextPredNet(nn.Module):
         """(B,U1) int64 tokens + int32 device lengths -> (U1,B,O) time-major."""
         emb = self.embedding(inputs.transpose(0, 1).contiguous())  # (U1,B,H)
         return self.out_proj(self.rnn(emb, lens_dev))
+
+    def set_compute_precision(self, p: str):
+        """"fp32" | "fp16" for every recurrent stack below this module (HipLSTM.compute_precision); returns self."""
+        for m in self.modules():
+            if isinstance(m, HipLSTM):
+                m.compute_precision = p
+        return self
 
     def forward(self, inputs: torch.Tensor, input_lengths=None, prev_hidden_state=None):
         """Training branch (input_lengths given): (B,U1) tokens -> ((B,U1,O), hidden_states) with hidden_states what the

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import LinearFn
-from .rnn import RNN_CELLS
+from .rnn import RNN_CELLS, HipLSTM
 
 
 def lengths_to_device(lengths: Union[Sequence[int], torch.Tensor], device) -> torch.Tensor:
@@ -48,6 +48,13 @@ class AudioTransNet(nn.Module):
         (what the fused joint+loss consumes)."""
         x_tm = inputs.transpose(0, 1).contiguous()
         return self.out_proj(self.rnn(x_tm, lens_dev))
+
+    def set_compute_precision(self, p: str):
+        """"fp32" | "fp16" for every recurrent stack below this module (HipLSTM.compute_precision); returns self."""
+        for m in self.modules():
+            if isinstance(m, HipLSTM):
+                m.compute_precision = p
+        return self
 
     def forward(self, inputs: torch.Tensor, inputs_lengths) -> torch.Tensor:
         """Reference surface (encoder.py:78): (B,T,F), lengths -> (B,T,O)."""

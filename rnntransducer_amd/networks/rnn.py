@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import LstmStackFn
+from ..ops import LstmStackFn, check_compute_precision
 
 
 class HipLSTM(nn.Module):
@@ -35,6 +35,32 @@ class HipLSTM(nn.Module):
                 self.register_parameter(f"bias_hh_l{layer}{suffix}", nn.Parameter(torch.empty(G * hidden_size)))
         self.reset_parameters()
         self._step = 0
+        self.compute_precision = "fp32"
+
+    @property
+    def compute_precision(self) -> str:
+        """"fp32" (default) or "fp16": the arithmetic of the recurrences and of the big products inside each layer
+        (include/rnnt_hip.h, RNNT_PRECISION_F16 — f16 operand rounding, fp32 accumulation, no loss scaling needed).  A plain
+        attribute: not a parameter or buffer, so state_dict keys and checkpoints are the same in both modes.  Shapes without the
+        one-product forms compute fp32 whatever is asked: see effective_precision()."""
+        return self._compute_precision
+
+    @compute_precision.setter
+    def compute_precision(self, p: str) -> None:
+        self._compute_precision = check_compute_precision(p)
+
+    def effective_precision(self, T: int, B: int) -> str:
+        """What a forward / backward over a (T, B) batch really runs: "fp16" if every layer (and every batch slice) takes the
+        one-product forms (rnnt_hip_lstm_takes_f16), "fp32" if none does or compute_precision is "fp32", "mixed" otherwise."""
+        if self._compute_precision == "fp32":
+            return "fp32"
+        D = 2 if self.bidirectional else 1
+        cap = _lib.lib().rnnt_hip_lstm_max_batch(self.hidden_size, D, self.CELL)
+        slices = {min(cap, B - b0) for b0 in range(0, B, cap)} if 0 < cap < B else {B}
+        takes = [bool(_lib.lib().rnnt_hip_lstm_takes_f16(T, b, self.input_size if layer == 0 else D * self.hidden_size,
+                                                          self.hidden_size, D, self.CELL))
+                 for layer in range(self.num_layers) for b in slices]
+        return "fp16" if all(takes) else ("fp32" if not any(takes) else "mixed")
 
     def reset_parameters(self) -> None:
         stdv = 1.0 / math.sqrt(self.hidden_size)
@@ -63,7 +89,7 @@ class HipLSTM(nn.Module):
             raise _lib.RnntHipError(f"hidden_size={self.hidden_size} does not fit the persistent recurrence kernels")
         if B <= cap:
             return LstmStackFn.apply(x_tm, lens, self.hidden_size, self.num_layers, self.bidirectional, p, seed, self.CELL,
-                                     want_final, *self.flat_weights())
+                                     want_final, self._compute_precision, *self.flat_weights())
         if isinstance(lens, RaggedPlan):   # the table indexes the whole batch: slices of it run dense
             lens = lens.lens
         # batch rows are independent: run slices of the batch back to back (autograd sums the weight gradients)
@@ -71,7 +97,7 @@ class HipLSTM(nn.Module):
         for b0 in range(0, B, cap):
             outs.append(LstmStackFn.apply(x_tm[:, b0:b0 + cap].contiguous(), lens[b0:b0 + cap].contiguous(), self.hidden_size,
                                           self.num_layers, self.bidirectional, p, seed + 104729 * (b0 + 1), self.CELL,
-                                          want_final, *self.flat_weights()))
+                                          want_final, self._compute_precision, *self.flat_weights()))
         if not want_final:
             return torch.cat(outs, dim=1)
         return tuple(torch.cat([o[i] for o in outs], dim=1) for i in range(3))

@@ -18,6 +18,7 @@ import torch.nn as nn
 from ..ops import JointLogitsFn, JointLossFn, beam_search, greedy_decode
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
+from .rnn import HipLSTM
 
 
 class JointNet(nn.Module):
@@ -30,6 +31,13 @@ class JointNet(nn.Module):
         self.dec_out = prednet_params["output_size"]
         # parameter container only: fc is applied inside the fused kernels (A/C pre-GEMMs), never as one Linear
         self.fc = HipLinear(self.enc_out + self.dec_out, num_classes)
+
+    def set_compute_precision(self, p: str):
+        """"fp32" | "fp16" for every recurrent stack below this module (HipLSTM.compute_precision); returns self."""
+        for m in self.modules():
+            if isinstance(m, HipLSTM):
+                m.compute_precision = p
+        return self
 
     def joint(self, encoder_outputs: torch.Tensor, decoder_outputs: torch.Tensor) -> torch.Tensor:
         """(B,T,O_e), (B,U+1,O_d) -> logits (B,T,U+1,V) (materialising; transducer.py:54-69).  1-D inputs (one encoder frame,

@@ -12,7 +12,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import GEMM_ACCUM, GEMM_GELU_A, GEMM_GELU_B, GEMM_MUL_DGELU, GemmDesc, LstmBwdDesc, LstmDesc, RnntHipError, check
+from ._lib import (GEMM_ACCUM, GEMM_GELU_A, GEMM_GELU_B, GEMM_HP_F16, GEMM_MUL_DGELU, PRECISION_F16, PRECISION_FP32, GemmDesc, LstmBwdDesc,
+                   LstmDesc, RnntHipError, check)
 
 BIG = 1 << 40  # "no second level" divisor for the GEMM row maps
 
@@ -153,8 +154,9 @@ def hp_split(x: torch.Tensor, transpose: bool = False, shift: int = 0, K: Option
 
 
 def gemm_hp(a: HpTensor, b: HpTensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-            accumulate: bool = False, split_k: bool = True) -> torch.Tensor:
-    """C (M, N) [+]= A (M, K) . B (N, K)^T + bias on hp operands."""
+            accumulate: bool = False, split_k: bool = True, f16: bool = False) -> torch.Tensor:
+    """C (M, N) [+]= A (M, K) . B (N, K)^T + bias on hp operands.  f16=True: the one-product form (RNNT_GEMM_HP_F16) — only the hi
+    halves are multiplied (f16 operand rounding, fp32 accumulation)."""
     if a.K != b.K:
         raise ValueError(f"contraction lengths differ: {a.K} vs {b.K}")
     M, N, K = a.rows, b.rows, a.K
@@ -167,15 +169,16 @@ def gemm_hp(a: HpTensor, b: HpTensor, out: Optional[torch.Tensor] = None, bias: 
     nws = _lib.lib().rnnt_hip_gemm_hp_workspace_bytes(M, N, K) if split_k else 0
     ws = torch.empty(nws, device=out.device, dtype=torch.uint8) if nws else None
     check(_lib.lib().rnnt_hip_gemm_hp(_addr(a.planes), _addr(a.amax), _addr(b.planes), _addr(b.amax), M, N, K, _addr(out), N, _addr(bias),
-                                      GEMM_ACCUM if accumulate else 0, _addr(ws), nws, _stream()), "rnnt_hip_gemm_hp")
+                                      (GEMM_ACCUM if accumulate else 0) | (GEMM_HP_F16 if f16 else 0), _addr(ws), nws, _stream()),
+          "rnnt_hip_gemm_hp")
     return out
 
 
-def gemm_hp_grouped(pairs, outs=None, accumulate: bool = False, xcd_skip: int = 0, check: bool = False):
+def gemm_hp_grouped(pairs, outs=None, accumulate: bool = False, xcd_skip: int = 0, check: bool = False, f16: bool = False):
     """[C_i (M_i, N_i) [+]= A_i . B_i^T] for up to 4 (A, B) pairs of hp operands in ONE queue-driven launch; `xcd_skip`: bit mask of
     XCDs whose workgroups leave at once (the launch then runs on the other XCDs only).  `check`: read back (synchronising) the
     launch's self-check — word 9 of the workspace is 1 when units were left undone because the mask named XCDs the device does not
-    expose (include/rnnt_hip.h) — and raise RnntHipError in that case."""
+    expose (include/rnnt_hip.h) — and raise RnntHipError in that case.  f16=True: every product in the one-product form (as gemm_hp)."""
     n = len(pairs)
     if not 1 <= n <= 4:
         raise ValueError("1..4 products per grouped launch")
@@ -189,7 +192,7 @@ def gemm_hp_grouped(pairs, outs=None, accumulate: bool = False, xcd_skip: int = 
             raise ValueError(f"out[{i}] must be a contiguous float32 ({a.rows}, {b.rows}) tensor")
         pr[i].A, pr[i].a_amax, pr[i].B, pr[i].b_amax = _addr(a.planes), _addr(a.amax), _addr(b.planes), _addr(b.amax)
         pr[i].M, pr[i].N, pr[i].K, pr[i].C, pr[i].ldc = a.rows, b.rows, a.K, _addr(out), b.rows
-        pr[i].flags = GEMM_ACCUM if accumulate else 0
+        pr[i].flags = (GEMM_ACCUM if accumulate else 0) | (GEMM_HP_F16 if f16 else 0)
         res.append(out)
     nws = _lib.lib().rnnt_hip_gemm_hp_grouped_workspace_bytes(pr, n)
     ws = torch.empty(nws, device=res[0].device, dtype=torch.uint8)
@@ -361,14 +364,30 @@ def _fill_lstm_desc(d: LstmDesc, T, B, I, H, D, lens, x, weights, y, y_drop, p, 
     d.status = _addr(lstm_status_word(ws.device))
 
 
+COMPUTE_PRECISIONS = {"fp32": PRECISION_FP32, "fp16": PRECISION_F16}
+
+
+def check_compute_precision(p) -> str:
+    if not isinstance(p, str) or p not in COMPUTE_PRECISIONS:
+        raise ValueError(f"compute_precision must be one of {sorted(COMPUTE_PRECISIONS)}, got {p!r}")
+    return p
+
+
 class LstmStackFn(torch.autograd.Function):
     """x (T,B,I) time-major, lens (B) int32 on device -> y (T,B,D*H); zero rows for t >= lens[b].
     `cell`: 0 LSTM, 1 GRU, 2 tanh-RNN, 3 ReLU-RNN (the reference's supported_rnns, encoder.py:48-52).
     `want_final`: also return (h_n, c_n) — (L*D, B, H) states after each sequence's own last step, what torch's RNN modules
-    return next to the output (decoder.py:115); not differentiable here (the reference never differentiates through them)."""
+    return next to the output (decoder.py:115); not differentiable here (the reference never differentiates through them).
+    Compute precision: an optional string "fp32" (default) | "fp16" in front of the weight tensors (autograd.Function.apply takes
+    no keywords) selects rnnt_hip_lstm_fwd_ex / _bwd_ex's mode; the backward uses the mode its forward ran."""
 
     @staticmethod
     def forward(ctx, x, lens, hidden, num_layers, bidirectional, dropout_p, seed, cell, want_final, *weights):
+        precision = "fp32"
+        ctx.has_precision_arg = bool(weights) and isinstance(weights[0], str)
+        if ctx.has_precision_arg:
+            precision, weights = check_compute_precision(weights[0]), weights[1:]
+        prec = COMPUTE_PRECISIONS[precision]
         plan = None
         if isinstance(lens, RaggedPlan):   # ragged batch with its valid-frame table: the big products and the recurrences skip padding
             plan, lens = lens, lens.lens
@@ -418,10 +437,11 @@ class LstmStackFn(torch.autograd.Function):
             y_drop = torch.empty_like(y) if p > 0 else None
             d = LstmDesc()
             _fill_lstm_desc(d, T, B, I, H, D, lens, cur, wl, y, y_drop, p, seed + layer, gates, cst, ws, cell, plan=plan)
-            check(_lib.lib().rnnt_hip_lstm_fwd(C.byref(d), _stream()), "rnnt_hip_lstm_fwd")
+            check(_lib.lib().rnnt_hip_lstm_fwd_ex(C.byref(d), prec, _stream()), "rnnt_hip_lstm_fwd_ex")
             saved.append((cur, y, gates, cst, p))
             cur = y_drop if p > 0 else y
         ctx.meta = (T, B, H, D, num_layers, seed, cell)
+        ctx.prec = prec
         ctx.lens = lens
         ctx.plan = plan
         ctx.ws = ws
@@ -451,6 +471,7 @@ class LstmStackFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_unused):
         T, B, H, D, L, seed, cell = ctx.meta
+        prec = ctx.prec   # the forward's mode
         dy = _f32c(dy, "dy")
         weights = ctx.weights
         grads: List[Optional[torch.Tensor]] = [None] * len(weights)
@@ -499,16 +520,16 @@ class LstmStackFn(torch.autograd.Function):
                 bd.db_hh[k] = _addr(db_hh) if cell == 1 else None
                 grads[base], grads[base + 1], grads[base + 2], grads[base + 3] = dw_ih, dw_hh, db, db_hh
             if not overlap:
-                check(_lib.lib().rnnt_hip_lstm_bwd(C.byref(bd), main.cuda_stream), "rnnt_hip_lstm_bwd")
+                check(_lib.lib().rnnt_hip_lstm_bwd_ex(C.byref(bd), prec, main.cuda_stream), "rnnt_hip_lstm_bwd_ex")
                 dy = dx
                 continue
             if layer + 2 in side_done:   # this layer's workspace was last read by phase 2 of layer + 2
                 main.wait_event(side_done[layer + 2])
             bd.phase = 1
-            check(_lib.lib().rnnt_hip_lstm_bwd(C.byref(bd), main.cuda_stream), "rnnt_hip_lstm_bwd (recurrence + dx)")
+            check(_lib.lib().rnnt_hip_lstm_bwd_ex(C.byref(bd), prec, main.cuda_stream), "rnnt_hip_lstm_bwd_ex (recurrence + dx)")
             side.wait_event(main.record_event())
             bd.phase, bd.beside_recurrence = 2, 1 if layer > 0 else 0
-            check(_lib.lib().rnnt_hip_lstm_bwd(C.byref(bd), side.cuda_stream), "rnnt_hip_lstm_bwd (weight gradients)")
+            check(_lib.lib().rnnt_hip_lstm_bwd_ex(C.byref(bd), prec, side.cuda_stream), "rnnt_hip_lstm_bwd_ex (weight gradients)")
             side_done[layer] = side.record_event()
             keep.append((aux, dy, dx))
             dy = dx
@@ -516,7 +537,8 @@ class LstmStackFn(torch.autograd.Function):
             main.wait_stream(side)   # everything below (autograd's accumulation, the optimizer, frees) is ordered after phase 2
         del keep
         ctx.saved = None  # release the stash
-        return (dx if ctx.x_needs_grad else None, None, None, None, None, None, None, None, None, *grads)
+        return (dx if ctx.x_needs_grad else None, None, None, None, None, None, None, None, None,
+                *((None,) if ctx.has_precision_arg else ()), *grads)
 
 
 _SIDE_STREAMS: dict = {}
