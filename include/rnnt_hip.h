@@ -213,8 +213,8 @@ typedef struct rnnt_lstm_desc {
                      * (input projection, dX, dW_ih, dW_hh) then run over n_rows instead of T*B rows — operand tiles are gathered / results
                      * scattered through this table — and every sync group of the recurrence runs max(lens of its rows) steps instead of T
                      * (reverse direction: from that frame down).  Rows that are not listed are then NOT written in gates / cst / y_drop,
-                     * and y keeps what the caller put there: hand in y zero-filled (frames t >= lens[b] must read 0).  Results on valid
-                     * frames do not depend on it.  Honoured by the default kernels (v5 recurrences + half-pair products); other shapes
+                     * and y keeps what the caller put there: hand in y zero-filled (frames t >= lens[b] must read 0).  dx of such rows is
+                     * written as 0 by the backward call, as without the table.  Results on valid frames do not depend on it.  Honoured by the default kernels (v5 recurrences + half-pair products); other shapes
                      * ignore it and compute all T*B rows.  NULL: all rows.  Same table for the forward and the backward call. */
   int32_t n_rows;   /* entries of row_idx (= sum of lens); ignored when row_idx is NULL */
 } rnnt_lstm_desc;
@@ -297,7 +297,10 @@ int rnnt_hip_lstm_debug_read(const void* workspace, int32_t T, int32_t B, int32_
  * rnnt_hip_gemm_f32 + RNNT_GEMM_GELU_A) and fc.bias (V).  A(b,t,v) = A[b*a_sb + t*a_st + v],
  * C(b,u,v) = C[b*c_sb + u*c_su + v]  (so batch-major and time-major buffers both work, no copy).
  * Outputs: nll (B) = -log P(y|x) per utterance; dA, dC (same strides as A, C) = d(sum_b gscale*nll_b)/dA,dC.
- *   labels (B,U) int32 (U = U1-1), t_lens (B) int32 in [1,T], u_lens (B) int32 in [0,U].
+ *   labels (B,U) int32 (U = U1-1), t_lens (B) int32 in [1,T], u_lens (B) int32 in [0,U].  U1 <= 512 for every V, forward and
+ *   backward alike.  Lengths are not checked on the device.  One exception to t_lens >= 1 is defined: t_lens[b] = 0 (an utterance
+ *   without frames has no alignment) gives nll[b] = +inf and exact zeros in row b of dA and dC, and leaves every other row bitwise
+ *   as a batch without row b computes it.
  * ---------------------------------------------------------------------------------------------- */
 size_t rnnt_hip_joint_loss_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V);
 int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,

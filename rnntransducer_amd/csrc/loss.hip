@@ -519,9 +519,13 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
 // LDS holds the per-cell scalars only (read as broadcasts).  The blank / label corrections leave the inner loop: the one wave whose
 // 64 entries contain the blank (a label) subtracts them in a second, exp-free pass.  Arithmetic per element: two adds, v_exp_f32
 // (2^x on operands pre-multiplied by log2 e), one multiply, two accumulations.
-// grid (ceil(T/32), ceil(V / (64 NW)), B), 64 NW threads; dynamic LDS: cells[TT][U1] (CellS, lse in the log2 domain) | ys[U1]
+// grid (ceil(T/32), ceil(V / (64 NW)), B), 64 NW threads; dynamic LDS: cells[TT][UL] (CellS, lse in the log2 domain) | ys[U1]
+// CHUNKED = false: UL = U1, the whole table at once (every U+1 whose table fits in LDS: 516 (U+1) bytes <= 160 KiB, U+1 <= 317).
+// CHUNKED = true : the table holds UL (a multiple of UC) label positions at a time and is rebuilt per chunk; accA keeps accumulating
+// in registers across the chunks and the dC rows are written per 8-row block as before, so the arithmetic (and its order) is the
+// unchunked kernel's.  Every wave stays to the end (the chunks' barriers), the ones beyond the vocabulary only help build the table.
 // ------------------------------------------------------------------------------------------------
-template <int NW>
+template <int NW, bool CHUNKED>
 __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                             const float* __restrict__ bias, const int* __restrict__ labels,
                                                             const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -530,11 +534,12 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
                                                             const double* __restrict__ ll, int T, int U1, int V, int blank,
                                                             long a_sb, long a_st, long c_sb, long c_su, float gscale_in,
                                                             const float* __restrict__ gvec, int gvec_stride,
-                                                            float* __restrict__ dA, float* __restrict__ dCp) {
+                                                            float* __restrict__ dA, float* __restrict__ dCp, int ul) {
+  const int UL = CHUNKED ? ul : U1;                      // label positions per table
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float2* wl = reinterpret_cast<float2*>(smem);          // [TT][U1] {occupancy w, row lse * log2 e}: what the inner loop reads (8-byte broadcasts)
-  float2* cbe = wl + TT * U1;                            // [TT][U1] {P(blank transition), P(label transition)}: the correction pass
-  int* ys = reinterpret_cast<int*>(cbe + TT * U1);
+  float2* wl = reinterpret_cast<float2*>(smem);          // [TT][UL] {occupancy w, row lse * log2 e}: what the inner loop reads (8-byte broadcasts)
+  float2* cbe = wl + TT * UL;                            // [TT][UL] {P(blank transition), P(label transition)}: the correction pass
+  int* ys = reinterpret_cast<int*>(cbe + TT * UL);       // [U1]
 
   const int b = blockIdx.z, tile = blockIdx.x, t0 = tile * TT, ntiles = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -543,6 +548,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
   const int v = vw0 + lane;
   const bool vok = v < V;
   const int Tb = t_lens[b], Ub = u_lens[b];
+  const int Tbc = max(Tb, 1);                         // t_lens[b] = 0 (no cell): the table's clamped loads stay at frame 0 of the row
   const long rowbase = (long)b * U1 * T;
   const double logZ = ll[b];
   const float gscale = gvec ? gscale_in * gvec[(long)b * gvec_stride] : gscale_in;
@@ -552,96 +558,106 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
   const int nf = max(0, min(TT, Tb - t0));            // valid frames of this tile (uniform)
 
   for (int i = tid; i < U1; i += 64 * NW) ys[i] = (i < U1 - 1) ? labels[(long)b * (U1 - 1) + i] : -1;
-  // the cell table: four cells per thread and round, every load unconditional (indices clamped into the lattice, results dropped by
-  // selects) so that the 4 x 8 loads of a round are in flight together; consecutive threads -> consecutive frames (coalesced rows)
   const float bias_blank = bias[blank];
-  for (int i0 = tid; i0 < TT * U1; i0 += 64 * NW * 4) {
-    CellS c[4];
-    bool in[4];
-    int dst[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = i0 + q * 64 * NW;
-      const int u = min(i / TT, U1 - 1), tl = i % TT, t = t0 + tl;
-      in[q] = i < TT * U1 && t < Tb && u <= Ub;
-      dst[q] = i < TT * U1 ? tl * U1 + u : -1;
-      const int tc = min(t, Tb - 1), uc = min(u, Ub);   // a cell of the lattice whatever (t, u) is
-      const float zb = Ab[(long)tc * a_st + blank] + Cb[(long)uc * c_su + blank] + bias_blank;
-      c[q] = cell_scalars(blk, emit, alpha, beta, rowbase, T, tc, uc, Tb, Ub, logZ, zb);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (dst[q] >= 0) {
-        // cells outside the utterance's lattice: w = 0 and an lse that sends 2^(x - lse) to 0, so the inner loop needs no per-cell test
-        wl[dst[q]] = in[q] ? make_float2(c[q].w, c[q].lse * LOG2E_F) : make_float2(0.f, 1e30f);
-        cbe[dst[q]] = in[q] ? make_float2(c[q].cb, c[q].ce) : make_float2(0.f, 0.f);
-      }
-    }
-  }
-  __syncthreads();
-  if (vw0 >= V) return;   // (whole wave beyond the vocabulary: nothing to do, and no barrier follows)
-
   float a2[TT], accA[TT];
-#pragma unroll
-  for (int tl = 0; tl < TT; ++tl) {
-    a2[tl] = (tl < nf && vok) ? Ab[(long)(t0 + tl) * a_st + v] * LOG2E_F : 0.f;
-    accA[tl] = 0.f;
-  }
-  const float bias_v = vok ? bias[v] : 0.f;
   const bool has_blank = blank >= vw0 && blank < vw0 + 64;   // uniform over the wave
   constexpr int UC = 8;
-  for (int u0 = 0; u0 < U1; u0 += UC) {
-    float accC[UC], cs2[UC];
+  for (int uc0 = 0; uc0 < U1; uc0 += UL) {
+    const int nrow = min(UL, U1 - uc0);                  // label positions uc0 .. uc0 + nrow - 1 in this table
+    if (uc0 > 0) __syncthreads();                        // every wave is done with the previous chunk's table
+    // the cell table: four cells per thread and round, every load unconditional (indices clamped into the lattice, results dropped by
+    // selects) so that the 4 x 8 loads of a round are in flight together; consecutive threads -> consecutive frames (coalesced rows)
+    for (int i0 = tid; i0 < TT * nrow; i0 += 64 * NW * 4) {
+      CellS c[4];
+      bool in[4];
+      int dst[4];
 #pragma unroll
-    for (int j = 0; j < UC; ++j) {
-      const int u = min(u0 + j, U1 - 1);
-      accC[j] = 0.f;
-      cs2[j] = vok ? (Cb[(long)u * c_su + v] + bias_v) * LOG2E_F : 0.f;
+      for (int q = 0; q < 4; ++q) {
+        const int i = i0 + q * 64 * NW;
+        const int u = min(uc0 + i / TT, U1 - 1), tl = i % TT, t = t0 + tl;
+        in[q] = i < TT * nrow && t < Tb && u <= Ub;
+        dst[q] = i < TT * nrow ? tl * UL + (u - uc0) : -1;
+        const int tc = min(t, Tbc - 1), uc = max(min(u, Ub), 0);   // a cell of the lattice whatever (t, u) is (frame 0 of an empty row)
+        const float zb = Ab[(long)tc * a_st + blank] + Cb[(long)uc * c_su + blank] + bias_blank;
+        c[q] = cell_scalars(blk, emit, alpha, beta, rowbase, T, tc, uc, Tbc, Ub, logZ, zb);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (dst[q] >= 0) {
+          // cells outside the utterance's lattice: w = 0 and an lse that sends 2^(x - lse) to 0, so the inner loop needs no per-cell test
+          wl[dst[q]] = in[q] ? make_float2(c[q].w, c[q].lse * LOG2E_F) : make_float2(0.f, 1e30f);
+          cbe[dst[q]] = in[q] ? make_float2(c[q].cb, c[q].ce) : make_float2(0.f, 0.f);
+        }
+      }
     }
-    if (u0 <= Ub) {
-      // branch-free over the whole 32 x 8 block (cells outside the lattice contribute exact zeros; label positions beyond U1 - 1
-      // re-read the last row's table entries, whose sums are not stored): the 256 table reads and v_exp_f32 pipeline freely
+    __syncthreads();
+    if (vw0 >= V) {   // (whole wave beyond the vocabulary: nothing to do; unchunked no barrier follows, chunked it builds the next table)
+      if (CHUNKED) continue;
+      return;
+    }
+
+    if (uc0 == 0) {
 #pragma unroll
       for (int tl = 0; tl < TT; ++tl) {
-#pragma unroll
-        for (int j = 0; j < UC; ++j) {
-          const float2 c = wl[tl * U1 + min(u0 + j, U1 - 1)];
-          // the softmax probability (<= 1: the exponent is z - lse <= 0) times the cell's occupancy
-          const float g = c.x * __builtin_amdgcn_exp2f(a2[tl] + cs2[j] - c.y);
-          accA[tl] += (u0 + j < U1) ? g : 0.f;   // (a -1e30 entry in cs2 instead of this select: hipcc then spilled — 3.3 instead of 2.1 ms)
-          accC[j] += g;
-        }
-        // two frames (16 table reads) per scheduling region: without the fence hipcc hoists all 256 reads of the block to its top
-        // (288 registers: one wave per SIMD; with a register cap: spills), with it 131 registers and three waves per SIMD cover the reads
-        if (tl & 1) __builtin_amdgcn_sched_barrier(0);
+        a2[tl] = (tl < nf && vok) ? Ab[(long)(t0 + tl) * a_st + v] * LOG2E_F : 0.f;
+        accA[tl] = 0.f;
       }
-      // corrections: - P(blank transition) on the blank entry, - P(label transition) on the label's entry
+    }
+    const float bias_v = vok ? bias[v] : 0.f;
+    for (int u0 = uc0; u0 < uc0 + nrow; u0 += UC) {
+      float accC[UC], cs2[UC];
 #pragma unroll
       for (int j = 0; j < UC; ++j) {
-        const int u = u0 + j;
-        if (u <= Ub) {
-          const int y = ys[u];
-          const bool mine = y >= vw0 && y < vw0 + 64;   // uniform
-          if (mine || has_blank) {
+        const int u = min(u0 + j, U1 - 1);
+        accC[j] = 0.f;
+        cs2[j] = vok ? (Cb[(long)u * c_su + v] + bias_v) * LOG2E_F : 0.f;
+      }
+      if (u0 <= Ub) {
+        // branch-free over the whole 32 x 8 block (cells outside the lattice contribute exact zeros; label positions beyond U1 - 1
+        // re-read the last row's table entries, whose sums are not stored): the 256 table reads and v_exp_f32 pipeline freely
 #pragma unroll
-            for (int tl = 0; tl < TT; ++tl) {
-              if (tl < nf) {
-                const float2 c = cbe[tl * U1 + u];
-                const float corr = (v == blank ? c.x : 0.f) + (v == y ? c.y : 0.f);
-                accA[tl] -= corr;
-                accC[j] -= corr;
+        for (int tl = 0; tl < TT; ++tl) {
+#pragma unroll
+          for (int j = 0; j < UC; ++j) {
+            const float2 c = wl[tl * UL + (min(u0 + j, U1 - 1) - uc0)];
+            // the softmax probability (<= 1: the exponent is z - lse <= 0) times the cell's occupancy
+            const float g = c.x * __builtin_amdgcn_exp2f(a2[tl] + cs2[j] - c.y);
+            accA[tl] += (u0 + j < U1) ? g : 0.f;   // (a -1e30 entry in cs2 instead of this select: hipcc then spilled — 3.3 instead of 2.1 ms)
+            accC[j] += g;
+          }
+          // two frames (16 table reads) per scheduling region: without the fence hipcc hoists all 256 reads of the block to its top
+          // (288 registers: one wave per SIMD; with a register cap: spills), with it 131 registers and three waves per SIMD cover the reads
+          if (tl & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        // corrections: - P(blank transition) on the blank entry, - P(label transition) on the label's entry
+#pragma unroll
+        for (int j = 0; j < UC; ++j) {
+          const int u = u0 + j;
+          if (u <= Ub) {
+            const int y = ys[u];
+            const bool mine = y >= vw0 && y < vw0 + 64;   // uniform
+            if (mine || has_blank) {
+#pragma unroll
+              for (int tl = 0; tl < TT; ++tl) {
+                if (tl < nf) {
+                  const float2 c = cbe[tl * UL + (u - uc0)];
+                  const float corr = (v == blank ? c.x : 0.f) + (v == y ? c.y : 0.f);
+                  accA[tl] -= corr;
+                  accC[j] -= corr;
+                }
               }
             }
           }
         }
       }
-    }
-    if (vok) {
+      if (vok) {
 #pragma unroll
-      for (int j = 0; j < UC; ++j)
-        if (u0 + j < U1) dCtile[(long)(u0 + j) * V + v] = accC[j];   // rows beyond Ub: zeros (reduce_dc_kernel sums every row)
+        for (int j = 0; j < UC; ++j)
+          if (u0 + j < U1) dCtile[(long)(u0 + j) * V + v] = accC[j];   // rows beyond Ub: zeros (reduce_dc_kernel sums every row)
+      }
     }
   }
+  if (vw0 >= V) return;
   if (vok) {
 #pragma unroll
     for (int tl = 0; tl < TT; ++tl)
@@ -793,21 +809,35 @@ static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_
   const int ntiles = (int)ceil_div(T, TT);
   const double cells = (double)B * T * U1;
   ProfScope prof(RNNT_K_LATGRAD, 4.0 * 2.0 * ((double)B * T * V + (double)B * U1 * V) + 24.0 * cells, s);
-  if (large_vocab(V)) {   // a lane per vocabulary entry, the vocabulary a grid dimension (grad_sepv_kernel)
-    const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 4;
-    RNNT_CHECK_ARG(lds <= 160 * 1024, "joint_loss: U+1 = %d needs %zu B of LDS (> 160 KiB)", U1, lds);
+  constexpr size_t LDS_MAX = 160 * 1024;
+  const size_t lds_sep = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 64 * 4 * 2 + (size_t)U1 * 4;   // 1028 (U+1): U+1 <= 159
+  // a lane per vocabulary entry, the vocabulary a grid dimension (grad_sepv_kernel): V >= 256, and every U+1 whose grad_sep_kernel
+  // table does not fit in LDS (any V)
+  if (large_vocab(V) || lds_sep > LDS_MAX) {
     constexpr int NW = 4;   // 256 vocabulary entries per workgroup (8 waves per workgroup measured slower: 5.2 vs 4.6 ms at config 5)
-    if (lds > 64 * 1024)
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(grad_sepv_kernel<NW>, dim3(ntiles, (unsigned)ceil_div(V, 64 * NW), B), dim3(64 * NW), lds, s, A, C, bias, labels, t_lens,
-                       u_lens, w.blk, w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec,
-                       gvec_stride, dA, w.dCp);
+    const dim3 grid(ntiles, (unsigned)ceil_div(V, 64 * NW), B), block(64 * NW);
+    const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
+    if (lds <= LDS_MAX) {
+      if (lds > 64 * 1024)
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, false>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+                         w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
+                         w.dCp, U1);
+    } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
+      const size_t per_row = (size_t)TT * sizeof(CellS);
+      const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
+      const int nchunks = (int)ceil_div(U1, ul_max);
+      const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
+      const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, true>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+                         w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
+                         w.dCp, ul);
+    }
   } else {
-    const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 64 * 4 * 2 + (size_t)U1 * 4;
-    RNNT_CHECK_ARG(lds <= 160 * 1024, "joint_loss: U+1 = %d needs %zu B of LDS (> 160 KiB)", U1, lds);
-    if (lds > 64 * 1024)
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(grad_sep_kernel, dim3(ntiles, B), dim3(256), lds, s, A, C, bias, labels, t_lens, u_lens, w.blk,
+    if (lds_sep > 64 * 1024)
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
+    hipLaunchKernelGGL(grad_sep_kernel, dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
                        w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp);
   }
   RNNT_CHECK_LAUNCH();
@@ -865,6 +895,7 @@ extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_s
                  "joint_loss_bwd: bad dims / null pointer");
   RNNT_CHECK_ARG(A && C && bias && dA && dC, "joint_loss_bwd: null A/C/bias/dA/dC");
   RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "joint_loss_bwd: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
+  RNNT_CHECK_ARG(U1 <= 64 * 8, "joint_loss_bwd: U+1 = %d exceeds the 512 label positions of the forward", U1);
   const LossWs w = carve(workspace, B, T, U1, V, true);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_loss_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, gvec_stride, dA,

@@ -1264,6 +1264,19 @@ __global__ void permute_w_kernel(const float* __restrict__ w0, const float* __re
   const float* w = d ? w1 : w0;
   out[d * per + idx] = (r & 3) < ngate ? w[(long)((r & 3) * H + (r >> 2)) * I + k] : 0.f;
 }
+// dX rows of padded frames (t >= lens[b]) under a ragged plan (rnnt_lstm_desc.row_idx): the products skip them (row-gathered dX) or
+// read dG rows the recurrence never wrote (dense dX), so they are set to exact zeros here, what the unplanned call leaves there.
+// One wavefront per time-major row, grid-stride; rows of valid frames are not touched.
+__global__ void __launch_bounds__(256) zero_padded_rows_kernel(float* __restrict__ x, const int* __restrict__ lens, int T, int B, int I) {
+  const int lane = threadIdx.x & 63;
+  const long nrow = (long)T * B;
+  const long nw = ((long)gridDim.x * blockDim.x) >> 6;
+  for (long r = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < nrow; r += nw) {
+    if ((int)(r / B) < lens[r % B]) continue;
+    float* row = x + r * I;
+    for (int i = lane; i < I; i += 64) row[i] = 0.f;
+  }
+}
 // inverse for gradients: dw[d][(g*H + j)*I + k] = in[(d*4H + 4j+g)*I + k]
 __global__ void unpermute_w_kernel(const float* __restrict__ in, int H, int I, long in_dir_stride, int ngate,
                                    float* __restrict__ o0, float* __restrict__ o1, int accumulate, float* __restrict__ p0 = nullptr,
@@ -2095,6 +2108,11 @@ static int lstm_bwd_impl(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void*
       g.B = w.wp; g.b_sn = 1; g.b_sk = I;
       g.C = bd->dx; g.c_div = 1; g.c_so = I; g.c_si = 0;
       if ((rc = rnnt_hip_gemm_f32(&g, s))) return rc;
+    }
+    if (ragged) {
+      const long nrow = (long)T * B;
+      hipLaunchKernelGGL(zero_padded_rows_kernel, dim3((unsigned)(ceil_div(nrow, 4) < 2048 ? ceil_div(nrow, 4) : 2048)), dim3(256), 0, s, bd->dx, d->lens, T, B, I);
+      RNNT_CHECK_LAUNCH();
     }
   }
   if (!do_weights) return RNNT_OK;

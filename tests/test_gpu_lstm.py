@@ -10,6 +10,14 @@ pytestmark = pytest.mark.gpu
 FWD_ATOL, GRAD_RTOL = 2e-5, 2e-4
 
 
+def _poison_free_memory():
+    """NaN-fill device memory and hand it back to the caching allocator (its large and its small pool), so that the next buffers come
+    out of it: whatever a kernel leaves unwritten then reads NaN instead of the zeros of fresh memory."""
+    big = torch.full((64 << 20,), float("nan"), device="cuda")
+    small = [torch.full((1 << 18,), float("nan"), device="cuda") for _ in range(32)]
+    del big, small
+
+
 def _oracle(x, lens, ref, dy):
     T = x.shape[1]
     xr = x.double().requires_grad_(True)
@@ -119,6 +127,7 @@ def test_ragged_plan_skips_padding_without_changing_results(B, T, I, H, L, bi, c
         def run(lens_arg):
             for q in hip.parameters():
                 q.grad = None
+            _poison_free_memory()
             xx = x_tm.clone().requires_grad_(True)
             pp = p if L > 1 else 0.0
             y = LstmStackFn.apply(xx, lens_arg, H, L, bi, pp, 4242, hip.CELL, False, *hip.flat_weights())
@@ -132,8 +141,9 @@ def test_ragged_plan_skips_padding_without_changing_results(B, T, I, H, L, bi, c
         if p > 0:   # same seed, same masks: the dense run is the reference
             y_d, dx_d, gr_d = run(lens_dev)
             assert (y_p - y_d).abs().max().item() < 1e-6
-            for b in range(B):   # dx of padded frames is unspecified with a plan (never consumed): compare valid frames
-                assert (dx_p[:lens[b], b] - dx_d[:lens[b], b]).abs().max().item() < 1e-5 * max(1.0, dx_d.abs().max().item())
+            for b in range(B):   # padded frames: exact zeros with a plan, as without one
+                assert torch.all(dx_p[lens[b]:, b] == 0) and torch.all(dx_d[lens[b]:, b] == 0)
+            assert (dx_p - dx_d).abs().max().item() < 1e-5 * max(1.0, dx_d.abs().max().item())
             for k in gr_d:
                 assert (gr_p[k] - gr_d[k]).abs().max().item() < 2e-5 * max(gr_d[k].abs().max().item(), 1e-3), k
             continue
@@ -147,10 +157,9 @@ def test_ragged_plan_skips_padding_without_changing_results(B, T, I, H, L, bi, c
             e = (got.double().cpu() - want).abs().max().item()
             assert e < GRAD_RTOL * scale + 1e-6, f"{order} {name}: err {e} scale {scale}"
 
-        dxv = dx_p.transpose(0, 1).clone()
         for b in range(B):
-            dxv[b, lens[b]:] = 0     # (unspecified with a plan; the oracle has 0 there)
-        close("dx", dxv, ref_dx)
+            assert torch.all(dx_p[lens[b]:, b] == 0), f"{order}: dx of padded frames of row {b}"
+        close("dx", dx_p.transpose(0, 1), ref_dx)
         for name, q in ref.named_parameters():
             close(name, gr_p[name], q.grad)
 
@@ -180,18 +189,55 @@ def test_ragged_plan_edge_cases(B, T, lens, monkeypatch):
     dy = torch.randn(B, T, 2 * H, generator=g)
     ref_out, ref_dx = _oracle(x, lens, ref, dy)
     x_tm = x.transpose(0, 1).contiguous().cuda().requires_grad_(True)
+    _poison_free_memory()
     y = hip(x_tm, RaggedPlan(lens, T, "cuda"))
     y.backward(dy.transpose(0, 1).contiguous().cuda())
     torch.cuda.synchronize()
     assert (y.detach().transpose(0, 1).double().cpu() - ref_out).abs().max().item() < FWD_ATOL
-    dx = x_tm.grad.transpose(0, 1).clone()
+    dx = x_tm.grad.transpose(0, 1)
     for b in range(B):
         assert torch.all(y[lens[b]:, b] == 0)
-        dx[b, lens[b]:] = 0
+        assert torch.all(x_tm.grad[lens[b]:, b] == 0), f"dx of padded frames of row {b}"
     for name, got, want in [("dx", dx, ref_dx)] + [(k, getattr(hip, k).grad, p.grad) for k, p in ref.named_parameters()]:
         scale = max(want.abs().max().item(), 1e-3)
         e = (got.double().cpu() - want).abs().max().item()
         assert e < GRAD_RTOL * scale + 1e-6, f"{name}: err {e} scale {scale}"
+
+
+@pytest.mark.parametrize("I", [32, 80, 127, 128, 200])
+def test_ragged_plan_dx_of_padded_frames_is_zero(I, monkeypatch):
+    """dx under a plan for input widths on both sides of the half-pair dX product (I >= 128: rows scattered through the table;
+    32 <= I < 128, the 80 mel bins among them: a dense product over all T*B rows of dG): padded frames are exact zeros, valid frames
+    match torch float64.  Freed memory is NaN-filled first, so a row nobody writes cannot pass as zero."""
+    import os
+    from rnntransducer_amd import _lib
+    from rnntransducer_amd.networks.rnn import HipLSTM
+    from rnntransducer_amd.ops import RaggedPlan
+    monkeypatch.setenv("RNNT_GEMM_FORCE_HP", "1")
+    B, T, H, lens = 8, 160, 128, [160, 1, 57, 130, 2, 160, 33, 1]   # T*B >= 1024: the half-pair products
+    if not any(os.environ.get(k) for k in ("RNNT_LSTM_NO_V5", "RNNT_GEMM_NO_HP", "RNNT_LSTM_V1", "RNNT_LSTM_V2", "RNNT_LSTM_EXACT_MATH")):
+        assert _lib.lib().rnnt_hip_lstm_takes_row_idx(T, B, I, H, 2, 0) == 1   # the table is honoured at this shape
+    torch.manual_seed(I)
+    ref = nn.LSTM(I, H, 2, batch_first=True, bidirectional=True).double()
+    hip = HipLSTM(I, H, 2, dropout=0.0, bidirectional=True)
+    hip.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    hip = hip.cuda()
+    g = torch.Generator().manual_seed(I)
+    x = torch.randn(B, T, I, generator=g)
+    for b in range(B):
+        x[b, lens[b]:] = 0
+    dy = torch.randn(B, T, 2 * H, generator=g)
+    _, ref_dx = _oracle(x, lens, ref, dy)
+    x_tm = x.transpose(0, 1).contiguous().cuda().requires_grad_(True)
+    _poison_free_memory()
+    y = hip(x_tm, RaggedPlan(lens, T, "cuda"))
+    y.backward(dy.transpose(0, 1).contiguous().cuda())
+    torch.cuda.synchronize()
+    for b in range(B):
+        assert torch.all(x_tm.grad[lens[b]:, b] == 0), f"dx of padded frames of row {b}"
+    scale = max(ref_dx.abs().max().item(), 1e-3)
+    e = (x_tm.grad.transpose(0, 1).double().cpu() - ref_dx).abs().max().item()
+    assert e < GRAD_RTOL * scale + 1e-6, f"dx: err {e} scale {scale}"
 
 
 def test_lstm_init_matches_torch_rng_stream():
