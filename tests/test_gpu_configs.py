@@ -6,12 +6,20 @@
   * a full-model step at config-2 layer sizes (4x512 bi-LSTM, 1x512 prediction net, T=1000, U=40) against
     `OracleJointNet(...).double()`: loss and every parameter gradient — at B=2 AND on the launch that bench.py times (B=32: 8 sync
     groups x 32 workgroups), where the 30 other rows get upstream weight 0 so the same 2-utterance oracle applies;
-  * the same at config-3 geometry (T=2000, U=120, B=8: the 4-row-group kernels) and at config-5 layer sizes (6x640, V=2048, T=1500);
+  * the same at config-3 geometry (T=2000, U=120, B=8: the 4-row-group kernels) and at config-5 layer sizes (6x640, V=2048, T=1500:
+    at B=2 and on the B=16 launch bench.py times);
+  * the reference's shipped config.json (8x1024 bi-GRU encoder, 2x1024 LSTM prediction net, O=512, V=72, T=1000, U=40): every
+    parameter gradient at B=2 and on the B=16 launch bench.py times — the v3 / v4 register-form recurrences, which no other config runs;
   * one bi-LSTM layer at the timed geometry (B=32, T=1000, H=512) against torch.nn.LSTM in float64, fixed and ragged lengths;
+  * one bi-GRU / bi-LSTM layer at H = 1024 / 768 and T = 1000 against torch float64: the shipped encoder's inner and first layer,
+    scattered length classes (dense and with the valid-frame table these shapes ignore), a batch the module splits along B, and the
+    opt-in v5 forms (RNNT_LSTM_V5_WIDE=1);
   * config 3 at full size: the joint + loss segment never allocates anything near a (B,T,U+1,V) tensor.
 
 Tolerances (fp32 path vs float64 oracle): NLL 1e-5 relative (north_star: 1e-4); input/weight gradients of the fused
-entry 5e-5 of max(1, |ref|max); parameter gradients of the whole model 2e-4 of the tensor's max.
+entry 5e-5 of max(1, |ref|max); parameter gradients of the whole model 2e-4 of the tensor's max; single layers: outputs 2e-5
+absolute, dx 2e-4 of its max, weight and bias gradients 2e-4 of the max of each gate's block, padded outputs and padded dx exact
+zeros on NaN-poisoned memory.
 """
 from argparse import Namespace
 
@@ -20,6 +28,7 @@ import pytest
 import torch
 
 from conftest import usable_cores
+from test_gpu_lstm import _poison_free_memory
 from oracle.rnnt_oracle import OracleJointNet, make_batch, rnnt_loss_c, training_loss
 
 pytestmark = pytest.mark.gpu
@@ -197,10 +206,28 @@ def test_full_model_config3_geometry_step_vs_float64_oracle():
     _assert_step_matches("config-3 geometry, B=8 launch (rows 2.. weight 0)", loss, grads, ref_loss, ref_grads)
 
 
+def _assert_b2_and_timed_launch(tag, model, small, big, ref_loss, ref_grads):
+    """HIP steps against the float64 oracle of `small` (two utterances): (a) at B=2; (b) on `big`, the launch bench.py times, whose rows
+    0-1 are `small` and whose other rows get upstream weight 0; (c) every NLL of (b) finite, and rows 0-1 give the same NLL in both
+    launches (batch invariance).  -> allocator peak of (b) in bytes."""
+    loss2, nll2, grads2 = _hip_step_on_first_rows(model, small, 2)
+    _assert_step_matches(f"{tag}, B=2", loss2, grads2, ref_loss, ref_grads)
+    del grads2
+    torch.cuda.reset_peak_memory_stats()
+    loss_b, nll_b, grads_b = _hip_step_on_first_rows(model, big, 2)
+    peak = torch.cuda.max_memory_allocated()
+    assert torch.isfinite(nll_b).all(), nll_b
+    _assert_step_matches(f"{tag}, B={big[0].shape[0]} launch (rows 2.. weight 0)", loss_b, grads_b, ref_loss, ref_grads)
+    assert torch.allclose(nll_b[:2], nll2, rtol=5e-6, atol=0), (nll_b[:2], nll2)
+    return peak
+
+
 def test_full_model_config5_dims_step_vs_float64_oracle():
-    """BASELINE configs[4] layer sizes: 6x640 bi-LSTM encoder (20-unit workgroups, K padded to 768), 1x640 prediction net, O=640,
-    V=2048 (vocab-tiled lattice kernels), T=1500, U=80, two utterances (second one with 2U/3 labels), INITIAL weights, dropout off: loss 1e-5
-    relative, every parameter gradient 2e-4 of its maximum against the float64 oracle (separable joint: 10 GB per concat copy)."""
+    """BASELINE configs[4] layer sizes: 6x640 bi-LSTM encoder (20-unit workgroups, K padded to 768, two-barrier backward), 1x640
+    prediction net, O=640, V=2048 (vocab-tiled lattice kernels), T=1500, U=80, two utterances (second one with 2U/3 labels), INITIAL
+    weights, dropout off: loss 1e-5 relative, every parameter gradient 2e-4 of its maximum against the float64 oracle (separable joint:
+    10 GB per concat copy) — at B=2 and on the B=16 launch bench.py times (two sync groups per direction, rows 2.. weight 0), plus
+    batch invariance of the per-utterance NLL."""
     from rnntransducer_amd import RNNTransducer
     V = 2048
     tn = dict(input_size=80, hidden_size=640, output_size=640, num_layers=6, rnn_type="lstm", dropout=0.0, bidirectional=True)
@@ -210,13 +237,38 @@ def test_full_model_config5_dims_step_vs_float64_oracle():
     small = _two_utterances_equal_frames_ragged_labels(1500, 80, V, seed=13)
     ref_loss, ref_grads = _oracle_step(tn, pn, V, model, small, per_utterance=True, separable=True)
     model = model.cuda().train()
-    loss, nll, grads = _hip_step_on_first_rows(model, small, 2)
-    _assert_step_matches("config-5 dims, B=2", loss, grads, ref_loss, ref_grads)
+    big = _embed_rows(small, make_batch(16, 1500, 80, V, ragged=False, seed=14))
+    _assert_b2_and_timed_launch("config-5 dims", model, small, big, ref_loss, ref_grads)
+
+
+def test_full_model_shipped_config_step_vs_float64_oracle():
+    """The reference's shipped config/config.json (bench.py --config shipped): 8x1024 bi-GRU encoder (the v3 / v4 register-form
+    recurrences, two 8-row sync groups per direction at B=16; the GRU backward without the fused dX split or the grouped weight-gradient
+    launch), 2x1024 LSTM prediction net, O=512, V=72, T=1000, U=40, INITIAL weights, dropout off.  Two utterances (second one with 2U/3
+    labels) against the float64 oracle: loss 1e-5 relative and every parameter gradient — all 8 encoder layers, every GRU bias, both
+    prediction-net layers, out_proj — 2e-4 of its maximum, at B=2 and on the B=16 launch bench.py times (rows 2.. weight 0), plus
+    batch invariance of the per-utterance NLL."""
+    import time
+    from rnntransducer_amd import RNNTransducer
+    V = 72
+    tn = dict(input_size=80, hidden_size=1024, output_size=512, num_layers=8, rnn_type="gru", dropout=0.0, bidirectional=True)
+    pn = dict(embedding_size=V, hidden_size=1024, output_size=512, num_layers=2, rnn_type="lstm", dropout=0.0)
+    torch.manual_seed(3)
+    model = RNNTransducer(dict(pn), dict(tn), dict(num_classes=V), ARGS)
+    small = _two_utterances_equal_frames_ragged_labels(1000, 40, V, seed=17)
+    t0 = time.perf_counter()
+    ref_loss, ref_grads = _oracle_step(tn, pn, V, model, small, per_utterance=True, separable=True)
+    t1 = time.perf_counter()
+    model = model.cuda().train()
+    big = _embed_rows(small, make_batch(16, 1000, 40, V, ragged=False, seed=18))
+    peak = _assert_b2_and_timed_launch("shipped config", model, small, big, ref_loss, ref_grads)
+    print(f"shipped config: float64 oracle {t1 - t0:.1f} s, HIP steps {time.perf_counter() - t1:.1f} s; "
+          f"B=16 step allocator peak {peak / 2**30:.2f} GiB")
 
 
 def _lstm_float64_by_length_class(ref, x, lens, dy):
-    """torch.nn.LSTM float64 on a ragged batch WITHOUT a PackedSequence (whose CPU autograd is O(T^2): 139 s at this size): rows of
-    equal length form one plain batch cut to that length — a packed batch treats rows independently and ends each at its own
+    """torch.nn.LSTM / GRU float64 on a ragged batch WITHOUT a PackedSequence (whose CPU autograd is O(T^2): 139 s at this size): rows
+    of equal length form one plain batch cut to that length — a packed batch treats rows independently and ends each at its own
     length, so this is the same function.  -> (out (B,T,D*H) zero on padding, dx); parameter gradients accumulate in `ref`."""
     T = x.shape[1]
     out = torch.zeros(x.shape[0], T, dy.shape[-1], dtype=torch.float64)
@@ -231,6 +283,49 @@ def _lstm_float64_by_length_class(ref, x, lens, dy):
     return out, dx
 
 
+def _layer_inputs(B, T, I, H, lens, seed):
+    """x (B,T,I) zero on padding, dy (B,T,2H) and the length list with its classes scattered over the rows, as a collate hands them."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, T, I, generator=g)
+    dy = torch.randn(B, T, 2 * H, generator=g)
+    perm = torch.randperm(B, generator=g).tolist()
+    lens = [lens[i] for i in perm]
+    for b in range(B):
+        x[b, lens[b]:] = 0
+    return x, dy, lens
+
+
+def _assert_layer_matches(tag, hip, ref, x, dy, lens, ref_out, ref_dx, lens_arg):
+    """One HIP layer call (fwd + bwd) on NaN-poisoned memory against the float64 result: outputs within 2e-5, padded outputs and padded
+    dx exact zeros (not masked before comparing), dx within 2e-4 of its max and every weight / bias gradient within 2e-4 of the max
+    of its own gate block (the gates' rows are stacked along dim 0; a gate whose gradients are small next to the others' is held to
+    its own scale — a 1e-3 relative error in the GRU z gate's bias gradient stays below 2e-4 of the whole tensor's max)."""
+    B = x.shape[0]
+    for q in hip.parameters():
+        q.grad = None
+    _poison_free_memory()
+    x_tm = x.transpose(0, 1).contiguous().cuda().requires_grad_(True)
+    y = hip(x_tm, lens_arg)
+    y.backward(dy.transpose(0, 1).contiguous().cuda())
+    torch.cuda.synchronize()
+    err = (y.detach().transpose(0, 1).double().cpu() - ref_out).abs().max().item()
+    assert err < 2e-5, f"{tag}: forward err {err}"
+    for b in range(B):
+        assert torch.all(y[lens[b]:, b] == 0), f"{tag}: output of padded frames of row {b}"
+        assert torch.all(x_tm.grad[lens[b]:, b] == 0), f"{tag}: dx of padded frames of row {b}"
+    worst = ("", 0.0)
+    gates = ref.weight_ih_l0.shape[0] // ref.hidden_size
+    blocks = [("dx", x_tm.grad.transpose(0, 1), ref_dx)]
+    for k, p in ref.named_parameters():
+        blocks += [(f"{k}[gate {i}]", got, want) for i, (got, want) in enumerate(zip(getattr(hip, k).grad.chunk(gates), p.grad.chunk(gates)))]
+    for nm, got, want in blocks:
+        scale = max(want.abs().max().item(), 1e-3)
+        e = (got.double().cpu() - want).abs().max().item() / scale
+        worst = max(worst, (nm, e), key=lambda t: t[1])
+        assert e < 2e-4, f"{tag} {nm}: {e:.3e} of max {scale:.3e}"
+    print(f"{tag}: forward err {err:.2e}, worst gradient {worst[0]} {worst[1]:.2e} of max")
+
+
 @pytest.mark.parametrize("name,I,lens", [
     ("fixed lengths, inner-layer width (the launch bench.py times)", 1024, [1000] * 32),
     ("four length classes, layer-0 width (the c4 / --ragged shape)", 80, [1000] * 8 + [873] * 8 + [640] * 8 + [501] * 8),
@@ -238,48 +333,70 @@ def _lstm_float64_by_length_class(ref, x, lens, dy):
 def test_lstm_layer_at_the_timed_launch_geometry_vs_torch_float64(name, I, lens):
     """One bi-LSTM layer at BASELINE configs[1]'s launch geometry — B=32, T=1000, H=512: 8 sync groups x 32 workgroups, 1000 steps of
     the tagged exchange — against torch.nn.LSTM float64 on the CPU: outputs, dx and every weight gradient (VERDICT r2 weak #1b: the
-    B=32 tests stopped at T=40)."""
+    B=32 tests stopped at T=40).  Padded outputs and padded dx are exact zeros, dense and with the valid-frame table."""
     from rnntransducer_amd.networks.rnn import HipLSTM
+    from rnntransducer_amd.ops import RaggedPlan
     B, T, H = 32, 1000, 512
     torch.manual_seed(31 + I)
     ref = torch.nn.LSTM(I, H, 1, batch_first=True, bidirectional=True).double()
     hip = HipLSTM(I, H, 1, dropout=0.0, bidirectional=True)
     hip.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
     hip = hip.cuda()
-    g = torch.Generator().manual_seed(5)
-    x = torch.randn(B, T, I, generator=g)
-    dy = torch.randn(B, T, 2 * H, generator=g)
-    perm = torch.randperm(B, generator=g).tolist()
-    lens = [lens[i] for i in perm]           # classes scattered over the rows, as a collate would hand them
-    for b in range(B):
-        x[b, lens[b]:] = 0
+    x, dy, lens = _layer_inputs(B, T, I, H, lens, seed=5)
     torch.set_num_threads(usable_cores())
     ref_out, ref_dx = _lstm_float64_by_length_class(ref, x, lens, dy)
-    from rnntransducer_amd.ops import RaggedPlan
-    lens_dev = torch.tensor(lens, dtype=torch.int32, device="cuda")
-    variants = [("dense", lens_dev)]
+    variants = [("dense", torch.tensor(lens, dtype=torch.int32, device="cuda"))]
     if min(lens) < T:   # the same launch with the valid-frame table (what training_step builds from the collate's length list)
         variants.append(("valid-frame table", RaggedPlan(lens, T, "cuda")))
     for vname, lens_arg in variants:
-        for q in hip.parameters():
-            q.grad = None
-        x_tm = x.transpose(0, 1).contiguous().cuda().requires_grad_(True)
-        y = hip(x_tm, lens_arg)
-        y.backward(dy.transpose(0, 1).contiguous().cuda())
-        torch.cuda.synchronize()
-        err = (y.detach().transpose(0, 1).double().cpu() - ref_out).abs().max().item()
-        assert err < 2e-5, f"{name} / {vname}: forward err {err}"
-        dx = x_tm.grad.transpose(0, 1).clone()
-        for b in range(B):
-            assert torch.all(y[lens[b]:, b] == 0)
-            dx[b, lens[b]:] = 0   # (gradient w.r.t. padded input frames: unspecified with the table, never consumed)
-        worst = ("", 0.0)
-        for nm, got, want in [("dx", dx, ref_dx)] + [(k, getattr(hip, k).grad, p.grad) for k, p in ref.named_parameters()]:
-            scale = max(want.abs().max().item(), 1e-3)
-            e = (got.double().cpu() - want).abs().max().item() / scale
-            worst = max(worst, (nm, e), key=lambda t: t[1])
-            assert e < 2e-4, f"{name} / {vname} {nm}: {e:.3e} of max {scale:.3e}"
-        print(f"B=32 T=1000 H=512 I={I} ({name}, {vname}): forward err {err:.2e}, worst gradient {worst[0]} {worst[1]:.2e} of max")
+        _assert_layer_matches(f"B=32 T=1000 H=512 I={I} ({name}, {vname})", hip, ref, x, dy, lens, ref_out, ref_dx, lens_arg)
+
+
+_FOUR_CLASSES = (1000, 873, 640, 501)
+
+
+@pytest.mark.parametrize("cell,H,I,B,classes,wide", [
+    ("gru", 1024, 2048, 16, (1000,), False),        # shipped encoder, inner layer, the launch bench.py times (2 x 8-row groups / dir)
+    ("gru", 1024, 80, 16, _FOUR_CLASSES, True),     # shipped encoder, layer 0, ragged: in-kernel length masking over 1000 steps
+    ("gru", 1024, 80, 40, _FOUR_CLASSES, False),    # beyond one launch: 32 rows (2 x 16-row groups / dir) + 8 rows (2 x 4-row groups)
+    ("lstm", 1024, 1024, 16, _FOUR_CLASSES, True),  # shipped prediction-net width as a bi-LSTM layer
+    ("gru", 768, 80, 16, _FOUR_CLASSES, False),     # the other width whose default is v3 / v4
+], ids=["gru1024-I2048-B16-fixed", "gru1024-I80-B16-ragged", "gru1024-I80-B40-ragged", "lstm1024-I1024-B16-ragged",
+        "gru768-I80-B16-ragged"])
+def test_wide_recurrent_layer_at_the_timed_length_vs_torch_float64(monkeypatch, cell, H, I, B, classes, wide):
+    """One bidirectional GRU / LSTM layer at H = 1024 / 768 over T = 1000 steps — the v3 / v4 register-form recurrences (8 waves) that
+    the shipped config runs, which test_gpu_lstm.py checks for at most 6 steps — against torch.nn.GRU / LSTM float64 on the CPU:
+    outputs, dx and every weight and bias gradient; padded outputs and padded dx exact zeros.  Ragged cases scatter the length
+    classes over the rows and run dense and with a valid-frame table, which these shapes ignore (the reverse direction then starts at
+    each row's own last frame by in-kernel masking alone).  `wide`: the same calls again under the opt-in v5 forms (RNNT_LSTM_V5_WIDE=1)
+    against the same float64 result."""
+    from rnntransducer_amd import _lib
+    from rnntransducer_amd.networks.rnn import HipGRU, HipLSTM
+    from rnntransducer_amd.ops import RaggedPlan
+    T = 1000
+    monkeypatch.delenv("RNNT_LSTM_V5_WIDE", raising=False)
+    torch.manual_seed(H + I + B)
+    ref = (torch.nn.GRU if cell == "gru" else torch.nn.LSTM)(I, H, 1, batch_first=True, bidirectional=True).double()
+    hip = (HipGRU if cell == "gru" else HipLSTM)(I, H, 1, dropout=0.0, bidirectional=True)
+    hip.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    hip = hip.cuda()
+    x, dy, lens = _layer_inputs(B, T, I, H, [classes[i * len(classes) // B] for i in range(B)], seed=H + B)
+    cap = _lib.lib().rnnt_hip_lstm_max_batch(H, 2, hip.CELL)
+    assert (B > cap) == (B == 40), f"one launch takes {cap} rows at H={H}"   # B=40 is the one case the module splits along B
+    torch.set_num_threads(usable_cores())
+    ref_out, ref_dx = _lstm_float64_by_length_class(ref, x, lens, dy)
+    variants = [("dense", torch.tensor(lens, dtype=torch.int32, device="cuda"))]
+    if min(lens) < T:
+        variants.append(("valid-frame table", RaggedPlan(lens, T, "cuda")))
+    forms = [("v3/v4", False)] + ([("v5 wide", True)] if wide else [])
+    for form, on in forms:
+        if on:
+            monkeypatch.setenv("RNNT_LSTM_V5_WIDE", "1")
+        if B <= cap:   # the default forms ignore the table at this width; the v5 forms honour it
+            assert _lib.lib().rnnt_hip_lstm_takes_row_idx(T, B, I, H, 2, hip.CELL) == int(on)
+        for vname, lens_arg in variants:
+            _assert_layer_matches(f"{cell.upper()} B={B} T={T} H={H} I={I} ({form}, {vname})", hip, ref, x, dy, lens, ref_out, ref_dx,
+                                  lens_arg)
 
 
 def test_config3_full_size_joint_loss_never_materialises_btuv():

@@ -430,10 +430,12 @@ def test_gru_and_elman_cells_on_half_pair_operands(monkeypatch, cell):
 
 
 def test_batches_beyond_one_launch_are_split_along_b():
-    """B=70 LSTM (one launch takes <= 64 rows) and a 1024-wide GRU with B=20 (grouped form takes <= 16 rows at that width):
-    the module runs batch slices back to back; results equal the oracle."""
+    """B=70 LSTM (one launch takes <= 64 rows) and a 1024-wide GRU with B=40 (the grouped form takes <= 32 rows at that width on a
+    256-CU device: two 16-row groups per direction): the module runs batch slices back to back; results equal the oracle."""
+    from rnntransducer_amd import _lib
     from rnntransducer_amd.networks.rnn import HipGRU, HipLSTM
-    for cls, ref_cls, (B, T, I, H) in ((HipLSTM, nn.LSTM, (70, 5, 8, 16)), (HipGRU, nn.GRU, (20, 6, 8, 1024))):
+    for cls, ref_cls, (B, T, I, H) in ((HipLSTM, nn.LSTM, (70, 5, 8, 16)), (HipGRU, nn.GRU, (40, 6, 8, 1024))):
+        assert B > _lib.lib().rnnt_hip_lstm_max_batch(H, 2, cls.CELL), (cls.__name__, H)   # really more than one launch
         torch.manual_seed(B)
         ref = ref_cls(I, H, 1, batch_first=True, bidirectional=True).double()
         hip = cls(I, H, 1, bidirectional=True)
