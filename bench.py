@@ -16,9 +16,10 @@ fp32, inter-layer dropout 0.2.  Weak scaling: per-GPU work fixe
 
 Rank 0 prints ONE JSON line with the driver's contract plus
   "roofline"     for the kernel that took the most time inside the timed region (live HIP-event timing from the
-                 library's opt-in profiler; algorithmic FLOPs/bytes per launch are computed in the launch wrappers),
+                 library's opt-in profiler; algorithmic FLOPs/bytes per launch are computed in the launch wrappers).
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.  With `--full` (N=1 only) the line also has
   "cpu_baseline" the CPU oracle (torch-CPU composite of the reference path + C loss) timed on this box's host cores
-                 on a bounded sample, N=1 only,
+                 on a bounded sample,
   "loss_rel_delta" / "grad_max_abs_dev"  the HIP path against the FLOAT64 oracle at the INITIAL weights, measured BEFORE the
                  timed steps on the launch geometry that is timed: the HIP side runs the FULL bench batch (B rows, the same sync
                  groups / workgroup count as a timed step) with per-utterance losses, and back-propagates the mean over the first
@@ -26,6 +27,7 @@ Rank 0 prints ONE JSON line with the driver's contract plus
                  gradients are comparable with the oracle's run on those utterances.  Gate: loss 1e-4 relative, gradients 2e-4 of
                  the tensor's maximum — the fixture tests' bound, no widening.  The same comparison on the weights the timed steps
                  left is reported under "parity_after_training" (informational: conditioning, not a gate).
+                 A plain run still makes the HIP side's pass at the initial weights (see hip_parity_pass), without the oracle.
 `--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (see dump_outputs); the inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
 """
@@ -137,13 +139,13 @@ def cpu_baseline(model, tn, pn, V, batch, sample_b, threads, timed_steps=3):
     return sample_b / med, med, times
 
 
-def parity_vs_float64_oracle(model, opt, tn, pn, V, batch, nb, threads, with_fp32_oracle):
-    """Loss + the three probe gradients (SURVEY §8d "Loss delta") of the HIP path on the CURRENT weights, dropout off, against the
-    float64 oracle on the first `nb` utterances of the bench batch.  The HIP side runs the WHOLE bench batch — the launch that is
-    timed: same B, same sync groups, same workgroup count — with reduction "none" and back-propagates nll[:nb].mean(): rows >= nb
-    get upstream weight 0 and, rows being independent, contribute nothing to any gradient."""
-    from oracle.rnnt_oracle import training_loss
-    torch.set_num_threads(threads)
+def hip_parity_pass(model, opt, batch, nb):
+    """The HIP side of the parity leg on the CURRENT weights, dropout off: the WHOLE bench batch — the launch that is timed: same B,
+    same sync groups, same workgroup count — with reduction "none", back-propagating nll[:nb].mean(): rows >= nb get upstream
+    weight 0 and, rows being independent, contribute nothing to any gradient.  Leaves the gradients cleared and the mode as it was.
+    -> (loss, per-row NLL, probe gradients), the last two float64 on the host.
+    Every forward advances the recurrent layers' call counters, from which they derive their dropout seeds (networks/rnn.py), so a
+    run that skips this pass would time steps with other dropout masks than a run that makes it."""
     was_training = model.training
     model.eval()
     opt.zero_grad()
@@ -156,6 +158,15 @@ def parity_vs_float64_oracle(model, opt, tn, pn, V, batch, nb, threads, with_fp3
     hip_grads = {k: p.grad.detach().double().cpu().clone() for k, p in model.jointnet.named_parameters() if k in GRAD_PROBES}
     opt.zero_grad()
     model.train(was_training)
+    return hip_loss, hip_nll, hip_grads
+
+
+def parity_vs_float64_oracle(model, opt, tn, pn, V, batch, nb, threads, with_fp32_oracle):
+    """Loss + the three probe gradients (SURVEY §8d "Loss delta") of the HIP path on the CURRENT weights, dropout off (hip_parity_pass),
+    against the float64 oracle on the first `nb` utterances of the bench batch."""
+    from oracle.rnnt_oracle import training_loss
+    torch.set_num_threads(threads)
+    hip_loss, hip_nll, hip_grads = hip_parity_pass(model, opt, batch, nb)
     oracle = _oracle_for(model, tn, pn, V, double=True)
     cpu_sub = tuple((x[:nb].cpu() if isinstance(x, torch.Tensor) else x[:nb]) for x in batch)
     # the checker runs its LSTMs one utterance at a time on its own valid prefix instead of through a PackedSequence: the same function
@@ -316,9 +327,13 @@ def main():
     ap.add_argument("--config", default="c2", choices=list(CONFIGS))
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--ragged", action="store_true", help="KsponSpeech-shaped ragged lengths (SURVEY §8d c4 variant)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=4, help="utterances in the CPU-baseline sample")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use (measured)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run the CPU legs — the float64 parity gate before the timed steps, the post-training parity and "
+                         "the CPU baseline after them; without it a run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="skip the parity leg altogether: its HIP pass at the initial weights and, with --full, the CPU legs")
+    ap.add_argument("--cpu-sample", type=int, default=4, help="--full: utterances in the CPU-baseline sample")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: 0 = every core this process may use (measured)")
     ap.add_argument("--parity-sample", type=int, default=2, help="utterances in the float64 parity leg")
     ap.add_argument("--profile-every", type=int, default=5,
                     help="the library's HIP-event profiler (2 events around every kernel: +0.56 ms on a 25 ms c2 step when it is on "
@@ -414,16 +429,20 @@ def main():
         torch.cuda.synchronize()
 
     # parity gate FIRST: initial weights, the full bench batch on the HIP side (the launch geometry that is timed), float64 oracle
-    # on the first --parity-sample utterances, strict tolerances (loss 1e-4 relative, gradients 2e-4 of the tensor's maximum)
+    # on the first --parity-sample utterances, strict tolerances (loss 1e-4 relative, gradients 2e-4 of the tensor's maximum).
+    # Without --full only the HIP pass runs: the timed steps then draw the dropout masks of a --full run (hip_parity_pass)
     parity = None
-    want_cpu_legs = world == 1 and not a.no_cpu_baseline
+    want_parity = world == 1 and not a.no_cpu_baseline
+    want_cpu_legs = want_parity and a.full
+    npar = min(a.parity_sample, B)
     if want_cpu_legs:
         cores, cpu_model = host_cpu_info()
         threads = a.cpu_threads or cores
-        npar = min(a.parity_sample, B)
         lrd, gdev, _, finite = parity_vs_float64_oracle(model, opt, tn, pn, V, batch, npar, threads, with_fp32_oracle=False)
         parity = {"loss_rel_delta": lrd, "grad_max_abs_dev": gdev, "all_rows_finite": finite,
                   "ok": bool(finite and lrd <= 1e-4 and all(grad_within_tolerance(v) for v in gdev.values()))}
+    elif want_parity:
+        hip_parity_pass(model, opt, batch, npar)
 
     for _ in range(a.warmup):
         step()

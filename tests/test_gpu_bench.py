@@ -1,4 +1,5 @@
-"""bench.py contract (driver reads this JSON line) on the tiny BASELINE config 1, and __graft_entry__.smoke()."""
+"""bench.py contract (driver reads this JSON line) on the tiny BASELINE config 1, a plain run against a --full run on config 2,
+and __graft_entry__.smoke()."""
 import json
 import os
 import subprocess
@@ -13,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_emits_one_contract_line_with_roofline_and_cpu_baseline(tmp_path):
     dump = tmp_path / "outputs"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "3", "--warmup", "1",
-                          "--cpu-sample", "2", "--cpu-threads", "4", "--dump-outputs", str(dump)], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c1", "--steps", "3", "--warmup",
+                          "1", "--cpu-sample", "2", "--cpu-threads", "4", "--dump-outputs", str(dump)], capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -48,6 +49,35 @@ def test_bench_emits_one_contract_line_with_roofline_and_cpu_baseline(tmp_path):
     assert sum((dump / f).stat().st_size for f in files) <= 64 << 20
     assert abs(float(np.load(dump / "loss.npy")) - j["last_loss"]) < 1e-3
     assert np.isfinite(np.load(dump / "grad.jointnet.fc.weight.npy")).all()
+
+
+def test_plain_bench_run_times_what_the_full_run_times(tmp_path):
+    """A run without --full prints the same contract line without the CPU legs, and its timed steps compute what those of a --full
+    run compute.  On c2, whose 4-layer encoder applies inter-layer dropout: the masks follow the recurrent layers' call counters, so the
+    dumped outputs agree only if both runs time the same masks (another mask moves the gradients by far more than the bound)."""
+    common = ["--config", "c2", "--steps", "2", "--warmup", "1", "--parity-sample", "1"]
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-sample", "1"])):
+        dump = tmp_path / mode
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra + ["--dump-outputs", str(dump)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs[mode] = (json.loads(lines[0]), dump)
+    plain, full = runs["plain"][0], runs["full"][0]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and "roofline" in plain
+    for k in ("cpu_baseline", "speedup_vs_cpu_baseline", "parity", "loss_rel_delta", "grad_max_abs_dev", "parity_after_training"):
+        assert k not in plain and k in full, k
+    assert full["parity"]["ok"] is True
+    assert abs(plain["last_loss"] - full["last_loss"]) <= 1e-6 * abs(full["last_loss"])
+    files = sorted(os.listdir(runs["full"][1]))
+    assert files and sorted(os.listdir(runs["plain"][1])) == files
+    for f in files:
+        a, b = np.load(runs["plain"][1] / f), np.load(runs["full"][1] / f)
+        assert a.shape == b.shape and np.abs(a - b).max() <= 1e-6 * max(float(np.abs(b).max()), 1e-30), f
 
 
 def test_smoke_entry_point():

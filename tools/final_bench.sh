@@ -11,6 +11,7 @@ for c in $CFGS; do
     shipped) ARGS="--config shipped --steps 10 --warmup 3 --cpu-sample 2"; OUT=shipped ;;
     *) ARGS="--config $c"; OUT=$c ;;
   esac
+  ARGS="--full $ARGS"   # the records keep the parity gate and the CPU baseline
   echo "== bench.py $ARGS" | tee -a gpurun_out/$TAG/progress.log
   python3 bench.py $ARGS > gpurun_out/$TAG/bench_$OUT.log 2> gpurun_out/$TAG/bench_$OUT.err; echo "rc=$?" | tee -a gpurun_out/$TAG/progress.log
   tail -c 300 gpurun_out/$TAG/bench_$OUT.err | tail -2
