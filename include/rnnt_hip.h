@@ -86,7 +86,7 @@ int rnnt_hip_prof_collect(double* ms, double* work, int64_t* count, int nkinds);
                                   * library default is the split-bf16 form (see below)                      */
 #define RNNT_GEMM_HP_F16 32u     /* rnnt_hip_gemm_hp / rnnt_hp_problem only: ONE product hi.hi per fp32 product (the lo
                                   * halves of both operands are not read) — f16 operand rounding, fp32 accumulation; see
-                                  * RNNT_PRECISION_F16.  The opt-in 3-stage kernel (RNNT_GEMM_HP_3STAGE) declines it. */
+                                  * RNNT_PRECISION_F16. */
 
 typedef struct rnnt_gemm_desc {
   int64_t M, N, K;
@@ -246,7 +246,7 @@ int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream);
 int rnnt_hip_lstm_fwd_ex(const rnnt_lstm_desc* d, uint32_t precision, void* stream);
 /* 1 if a layer of this shape really runs the one-product forms under RNNT_PRECISION_F16 (v5 recurrences in both directions of time
  * and the half-pair products), 0 if it computes in fp32 whatever it is asked (lstm.hip's v3 / v4 forms: H > 640 unless opted in,
- * RNNT_LSTM_NO_V5, the ReLU cell; products below the half-pair limits; RNNT_GEMM_HP_3STAGE).  Products that stay on
+ * RNNT_LSTM_NO_V5, the ReLU cell; products below the half-pair limits).  Products that stay on
  * rnnt_hip_gemm_f32 inside an f16 layer (an input narrower than 32 / 128 features) are fp32 either way. */
 int32_t rnnt_hip_lstm_takes_f16(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell);
 

@@ -59,8 +59,6 @@ int hp_split_t(const float* x, int64_t R, int64_t K, int64_t ld, int64_t Ksrc, i
 int hp_split_both(const float* x, int64_t M, int64_t C, int64_t ld, const uint32_t* rowmax, const uint32_t* colmax, void* planes_rm,
                   void* planes_t, hipStream_t s, const int* rowidx = nullptr);
 size_t hp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
-// RNNT_GEMM_HP_3STAGE is set: hp_gemm runs the opt-in 3-stage kernel, which has no one-product form (declines RNNT_GEMM_HP_F16)
-bool hp_gemm_3stage();
 int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t* b_amax, int64_t M, int64_t N, int64_t K, float* C,
             int64_t c_div, int64_t c_so, int64_t c_si, const float* bias, unsigned flags, void* workspace, size_t workspace_bytes,
             hipStream_t s, const int* a_rowidx = nullptr, int64_t a_plane_rows = 0, const int* c_rowidx = nullptr);

@@ -25,8 +25,6 @@
 
 #include <stdlib.h>
 
-#include <type_traits>
-
 namespace rnnt {
 namespace {
 
@@ -313,116 +311,12 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
   const int kt0 = z * p.kt_per_split;
   const int nk = min(p.nkt - kt0, p.kt_per_split);
 
-#ifdef HP_PIPE
-  // Software-pipelined main loop — build variant only (-DHP_PIPE=1), NOT the default: it measured within 1 % of the plain loop below
-  // (profiles/r03_gemm_hp_bound_probe.txt: dX 610 vs 617 us, proj 755 vs 741, dW 589 vs 592).  The probe variants of the same file
-  // say why: the MFMAs alone run at 0.83 of the nominal f16 peak (power-limited clock); with the operand fragments read from LDS at
-  // 0.61-0.63 WHETHER OR NOT the reads are issued a quarter tile ahead (so it is not exposed LDS latency: every ds_read_b128 costs the
-  // SIMD about 20 cycles of MFMA issue while its 1 KB lands in the register file), and the operand fetch alone (LDS-DMA, no MFMA) takes
-  // 0.72 of the full kernel's time at 77 % L2 hits (one 64 KB round trip per K-tile and CU: a 2-stage ring cannot keep more in flight).
-  // Every ds_read_b128 is issued at least 12 MFMAs (usually a whole quarter = 24) ahead of its first use:
-  //   quarter  operands (A half, B half)   loads issued during it
-  //   Q0       a(mq 0), set0 = b(nq 0)     set1 <- b(nq 1)
-  //   Q1       a(mq 0), set1               a[i] <- A(mq 1) block i, as soon as block i's MFMAs are issued
-  //   Q2       a(mq 1), set1               set0 <- b(nq 0) again;  then vmcnt(0) + lgkmcnt(0) + BARRIER (the only one per K-tile)
-  //   Q3       a(mq 1), set0               LDS-DMA of K-tile kt + 2 into THIS tile's (now fully read) stage;  set1 <- next tile's b(nq 0),
-  //                                        a[i] <- next tile's A(mq 0) block i — from the other stage, whose DMA the barrier waited for
-  // The two B register sets swap roles every K-tile (the loop body is instantiated for both parities).  Every accumulator still sees
-  // its K-tiles and, inside one, its three products in the same order: results are bitwise those of the plain loop (HP_NO_PIPE).
-  f16x8 a[4][2], bs[2][2][2];
-  auto ld_a = [&](const char* sb, int mq, int i) {
-    a[i][0] = *reinterpret_cast<const f16x8*>(sb + (a_base + (4 * mq + i) * 2048));
-    if constexpr (!F16) a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + (4 * mq + i) * 2048));
-  };
-  auto ld_b = [&](int set, const char* sb, int nq) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      bs[set][j][0] = *reinterpret_cast<const f16x8*>(sb + (b_base + (2 * nq + j) * 2048));
-      if constexpr (!F16) bs[set][j][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + (2 * nq + j) * 2048));
-    }
-  };
-  // blocks i0, i0 + 1 of A half mq against B half nq (register set `set`): 12 MFMAs, four independent accumulators between dependent ones
-  auto mma2 = [&](int mq, int nq, int set, int i0) {
-#pragma unroll
-    for (int t = F16 ? 2 : 0; t < 3; ++t)
-#pragma unroll
-      for (int i = i0; i < i0 + 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          f32x4 c = acc[4 * mq + i][2 * nq + j];
-          if (t == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][1], bs[set][j][0], c, 0, 0, 0);   // smallest terms first
-          else if (t == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], bs[set][j][1], c, 0, 0, 0);
-          else c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], bs[set][j][0], c, 0, 0, 0);
-          acc[4 * mq + i][2 * nq + j] = c;
-        }
-  };
-#define HP_PIN() __builtin_amdgcn_sched_barrier(0)   /* nothing moves across: the loads stay where the table above puts them */
-
-  stage(0, kt0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (nk > 1) stage(1, kt0 + 1);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) ld_a(lds, 0, i);
-  ld_b(0, lds, 0);
-  HP_PIN();
-
-  auto ktile = [&](auto parity, const int kt) {
-    constexpr int S0 = decltype(parity)::value, S1 = S0 ^ 1;   // B register sets: S0 holds nq 0 on entry
-    const char* sb = lds + S0 * HP_STAGE;                       // stage of this K-tile: kt0-relative parity == S0 by construction
-    const char* nb = lds + S1 * HP_STAGE;
-    // Q0  (the loads of set1 sit BEHIND the first 12 MFMAs: at the loop head hipcc waits with lgkmcnt(0) — it cannot count what the
-    //      previous iteration left in flight — and loads issued in front of that wait would be waited for at once)
-    mma2(0, 0, S0, 0);
-    HP_PIN();            // (blocks 2, 3 of A arrived 12 MFMAs later than blocks 0, 1: their MFMAs stay behind those of 0, 1)
-    ld_b(S1, sb, 1);
-    HP_PIN();
-    mma2(0, 0, S0, 2);
-    HP_PIN();
-    // Q1
-    mma2(0, 1, S1, 0);
-    HP_PIN();
-    ld_a(sb, 1, 0); ld_a(sb, 1, 1);
-    HP_PIN();
-    mma2(0, 1, S1, 2);
-    HP_PIN();
-    ld_a(sb, 1, 2); ld_a(sb, 1, 3);
-    ld_b(S0, sb, 0);
-    HP_PIN();
-    // Q2
-    mma2(1, 1, S1, 0);
-    HP_PIN();
-    mma2(1, 1, S1, 2);
-    HP_PIN();
-    __syncthreads();   // vmcnt(0): the LDS-DMA of K-tile kt + 1 has landed; lgkmcnt(0): every read of this stage is done
-    HP_PIN();
-#ifndef HP_DBG_NO_DMA
-    if (kt + 2 < nk) stage(S0, kt0 + kt + 2);
-#endif
-    // Q3 (+ the first fragments of K-tile kt + 1; behind the last K-tile these read stale LDS into dead registers)
-    ld_b(S1, nb, 0);
-    HP_PIN();
-    mma2(1, 0, S0, 0);
-    HP_PIN();
-    ld_a(nb, 0, 0); ld_a(nb, 0, 1);
-    HP_PIN();
-    mma2(1, 0, S0, 2);
-    HP_PIN();
-    ld_a(nb, 0, 2); ld_a(nb, 0, 3);
-    HP_PIN();
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    ktile(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < nk) ktile(std::integral_constant<int, 1>{}, kt + 1);
-  }
-#undef HP_PIN
-#else
   stage(0, kt0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    // (measured in one process, tools/gemm_hp_ab.py: issuing the LDS-DMA of waves 4-7 half a tile later than that of their SIMD
+    // (measured in one process: issuing the LDS-DMA of waves 4-7 half a tile later than that of their SIMD
     // partners 0-3 is 5 % SLOWER, s_setprio around the MFMA clusters 1 % slower, 256 x 128 tiles with a 3-stage ring 13 % slower)
 #ifndef HP_DBG_NO_DMA   // (diagnostic builds: tools/gemm_hp_bound_probe.sh times the loop without its operand fetch / without its MFMAs)
     if (kt + 1 < nk) stage(cur ^ 1, kt0 + kt + 1);   // lands under this tile's 96 MFMAs
@@ -479,8 +373,6 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
     __syncthreads();   // drains the LDS-DMA of the next stage (vmcnt(0)) and fences this stage's reads
 #endif
   }
-
-#endif
   // epilogue: D block (i, j): lane -> rows 4*(lane>>4) + reg, column lane&15
   const int mode = p.splits > 1 ? 0 : ((p.flags & RNNT_GEMM_ACCUM) ? 2 : 1);  // uniform: slab | store | accumulate
   float* slab = p.splits > 1 ? p.slab + (long)z * p.M * p.N : nullptr;
@@ -610,131 +502,6 @@ __global__ void hpq_check_kernel(unsigned* counter, unsigned total, unsigned* st
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// 256 x 128 x 32 tile, 8 waves as 4 (M) x 2 (N), 64 x 64 of C per wave (4 x 4 blocks, 48 MFMAs per K-tile), THREE 48 KB LDS stages:
-// the LDS-DMA of K-tile t+2 is issued before tile t is multiplied and is only waited for (counted vmcnt, raw s_barrier: a
-// __syncthreads() would drain it) at the end of tile t+1 — two tiles of MFMA time to land instead of one.
-// (Opt-in variant, RNNT_GEMM_HP_3STAGE: it has no one-product form and declines RNNT_GEMM_HP_F16 — three products always; while it
-// is selected rnnt_hip_lstm_takes_f16 reports 0 and the LSTM entries run fp32.)
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int HP3_BM = 256, HP3_BN = 128, HP3_STAGE = (HP3_BM + HP3_BN) * 128, HP3_NST = 3;
-
-__global__ void __launch_bounds__(512, 1) gemm_hp3_kernel(const HpGemmK p) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int bid = hp_xcd_remap(blockIdx.x, ntiles);
-  const int m0 = (bid % p.tiles_m) * HP3_BM, n0 = (bid / p.tiles_m) * HP3_BN;
-
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.A), 0, (int)p.a_bytes, HP_RSRC);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.B), 0, (int)p.b_bytes, HP_RSRC);
-
-  // LDS-DMA pieces: A rows (8j + wave) * 8 .. + 7 for j = 0..3, B rows (8j + wave) * 8 .. + 7 for j = 0..1
-  unsigned va[4], vb[2];
-  {
-    const int src_slot = (lane & 7) ^ (((lane >> 4) & 3) | ((wave & 1) << 2));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = (8 * j + wave) * 8 + (lane >> 3);
-      va[j] = (unsigned)min(m0 + row, p.M - 1) * p.a_pitch + 16u * src_slot;
-      if (j < 2) vb[j] = (unsigned)min(n0 + row, p.N - 1) * p.b_pitch + 16u * src_slot;
-    }
-  }
-  const int kt0 = blockIdx.y * p.kt_per_split;
-  const int nk = min(p.nkt - kt0, p.kt_per_split);
-  auto stage = [&](int buf, int kt) {   // kt >= nk: offsets beyond the planes read zeros (keeps the vmcnt arithmetic uniform)
-    char* base = lds + buf * HP3_STAGE;
-    const int koff = kt < nk ? (kt0 + kt) * 128 : 0x7ff00000;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(base + (8 * j + wave) * 1024), 16, va[j], koff, 0, 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(base + HP3_BM * 128 + (8 * j + wave) * 1024), 16, vb[j], koff, 0, 0);
-  };
-
-  const int frag0 = (lane & 15) * 128 + 16 * ((lane >> 4) ^ ((lane & 15) >> 1));
-  const int a_base = wr * (64 * 128) + frag0;
-  const int b_base = HP3_BM * 128 + wc * (64 * 128) + frag0;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  stage(0, 0);
-  stage(1, 1);
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // stage 0 landed (this wave's share); the barrier makes it everyone's
-  __builtin_amdgcn_s_barrier();
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int nxt2 = cur == 0 ? 2 : cur - 1;          // (cur + 2) % 3: the buffer read during the previous iteration
-    stage(nxt2, kt + 2);
-    const char* sb = lds + cur * HP3_STAGE;
-    f16x8 a[4][2], b[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      a[i][0] = *reinterpret_cast<const f16x8*>(sb + (a_base + i * 2048));
-      a[i][1] = *reinterpret_cast<const f16x8*>(sb + ((a_base ^ 64) + i * 2048));
-      b[i][0] = *reinterpret_cast<const f16x8*>(sb + (b_base + i * 2048));
-      b[i][1] = *reinterpret_cast<const f16x8*>(sb + ((b_base ^ 64) + i * 2048));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][1], b[j][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][0], b[j][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");   // tile kt+1 landed; tile kt+2 stays in flight
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    cur = cur == 2 ? 0 : cur + 1;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-fill DMAs of the last two iterations
-
-  const int mode = p.splits > 1 ? 0 : ((p.flags & RNNT_GEMM_ACCUM) ? 2 : 1);
-  float* slab = p.splits > 1 ? p.slab + (long)blockIdx.y * p.M * p.N : nullptr;
-  float bias_v[4], sb4[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-    bias_v[j] = (mode != 0 && p.bias && n < p.N) ? p.bias[n] : 0.f;
-    sb4[j] = hp_inv_scale_from_amax(p.b_amax[min(n, p.N - 1)]);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int m = m0 + wr * 64 + i * 16 + 4 * (lane >> 4) + reg;
-      const bool mok = m < p.M;
-      const int mc = mok ? m : 0;
-      const float sa = hp_inv_scale_from_amax(p.a_amax[mc]);
-      float* crow = mode == 0 ? slab + (long)mc * p.N : p.C + (long)(mc / p.c_div) * p.c_so + (long)(mc % p.c_div) * p.c_si;
-      float old[4] = {0.f, 0.f, 0.f, 0.f};
-      if (mode == 2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-          if (mok && n < p.N) old[j] = crow[n];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-        if (mok && n < p.N) crow[n] = acc[i][j][reg] * sa * sb4[j] + bias_v[j] + old[j];
-      }
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256) hp_splitk_reduce_kernel(const HpGemmK p) {
   const long total = (long)p.M * p.N;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -752,8 +519,6 @@ __global__ void __launch_bounds__(256) hp_splitk_reduce_kernel(const HpGemmK p) 
 }  // namespace
 
 // internal entry points shared with lstm.hip -------------------------------------------------------------------------
-bool hp_gemm_3stage() { return getenv("RNNT_GEMM_HP_3STAGE") != nullptr; }
-
 size_t hp_plane_bytes(int64_t rows, int64_t K) { return (size_t)rows * (size_t)ceil_div(K, 32) * 128; }
 
 int hp_colmax(const float* x, int64_t rows, int64_t C, int64_t ld, uint32_t* amax, hipStream_t s) {
@@ -801,7 +566,7 @@ int hp_split_both(const float* x, int64_t M, int64_t C, int64_t ld, const uint32
 }
 
 size_t hp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  const long tiles = ceil_div(M, HP_BM) * ceil_div(N, HP_BN);   // the coarser tiling: an upper bound on the splits either kernel takes
+  const long tiles = ceil_div(M, HP_BM) * ceil_div(N, HP_BN);
   const long nkt = ceil_div(K, HP_BK);
   if (tiles >= 192 || nkt < 64) return 0;
   long want = ceil_div(256, tiles);
@@ -828,14 +593,12 @@ int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t
   k.C = C; k.c_div = (int)(c_div > 0x7fffffff ? 0x7fffffff : c_div); k.c_so = c_so; k.c_si = c_si;
   k.bias = bias; k.flags = flags;
   k.a_rowidx = a_rowidx; k.c_rowidx = c_rowidx;
-  const bool k3 = hp_gemm_3stage() && !a_rowidx && !c_rowidx;   // opt-in: 256x128 tiles / 3-stage LDS ring (measured 10-14 % slower than 256x256 / 2 stages)
-  const bool f16 = (flags & RNNT_GEMM_HP_F16) != 0u && !k3;   // (the 3-stage variant declines the one-product form)
-  k.tiles_m = (int)ceil_div(M, HP_BM); k.tiles_n = (int)ceil_div(N, k3 ? HP3_BN : HP_BN);
+  const bool f16 = (flags & RNNT_GEMM_HP_F16) != 0u;
+  k.tiles_m = (int)ceil_div(M, HP_BM); k.tiles_n = (int)ceil_div(N, HP_BN);
   const int tiles = k.tiles_m * k.tiles_n;
   {  // band height of the tile walk: 8 x 4 tiles in flight per XCD when an XCD's share is >= 32 tiles, 4 x 2 for the small outputs
     static const int env_gm = getenv("RNNT_GEMM_HP_GROUP_M") ? atoi(getenv("RNNT_GEMM_HP_GROUP_M")) : -1;
     k.group_m = env_gm >= 0 ? env_gm : (tiles >= 256 ? 8 : 4);
-    if (k3) k.group_m = 0;
   }
   int splits = 1;
   if (workspace && tiles < 192 && k.nkt >= 64) {  // too few tiles for 256 CUs and a deep contraction (weight gradients): split K
@@ -850,13 +613,11 @@ int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t
   splits = (int)ceil_div(k.nkt, k.kt_per_split);
   k.splits = splits;
   k.slab = (float*)workspace;
-  if (k3) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HP3_NST * HP3_STAGE));
-  else if (f16) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
+  if (f16) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
   else RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
   {
     ProfScope prof(RNNT_K_GEMM_HP, 2.0 * (double)M * (double)N * (double)K, s);
-    if (k3) hipLaunchKernelGGL(gemm_hp3_kernel, dim3(tiles, splits), dim3(512), HP3_NST * HP3_STAGE, s, k);
-    else if (f16) hipLaunchKernelGGL(gemm_hp_kernel<true>, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
+    if (f16) hipLaunchKernelGGL(gemm_hp_kernel<true>, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
     else hipLaunchKernelGGL(gemm_hp_kernel<false>, dim3(tiles, splits), dim3(512), 2 * HP_STAGE, s, k);
     RNNT_CHECK_LAUNCH();
     if (splits > 1) {

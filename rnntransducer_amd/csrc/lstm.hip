@@ -1525,8 +1525,7 @@ bool make_plan3(int B, int H, int D, int cus, bool bwd, Plan2* pl) {
   // (its backward keeps one of the six output blocks' W_hh pieces in LDS: with all 216 operand registers per lane it spilled 66-80
   //  and lost to the 16-unit / 4-wave form, 66.0 vs 63.8 ms per c5 step; with 180 it takes 45.5)
   (void)bwd;
-  const bool h640 = nks == 5 && !getenv("RNNT_LSTM_NO_H640_FORM");
-  if ((nks >= 6 || h640) && getenv("RNNT_LSTM_NO_8WAVE")) return false;
+  const bool h640 = nks == 5;
   const int MB = h640 ? 5 : 4, HS = 4 * MB;
   const int NC = H / HS;
   const int Gmax = cus / (D * NC);
@@ -1640,29 +1639,6 @@ int launch_persistent(K kernel, const LstmK& k, const Plan& pl, size_t lds, hipS
   return RNNT_OK;
 }
 
-#define DISPATCH_HS_BQ_C(KERNEL, C, pl, ...)                                                \
-  do {                                                                                      \
-    const int key_ = (pl).HS * 10 + (pl).BQ;                                                \
-    switch (key_) {                                                                         \
-      case 41: rc = launch_persistent2(KERNEL<4, 1, C>, __VA_ARGS__); break;                \
-      case 42: rc = launch_persistent2(KERNEL<4, 2, C>, __VA_ARGS__); break;                \
-      case 44: rc = launch_persistent2(KERNEL<4, 4, C>, __VA_ARGS__); break;                \
-      case 81: rc = launch_persistent2(KERNEL<8, 1, C>, __VA_ARGS__); break;                \
-      case 82: rc = launch_persistent2(KERNEL<8, 2, C>, __VA_ARGS__); break;                \
-      case 84: rc = launch_persistent2(KERNEL<8, 4, C>, __VA_ARGS__); break;                \
-      case 161: rc = launch_persistent2(KERNEL<16, 1, C>, __VA_ARGS__); break;              \
-      case 162: rc = launch_persistent2(KERNEL<16, 2, C>, __VA_ARGS__); break;              \
-      case 164: rc = launch_persistent2(KERNEL<16, 4, C>, __VA_ARGS__); break;              \
-      default: set_error("lstm: no v2 kernel for HS=%d BQ=%d", (pl).HS, (pl).BQ); rc = RNNT_ERR_UNSUPPORTED; \
-    }                                                                                       \
-  } while (0)
-#define DISPATCH_HS_BQ(KERNEL, cell, pl, ...)                                               \
-  do {                                                                                      \
-    if ((cell) == RNNT_CELL_LSTM) DISPATCH_HS_BQ_C(KERNEL, 0, pl, __VA_ARGS__);             \
-    else if ((cell) == RNNT_CELL_GRU) DISPATCH_HS_BQ_C(KERNEL, 1, pl, __VA_ARGS__);         \
-    else DISPATCH_HS_BQ_C(KERNEL, 2, pl, __VA_ARGS__);                                      \
-  } while (0)
-
 int check_desc(const rnnt_lstm_desc* d, Plan* pl, LstmWs* w) {
   RNNT_CHECK_ARG(d != nullptr, "lstm: null descriptor");
   RNNT_CHECK_ARG(d->T >= 1 && d->I >= 1, "lstm: T and I must be positive (T=%d I=%d)", d->T, d->I);
@@ -1727,12 +1703,12 @@ bool shape_takes_row_idx(int T, int B, int I, int H, int D, int cell, int cus) {
   return use_hp(T, B, I, H, D) && I >= 32 && T > 1 && make_plan3(B, H, D, cus, true, &p2) && lstm5_supported(T, B, H, D, cell);
 }
 // RNNT_PRECISION_F16 is honoured where the WHOLE layer runs the forms that have a one-product variant: v5 recurrences in both
-// directions of time and the half-pair products (gemm_hp.hip's default kernel).  Everywhere else the layer computes in fp32, bitwise
+// directions of time and the half-pair products (gemm_hp.hip).  Everywhere else the layer computes in fp32, bitwise
 // what RNNT_PRECISION_FP32 computes.  Same answer in the forward and the backward call of a layer (it depends on the shape only).
 bool shape_takes_f16(int T, int B, int I, int H, int D, int cell, int cus) {
   Plan2 pf, pb;
   return use_hp(T, B, I, H, D) && make_plan3(B, H, D, cus, false, &pf) && make_plan3(B, H, D, cus, true, &pb) &&
-         lstm5_supported(T, B, H, D, cell) && !hp_gemm_3stage();
+         lstm5_supported(T, B, H, D, cell);
 }
 bool ragged_plan(const rnnt_lstm_desc* d, const LstmWs& w, int cus) {
   return d->row_idx && d->n_rows > 0 && d->n_rows < (int64_t)d->T * d->B && w.hp && d->x_sb == d->I && d->x_st == (int64_t)d->B * d->I &&
@@ -1796,23 +1772,6 @@ extern "C" size_t rnnt_hip_lstm_workspace_bytes(int32_t T, int32_t B, int32_t I,
   return carve_lstm(nullptr, T, B, I, H, D, pl).total;
 }
 
-#define DISPATCH_MT_NT(KERNEL, pl, ...)                                                     \
-  do {                                                                                      \
-    const int key_ = (pl).MT * 10 + (pl).NT;                                                \
-    switch (key_) {                                                                         \
-      case 11: rc = launch_persistent(KERNEL<1, 1>, __VA_ARGS__); break;                    \
-      case 12: rc = launch_persistent(KERNEL<1, 2>, __VA_ARGS__); break;                    \
-      case 14: rc = launch_persistent(KERNEL<1, 4>, __VA_ARGS__); break;                    \
-      case 21: rc = launch_persistent(KERNEL<2, 1>, __VA_ARGS__); break;                    \
-      case 22: rc = launch_persistent(KERNEL<2, 2>, __VA_ARGS__); break;                    \
-      case 24: rc = launch_persistent(KERNEL<2, 4>, __VA_ARGS__); break;                    \
-      case 41: rc = launch_persistent(KERNEL<4, 1>, __VA_ARGS__); break;                    \
-      case 42: rc = launch_persistent(KERNEL<4, 2>, __VA_ARGS__); break;                    \
-      case 44: rc = launch_persistent(KERNEL<4, 4>, __VA_ARGS__); break;                    \
-      default: set_error("lstm: no kernel for MT=%d NT=%d", (pl).MT, (pl).NT); rc = RNNT_ERR_UNSUPPORTED; \
-    }                                                                                       \
-  } while (0)
-
 static int lstm_fwd_impl(const rnnt_lstm_desc* d, uint32_t precision, void* stream) {
   Plan pl;
   LstmWs w;
@@ -1868,48 +1827,48 @@ static int lstm_fwd_impl(const rnnt_lstm_desc* d, uint32_t precision, void* stre
   };
   if (make_plan3(d->B, d->H, d->D, cus, false, &p2)) {
     adopt(p2);
-    const int nks = p2.Kp / 128;
-#define LAUNCH_V3(N)                                                                                              \
-    do {                                                                                                          \
-      if (d->cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd3_kernel<N, 0>, k, p2, p2.lds_fwd, s, "lstm_fwd3"); \
-      else if (d->cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd3_kernel<N, 1>, k, p2, p2.lds_fwd, s, "lstm_fwd3"); \
-      else rc = launch_persistent2(lstm_fwd3_kernel<N, 2>, k, p2, p2.lds_fwd, s, "lstm_fwd3");                     \
-    } while (0)
+    const int nks = p2.Kp / 128, c = cell_form(d->cell);
     if (lstm5_supported(d->T, d->B, d->H, d->D, d->cell)) {  // v5: tagged-payload exchange, f16 matrix cores (lstm5.hip)
       rc = lstm5_fwd_launch(k, p2, d->cell, s, f16);
     } else if (p2.MB == 5) {  // H = 640: 5 blocks, 8 waves x 3 k-steps over K padded to 768
       const size_t lds5 = p2.lds_fwd + 8 * 1 * 3 * 3 * 1024;  // one of the five blocks' pieces in LDS
-      if (d->cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd3_kernel<3, 0, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
-      else if (d->cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd3_kernel<3, 1, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
-      else rc = launch_persistent2(lstm_fwd3_kernel<3, 2, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
-    } else if (nks == 4 && !getenv("RNNT_LSTM_NO_8WAVE")) {  // H = 512 forward: 8 waves x 2 k-steps (12.5 vs 13.1 ms per c2 step)
-      p2.lds_fwd = (size_t)8 * 4 * 64 * 16 + 16;
-      if (d->cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd3_kernel<2, 0, 8>, k, p2, p2.lds_fwd, s, "lstm_fwd3", 512);
-      else if (d->cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd3_kernel<2, 1, 8>, k, p2, p2.lds_fwd, s, "lstm_fwd3", 512);
-      else rc = launch_persistent2(lstm_fwd3_kernel<2, 2, 8>, k, p2, p2.lds_fwd, s, "lstm_fwd3", 512);
-    } else if (nks == 1) LAUNCH_V3(1);
-    else if (nks == 2) LAUNCH_V3(2);
-    else if (nks == 3) LAUNCH_V3(3);
-    else if (nks == 4) LAUNCH_V3(4);
-    else if (nks == 5) LAUNCH_V3(5);
-    else {  // H = 768 / 1024: 8 waves x 3 / 4 k-steps
-#define LAUNCH_V38(N)                                                                                                       \
-      do {  /* one of the four blocks' pieces in LDS */                                                                     \
-        const size_t lds8 = p2.lds_fwd + 8 * 1 * (N) * 3 * 1024;                                                            \
-        if (d->cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd3_kernel<N, 0, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512); \
-        else if (d->cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd3_kernel<N, 1, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512); \
-        else rc = launch_persistent2(lstm_fwd3_kernel<N, 2, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512);                     \
-      } while (0)
-      if (nks == 6) LAUNCH_V38(3);
-      else LAUNCH_V38(4);
-#undef LAUNCH_V38
+      rc = dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+        return launch_persistent2(lstm_fwd3_kernel<3, C, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
+      });
+    } else if (nks == 4) {  // H = 512 forward: 8 waves x 2 k-steps (12.5 vs 13.1 ms per c2 step)
+      const size_t lds = (size_t)8 * 4 * 64 * 16 + 16;
+      rc = dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+        return launch_persistent2(lstm_fwd3_kernel<2, C, 8>, k, p2, lds, s, "lstm_fwd3", 512);
+      });
+    } else if (nks <= 3) {
+      rc = dispatch<1, 2, 3>(nks, "lstm_fwd3 k-steps", [&](auto N) {
+        return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+          return launch_persistent2(lstm_fwd3_kernel<N, C>, k, p2, p2.lds_fwd, s, "lstm_fwd3");
+        });
+      });
+    } else {  // H = 768 / 1024: 8 waves x 3 / 4 k-steps
+      rc = dispatch<3, 4>(p2.Kp / (32 * 8), "lstm_fwd3 k-steps", [&](auto N) {
+        const size_t lds8 = p2.lds_fwd + 8 * 1 * N * 3 * 1024;  // one of the four blocks' pieces in LDS
+        return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+          return launch_persistent2(lstm_fwd3_kernel<N, C, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512);
+        });
+      });
     }
-#undef LAUNCH_V3
   } else if (make_plan2(d->B, d->H, d->D, cus, &p2)) {
     adopt(p2);
-    DISPATCH_HS_BQ(lstm_fwd2_kernel, d->cell, p2, k, p2, p2.lds_fwd, s, "lstm_fwd2");
+    rc = dispatch<4, 8, 16>(p2.HS, "lstm_fwd2 HS", [&](auto HS) {
+      return dispatch<1, 2, 4>(p2.BQ, "lstm_fwd2 BQ", [&](auto BQ) {
+        return dispatch<0, 1, 2>(cell_form(d->cell), "lstm_fwd2 cell", [&](auto C) {
+          return launch_persistent2(lstm_fwd2_kernel<HS, BQ, C>, k, p2, p2.lds_fwd, s, "lstm_fwd2");
+        });
+      });
+    });
   } else if (d->cell == RNNT_CELL_LSTM) {
-    DISPATCH_MT_NT(lstm_fwd_kernel, pl, k, pl, pl.lds_fwd, s, "lstm_fwd");
+    rc = dispatch<1, 2, 4>(pl.MT, "lstm_fwd MT", [&](auto MT) {
+      return dispatch<1, 2, 4>(pl.NT, "lstm_fwd NT", [&](auto NT) {
+        return launch_persistent(lstm_fwd_kernel<MT, NT>, k, pl, pl.lds_fwd, s, "lstm_fwd");
+      });
+    });
   } else {
     set_error("rnn: GRU / Elman cells need the grouped decomposition (B/G <= 16 rows per group); B=%d H=%d does not fit", d->B, d->H);
     rc = RNNT_ERR_UNSUPPORTED;
@@ -1976,20 +1935,7 @@ static int lstm_bwd_impl(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void*
     adopt(p2);
     fused_db = true;
     db_rows = p2.G * 4 * p2.BQ;
-    const int nks = p2.Kp / 128;
-#define LAUNCH_V4_C(N, BQ_, C) rc = launch_persistent2(lstm_bwd4_kernel<2 * (N), BQ_, C>, k, p2, p2.lds_bwd, s, "lstm_bwd4")
-#define LAUNCH_V4_B(N, C)                           \
-    do {                                            \
-      if (p2.BQ == 1) LAUNCH_V4_C(N, 1, C);         \
-      else if (p2.BQ == 2) LAUNCH_V4_C(N, 2, C);    \
-      else LAUNCH_V4_C(N, 4, C);                    \
-    } while (0)
-#define LAUNCH_V4(N)                                               \
-    do {                                                           \
-      if (d->cell == RNNT_CELL_LSTM) LAUNCH_V4_B(N, 0);            \
-      else if (d->cell == RNNT_CELL_GRU) LAUNCH_V4_B(N, 1);        \
-      else LAUNCH_V4_B(N, 2);                                      \
-    } while (0)
+    const int c = cell_form(d->cell);
     if (lstm5_supported(d->T, d->B, d->H, d->D, d->cell)) {  // v5 (lstm5.hip)
       if (w.hp) {  // the recurrence also leaves the column maxima of dG (the scales of the half-pair dG^T planes): no extra pass
         const int64_t Mr = (int64_t)T * B, N4r = (int64_t)D * 4 * H;
@@ -2019,51 +1965,45 @@ static int lstm_bwd_impl(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void*
     } else if (!do_recur) {
       // phase 2: nothing to launch here
     } else if (p2.MB == 5) {  // H = 640: own 80 gate columns (3 k-steps), 48 output blocks over 8 waves
-#define LAUNCH_V45_C(BQ_, C) rc = launch_persistent2(lstm_bwd4_kernel<6, BQ_, C, 8, 5, 1>, k, p2, p2.lds_bwd + 8 * 1 * 3 * 3 * 1024, s, "lstm_bwd4", 512)
-#define LAUNCH_V45_B(C)                           \
-      do {                                        \
-        if (p2.BQ == 1) LAUNCH_V45_C(1, C);       \
-        else if (p2.BQ == 2) LAUNCH_V45_C(2, C);  \
-        else LAUNCH_V45_C(4, C);                  \
-      } while (0)
-      if (d->cell == RNNT_CELL_LSTM) LAUNCH_V45_B(0);
-      else if (d->cell == RNNT_CELL_GRU) LAUNCH_V45_B(1);
-      else LAUNCH_V45_B(2);
-#undef LAUNCH_V45_B
-#undef LAUNCH_V45_C
-    } else if (nks == 1) LAUNCH_V4(1);  // (H = 512 backward with 8 waves: 12.9 vs 11.9 ms per c2 step -> stays at 4)
-    else if (nks == 2) LAUNCH_V4(2);
-    else if (nks == 3) LAUNCH_V4(3);
-    else if (nks == 4) LAUNCH_V4(4);
-    else if (nks == 5) LAUNCH_V4(5);
-    else {  // H = 768 / 1024: 8 waves, 6 / 8 output blocks each
-#define LAUNCH_V48_C(N, BQ_, C) rc = launch_persistent2(lstm_bwd4_kernel<N, BQ_, C, 8, 4, 2>, k, p2, p2.lds_bwd + 8 * 2 * 2 * 3 * 1024, s, "lstm_bwd4", 512)
-#define LAUNCH_V48_B(N, C)                           \
-      do {                                           \
-        if (p2.BQ == 1) LAUNCH_V48_C(N, 1, C);       \
-        else if (p2.BQ == 2) LAUNCH_V48_C(N, 2, C);  \
-        else LAUNCH_V48_C(N, 4, C);                  \
-      } while (0)
-#define LAUNCH_V48(N)                                          \
-      do {                                                     \
-        if (d->cell == RNNT_CELL_LSTM) LAUNCH_V48_B(N, 0);     \
-        else if (d->cell == RNNT_CELL_GRU) LAUNCH_V48_B(N, 1); \
-        else LAUNCH_V48_B(N, 2);                               \
-      } while (0)
-      if (nks == 6) LAUNCH_V48(6);
-      else LAUNCH_V48(8);
-#undef LAUNCH_V48
-#undef LAUNCH_V48_B
-#undef LAUNCH_V48_C
+      rc = dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+        return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
+          return launch_persistent2(lstm_bwd4_kernel<6, BQ, C, 8, 5, 1>, k, p2, p2.lds_bwd + 8 * 1 * 3 * 3 * 1024, s, "lstm_bwd4", 512);
+        });
+      });
+    } else if (p2.Kp <= 512) {  // (H = 512 backward with 8 waves: 12.9 vs 11.9 ms per c2 step -> stays at 4)
+      rc = dispatch<2, 4, 6, 8>(p2.Kp / (16 * 4), "lstm_bwd4 output blocks", [&](auto NOB) {
+        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+          return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
+            return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd4");
+          });
+        });
+      });
+    } else {  // H = 768 / 1024: 8 waves, 6 / 8 output blocks each
+      rc = dispatch<6, 8>(p2.Kp / (16 * 8), "lstm_bwd4 output blocks", [&](auto NOB) {
+        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+          return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
+            return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C, 8, 4, 2>, k, p2, p2.lds_bwd + 8 * 2 * 2 * 3 * 1024, s, "lstm_bwd4", 512);
+          });
+        });
+      });
     }
-#undef LAUNCH_V4
-#undef LAUNCH_V4_B
-#undef LAUNCH_V4_C
   } else if (make_plan2(d->B, d->H, d->D, cus, &p2)) {
     adopt(p2);
-    if (do_recur) DISPATCH_HS_BQ(lstm_bwd2_kernel, d->cell, p2, k, p2, p2.lds_bwd, s, "lstm_bwd2");
+    if (do_recur)
+      rc = dispatch<4, 8, 16>(p2.HS, "lstm_bwd2 HS", [&](auto HS) {
+        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd2 BQ", [&](auto BQ) {
+          return dispatch<0, 1, 2>(cell_form(d->cell), "lstm_bwd2 cell", [&](auto C) {
+            return launch_persistent2(lstm_bwd2_kernel<HS, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd2");
+          });
+        });
+      });
   } else if (d->cell == RNNT_CELL_LSTM) {
-    if (do_recur) DISPATCH_MT_NT(lstm_bwd_kernel, pl, k, pl, pl.lds_bwd, s, "lstm_bwd");
+    if (do_recur)
+      rc = dispatch<1, 2, 4>(pl.MT, "lstm_bwd MT", [&](auto MT) {
+        return dispatch<1, 2, 4>(pl.NT, "lstm_bwd NT", [&](auto NT) {
+          return launch_persistent(lstm_bwd_kernel<MT, NT>, k, pl, pl.lds_bwd, s, "lstm_bwd");
+        });
+      });
   } else {
     set_error("rnn: GRU / Elman cells need the grouped decomposition; B=%d H=%d does not fit", d->B, d->H);
     rc = RNNT_ERR_UNSUPPORTED;

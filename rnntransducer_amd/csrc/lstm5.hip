@@ -95,8 +95,8 @@ __device__ __forceinline__ bool poll_tagged(F&& load_and_check, unsigned* status
 // ================================================================================================
 // forward.  dynamic LDS: part[2 parities][NWV waves][MB blocks][64] f32x4 | wmax[8] | abort | pubs[16][HS]
 // NKS: 32-deep k-steps per wave (Kp = NWV * 32 * NKS >= H, zero padded).  CELL: 0 LSTM, 1 GRU, 2 tanh Elman RNN.
-// NWV x MB: 4 x 4 (H = 128..512: 16 units per workgroup), 8 x 5 (H = 640: 20 units per workgroup so that a sync group has 32
-// members and fits one XCD; K padded to 768) or 8 x 4 (H = 768 / 1024: NKS = 3 / 4, 48 / 64 workgroups per group).  Wave w < MB owns gate-column block w (one cell per lane).
+// NWV x MB: 4 x 4 (H = 128..384: 16 units per workgroup), 8 x 5 (H = 640: 20 units per workgroup so that a sync group has 32
+// members and fits one XCD; K padded to 768) or 8 x 4 (H = 512 / 768 / 1024: NKS = 2 / 3 / 4, 32 / 48 / 64 workgroups per group).  Wave w < MB owns gate-column block w (one cell per lane).
 // F16: one-product form (whi . h_hi only).
 // ================================================================================================
 template <int NKS, int CELL, int NWV = 4, int MB = 4, bool F16 = false>
@@ -405,8 +405,8 @@ __global__ void __launch_bounds__(64 * NWV) lstm_fwd5_kernel(const LstmK p) {
 //   Arithmetic: dG rows scaled per (row, workgroup) by a power of two from the row's maximum over the 64 own columns (LDS
 //   ds_max), W_hh by the slice maximum; 3 f16 products; the product is descaled before it is published.
 // dynamic LDS: red[NT] f32x4 | dgs[16][DGS_LD] float | rowexp[2][16] | wmax[8] | abort
-// NMB: 16-unit output blocks per wave (Kp / 16 / NWV).  NWV x MB: 4 x 4 (H = 128..512), 8 x 5 (H = 640, K padded to 768) or 8 x 4
-// (H = 768 / 1024: 48 / 64 producers per group, NCMAX = 64; such a group spans XCDs and runs the write-through exchange).
+// NMB: 16-unit output blocks per wave (Kp / 16 / NWV).  NWV x MB: 8 x 5 (H = 640, K padded to 768) or 8 x 4 (H = 768 / 1024: 48 / 64
+// producers per group, NCMAX = 64; such a group spans XCDs and runs the write-through exchange); H <= 512 runs lstm_bwd5f_kernel.
 // F16: one-product form (whi . dG_hi only).
 // ================================================================================================
 template <int NMB, int BQ, int CELL, int NWV = 4, int MB = 4, int NCMAX = 32, bool F16 = false>
@@ -755,8 +755,8 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5_kernel(const LstmK p) {
 }
 
 // ================================================================================================
-// backward, ONE barrier per step (H = 128..512: 4 waves x 16 units, <= 32 producers per group; lstm_bwd5_kernel keeps the other shapes
-// and is the A/B partner: RNNT_LSTM_BWD5_2B=1).  Same decomposition, exchange protocol and arithmetic as lstm_bwd5_kernel; what
+// backward, ONE barrier per step (H = 128..384: 4 waves x 16 units, H = 512: 8 waves; <= 32 producers per group; lstm_bwd5_kernel keeps
+// the other shapes).  Same decomposition, exchange protocol and arithmetic as lstm_bwd5_kernel; what
 // changed is who does what inside the workgroup (profiles/r02_lstm_phase_cycles_v5_final.txt: of 4 521 cycles per step 748 were
 // "partial sums + barrier" and 2 021 "scale + MFMA + publication", where every wave converted the whole 16 x 64 dG image to f16 pairs):
 //   1. Wave w gathers AND owns exchange rows w*BQ .. w*BQ+BQ-1: lane = class * PPW + (unit quad * BQ + row), class = the producers
@@ -1194,17 +1194,16 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd5f_kernel(const LstmK p) {
 }  // namespace
 
 // host side ----------------------------------------------------------------------------------------------------
-// v5 takes H in {128, 256, 384, 512} (4 waves x 16 units) and H = 640 (8 waves x 20 units, K padded to 768), cells LSTM / GRU /
+// v5 takes H in {128, 256, 384, 512} (16 units per workgroup) and H = 640 (8 waves x 20 units, K padded to 768), cells LSTM / GRU /
 // tanh RNN; everything else stays on v3 / v4
 bool lstm5_supported(int T, int B, int H, int D, int cell) {
   if (getenv("RNNT_LSTM_NO_V5") || getenv("RNNT_LSTM_V1") || getenv("RNNT_LSTM_V2") || getenv("RNNT_LSTM_EXACT_MATH")) return false;
   if ((long)T * B * D * 4 * H * 4 >= (1l << 31)) return false;   // the stash is addressed with 32-bit buffer offsets
-  const bool h640 = H == 640 && !getenv("RNNT_LSTM_NO_H640_FORM") && !getenv("RNNT_LSTM_NO_8WAVE");
   // H = 768 / 1024 (8 waves, 48 / 64 workgroups per group): opt-in.  Such a group spans XCDs, every step moves 16 rows x H x 4 B to
   // each of its workgroups through the fabric, and the shipped config (8 x 1024 bi-GRU, B = 16) measured 152.5 ms per step against
   // 146.7 with lstm.hip's v3 / v4 forms (154.0 vs 145.6 with one 16-row group per direction instead of two 8-row groups).
-  const bool wide = (H == 768 || H == 1024) && getenv("RNNT_LSTM_V5_WIDE") && !getenv("RNNT_LSTM_NO_8WAVE");
-  return ((H % 128 == 0 && H >= 128 && H <= 512) || h640 || wide) && cell != RNNT_CELL_RNN_RELU;
+  const bool wide = (H == 768 || H == 1024) && getenv("RNNT_LSTM_V5_WIDE");
+  return ((H % 128 == 0 && H >= 128 && H <= 512) || H == 640 || wide) && cell != RNNT_CELL_RNN_RELU;
 }
 
 static int env_pause(const char* name) {   // "e" or "e,l"
@@ -1223,48 +1222,30 @@ static int fwd_launch_t(const LstmK& k_in, const Plan2& pl, int cell, hipStream_
   // profiles/r02_poll_pause_ab.txt): 8-row groups at H = 512 (c2) 6.30 -> 6.10 ms of forward recurrences per step with 8 x 64 cycles,
   // H = 640 (c5) 17.8 -> 17.4 with 6; 4-row groups (c3) lose 3 % with any pause.
   { const int e = env_pause("RNNT_LSTM_FWD_PAUSE"); k.pause = e >= 0 ? e : (pl.Bg >= 8 ? (k.H == 640 ? 6 : 8) : 0); }
-  const int nks = k.Kp / 128;
-  int rc = RNNT_ERR_UNSUPPORTED;
+  const int c = cell_form(cell);
   if (pl.MB == 5) {   // H = 640
     const size_t lds = (size_t)2 * 8 * 5 * 64 * 16 + 32 + 16 + 16 * 20 * 4;
-    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<3, 0, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
-    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<3, 1, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
-    else rc = launch_persistent2(lstm_fwd5_kernel<3, 2, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
-    return rc;
+    return dispatch<0, 1, 2>(c, "lstm_fwd5 cell", [&](auto C) {
+      return launch_persistent2(lstm_fwd5_kernel<3, C, 8, 5, F16>, k, pl, lds, s, "lstm_fwd5", 512);
+    });
   }
   // H = 512: 8 waves x 2 k-steps instead of 4 x 4.  The MFMA phase is pipe-bound either way (192 MFMAs per workgroup and step on 4
   // SIMDs = 768 cycles) but 8 waves spread the operand polls, the de-interleave and the stash over twice the issue slots:
-  // 4 900 vs 5 324 cycles per step, 31.4 vs 32.1 ms per c2 step (profiles/r02_lstm_phase_cycles_v5.txt).  RNNT_LSTM_FWD5_4W=1: 4 waves.
-  const bool w8 = k.H == 512 && !getenv("RNNT_LSTM_FWD5_4W") && !getenv("RNNT_LSTM_NO_8WAVE");
-  if (k.H > 512 || w8) {   // H = 768 / 1024: 8 waves x 3 / 4 k-steps each
+  // 4 900 vs 5 324 cycles per step, 31.4 vs 32.1 ms per c2 step (profiles/r02_lstm_phase_cycles_v5.txt).
+  if (k.H >= 512) {   // H = 512 / 768 / 1024: 8 waves x 2 / 3 / 4 k-steps each
     const size_t lds = (size_t)2 * 8 * 4 * 64 * 16 + 32 + 16 + 16 * 16 * 4;
-#define L58(N)                                                                                                       \
-    do {                                                                                                             \
-      if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);      \
-      else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);  \
-      else rc = launch_persistent2(lstm_fwd5_kernel<N, 2, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);                   \
-    } while (0)
-    if (k.Kp == 768) L58(3);
-    else if (k.Kp == 1024) L58(4);
-    else if (k.Kp == 512) L58(2);
-    else set_error("lstm_fwd5: H = %d not supported", k.H);
-#undef L58
-    return rc;
+    return dispatch<2, 3, 4>(k.Kp / (32 * 8), "lstm_fwd5 k-steps", [&](auto N) {
+      return dispatch<0, 1, 2>(c, "lstm_fwd5 cell", [&](auto C) {
+        return launch_persistent2(lstm_fwd5_kernel<N, C, 8, 4, F16>, k, pl, lds, s, "lstm_fwd5", 512);
+      });
+    });
   }
   const size_t lds = (size_t)2 * 4 * 4 * 64 * 16 + 32 + 16 + 16 * 16 * 4;
-#define L5(N)                                                                                              \
-  do {                                                                                                     \
-    if (cell == RNNT_CELL_LSTM) rc = launch_persistent2(lstm_fwd5_kernel<N, 0, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");      \
-    else if (cell == RNNT_CELL_GRU) rc = launch_persistent2(lstm_fwd5_kernel<N, 1, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");  \
-    else rc = launch_persistent2(lstm_fwd5_kernel<N, 2, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");                      \
-  } while (0)
-  if (nks == 1) L5(1);
-  else if (nks == 2) L5(2);
-  else if (nks == 3) L5(3);
-  else if (nks == 4) L5(4);
-  else set_error("lstm_fwd5: H = %d not supported", k.H);
-#undef L5
-  return rc;
+  return dispatch<1, 2, 3>(k.Kp / (32 * 4), "lstm_fwd5 k-steps", [&](auto N) {
+    return dispatch<0, 1, 2>(c, "lstm_fwd5 cell", [&](auto C) {
+      return launch_persistent2(lstm_fwd5_kernel<N, C, 4, 4, F16>, k, pl, lds, s, "lstm_fwd5");
+    });
+  });
 }
 
 template <bool F16>
@@ -1273,96 +1254,43 @@ static int bwd_launch_t(const LstmK& k_in, const Plan2& pl, int cell, hipStream_
   // one-barrier form: c2 7.83 -> 7.55 ms of backward recurrences per step with 8 x 64 cycles, c3 13.4 -> 13.1; 12 and more lose again
   const int env_p = env_pause("RNNT_LSTM_BWD_PAUSE");
   k.pause = env_p >= 0 ? env_p : 0;   // lstm_bwd5_kernel (H = 640 at c5): any pause loses (22.3 -> 22.6 ms with 4, 24.0 with 12)
-  const int nks = k.Kp / 128;
-  int rc = RNNT_ERR_UNSUPPORTED;
-#define B5Q(NM, C, ...)                                                                               \
-  do {                                                                                                \
-    if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5_kernel<NM, 1, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);       \
-    else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5_kernel<NM, 2, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);  \
-    else rc = launch_persistent2(lstm_bwd5_kernel<NM, 4, C, __VA_ARGS__, F16>, k, pl, lds, s, "lstm_bwd5", threads);                  \
-  } while (0)
+  const int c = cell_form(cell);
   if (pl.MB == 5) {   // H = 640: 80 own gate columns (3 k-steps), 48 output blocks over 8 waves
-    const int threads = 512;
     const size_t lds = (size_t)512 * 16 + 16 * (32 * 3 + 4) * 4 + 32 * 4 + 32 + 16;
-    if (cell == RNNT_CELL_LSTM) B5Q(6, 0, 8, 5, 32);
-    else if (cell == RNNT_CELL_GRU) B5Q(6, 1, 8, 5, 32);
-    else B5Q(6, 2, 8, 5, 32);
-    return rc;
+    return dispatch<1, 2, 4>(pl.BQ, "lstm_bwd5 BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(c, "lstm_bwd5 cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd5_kernel<6, BQ, C, 8, 5, 32, F16>, k, pl, lds, s, "lstm_bwd5", 512);
+      });
+    });
   }
-  // (H = 512 with 8 waves x 4 output blocks: the MFMA + publication phase drops from 1 961 to 1 432 cycles but the wait for the
-  //  partial sums grows from 768 to 1 894: 5 953 vs 5 156 cycles per step -> stays at 4 waves)
   if (k.H > 512) {   // H = 768 / 1024: 8 waves, 6 / 8 output blocks each, up to 64 producers per group
-    const int threads = 512;
     const size_t lds = (size_t)512 * 16 + 16 * (32 * 2 + 4) * 4 + 32 * 4 + 32 + 16;
-#define B58(NM)                                          \
-    do {                                                 \
-      if (cell == RNNT_CELL_LSTM) B5Q(NM, 0, 8, 4, 64);  \
-      else if (cell == RNNT_CELL_GRU) B5Q(NM, 1, 8, 4, 64); \
-      else B5Q(NM, 2, 8, 4, 64);                         \
-    } while (0)
-    if (k.Kp == 768) B58(6);
-    else if (k.Kp == 1024) B58(8);
-    else set_error("lstm_bwd5: H = %d not supported", k.H);
-#undef B58
-    return rc;
+    return dispatch<6, 8>(k.Kp / (16 * 8), "lstm_bwd5 output blocks", [&](auto NM) {
+      return dispatch<1, 2, 4>(pl.BQ, "lstm_bwd5 BQ", [&](auto BQ) {
+        return dispatch<0, 1, 2>(c, "lstm_bwd5 cell", [&](auto C) {
+          return launch_persistent2(lstm_bwd5_kernel<NM, BQ, C, 8, 4, 64, F16>, k, pl, lds, s, "lstm_bwd5", 512);
+        });
+      });
+    });
   }
-  if (k.H == 512 && getenv("RNNT_LSTM_BWD5_8W")) {   // 8 waves x 4 output blocks (two waves per SIMD share the MFMA pipe)
-    const int threads = 512;
-    const size_t lds = (size_t)512 * 16 + 16 * (32 * 2 + 4) * 4 + 32 * 4 + 32 + 16;
-    if (cell == RNNT_CELL_LSTM) B5Q(4, 0, 8, 4, 32);
-    else if (cell == RNNT_CELL_GRU) B5Q(4, 1, 8, 4, 32);
-    else B5Q(4, 2, 8, 4, 32);
-    return rc;
+  // H <= 512: the one-barrier form
+  if (env_p < 0) k.pause = 8 | (8 << 8);
+  const size_t lds = (size_t)2 * 2 * 16 * (32 * 2 + 8) * 2 + 32 * 4 + 32 + 16;
+  if (k.Kp == 512) {   // H = 512: 8 waves x 4 output blocks (two waves per SIMD keep the MFMA pipe busy; one wave issues a
+                       // v_mfma_f32_16x16x32_f16 only every 20-25 cycles), waves 4..7 share the MFMA + publication phase only
+    return dispatch<1, 2, 4>(pl.BQ, "lstm_bwd5f BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(c, "lstm_bwd5f cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd5f_kernel<4, BQ, C, 8, F16>, k, pl, lds, s, "lstm_bwd5f", 512);
+      });
+    });
   }
-  if (!getenv("RNNT_LSTM_BWD5_2B")) {   // one-barrier form (default); RNNT_LSTM_BWD5_2B=1: lstm_bwd5_kernel (A/B partner)
-    if (env_p < 0) k.pause = 8 | (8 << 8);
-    const int threads = 256;
-    const size_t lds = (size_t)2 * 2 * 16 * (32 * 2 + 8) * 2 + 32 * 4 + 32 + 16;
-#define B5F(NM)                                                                                                   \
-    do {                                                                                                          \
-      if (cell == RNNT_CELL_LSTM) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);       \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 0, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
-      else if (cell == RNNT_CELL_GRU) { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);  \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 1, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
-      else { if (pl.BQ == 1) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 1, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else if (pl.BQ == 2) rc = launch_persistent2(lstm_bwd5f_kernel<NM, 2, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads);                             \
-        else rc = launch_persistent2(lstm_bwd5f_kernel<NM, 4, 2, 4, F16>, k, pl, lds, s, "lstm_bwd5f", threads); }                                             \
-    } while (0)
-    if (nks == 4 && !getenv("RNNT_LSTM_BWD5F_4W")) {   // H = 512: 8 waves x 4 output blocks (two waves per SIMD keep the MFMA pipe busy; one wave issues a
-      const int threads8 = 512;                         // v_mfma_f32_16x16x32_f16 only every 20-25 cycles), waves 4..7 share the MFMA + publication phase only
-#define B5F8(BQV, C) rc = launch_persistent2(lstm_bwd5f_kernel<4, BQV, C, 8, F16>, k, pl, lds, s, "lstm_bwd5f", threads8)
-      if (cell == RNNT_CELL_LSTM) { if (pl.BQ == 1) B5F8(1, 0); else if (pl.BQ == 2) B5F8(2, 0); else B5F8(4, 0); }
-      else if (cell == RNNT_CELL_GRU) { if (pl.BQ == 1) B5F8(1, 1); else if (pl.BQ == 2) B5F8(2, 1); else B5F8(4, 1); }
-      else { if (pl.BQ == 1) B5F8(1, 2); else if (pl.BQ == 2) B5F8(2, 2); else B5F8(4, 2); }
-#undef B5F8
-      return rc;
-    }
-    if (nks == 1) B5F(2);
-    else if (nks == 2) B5F(4);
-    else if (nks == 3) B5F(6);
-    else if (nks == 4) B5F(8);
-    else set_error("lstm_bwd5: H = %d not supported", k.H);
-#undef B5F
-    return rc;
-  }
-  const int threads = 256;
-  const size_t lds = (size_t)256 * 16 + 16 * (32 * 2 + 4) * 4 + 32 * 4 + 32 + 16;
-#define B5(NM)                                       \
-  do {                                               \
-    if (cell == RNNT_CELL_LSTM) B5Q(NM, 0, 4, 4, 32);          \
-    else if (cell == RNNT_CELL_GRU) B5Q(NM, 1, 4, 4, 32);      \
-    else B5Q(NM, 2, 4, 4, 32);                                 \
-  } while (0)
-  if (nks == 1) B5(2);
-  else if (nks == 2) B5(4);
-  else if (nks == 3) B5(6);
-  else if (nks == 4) B5(8);
-  else set_error("lstm_bwd5: H = %d not supported", k.H);
-#undef B5
-#undef B5Q
-  return rc;
+  return dispatch<2, 4, 6>(k.Kp / (16 * 4), "lstm_bwd5f output blocks", [&](auto NM) {
+    return dispatch<1, 2, 4>(pl.BQ, "lstm_bwd5f BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(c, "lstm_bwd5f cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd5f_kernel<NM, BQ, C, 4, F16>, k, pl, lds, s, "lstm_bwd5f");
+      });
+    });
+  });
 }
 
 int lstm5_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s, bool f16) {

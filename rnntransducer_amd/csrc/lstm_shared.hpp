@@ -187,6 +187,18 @@ inline int device_cus() {
   return cus;
 }
 
+// The recurrence kernels' CELL template argument: 0 LSTM, 1 GRU, 2 both Elman cells (tanh or ReLU is chosen by p.cell at run time).
+inline int cell_form(int cell) { return cell == RNNT_CELL_LSTM ? 0 : (cell == RNNT_CELL_GRU ? 1 : 2); }
+
+// Launch-site dispatch on a run-time value: calls f(std::integral_constant<int, V>{}) for the one V among Vs equal to v and returns
+// its result; RNNT_ERR_UNSUPPORTED (with the error text) when none is.  Only the listed Vs are instantiated, so each launch site names
+// exactly the kernels it can launch.
+template <int... Vs, class F>
+int dispatch(int v, const char* what, F&& f) {
+  int rc = RNNT_ERR_UNSUPPORTED;
+  if (!((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...)) set_error("%s: no kernel for %d", what, v);
+  return rc;
+}
 
 
 

@@ -13,7 +13,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rnntransducer_amd.csrc.build import source_digest  # noqa: E402
 
-KINDS = (("gemm_hp_kernel", ("gemm_hp_kernel", "gemm_hp3_kernel")),
+KINDS = (("gemm_hp_kernel", ("gemm_hp_kernel",)),
          ("gemm_bf16s_kernel", ("gemm_bf16s_kernel", "gemm_bf16s256_kernel")), ("gemm_f32_kernel", ("gemm_f32_kernel",)),
          ("lstm_fwd_kernel", ("lstm_fwd5_kernel", "lstm_fwd3_kernel", "lstm_fwd2_kernel", "lstm_fwd_kernel")),
          ("lstm_bwd_kernel", ("lstm_bwd5f_kernel", "lstm_bwd5_kernel", "lstm_bwd4_kernel", "lstm_bwd2_kernel", "lstm_bwd_kernel")),
