@@ -11,8 +11,8 @@
  *   - return 0 on success, <0 on error; rnnt_hip_last_error() gives a thread-local message;
  *   - the CALLER owns all memory incl. workspaces (sizes from *_workspace_bytes); the library never
  *     allocates or frees device memory, never synchronises the device (the two *_check / *_debug_read
- *     diagnostics aside) and keeps no global mutable state other than the opt-in profiler below
- *     (off by default: event lists + a mutex behind rnnt_hip_prof_enable) and the thread-local error string;
+ *     diagnostics aside) and keeps no global mutable state other than the opt-in profiler and launch record below
+ *     (off by default: event lists / a text record, each behind a mutex) and the thread-local error string;
  *   - all float tensors are fp32, all lengths/labels int32, token ids int64 (dataloader.py:21-24,28-36);
  *   - "time-major" = (T,B,F) contiguous; "batch-major" = (B,T,F) contiguous.
  */
@@ -42,7 +42,7 @@ int rnnt_hip_device_cus(void);
 /* ------------------------------------------------------------------------------------------------
  * Opt-in live profiler (used by bench.py only).  While enabled, every kernel launch below is bracketed by two
  * HIP events recorded on the launch stream; collect() synchronises on them, sums elapsed ms / algorithmic work /
- * launch counts per kernel kind, and resets.  This is the only global state in the library, off by default.
+ * launch counts per kernel kind, and resets.  Off by default.
  * `work` unit: FLOPs for RNNT_K_GEMM and RNNT_K_GEMM_HP, algorithmic bytes for all other kinds.
  * ---------------------------------------------------------------------------------------------- */
 enum {
@@ -59,6 +59,14 @@ enum {
 };
 int rnnt_hip_prof_enable(int on);
 int rnnt_hip_prof_collect(double* ms, double* work, int64_t* count, int nkinds);
+
+/* Opt-in record of the persistent recurrence kernels launched (used by the tests that pin which kernel instance a shape runs).
+ * enable(1) clears the record and starts it, enable(0) stops it and keeps what it holds.  While on, every launch of a recurrence
+ * kernel (rnnt_hip_lstm_fwd / _bwd and their _ex forms) appends one line: the kernel's device symbol, whose template arguments
+ * name the instance.  launch_log() copies the record (NUL-terminated, truncated to n - 1 bytes) and returns its full length.
+ * Off by default; when off a launch pays one branch. */
+int rnnt_hip_lstm_launch_log_enable(int on);
+int64_t rnnt_hip_lstm_launch_log(char* buf, size_t n);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense fp32 GEMM on f32-input MFMA (v_mfma_f32_32x32x2_f32):  C = op(A) . op(B) (+ bias)

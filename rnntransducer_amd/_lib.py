@@ -96,6 +96,8 @@ SYMBOLS = {
     "rnnt_hip_device_cus": (C.c_int, []),
     "rnnt_hip_prof_enable": (C.c_int, [C.c_int]),
     "rnnt_hip_prof_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "rnnt_hip_lstm_launch_log_enable": (C.c_int, [C.c_int]),
+    "rnnt_hip_lstm_launch_log": (c_i64, [C.c_char_p, C.c_size_t]),
     "rnnt_hip_gemm_workspace_bytes": (C.c_size_t, [c_i64, c_i64, c_i64]),
     "rnnt_hip_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p]),
     "rnnt_hip_hp_bytes": (C.c_size_t, [c_i64, c_i64]),

@@ -2,8 +2,10 @@
 #include "common.hpp"
 
 #include <math.h>
+#include <string.h>
 
 #include <mutex>
+#include <string>
 #include <vector>
 
 namespace rnnt {
@@ -69,6 +71,45 @@ extern "C" int rnnt_hip_prof_collect(double* ms, double* work, int64_t* count, i
   }
   g_prof.clear();
   return RNNT_OK;
+}
+
+namespace rnnt {
+// ---- opt-in record of the recurrence kernels launched: one device symbol per launch, in launch order ----
+std::atomic<bool> g_launch_log_on{false};
+namespace {
+std::string g_launch_log;
+std::mutex g_launch_log_mu;
+}  // namespace
+
+void launch_log_note(const void* kernel, hipStream_t s) {
+  const char* name = hipKernelNameRefByPtr(kernel, s);
+  char fallback[32];
+  if (!name) {
+    snprintf(fallback, sizeof(fallback), "%p", kernel);
+    name = fallback;
+  }
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  g_launch_log += name;
+  g_launch_log += '\n';
+}
+}  // namespace rnnt
+
+extern "C" int rnnt_hip_lstm_launch_log_enable(int on) {
+  std::lock_guard<std::mutex> lk(rnnt::g_launch_log_mu);
+  if (on) rnnt::g_launch_log.clear();
+  rnnt::g_launch_log_on.store(on != 0, std::memory_order_relaxed);
+  return RNNT_OK;
+}
+
+extern "C" int64_t rnnt_hip_lstm_launch_log(char* buf, size_t n) {
+  std::lock_guard<std::mutex> lk(rnnt::g_launch_log_mu);
+  const std::string& r = rnnt::g_launch_log;
+  if (buf && n > 0) {
+    const size_t m = r.size() < n - 1 ? r.size() : n - 1;
+    memcpy(buf, r.data(), m);
+    buf[m] = '\0';
+  }
+  return (int64_t)r.size();
 }
 
 namespace rnnt {

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "rnnt_hip.h"
 
 namespace rnnt {
@@ -40,6 +42,12 @@ struct ProfScope {
   hipStream_t stream_;
   void* start_;
 };
+
+// Opt-in record of the persistent recurrence kernels launched (api.hip, rnnt_hip_lstm_launch_log_enable): the launch helpers of
+// lstm.hip / lstm5.hip call launch_log_note with the kernel's host pointer after each launch when g_launch_log_on is set (off: one
+// branch per launch).
+extern std::atomic<bool> g_launch_log_on;
+void launch_log_note(const void* kernel, hipStream_t s);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

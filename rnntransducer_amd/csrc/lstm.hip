@@ -1468,6 +1468,9 @@ bool make_plan(int B, int H, int D, int cus, Plan* pl) {
     for (int Hs = 4; Hs <= 16; Hs *= 2) {
       if (H % Hs != 0) continue;
       const int MT = Hs / 4, NC = H / Hs;
+      // each of the 256 threads owns one cell of one 4-unit x 16-row tile: at most 4 tiles (an 8-unit slice of 64 rows left half
+      // its units uncomputed)
+      if (MT * NT > 4) continue;
       const size_t lds_fwd = (size_t)4 * Hs * pl->LDW * 4 + (size_t)4 * MT * NT * 64 * 16 + 16;
       const size_t lds_bwd = (size_t)KG * MT * 64 * 16 + (size_t)16 * MT * 4 * NT * 16 * 4 + 16;
       const size_t lds = lds_fwd > lds_bwd ? lds_fwd : lds_bwd;
@@ -1636,6 +1639,7 @@ int launch_persistent(K kernel, const LstmK& k, const Plan& pl, size_t lds, hipS
     hipLaunchKernelGGL(kernel, dim3(k.D * k.NC), dim3(256), lds, s, k);
   }
   RNNT_CHECK_LAUNCH();
+  if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note((const void*)kernel, s);
   return RNNT_OK;
 }
 

@@ -228,6 +228,7 @@ int launch_persistent2(K kernel, const LstmK& k_in, const Plan2& pl, size_t lds,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, k);
   }
   RNNT_CHECK_LAUNCH();
+  if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note((const void*)kernel, s);
   return RNNT_OK;
 }
 

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -556,6 +557,45 @@ def lstm_check(ws: torch.Tensor) -> None:
     """C-ABI diagnostic for callers that pass status = NULL (the workspace's own per-launch word); the package itself uses
     the sticky device word: see lstm_status_check()."""
     check(_lib.lib().rnnt_hip_lstm_check(_addr(ws), _stream()), "rnnt_hip_lstm_check")
+
+
+_MANGLED_INSTANCE = re.compile(r"\d(lstm_\w+?)_kernelI((?:L[bi]n?\d+E)+)E")
+_PLAIN_INSTANCE = re.compile(r"\b(lstm_\w+?)_kernel<([^<>]*)>")
+
+
+def recurrence_instance(symbol: str) -> str:
+    """The instance a recurrence kernel's device symbol names, mangled or demangled, as 'lstm_fwd5<3,0,8,5,0>' (kernel name without
+    '_kernel', template arguments in order, bools as 0 / 1)."""
+    m = _MANGLED_INSTANCE.search(symbol)
+    if m:
+        args = [("-" if neg else "") + v for _, neg, v in re.findall(r"L([bi])(n?)(\d+)E", m.group(2))]
+    else:
+        m = _PLAIN_INSTANCE.search(symbol)
+        if not m:
+            raise ValueError(f"not a recurrence kernel symbol: {symbol!r}")
+        args = [{"true": "1", "false": "0"}.get(a.strip(), a.strip()) for a in m.group(2).split(",")]
+    return f"{m.group(1)}<{','.join(args)}>"
+
+
+class lstm_launch_record:
+    """Records the recurrence kernels launched inside the `with` block (rnnt_hip_lstm_launch_log_enable): afterwards `symbols` holds
+    their device symbols and `instances` the instances they name (recurrence_instance), in launch order."""
+
+    def __enter__(self):
+        check(_lib.lib().rnnt_hip_lstm_launch_log_enable(1), "rnnt_hip_lstm_launch_log_enable")
+        self.symbols: List[str] = []
+        self.instances: List[str] = []
+        return self
+
+    def __exit__(self, *exc):
+        L = _lib.lib()
+        check(L.rnnt_hip_lstm_launch_log_enable(0), "rnnt_hip_lstm_launch_log_enable")
+        n = L.rnnt_hip_lstm_launch_log(None, 0)
+        buf = C.create_string_buffer(n + 1)
+        L.rnnt_hip_lstm_launch_log(buf, n + 1)
+        self.symbols = buf.value.decode().splitlines()
+        self.instances = [recurrence_instance(s) for s in self.symbols]
+        return False
 
 
 # --------------------------------------------------------------------------------------------------

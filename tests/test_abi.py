@@ -130,3 +130,20 @@ def test_ragged_plan_lists_the_valid_time_major_rows():
     assert RaggedPlan([4, 4], 4, "cpu").dense and RaggedPlan([4, 4], 4, "cpu").row_idx is None
     with pytest.raises(ValueError):
         RaggedPlan([5, 2], 4, "cpu")
+
+
+def test_lstm_launch_record_entry_points():
+    """rnnt_hip_lstm_launch_log_enable / rnnt_hip_lstm_launch_log: host-only state, usable without a device.  enable(1) starts an
+    empty record, the query reports the full length and truncates to the buffer it is given; nothing is recorded here (no launch)."""
+    import ctypes as C
+    from rnntransducer_amd import _lib
+    from rnntransducer_amd.ops import lstm_launch_record
+    L = _lib.lib()
+    assert L.rnnt_hip_lstm_launch_log_enable(1) == 0
+    assert L.rnnt_hip_lstm_launch_log(None, 0) == 0
+    buf = C.create_string_buffer(b"x" * 8)
+    assert L.rnnt_hip_lstm_launch_log(buf, 8) == 0 and buf.value == b""
+    assert L.rnnt_hip_lstm_launch_log_enable(0) == 0
+    with lstm_launch_record() as rec:
+        pass
+    assert rec.symbols == [] and rec.instances == []

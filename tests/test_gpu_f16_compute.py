@@ -165,12 +165,11 @@ def test_single_layer_f16_mode_vs_float64(monkeypatch, cell, H, bi):
     worst = {}
     for plan in (False, True):
         y, dx, grads = _hip_run(hip, x, lens, dy, "fp16", plan=plan)
-        for b in range(B):   # dx of padded frames is unspecified with a plan (never consumed); the oracle has 0 there
-            dx[b, lens[b]:] = 0
         e = (y - out64).abs().max().item()
         assert e < OUT_ATOL, f"plan={plan}: output err {e}"
-        for b in range(B):
+        for b in range(B):   # padded frames: exact zeros, with and without a plan
             assert torch.all(y[b, lens[b]:] == 0)
+            assert torch.all(dx[b, lens[b]:] == 0), f"plan={plan}: dx of padded frames, row {b}"
         for name, got, want in [("dx", dx, dx64)] + [(k, grads[k], g64[k]) for k in g64]:
             rn, cos = _grad_stats(got, want)
             worst[name] = max(worst.get(name, 0.0), rn)
