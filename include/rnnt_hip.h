@@ -484,6 +484,79 @@ size_t rnnt_hip_beam_workspace_bytes(const rnnt_beam_desc* d);  /* 0 if the desc
 int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming greedy recognition (model.py:12-18: the model "continuously processes input samples and streams output
+ * symbols"; unidirectional encoder, networks/encoder.py:62; single-step prediction net with carried state,
+ * networks/decoder.py:121-123; the greedy loop of networks/transducer.py:95-145).  Features arrive in chunks of T frames per
+ * batch of B independent streams; the per-stream state is carried in caller-owned device buffers.  Every per-element
+ * product is computed in an order that depends neither on T, on B nor on the chunk boundaries, so any chunking of an
+ * utterance gives the same bits (csrc/stream.hip).  fp32 throughout.
+ *
+ * rnnt_hip_stream_rnn_chunk: the encoder over one chunk (networks/encoder.py:93-103 with hidden state carried in and out).
+ *   Stream b runs frames t < lens[b] (0..T); its state is left bitwise as it is past them.  h (L,B,H) (and c for LSTM) hold
+ *   the state before the chunk on entry and after it on return.  out[t,b,:] = out_proj(h_top) at b*out_sb + t*out_st
+ *   floats, zeros for t >= lens[b].  If A is not NULL it also writes the encoder half of the joint
+ *   (networks/transducer.py:64-69), A (T,B,V) time-major = gelu(out) fc_w[:, :O]^T + fc_b, fc_w rows ld_fc floats apart.
+ *   T + L + 1 (+1 with A) kernel launches, none of which waits on another workgroup.
+ * ---------------------------------------------------------------------------------------------- */
+#define RNNT_STREAM_MAX_LAYERS 8
+typedef struct rnnt_stream_rnn_desc {
+  int32_t T, B, F, H, L, cell; /* chunk frames, streams, input width, hidden, layers (1..8), RNNT_CELL_* */
+  int32_t O, V;          /* out_proj width; vocabulary (only with A) */
+  const float* x;        /* frame t of stream b at x + b*x_sb + t*x_st, F floats */
+  int64_t x_sb, x_st;
+  const int32_t* lens;   /* (B) device, in [0, T] */
+  const float* w_ih[RNNT_STREAM_MAX_LAYERS]; /* encoder.rnn.weight_ih_l{k} (G*H, F or H) */
+  const float* w_hh[RNNT_STREAM_MAX_LAYERS];
+  const float* b_ih[RNNT_STREAM_MAX_LAYERS];
+  const float* b_hh[RNNT_STREAM_MAX_LAYERS];
+  float* h;              /* (L,B,H) in/out */
+  float* c;              /* (L,B,H) in/out, LSTM only */
+  const float* w_o;      /* encoder.out_proj.weight (O,H) */
+  const float* b_o;      /* (O) */
+  float* out;
+  int64_t out_sb, out_st;
+  const float* fc_w;     /* fc.weight, or NULL */
+  int64_t ld_fc;
+  const float* fc_b;
+  float* A;              /* (T,B,V) or NULL */
+  void* workspace;       /* rnnt_hip_stream_rnn_workspace_bytes(d) bytes, 256-byte aligned */
+  size_t workspace_bytes;
+} rnnt_stream_rnn_desc;
+size_t rnnt_hip_stream_rnn_workspace_bytes(const rnnt_stream_rnn_desc* d);
+int rnnt_hip_stream_rnn_chunk(const rnnt_stream_rnn_desc* d, void* stream);
+
+/* rnnt_hip_stream_greedy: the greedy loop of networks/transducer.py:120-141 continued from carried state.  Per stream b (one
+ *   workgroup each), for t < lens[b]: up to max_iters times { tok = argmax_v (A[t,b,v] + C[b,v]); blank ends the frame; tok
+ *   is appended to tokens[b] unless it equals last[b]; the prediction net advances with tok from (h, c) and C becomes
+ *   gelu(out_proj(h_top)) fc_w[:, O_enc:]^T }.  h / c / C / last are read on entry and written back; a stream with no frames
+ *   is not touched.  ntok[b] = tokens appended in this call (at most max_out are stored).
+ * rnnt_hip_stream_greedy_reset: rows[0..n_rows) start a new utterance as transducer.py:116-119 does: zero state, one
+ *   prediction-net step on blank, last = blank.  Other rows are not touched.  A, lens, tokens, ntok unused. */
+typedef struct rnnt_stream_greedy_desc {
+  int32_t T, B, V, Hp, O, L, cell; /* as rnnt_decode_desc; T = chunk frames */
+  int32_t blank, max_iters, max_out;
+  const float* A;        /* (T,B,V) from rnnt_hip_stream_rnn_chunk */
+  const int32_t* lens;   /* (B) device */
+  const float* emb;
+  const float* w_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* w_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* b_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* b_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* w_o;
+  const float* b_o;
+  const float* w_d;      /* fc.weight[:, O_enc:], row stride ld_d floats */
+  int64_t ld_d;
+  float* h;              /* (L,B,Hp) in/out */
+  float* c;              /* (L,B,Hp) in/out, LSTM only */
+  float* C;              /* (B,V) in/out: the prediction-net half of the joint for the current state */
+  int64_t* last;         /* (B) in/out: last appended token */
+  int64_t* tokens;       /* (B,max_out) */
+  int32_t* ntok;         /* (B) */
+} rnnt_stream_greedy_desc;
+int rnnt_hip_stream_greedy(const rnnt_stream_greedy_desc* d, void* stream);
+int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, const int32_t* rows, int32_t n_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

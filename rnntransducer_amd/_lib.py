@@ -89,6 +89,29 @@ class BeamDesc(C.Structure):
                 ("scores", C.c_void_p), ("count", C.c_void_p), ("status", C.c_void_p), ("stats", C.c_void_p)]
 
 
+STREAM_MAX_LAYERS = 8
+
+
+class StreamRnnDesc(C.Structure):
+    _fields_ = [("T", c_i32), ("B", c_i32), ("F", c_i32), ("H", c_i32), ("L", c_i32), ("cell", c_i32), ("O", c_i32), ("V", c_i32),
+                ("x", C.c_void_p), ("x_sb", c_i64), ("x_st", c_i64), ("lens", C.c_void_p),
+                ("w_ih", C.c_void_p * STREAM_MAX_LAYERS), ("w_hh", C.c_void_p * STREAM_MAX_LAYERS),
+                ("b_ih", C.c_void_p * STREAM_MAX_LAYERS), ("b_hh", C.c_void_p * STREAM_MAX_LAYERS),
+                ("h", C.c_void_p), ("c", C.c_void_p), ("w_o", C.c_void_p), ("b_o", C.c_void_p),
+                ("out", C.c_void_p), ("out_sb", c_i64), ("out_st", c_i64), ("fc_w", C.c_void_p), ("ld_fc", c_i64),
+                ("fc_b", C.c_void_p), ("A", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class StreamGreedyDesc(C.Structure):
+    _fields_ = [("T", c_i32), ("B", c_i32), ("V", c_i32), ("Hp", c_i32), ("O", c_i32), ("L", c_i32), ("cell", c_i32),
+                ("blank", c_i32), ("max_iters", c_i32), ("max_out", c_i32), ("A", C.c_void_p), ("lens", C.c_void_p),
+                ("emb", C.c_void_p), ("w_ih", C.c_void_p * DECODE_MAX_LAYERS), ("w_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("b_ih", C.c_void_p * DECODE_MAX_LAYERS), ("b_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("w_o", C.c_void_p), ("b_o", C.c_void_p), ("w_d", C.c_void_p), ("ld_d", c_i64),
+                ("h", C.c_void_p), ("c", C.c_void_p), ("C", C.c_void_p), ("last", C.c_void_p),
+                ("tokens", C.c_void_p), ("ntok", C.c_void_p)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -149,6 +172,10 @@ SYMBOLS = {
     "rnnt_hip_prednet_step": (C.c_int, [C.POINTER(PrednetStepDesc), C.c_void_p]),
     "rnnt_hip_beam_workspace_bytes": (C.c_size_t, [C.POINTER(BeamDesc)]),
     "rnnt_hip_beam_search": (C.c_int, [C.POINTER(BeamDesc), C.c_void_p]),
+    "rnnt_hip_stream_rnn_workspace_bytes": (C.c_size_t, [C.POINTER(StreamRnnDesc)]),
+    "rnnt_hip_stream_rnn_chunk": (C.c_int, [C.POINTER(StreamRnnDesc), C.c_void_p]),
+    "rnnt_hip_stream_greedy": (C.c_int, [C.POINTER(StreamGreedyDesc), C.c_void_p]),
+    "rnnt_hip_stream_greedy_reset": (C.c_int, [C.POINTER(StreamGreedyDesc), C.c_void_p, c_i32, C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
 }

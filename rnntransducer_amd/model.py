@@ -120,6 +120,14 @@ class RNNTransducer(_Base):
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}
 
+    def init_stream(self, batch_size: int, device=None):
+        """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
+        return self.jointnet.init_stream(batch_size, self.blank_token_id, device)
+
+    def recognize_greedy_stream(self, chunk, chunk_lengths, state, max_iters: int = 3):
+        """JointNet.recognize_greedy_stream: the tokens each stream appends during this chunk of features."""
+        return self.jointnet.recognize_greedy_stream(chunk, chunk_lengths, state, max_iters)
+
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
         """model.py:62-79: loss + greedy search (max 3 symbols per frame).  `pred_tokens` is a list of B 1-D LongTensors

@@ -56,6 +56,62 @@ class AudioTransNet(nn.Module):
                 m.compute_precision = p
         return self
 
+    def stream_chunk(self, chunk: torch.Tensor, lens_dev: torch.Tensor, T_run: int, h: torch.Tensor, c, out: torch.Tensor,
+                     out_strides, fc=None):
+        """One chunk of the unidirectional encoder on carried state (csrc/stream.hip), in place on h / c.  lens_dev (B) int32 on
+        the device; only the first T_run = max(lens) frames run.  fc: (weight, bias) of the joint -> also returns its encoder
+        half A.  The callers check the lengths and the chunk's width; ops.stream_rnn_chunk checks every shape again."""
+        from ..ops import stream_rnn_chunk
+        return stream_rnn_chunk(chunk[:, :T_run], lens_dev, self.rnn.flat_weights(), self.rnn.CELL, h, c, self.out_proj.weight,
+                                self.out_proj.bias, out, out_strides, *(fc or (None, None)))
+
+    def check_stream_chunk(self, chunk: torch.Tensor, what: str) -> None:
+        """A chunk (B,T_c,F) float32 on the GPU with F = the encoder's input width."""
+        from ..streaming import check_chunk
+        check_chunk(chunk)
+        if chunk.shape[2] != self.rnn.input_size:
+            raise ValueError(f"{what}: chunk has {chunk.shape[2]} features, the encoder takes {self.rnn.input_size}")
+
+    def check_streamable(self, what: str) -> None:
+        if self.rnn.bidirectional:
+            raise ValueError(f"{what}: a bidirectional encoder needs future frames and cannot stream")
+        if self.training:
+            raise RuntimeError(f"{what} expects eval() mode (dropout inactive), like recognize_greedy")
+
+    @torch.no_grad()
+    def forward_stream(self, chunk: torch.Tensor, chunk_lengths, state=None):
+        """The encoder over one chunk with carried state: chunk (B,T_c,F) fp32 on the GPU, chunk_lengths B values in [0,T_c],
+        state None (zeros) or what the previous call returned -> (out (B,T_c,O), state).  state is torch's format: (h, c) of
+        (L,B,H) for LSTM, h otherwise; frames past a stream's length are ignored (its state carries unchanged) and come out as
+        zeros, as in `forward`.  Unidirectional encoders only; fp32 whatever compute_precision says.  Feeding an utterance
+        in any chunking gives the same bits."""
+        from ..streaming import host_lengths
+        self.check_streamable("forward_stream")
+        self.check_stream_chunk(chunk, "forward_stream")
+        B, T, _ = chunk.shape
+        lens = host_lengths(chunk_lengths, B, T)
+        L, H, lstm = self.rnn.num_layers, self.rnn.hidden_size, self.rnn.CELL == 0
+        if state is None:
+            h = torch.zeros(L, B, H, device=chunk.device)
+            c = torch.zeros_like(h) if lstm else None
+        else:
+            h, c = state if lstm else (state, None)
+            for name, t in (("h", h), ("c", c)) if lstm else (("h", h),):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (L, B, H) or t.dtype != torch.float32 \
+                        or t.device != chunk.device:
+                    raise ValueError(f"forward_stream: state {name} must be a float32 ({L},{B},{H}) tensor on {chunk.device} "
+                                     "(torch's format: (h, c) for LSTM, h otherwise)")
+            # a private dense copy: the caller's tensors stay as they are, whatever their strides
+            h, c = h.detach().clone(memory_format=torch.contiguous_format), \
+                (c.detach().clone(memory_format=torch.contiguous_format) if lstm else None)
+        O = self.out_proj.out_features
+        out = torch.zeros(B, T, O, device=chunk.device)
+        T_run = max(lens)
+        if T_run > 0:
+            lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
+            self.stream_chunk(chunk, lens_dev, T_run, h, c, out, (T * O, O))
+        return out, ((h, c) if lstm else h)
+
     def forward(self, inputs: torch.Tensor, inputs_lengths) -> torch.Tensor:
         """Reference surface (encoder.py:78): (B,T,F), lengths -> (B,T,O)."""
         lens = lengths_to_device(inputs_lengths, inputs.device)

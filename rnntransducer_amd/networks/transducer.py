@@ -11,11 +11,13 @@ with A = gelu(enc) W_e^T, C = gelu(dec) W_d^T (GELU is element-wise, fc is linea
 a host loop with a device sync per symbol.  `recognize_beams` (transducer.py:215-361, lm=None / hotwords=None) is one persistent
 launch too (csrc/beam.hip): the reference's pop / expand / prune / stop decisions, with memoised prediction-net steps and a
 prefix tree for y_star; LM and hotword rescoring (pyctcdecode / KenLM) stay out of scope.
+`init_stream` / `recognize_greedy_stream` run the same greedy search over a batch of streams fed in chunks, with the encoder,
+prediction-net and search state carried between chunks (rnntransducer_amd/streaming.py, csrc/stream.hip).
 """
 import torch
 import torch.nn as nn
 
-from ..ops import JointLogitsFn, JointLossFn, beam_search, greedy_decode
+from ..ops import JointLogitsFn, JointLossFn, beam_search, greedy_decode, stream_greedy
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -140,3 +142,42 @@ class JointNet(nn.Module):
                           expand_beam, None if visit_padded_frames else t_lens, **caps)
         outs = [hyps if return_scores else [y for y, _ in hyps] for hyps in res]
         return outs[0] if len(outs) == 1 else outs
+
+    def init_stream(self, batch_size: int, blank_token_id: int, device=None):
+        """A GreedyStreamState for `batch_size` streams, each starting as recognize_greedy starts an utterance
+        (transducer.py:116-119): zero encoder state, prediction net primed with one blank step from zero state, last token =
+        blank.  `device`, if given, must be the model's: the state lives beside the weights."""
+        from ..streaming import GreedyStreamState
+        self.encoder.check_streamable("init_stream")
+        return GreedyStreamState(self, batch_size, blank_token_id, device)
+
+    @torch.no_grad()
+    def recognize_greedy_stream(self, chunk: torch.Tensor, chunk_lengths, state, max_iters: int = 3):
+        """Greedy search over the next chunk of every stream: chunk (B,T_c,F) fp32 on the GPU, chunk_lengths B values in
+        [0,T_c] (frames past a stream's length are ignored; a stream with 0 frames is left bitwise unchanged), `state` from
+        this model's init_stream, updated in place.  Returns a list of B 1-D LongTensors: the tokens appended during this chunk.
+        The per-frame rule is recognize_greedy's; any chunking of an utterance gives the same bits as one chunk holding all of
+        it, and the tokens of recognize_greedy wherever no two logits are within fp32 rounding of each other.
+        Unidirectional encoders only; fp32 whatever compute_precision says."""
+        from ..streaming import host_lengths
+        self.encoder.check_streamable("recognize_greedy_stream")
+        self.encoder.check_stream_chunk(chunk, "recognize_greedy_stream")
+        B, T, _ = chunk.shape
+        state.check_fits(self, B, chunk.device)
+        if max_iters < 1:
+            raise ValueError(f"max_iters must be >= 1, got {max_iters}")
+        lens = host_lengths(chunk_lengths, B, T)
+        T_run = max(lens)
+        if T_run == 0:
+            return [torch.empty(0, dtype=torch.int64, device=chunk.device) for _ in range(B)]
+        lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)   # one copy, shared by both launches' reads
+        enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
+        A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
+                                      (self.fc.weight, self.fc.bias))
+        dec = self.decoder
+        tokens, ntok = stream_greedy(A, lens_dev, self.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                                     dec.out_proj.weight, dec.out_proj.bias, state.blank, max_iters, state.pred_h, state.pred_c,
+                                     state.pred_joint, state.last_token)
+        state.frames_seen += lens_dev
+        n = ntok.tolist()  # the only host sync of the chunk
+        return [tokens[b, :n[b]] for b in range(B)]

@@ -919,3 +919,147 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     if stats:
         return out, host.reshape(-1)[2 * B:].reshape(B, _lib.BEAM_NSTATS)
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# streaming greedy recognition (include/rnnt_hip.h: rnnt_hip_stream_rnn_chunk / rnnt_hip_stream_greedy[_reset]); the state
+# tensors belong to streaming.GreedyStreamState
+# --------------------------------------------------------------------------------------------------
+def _check_buffer(name: str, t: Optional[torch.Tensor], shape, dtype, device) -> None:
+    """A caller-owned buffer the streaming kernels index as a dense array of `shape`."""
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device \
+            or not t.is_contiguous():
+        got = (tuple(t.shape), t.dtype, str(t.device), "contiguous" if t.is_contiguous() else "strided") \
+            if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{name}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got {got}")
+
+
+def _check_rnn_weights(rnn_weights, cell: int, I0: int, H: int, what: str) -> None:
+    """Shapes of a uni-directional stack's [w_ih, w_hh, b_ih, b_hh] per layer (layer 0 reads I0 inputs, the others H)."""
+    ngate = {0: 4, 1: 3, 2: 1, 3: 1}.get(cell)
+    if ngate is None or not rnn_weights or len(rnn_weights) % 4 != 0:
+        raise ValueError(f"{what}: cell {cell!r} / {len(rnn_weights)} weight tensors")
+    for i, w in enumerate(rnn_weights):
+        want = [(ngate * H, I0 if i < 4 else H), (ngate * H, H), (ngate * H,), (ngate * H,)][i % 4]
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want:
+            raise ValueError(f"{what} weight #{i}: expected shape {want}, "
+                             f"got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+
+
+def stream_rnn_chunk(chunk: torch.Tensor, lens: torch.Tensor, rnn_weights, cell: int, h: torch.Tensor, c: Optional[torch.Tensor],
+                     out_w: torch.Tensor, out_b: torch.Tensor, out: torch.Tensor, out_strides: Tuple[int, int],
+                     fc_w: Optional[torch.Tensor] = None, fc_b: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Unidirectional encoder over one chunk with carried state.  chunk (B,T,F) fp32 (any strides with unit feature stride),
+    lens (B) int32 on device (frames per stream; the kernels never read past T whatever they hold), h / c (L,B,H) updated in
+    place (c: LSTM only, else None); frame t of stream b of out_proj(h_top) goes to out + b * out_strides[0] + t * out_strides[1]
+    (zeros past lens).  With fc_w / fc_b: returns A (T,B,V) = gelu(out) W_e^T + b (the encoder half of the joint).
+    The kernels index raw pointers: every shape is checked here, on the host, before anything is launched."""
+    _need_gpu(chunk, lens, h, c, out_w, out_b, out, fc_w, fc_b, *rnn_weights)
+    if chunk.dim() != 3 or chunk.dtype != torch.float32:
+        raise ValueError(f"chunk must be (B,T,F) float32, got {tuple(chunk.shape)} {chunk.dtype}")
+    B, T, F = chunk.shape
+    dev = chunk.device
+    if not isinstance(h, torch.Tensor) or h.dim() != 3:
+        raise ValueError("h must be an (L,B,H) tensor")
+    L, H = h.shape[0], h.shape[2]
+    _check_rnn_weights(rnn_weights, cell, F, H, "encoder")
+    if len(rnn_weights) != 4 * L:
+        raise ValueError(f"encoder: {len(rnn_weights) // 4} layers of weights for an ({L},B,H) state")
+    _check_buffer("encoder h", h, (L, B, H), torch.float32, dev)
+    if cell == _lib.CELL_LSTM:
+        _check_buffer("encoder c", c, (L, B, H), torch.float32, dev)
+    _check_buffer("lengths", lens, (B,), torch.int32, dev)
+    O = out_w.shape[0]
+    if tuple(out_w.shape) != (O, H) or tuple(out_b.shape) != (O,):
+        raise ValueError(f"out_proj {tuple(out_w.shape)} / {tuple(out_b.shape)} does not fit hidden size {H}")
+    sb, st = out_strides
+    if out.dtype != torch.float32 or not out.is_contiguous() or sb < 0 or st < 0 or \
+            (B - 1) * sb + (T - 1) * st + O > out.numel():
+        raise ValueError(f"out: a contiguous float32 buffer holding (B,T,O) = ({B},{T},{O}) at strides {out_strides}")
+    if chunk.stride(2) != 1:
+        chunk = chunk.contiguous()
+    d = _lib.StreamRnnDesc()
+    d.T, d.B, d.F, d.H, d.L, d.cell, d.O = T, B, F, H, L, cell, O
+    d.x, d.x_sb, d.x_st, d.lens = _addr(chunk), chunk.stride(0), chunk.stride(1), _addr(lens)
+    keep = [_f32c(t, "encoder weight") for t in rnn_weights]
+    for l in range(min(L, _lib.STREAM_MAX_LAYERS)):   # more layers: the entry refuses and names the limit
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
+    out_w, out_b = _f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias")
+    d.h, d.c, d.w_o, d.b_o = _addr(h), _addr(c), _addr(out_w), _addr(out_b)
+    d.out = _addr(out)
+    d.out_sb, d.out_st = sb, st
+    A = None
+    if fc_w is not None:
+        V = fc_w.shape[0]
+        if fc_w.dim() != 2 or fc_w.shape[1] < O or tuple(fc_b.shape) != (V,):
+            raise ValueError(f"fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} does not fit encoder width {O}")
+        fc_w, fc_b = _f32c(fc_w, "fc weight"), _f32c(fc_b, "fc bias")
+        A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
+        d.V, d.fc_w, d.ld_fc, d.fc_b, d.A = V, _addr(fc_w), fc_w.shape[1], _addr(fc_b), _addr(A)
+    nbytes = _lib.lib().rnnt_hip_stream_rnn_workspace_bytes(C.byref(d))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d.workspace, d.workspace_bytes = _addr(ws), nbytes
+    check(_lib.lib().rnnt_hip_stream_rnn_chunk(C.byref(d), _stream()), "rnnt_hip_stream_rnn_chunk")
+    return A
+
+
+def _stream_greedy_desc(T: int, B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, h, c, Cs, last):
+    """Descriptor of the streaming search; every weight and state shape checked against the others (raw pointers)."""
+    V, Ocat = fc_w.shape
+    Od = out_w.shape[0]
+    Hp, L = emb_w.shape[1], len(rnn_weights) // 4
+    if L > _lib.DECODE_MAX_LAYERS:
+        raise RnntHipError(f"streaming greedy search: {L} prediction-net layers (RNNT_DECODE_MAX_LAYERS = {_lib.DECODE_MAX_LAYERS})")
+    _check_prednet_weights(rnn_weights, cell, Hp)
+    if not 1 <= Od < Ocat or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or emb_w.shape[0] < V:
+        raise ValueError(f"streaming greedy search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding "
+                         f"{tuple(emb_w.shape)} do not fit together (the embedding needs a row per fc output)")
+    if not 0 <= blank < V:
+        raise ValueError(f"streaming greedy search: blank {blank} outside [0,{V})")
+    dev = fc_w.device
+    _check_buffer("prediction-net h", h, (L, B, Hp), torch.float32, dev)
+    if cell == _lib.CELL_LSTM:
+        _check_buffer("prediction-net c", c, (L, B, Hp), torch.float32, dev)
+    _check_buffer("prediction-net joint half", Cs, (B, V), torch.float32, dev)
+    _check_buffer("last token", last, (B,), torch.int64, dev)
+    d = _lib.StreamGreedyDesc()
+    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = T, B, V, Hp, Od, L, cell, blank
+    keep = [_f32c(t, "prediction-net weight") for t in rnn_weights]
+    keep += [_f32c(emb_w, "embedding"), _f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias"), _f32c(fc_w, "fc weight")]
+    d.emb = _addr(keep[-4])
+    for l in range(L):
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
+    d.w_o, d.b_o = _addr(keep[-3]), _addr(keep[-2])
+    d.w_d, d.ld_d = _addr(keep[-1], Ocat - Od), Ocat
+    d.h, d.c, d.C, d.last = _addr(h), _addr(c), _addr(Cs), _addr(last)
+    return d, keep
+
+
+def stream_greedy_reset(rows: torch.Tensor, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, h, c, Cs, last) -> None:
+    """Prime rows (int32 on device) of the prediction-net state as transducer.py:116-119: zero state, one blank step."""
+    _need_gpu(rows, fc_w, emb_w, h, Cs, last)
+    d, keep = _stream_greedy_desc(1, h.shape[1], fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, h, c, Cs, last)
+    _check_buffer("rows", rows, (rows.numel(),), torch.int32, fc_w.device)
+    if rows.numel() and not bool(((rows >= 0) & (rows < h.shape[1])).all()):
+        raise ValueError(f"rows must lie in [0, {h.shape[1]})")
+    check(_lib.lib().rnnt_hip_stream_greedy_reset(C.byref(d), _addr(rows), rows.numel(), _stream()), "rnnt_hip_stream_greedy_reset")
+
+
+def stream_greedy(A: torch.Tensor, lens: torch.Tensor, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, max_iters: int,
+                  h, c, Cs, last):
+    """Greedy search over one chunk from carried state.  A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; h / c / Cs /
+    last updated in place -> (tokens (B, T*max_iters) int64, ntok (B,) int32) appended in this chunk."""
+    _need_gpu(A, lens, fc_w, emb_w, h, Cs, last)
+    T, B = A.shape[0], A.shape[1]
+    d, keep = _stream_greedy_desc(T, B, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, h, c, Cs, last)
+    _check_buffer("A", A, (T, B, fc_w.shape[0]), torch.float32, fc_w.device)
+    _check_buffer("lengths", lens, (B,), torch.int32, fc_w.device)
+    if max_iters < 1:
+        raise ValueError(f"max_iters must be >= 1, got {max_iters}")
+    max_out = T * max_iters
+    tokens = torch.full((B, max_out), blank, device=A.device, dtype=torch.int64)
+    ntok = torch.zeros(B, device=A.device, dtype=torch.int32)
+    d.max_iters, d.max_out = max_iters, max_out
+    d.A, d.lens, d.tokens, d.ntok = _addr(A), _addr(lens), _addr(tokens), _addr(ntok)
+    check(_lib.lib().rnnt_hip_stream_greedy(C.byref(d), _stream()), "rnnt_hip_stream_greedy")
+    return tokens, ntok
