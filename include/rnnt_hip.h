@@ -557,6 +557,66 @@ int rnnt_hip_stream_greedy(const rnnt_stream_greedy_desc* d, void* stream);
 int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, const int32_t* rows, int32_t n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming beam search: the search of rnnt_hip_beam_search (networks/transducer.py:215-361 with lm=None, hotwords=None; the
+ * call the reference's inference.py:56-64 makes) fed in chunks.  After any sequence of chunks that together fed frames
+ * 0..n-1 of stream b, its n-best is what the offline search gives for an utterance of exactly those n frames, whatever the
+ * chunking: the frame loop is the same kernel code (csrc/beam_shared.hpp) and the reference sets A = B at every frame with
+ * nothing dropped (:287-288), so the whole last-frame B set is carried, with the state slots and prefix nodes it references.
+ *
+ * The workspace IS the carried state.  It starts with the layer-0 input table (V, G*Hp) (built by the reset entry when
+ * build_table != 0: the weights must not change while a state is open), followed per stream by a 256-byte header of int32
+ * { len(B), state slots in use, prefix nodes in use, committed length, RNNT_BEAM_ST_* status }, the A and B entries, the state
+ * slots, the slot remap table, the prefix nodes and a node remap table.
+ *
+ * Chunk call, one workgroup per stream, one launch: load the header; run frames t < lens[b] of A (from
+ * rnnt_hip_stream_rnn_chunk); collect the prefix tree (below); write the n-best; store the header.  lens[b] == 0: the
+ * stream's workspace is not touched, count[b] = -1 ("the previous list again") and status[b] = 0.
+ * Collection: every later hypothesis extends the y_star of a carried B entry, so the lowest common ancestor of their prefix
+ * nodes is final.  The tokens on the chain below the old root down to that ancestor go to commit[b] (ncommit[b] of them), the
+ * ancestor becomes the root, nodes on no path from it to a B entry are dropped and the rest compacted.  max_nodes therefore
+ * bounds the live tree.  Node lengths stay absolute (the final sort divides by len(y_star)).
+ * Results: tokens / out_lens hold only the tail of each y_star below the root (after this chunk's collection); the full y_star
+ * is every token committed since the stream's reset, leading blank first, followed by the tail.  max_len caps that tail.
+ * A cap overflow sets status[b] and the header's status; that stream is refused (same status again) until it is reset.  Other
+ * streams are not affected.
+ * Reset entry: rows[0..n_rows) (device int32) start a new utterance: B = { y_star [blank], score 0, state None }, committed
+ * length 1 (the blank).  Other rows are not touched.  A, lens and the outputs are unused there.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_stream_desc {
+  int32_t T, B, V;       /* chunk frames (0 allowed for the size query and the reset), streams, vocabulary (V >= 2) */
+  int32_t Hp, O, L;      /* as rnnt_decode_desc */
+  int32_t cell, blank;
+  int32_t beam, improved;
+  double state_beam, expand_beam;
+  int32_t max_candidates, max_pops, max_states, max_nodes, max_len;  /* caps (RNNT_BEAM_ST_*); max_len: uncommitted tail */
+  const float* A;        /* (T,B,V) from rnnt_hip_stream_rnn_chunk */
+  const int32_t* lens;   /* (B) device, frames of this chunk per stream, in [0, T] */
+  const float* emb;
+  const float* w_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* w_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* b_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* b_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* w_o;
+  const float* b_o;
+  const float* w_d;      /* fc.weight[:, O_enc:], row stride ld_d floats */
+  int64_t ld_d;
+  void* workspace;       /* rnnt_hip_beam_stream_workspace_bytes(d) bytes, 256-byte aligned: the carried state */
+  size_t workspace_bytes;
+  int32_t* tokens;       /* (B, beam, max_len) tail of y_star of rank r */
+  int32_t* out_lens;     /* (B, beam) tail lengths, 0 past count[b] */
+  double* scores;        /* (B, beam) asr_score */
+  int32_t* count;        /* (B) hypotheses returned, -1 for a stream without frames in this chunk */
+  int32_t* status;       /* (B) RNNT_BEAM_ST_* */
+  int32_t* commit;       /* (B, max_nodes) tokens committed by this chunk */
+  int32_t* ncommit;      /* (B) */
+  int32_t* stats;        /* (B, RNNT_BEAM_NSTATS) of this chunk (nodes: live after collection), or NULL */
+} rnnt_beam_stream_desc;
+size_t rnnt_hip_beam_stream_workspace_bytes(const rnnt_beam_stream_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_stream_reset(const rnnt_beam_stream_desc* d, const int32_t* rows, int32_t n_rows, int32_t build_table,
+                               void* stream);
+int rnnt_hip_beam_stream_chunk(const rnnt_beam_stream_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

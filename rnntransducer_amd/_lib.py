@@ -112,6 +112,19 @@ class StreamGreedyDesc(C.Structure):
                 ("tokens", C.c_void_p), ("ntok", C.c_void_p)]
 
 
+class BeamStreamDesc(C.Structure):
+    _fields_ = [("T", c_i32), ("B", c_i32), ("V", c_i32), ("Hp", c_i32), ("O", c_i32), ("L", c_i32), ("cell", c_i32),
+                ("blank", c_i32), ("beam", c_i32), ("improved", c_i32), ("state_beam", C.c_double), ("expand_beam", C.c_double),
+                ("max_candidates", c_i32), ("max_pops", c_i32), ("max_states", c_i32), ("max_nodes", c_i32), ("max_len", c_i32),
+                ("A", C.c_void_p), ("lens", C.c_void_p), ("emb", C.c_void_p),
+                ("w_ih", C.c_void_p * DECODE_MAX_LAYERS), ("w_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("b_ih", C.c_void_p * DECODE_MAX_LAYERS), ("b_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("w_o", C.c_void_p), ("b_o", C.c_void_p), ("w_d", C.c_void_p), ("ld_d", c_i64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("tokens", C.c_void_p), ("out_lens", C.c_void_p),
+                ("scores", C.c_void_p), ("count", C.c_void_p), ("status", C.c_void_p), ("commit", C.c_void_p),
+                ("ncommit", C.c_void_p), ("stats", C.c_void_p)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -176,6 +189,9 @@ SYMBOLS = {
     "rnnt_hip_stream_rnn_chunk": (C.c_int, [C.POINTER(StreamRnnDesc), C.c_void_p]),
     "rnnt_hip_stream_greedy": (C.c_int, [C.POINTER(StreamGreedyDesc), C.c_void_p]),
     "rnnt_hip_stream_greedy_reset": (C.c_int, [C.POINTER(StreamGreedyDesc), C.c_void_p, c_i32, C.c_void_p]),
+    "rnnt_hip_beam_stream_workspace_bytes": (C.c_size_t, [C.POINTER(BeamStreamDesc)]),
+    "rnnt_hip_beam_stream_reset": (C.c_int, [C.POINTER(BeamStreamDesc), C.c_void_p, c_i32, c_i32, C.c_void_p]),
+    "rnnt_hip_beam_stream_chunk": (C.c_int, [C.POINTER(BeamStreamDesc), C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
 }

@@ -12,424 +12,46 @@
 //     matvec, same bits), so only W_hh0 h and the deeper layers are streamed per step.
 //   * y_star is a prefix tree of (parent, token, length) nodes.  An A entry is (node, appended token or -1): its node is only
 //     made when it is popped, so nodes <= pops.  The dedupe rule (transducer.py:333,343) reads the last token only.
+// The kernel itself lives in beam_shared.hpp, shared with the streaming search (beam_stream.hip).
 // Per-utterance workspace (global memory, touched only by its workgroup): A entries of the current frame, B entries, state
 // slots (h, c, C), a slot remap table and the prefix nodes.  State slots are compacted at every frame start (only the
 // slots the carried B entries reference stay), so they scale with pops per frame.  Every loop is bounded by a cap; on
 // overflow the utterance writes its status and exits (all threads together: every branch below is workgroup-uniform).
-#include "decode_shared.hpp"
-
-namespace rnnt {
-namespace {
-
-struct Hyp {       // an A or B entry (32 bytes)
-  double score;    // asr_score (fp64: Python floats, transducer.py:322)
-  int node;        // prefix-tree node of y_star (without `tok`)
-  int tok;         // token appended to node's y_star, or -1
-  int state;       // slot of hidden_state, -1 = None (zeros)
-  int memo;        // slot holding step(state, last token) = (h', C), or -1
-  int live;        // still in A
-  int pad;
-};
-
-struct BeamK {
-  int T, B, V, Hp, O, L, cell, blank, beam, improved;
-  double state_beam, expand_beam;
-  int max_cands, max_pops, max_states, max_nodes, max_len;
-  const float* A;
-  const int* t_lens;
-  const float* emb;
-  const float* w_ih[DEC_MAX_LAYERS];
-  const float* w_hh[DEC_MAX_LAYERS];
-  const float* b_ih[DEC_MAX_LAYERS];
-  const float* b_hh[DEC_MAX_LAYERS];
-  const float* w_o;
-  const float* b_o;
-  const float* w_d;
-  long ld_d;
-  const float* table;  // (V, G*Hp) layer-0 input projection
-  char* ws;            // per-utterance workspaces, `ws_stride` bytes each
-  size_t ws_stride, off_b, off_slots, off_remap, off_nodes;
-  int slot_floats;     // h[L*Hp] | c[L*Hp] (LSTM) | C[V], padded to 4
-  int* tokens;
-  int* lens;
-  double* scores;
-  int* count;
-  int* status;
-  int* stats;
-};
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct BeamLayout {
-  size_t table_bytes, off_b, off_slots, off_remap, off_nodes, stride;
-  int slot_floats;
-};
-
-static BeamLayout beam_layout(const rnnt_beam_desc* d) {
-  BeamLayout l;
-  const int NG = d->cell == RNNT_CELL_LSTM ? 4 : (d->cell == RNNT_CELL_GRU ? 3 : 1);
-  l.table_bytes = align256((size_t)d->V * NG * d->Hp * sizeof(float));
-  l.slot_floats = (int)((d->L * d->Hp * (d->cell == RNNT_CELL_LSTM ? 2 : 1) + d->V + 3) & ~3);
-  l.off_b = align256((size_t)d->max_candidates * sizeof(Hyp));
-  l.off_slots = l.off_b + align256((size_t)d->max_pops * sizeof(Hyp));
-  l.off_remap = l.off_slots + align256((size_t)d->max_states * l.slot_floats * sizeof(float));
-  l.off_nodes = l.off_remap + align256((size_t)d->max_states * sizeof(int));
-  l.stride = l.off_nodes + align256((size_t)d->max_nodes * sizeof(int4));
-  return l;
-}
-
-// table[k] = W_ih0 emb[k] + b_ih0, one workgroup per token
-__global__ void __launch_bounds__(DEC_THREADS) beam_table_kernel(const BeamK p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* x = reinterpret_cast<float*>(smem);
-  const int k = blockIdx.x, NG = cell_gates(p.cell);
-  for (int i = threadIdx.x; i < p.Hp; i += DEC_THREADS) x[i] = p.emb[(long)k * p.Hp + i];
-  __syncthreads();
-  matvec(p.w_ih[0], p.Hp, NG * p.Hp, p.Hp, x, const_cast<float*>(p.table) + (long)k * NG * p.Hp, p.b_ih[0]);
-}
-
-// (key desc, index asc) merge: Python's max / stable sort keep the first of equal keys
-__device__ __forceinline__ bool better(double s, int i, double bs, int bi) { return s > bs || (s == bs && i < bi); }
-
-// dynamic LDS: redd[16] ctld[4] (double) | redi[16] ctl[16] (int) | redf[16] | h[L*Hp] | c[L*Hp] | gi[4Hp] | gh[4Hp] | x[Hp]
-//              | dec[O] | Cv[V] | logp[V]
-__global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* redd = reinterpret_cast<double*>(smem);
-  double* ctld = redd + 16;
-  int* redi = reinterpret_cast<int*>(ctld + 4);
-  int* ctl = redi + 16;
-  float* redf = reinterpret_cast<float*>(ctl + 16);
-  const int Hp = p.Hp, V = p.V, L = p.L;
-  float* h = redf + 16;
-  float* c = h + L * Hp;
-  float* gi = c + L * Hp;
-  float* gh = gi + 4 * Hp;
-  float* x = gh + 4 * Hp;
-  float* dec = x + Hp;
-  float* Cv = dec + p.O;
-  float* logp = Cv + V;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NW = DEC_THREADS / 64;
-  const int b = blockIdx.x;
-  const bool lstm = p.cell == RNNT_CELL_LSTM;
-  const int NG = cell_gates(p.cell);
-  char* ws = p.ws + (size_t)b * p.ws_stride;
-  Hyp* cands = reinterpret_cast<Hyp*>(ws);
-  Hyp* bents = reinterpret_cast<Hyp*>(ws + p.off_b);
-  float* slots = reinterpret_cast<float*>(ws + p.off_slots);
-  int* remap = reinterpret_cast<int*>(ws + p.off_remap);
-  int4* nodes = reinterpret_cast<int4*>(ws + p.off_nodes);  // (parent, token, len, -)
-  const int SF = p.slot_floats;
-
-  // block-wide argmax of (key desc, index asc); every thread returns the winner (index -1: no candidate)
-  auto block_argmax = [&](double key, int idx, double& best) -> int {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ok = __shfl_xor(key, o);
-      const int oi = __shfl_xor(idx, o);
-      if (better(ok, oi, key, idx)) { key = ok; idx = oi; }
-    }
-    if (lane == 0) { redd[wave] = key; redi[wave] = idx; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < NW; ++w)
-        if (better(redd[w], redi[w], key, idx)) { key = redd[w]; idx = redi[w]; }
-      ctld[0] = key;
-      ctl[0] = idx;
-    }
-    __syncthreads();
-    best = ctld[0];
-    const int r = ctl[0];
-    __syncthreads();
-    return r == 0x7fffffff ? -1 : r;
-  };
-  // block-wide float reduction in a fixed order (deterministic); max or sum
-  auto block_reduce = [&](float v, bool is_max) -> float {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v, o);
-      v = is_max ? fmaxf(v, ov) : v + ov;
-    }
-    if (lane == 0) redf[wave] = v;
-    __syncthreads();
-    float r = redf[0];
-    for (int w = 1; w < NW; ++w) r = is_max ? fmaxf(r, redf[w]) : r + redf[w];
-    __syncthreads();
-    return r;
-  };
-  auto fail = [&](int code) {
-    if (tid == 0) { p.status[b] = code; p.count[b] = 0; }
-    for (int r = tid; r < p.beam; r += DEC_THREADS) p.lens[(long)b * p.beam + r] = 0;
-  };
-
-  // y_star = [blank], state None (transducer.py:276-284)
-  if (tid == 0) {
-    nodes[0] = make_int4(-1, p.blank, 1, 0);
-    Hyp r0;
-    r0.score = 0.0; r0.node = 0; r0.tok = -1; r0.state = -1; r0.memo = -1; r0.live = 1; r0.pad = 0;
-    bents[0] = r0;
-  }
-  __syncthreads();
-  int nB = 1, nslots = 0, nnodes = 1;
-  long long pops_total = 0, steps_total = 0;
-  int max_pops_seen = 0, max_cands_seen = 0, max_slots_seen = 0;
-  int Tb = p.t_lens ? p.t_lens[b] : p.T;
-  Tb = Tb < 0 ? 0 : (Tb > p.T ? p.T : Tb);
-
-  for (int t = 0; t < Tb; ++t) {
-    // ---- A = B_prev (transducer.py:287-288); keep only the state slots it references, compacted in slot order ----
-    if (nB > p.max_cands) { fail(RNNT_BEAM_ST_CANDIDATES); return; }
-    for (int s = tid; s < nslots; s += DEC_THREADS) remap[s] = -1;
-    __syncthreads();
-    for (int i = tid; i < nB; i += DEC_THREADS) {
-      Hyp e = bents[i];
-      e.tok = -1;
-      e.live = 1;
-      cands[i] = e;
-      if (e.state >= 0) remap[e.state] = 1;
-      if (e.memo >= 0) remap[e.memo] = 1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int n = 0;
-      for (int s = 0; s < nslots; ++s)
-        if (remap[s] >= 0) remap[s] = n++;
-      ctl[1] = n;
-    }
-    __syncthreads();
-    const int nlive = ctl[1];
-    for (int s = 0; s < nslots; ++s) {  // increasing s, destination r <= s: never overwrites a slot still to be moved
-      const int r = remap[s];
-      if (r >= 0 && r != s) {
-        for (int i = tid; i < SF; i += DEC_THREADS) slots[(long)r * SF + i] = slots[(long)s * SF + i];
-        __syncthreads();
-      }
-    }
-    for (int i = tid; i < nB; i += DEC_THREADS) {
-      if (cands[i].state >= 0) cands[i].state = remap[cands[i].state];
-      if (cands[i].memo >= 0) cands[i].memo = remap[cands[i].memo];
-    }
-    __syncthreads();
-    nslots = nlive;
-    int nA = nB;
-    nB = 0;
-    double bestB = 0.0;
-    int npops = 0;
-    const float* At = p.A + ((long)t * p.B + b) * V;
-
-    for (;;) {  // at most max_pops + 1 passes
-      double abest;
-      double key = -__builtin_huge_val();
-      int idx = 0x7fffffff;
-      for (int i = tid; i < nA; i += DEC_THREADS)
-        if (cands[i].live && better(cands[i].score, i, key, idx)) { key = cands[i].score; idx = i; }
-      const int ia = block_argmax(key, idx, abest);
-      if (ia < 0) break;  // A empty (transducer.py:286; after a pop the reference's max(A) would raise here instead)
-      if (npops > 0 && nB >= p.beam && bestB > abest) break;  // :355-358
-      if (p.improved && (nB == 0 ? -9999.0 : bestB) >= p.state_beam + abest) break;  // :291-302
-      if (npops >= p.max_pops) { fail(RNNT_BEAM_ST_POPS); return; }
-
-      // ---- pop (transducer.py:304) ----
-      const Hyp a = cands[ia];
-      __syncthreads();
-      if (tid == 0) cands[ia].live = 0;
-      int node = a.node, last;
-      if (a.tok >= 0) {
-        if (nnodes >= p.max_nodes) { fail(RNNT_BEAM_ST_NODES); return; }
-        const int len = nodes[a.node].z + 1;
-        if (tid == 0) nodes[nnodes] = make_int4(a.node, a.tok, len, 0);
-        node = nnodes++;
-        last = a.tok;
-      } else {
-        last = nodes[a.node].y;
-      }
-      int S = a.memo;
-      if (S < 0) {  // one prediction-net step on y_star[-1] from the popped state (:307-312)
-        if (nslots >= p.max_states) { fail(RNNT_BEAM_ST_STATES); return; }
-        S = nslots++;
-        const float* st = a.state >= 0 ? slots + (long)a.state * SF : nullptr;
-        for (int i = tid; i < L * Hp; i += DEC_THREADS) {
-          h[i] = st ? st[i] : 0.f;
-          c[i] = (st && lstm) ? st[L * Hp + i] : 0.f;
-        }
-        for (int i = tid; i < Hp; i += DEC_THREADS) x[i] = p.emb[(long)last * Hp + i];
-        __syncthreads();
-        prednet_cells(p, h, c, gi, gh, x, p.table + (long)last * NG * Hp);
-        prednet_joint_half(p, h + (L - 1) * Hp, dec, Cv);
-        float* sl = slots + (long)S * SF;
-        for (int i = tid; i < L * Hp; i += DEC_THREADS) {
-          sl[i] = h[i];
-          if (lstm) sl[L * Hp + i] = c[i];
-        }
-        for (int v = tid; v < V; v += DEC_THREADS) sl[SF - V + v] = Cv[v];  // C sits at the end of the slot
-        ++steps_total;
-      }
-      const float* Cs = slots + (long)S * SF + (SF - V);
-      __syncthreads();
-
-      // ---- logp = log_softmax(joint) in fp32 (:313-315) ----
-      float m = -__builtin_huge_valf();
-      for (int v = tid; v < V; v += DEC_THREADS) {
-        const float z = At[v] + Cs[v];
-        logp[v] = z;
-        m = fmaxf(m, z);
-      }
-      m = block_reduce(m, true);
-      float s = 0.f;
-      for (int v = tid; v < V; v += DEC_THREADS) s += expf(logp[v] - m);
-      const float ls = logf(block_reduce(s, false));
-      float bp = -__builtin_huge_valf();
-      for (int v = tid; v < V; v += DEC_THREADS) {
-        const float l = (logp[v] - m) - ls;
-        logp[v] = l;
-        if (v >= 1) bp = fmaxf(bp, l);
-      }
-      const float thr = block_reduce(bp, true) - (float)p.expand_beam;  // best_prob = max(logp[1:]) (:317), fp32 tensor math
-
-      // ---- children (:319-350): blank -> B (old state, memo = this step), the rest -> A in k order ----
-      const double sb = a.score + (double)logp[p.blank];
-      if (tid == 0) {
-        Hyp e;
-        e.score = sb; e.node = node; e.tok = -1; e.state = a.state; e.memo = S; e.live = 0; e.pad = 0;
-        bents[nB] = e;  // nB == npops < max_pops
-      }
-      bestB = (nB == 0 || sb > bestB) ? sb : bestB;
-      ++nB;
-      int base = nA;
-      for (int k0 = 0; k0 < V; k0 += DEC_THREADS) {
-        const int k = k0 + tid;
-        const bool keep = k < V && k != p.blank && (!p.improved || logp[k] >= thr);
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) redi[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < NW; ++w) {
-          before += w < wave ? redi[w] : 0;
-          total += redi[w];
-        }
-        const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep && pos < p.max_cands) {
-          Hyp e;
-          e.score = a.score + (double)logp[k];
-          e.node = node; e.tok = k == last ? -1 : k; e.state = S; e.memo = -1; e.live = 1; e.pad = 0;
-          cands[pos] = e;
-        }
-        base += total;
-        __syncthreads();
-      }
-      if (base > p.max_cands) { fail(RNNT_BEAM_ST_CANDIDATES); return; }
-      nA = base;
-      ++npops;
-      __syncthreads();
-    }
-    pops_total += npops;
-    max_pops_seen = npops > max_pops_seen ? npops : max_pops_seen;
-    max_cands_seen = nA > max_cands_seen ? nA : max_cands_seen;
-    max_slots_seen = nslots > max_slots_seen ? nslots : max_slots_seen;
-  }
-
-  // ---- n-best (:360-361): stable sort by asr_score / len(y_star) descending, first `beam` ----
-  const int nout = nB < p.beam ? nB : p.beam;
-  for (int i = tid; i < nB; i += DEC_THREADS) bents[i].live = 1;
-  __syncthreads();
-  for (int r = 0; r < nout; ++r) {
-    double key = -__builtin_huge_val();
-    int idx = 0x7fffffff;
-    for (int i = tid; i < nB; i += DEC_THREADS)
-      if (bents[i].live) {
-        const double k = bents[i].score / (double)nodes[bents[i].node].z;
-        if (better(k, i, key, idx)) { key = k; idx = i; }
-      }
-    double kbest;
-    const int ib = block_argmax(key, idx, kbest);
-    const Hyp e = bents[ib];
-    const int len = nodes[e.node].z;
-    if (len > p.max_len) { fail(RNNT_BEAM_ST_LEN); return; }
-    if (tid == 0) {
-      bents[ib].live = 0;
-      int* out = p.tokens + ((long)b * p.beam + r) * p.max_len;
-      int n = e.node;
-      for (int j = len - 1; j >= 0; --j) {  // len steps: the root has length 1
-        const int4 nd = nodes[n];
-        out[j] = nd.y;
-        n = nd.x;
-      }
-      p.lens[(long)b * p.beam + r] = len;
-      p.scores[(long)b * p.beam + r] = e.score;
-    }
-    __syncthreads();
-  }
-  for (int r = nout + tid; r < p.beam; r += DEC_THREADS) p.lens[(long)b * p.beam + r] = 0;
-  if (tid == 0) {
-    p.count[b] = nout;
-    p.status[b] = RNNT_BEAM_ST_OK;
-    if (p.stats) {
-      int* st = p.stats + (long)b * RNNT_BEAM_NSTATS;
-      st[0] = (int)pops_total; st[1] = (int)steps_total; st[2] = max_pops_seen; st[3] = max_cands_seen;
-      st[4] = max_slots_seen; st[5] = nnodes;
-    }
-  }
-}
-
-}  // namespace
-}  // namespace rnnt
+#include "beam_shared.hpp"
 
 using namespace rnnt;
 
-static int beam_check(const rnnt_beam_desc* d) {
-  RNNT_CHECK_ARG(d != nullptr, "beam_search: null descriptor");
-  RNNT_CHECK_ARG(d->T >= 1 && d->B >= 1 && d->V >= 2 && d->Hp >= 4 && d->Hp % 4 == 0 && d->O >= 4 && d->O % 4 == 0,
-                 "beam_search: bad dims (V >= 2; hidden and output sizes must be multiples of 4)");
-  RNNT_CHECK_ARG(d->L >= 1 && d->L <= DEC_MAX_LAYERS, "beam_search: 1..%d prediction-net layers", DEC_MAX_LAYERS);
-  RNNT_CHECK_ARG(d->cell >= RNNT_CELL_LSTM && d->cell <= RNNT_CELL_RNN_RELU, "beam_search: unknown cell type");
-  RNNT_CHECK_ARG(d->blank >= 0 && d->blank < d->V && d->beam >= 1, "beam_search: bad blank / beam width");
-  RNNT_CHECK_ARG(d->max_candidates >= 1 && d->max_pops >= 1 && d->max_states >= 1 && d->max_nodes >= 1 && d->max_len >= 1,
-                 "beam_search: caps must be >= 1");
-  return RNNT_OK;
+static BeamLayout beam_layout(const rnnt_beam_desc* d) {
+  return beam_layout(d->V, d->Hp, d->L, d->cell, d->max_candidates, d->max_pops, d->max_states, d->max_nodes, false);
 }
 
 extern "C" size_t rnnt_hip_beam_workspace_bytes(const rnnt_beam_desc* d) {
-  if (beam_check(d) != RNNT_OK) return 0;
+  if (beam_check_dims(d, "beam_search", 1) != RNNT_OK) return 0;
   const BeamLayout l = beam_layout(d);
   return l.table_bytes + l.stride * (size_t)d->B;
 }
 
 extern "C" int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream) {
-  const int rc = beam_check(d);
+  int rc = beam_check_dims(d, "beam_search", 1);
   if (rc != RNNT_OK) return rc;
-  RNNT_CHECK_ARG(d->A && d->emb && d->w_o && d->b_o && d->w_d && d->tokens && d->lens && d->scores && d->count && d->status,
-                 "beam_search: null pointer");
-  RNNT_CHECK_ARG(d->ld_d % 4 == 0 && (reinterpret_cast<uintptr_t>(d->w_d) & 15) == 0, "beam_search: fc slice must be 16-byte aligned");
+  RNNT_CHECK_ARG(d->A && d->lens, "beam_search: null pointer");
+  BeamK k;
+  if ((rc = beam_fill_common(d, k, "beam_search")) != RNNT_OK) return rc;
+  k.t_lens = d->t_lens;
+  k.lens = d->lens;
   const BeamLayout l = beam_layout(d);
   RNNT_CHECK_ARG(d->workspace && (reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0 &&
                  d->workspace_bytes >= l.table_bytes + l.stride * (size_t)d->B,
                  "beam_search: workspace must be 256-byte aligned and hold rnnt_hip_beam_workspace_bytes() bytes");
-  BeamK k;
-  k.T = d->T; k.B = d->B; k.V = d->V; k.Hp = d->Hp; k.O = d->O; k.L = d->L; k.cell = d->cell; k.blank = d->blank;
-  k.beam = d->beam; k.improved = d->improved ? 1 : 0; k.state_beam = d->state_beam; k.expand_beam = d->expand_beam;
-  k.max_cands = d->max_candidates; k.max_pops = d->max_pops; k.max_states = d->max_states; k.max_nodes = d->max_nodes;
-  k.max_len = d->max_len;
-  k.A = d->A; k.t_lens = d->t_lens; k.emb = d->emb;
-  for (int i = 0; i < d->L; ++i) {
-    RNNT_CHECK_ARG(d->w_ih[i] && d->w_hh[i] && d->b_ih[i] && d->b_hh[i], "beam_search: null weight (layer %d)", i);
-    k.w_ih[i] = d->w_ih[i]; k.w_hh[i] = d->w_hh[i]; k.b_ih[i] = d->b_ih[i]; k.b_hh[i] = d->b_hh[i];
-  }
-  k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
-  k.table = reinterpret_cast<const float*>(d->workspace);
-  k.ws = reinterpret_cast<char*>(d->workspace) + l.table_bytes;
-  k.ws_stride = l.stride; k.off_b = l.off_b; k.off_slots = l.off_slots; k.off_remap = l.off_remap; k.off_nodes = l.off_nodes;
-  k.slot_floats = l.slot_floats;
-  k.tokens = d->tokens; k.lens = d->lens; k.scores = d->scores; k.count = d->count; k.status = d->status; k.stats = d->stats;
-  const size_t lds = 20 * sizeof(double) + 32 * sizeof(int) + 16 * sizeof(float) +
-                     ((size_t)2 * d->L * d->Hp + 9 * (size_t)d->Hp + d->O + 2 * (size_t)d->V) * sizeof(float);
+  beam_set_layout(k, d->workspace, l);
+  const size_t lds = beam_lds_bytes(d->L, d->Hp, d->O, d->V);
   RNNT_CHECK_ARG(lds <= 160 * 1024, "beam_search: state needs %zu B of LDS (> 160 KiB)", lds);
   if (lds > 64 * 1024)
-    RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)beam_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)beam_search_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V, (hipStream_t)stream);
   hipLaunchKernelGGL(beam_table_kernel, dim3(d->V), dim3(DEC_THREADS), (size_t)d->Hp * sizeof(float), (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(beam_search_kernel, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(beam_search_kernel<false>, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
 }

@@ -128,6 +128,16 @@ class RNNTransducer(_Base):
         """JointNet.recognize_greedy_stream: the tokens each stream appends during this chunk of features."""
         return self.jointnet.recognize_greedy_stream(chunk, chunk_lengths, state, max_iters)
 
+    def init_beam_stream(self, batch_size: int, beam_widths: int = 100, improved: bool = False, state_beam: float = 4.6,
+                         expand_beam: float = 2.3, device=None, **caps):
+        """JointNet.init_beam_stream with this model's blank: per-stream state for recognize_beams_stream."""
+        return self.jointnet.init_beam_stream(batch_size, self.blank_token_id, beam_widths, improved, state_beam, expand_beam,
+                                              device, **caps)
+
+    def recognize_beams_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False):
+        """JointNet.recognize_beams_stream: per stream the n-best list for the frames fed so far."""
+        return self.jointnet.recognize_beams_stream(chunk, chunk_lengths, state, return_scores=return_scores)
+
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
         """model.py:62-79: loss + greedy search (max 3 symbols per frame).  `pred_tokens` is a list of B 1-D LongTensors

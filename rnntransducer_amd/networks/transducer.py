@@ -13,6 +13,8 @@ launch too (csrc/beam.hip): the reference's pop / expand / prune / stop decision
 prefix tree for y_star; LM and hotword rescoring (pyctcdecode / KenLM) stay out of scope.
 `init_stream` / `recognize_greedy_stream` run the same greedy search over a batch of streams fed in chunks, with the encoder,
 prediction-net and search state carried between chunks (rnntransducer_amd/streaming.py, csrc/stream.hip).
+`init_beam_stream` / `recognize_beams_stream` do the same for the beam search: the whole hypothesis set is carried on the device
+(csrc/beam_stream.hip, the offline kernel's frame loop), with the stable prefix of every stream exposed after each chunk.
 """
 import torch
 import torch.nn as nn
@@ -159,9 +161,11 @@ class JointNet(nn.Module):
         The per-frame rule is recognize_greedy's; any chunking of an utterance gives the same bits as one chunk holding all of
         it, and the tokens of recognize_greedy wherever no two logits are within fp32 rounding of each other.
         Unidirectional encoders only; fp32 whatever compute_precision says."""
-        from ..streaming import host_lengths
+        from ..streaming import GreedyStreamState, host_lengths
         self.encoder.check_streamable("recognize_greedy_stream")
         self.encoder.check_stream_chunk(chunk, "recognize_greedy_stream")
+        if not isinstance(state, GreedyStreamState):
+            raise ValueError(f"recognize_greedy_stream takes the state of init_stream, got {type(state).__name__}")
         B, T, _ = chunk.shape
         state.check_fits(self, B, chunk.device)
         if max_iters < 1:
@@ -181,3 +185,45 @@ class JointNet(nn.Module):
         state.frames_seen += lens_dev
         n = ntok.tolist()  # the only host sync of the chunk
         return [tokens[b, :n[b]] for b in range(B)]
+
+    def init_beam_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
+                         state_beam: float = 4.6, expand_beam: float = 2.3, device=None, **caps):
+        """A streaming.BeamStreamState for `batch_size` streams, each starting as recognize_beams starts an utterance
+        (transducer.py:276-284): y_star = [blank], score 0, no prediction-net state.  The search options are fixed here: they
+        size the workspace and belong to the utterance.  `caps`: max_pops / max_candidates / max_states / max_nodes / max_len as
+        in ops.beam_search, with streaming defaults (ops.beam_stream_caps; max_nodes bounds the LIVE prefix tree, max_len the
+        uncommitted tail of a y_star); `state.workspace_bytes` / `state.bytes_per_stream` tell what they cost.  `device`, if
+        given, must be the model's.  The weights must not change while the state is open."""
+        from ..streaming import BeamStreamState
+        self.encoder.check_streamable("init_beam_stream")
+        return BeamStreamState(self, batch_size, blank_token_id, beam_widths, improved, state_beam, expand_beam, device, **caps)
+
+    @torch.no_grad()
+    def recognize_beams_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False):
+        """Beam search over the next chunk of every stream: chunk (B,T_c,F) fp32 on the GPU, chunk_lengths B values in [0,T_c],
+        `state` from this model's init_beam_stream, updated in place.  Returns a list of B n-best lists, each what
+        recognize_beams returns for the frames that stream has been fed so far (transducer.py:215-361 with lm=None: full y_star
+        with the leading blank, best first by asr_score / len(y_star), duplicates kept; (y_star, asr_score) pairs with
+        return_scores=True), whatever the chunking: same tokens, bitwise the same fp64 scores.  A stream that has seen no
+        frames returns [[blank]]; a stream with 0 frames in this chunk is left bitwise unchanged and returns its previous list.
+        `state.stable_prefix(b)` is the part of stream b's answer that no later chunk can change.
+        One launch for the search and one host sync per call.  A stream that outgrows a cap raises RnntHipError naming it after
+        the other streams have been updated; it must be reset before it is fed again.
+        Unidirectional encoders only; fp32 whatever compute_precision says."""
+        from ..streaming import BeamStreamState, host_lengths
+        self.encoder.check_streamable("recognize_beams_stream")
+        self.encoder.check_stream_chunk(chunk, "recognize_beams_stream")
+        if not isinstance(state, BeamStreamState):
+            raise ValueError(f"recognize_beams_stream takes the state of init_beam_stream, got {type(state).__name__}")
+        B, T, _ = chunk.shape
+        state.check_fits(self, B, chunk.device)
+        lens = host_lengths(chunk_lengths, B, T)
+        state.check_feedable(lens)
+        T_run = max(lens)
+        if T_run > 0:
+            lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
+            enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
+            A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
+                                          (self.fc.weight, self.fc.bias))
+            state.run_chunk(A, lens_dev)
+        return state.results(return_scores)

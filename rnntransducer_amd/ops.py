@@ -1063,3 +1063,83 @@ def stream_greedy(A: torch.Tensor, lens: torch.Tensor, fc_w, emb_w, rnn_weights,
     d.A, d.lens, d.tokens, d.ntok = _addr(A), _addr(lens), _addr(tokens), _addr(ntok)
     check(_lib.lib().rnnt_hip_stream_greedy(C.byref(d), _stream()), "rnnt_hip_stream_greedy")
     return tokens, ntok
+
+
+# --------------------------------------------------------------------------------------------------
+# streaming beam search (include/rnnt_hip.h: rnnt_hip_beam_stream_*); the workspace and the output buffers belong to
+# streaming.BeamStreamState
+# --------------------------------------------------------------------------------------------------
+BEAM_STREAM_CAPS = ("max_pops", "max_candidates", "max_states", "max_nodes", "max_len")
+
+
+def beam_stream_caps(V: int, beam: int, *, max_pops: Optional[int] = None, max_candidates: Optional[int] = None,
+                     max_states: Optional[int] = None, max_nodes: int = 8192, max_len: int = 256) -> dict:
+    """The streaming defaults of the caps of `beam_search`: max_pops = max(128, 4 * beam) pops per frame, max_candidates =
+    max_pops * V, max_states = 3 * max_pops, max_nodes = 8192 LIVE prefix nodes (the tree is collected after every chunk, so
+    this must hold the carried tree plus one chunk's growth of at most one node per pop), max_len = 256 tokens of a y_star
+    not yet committed.  The offline defaults size for a whole utterance without collection (max_pops 1024, 2^18 nodes)."""
+    max_pops = max(128, 4 * beam) if max_pops is None else max_pops
+    caps = dict(max_pops=max_pops, max_candidates=max_pops * V if max_candidates is None else max_candidates,
+                max_states=3 * max_pops if max_states is None else max_states, max_nodes=max_nodes, max_len=max_len)
+    for k, v in caps.items():
+        if not isinstance(v, int) or v < 1:
+            raise ValueError(f"streaming beam search: {k} must be an integer >= 1, got {v!r}")
+    return caps
+
+
+def beam_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, beam: int, improved: bool,
+                     state_beam: float, expand_beam: float, caps: dict):
+    """Descriptor of the streaming beam search with every weight shape checked against the others (raw pointers); the
+    workspace, A, lens and the outputs are the caller's to fill.  -> (descriptor, tensors to keep alive)."""
+    _need_gpu(fc_w, emb_w)
+    V, Ocat = fc_w.shape
+    Od = out_w.shape[0]
+    Hp, L = emb_w.shape[1], len(rnn_weights) // 4
+    if L > _lib.DECODE_MAX_LAYERS:
+        raise ValueError(f"beam search supports at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
+    _check_prednet_weights(rnn_weights, cell, Hp)
+    if not 1 <= Od < Ocat or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or emb_w.shape[0] < V:
+        raise ValueError(f"streaming beam search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding "
+                         f"{tuple(emb_w.shape)} do not fit together (the embedding needs a row per fc output)")
+    if not 0 <= blank < V or V < 2 or beam < 1 or B < 1:
+        raise ValueError(f"streaming beam search: blank {blank} outside [0,{V}), V {V} < 2, beam {beam} < 1 or {B} streams")
+    d = _lib.BeamStreamDesc()
+    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = 0, B, V, Hp, Od, L, cell, blank
+    d.beam, d.improved, d.state_beam, d.expand_beam = beam, int(bool(improved)), float(state_beam), float(expand_beam)
+    d.max_candidates, d.max_pops, d.max_states, d.max_nodes, d.max_len = (caps[k] for k in ("max_candidates", "max_pops",
+                                                                                           "max_states", "max_nodes", "max_len"))
+    keep = [_f32c(t, "prediction-net weight") for t in rnn_weights]
+    keep += [_f32c(emb_w, "embedding"), _f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias"), _f32c(fc_w, "fc weight")]
+    d.emb = _addr(keep[-4])
+    for l in range(L):
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
+    d.w_o, d.b_o = _addr(keep[-3]), _addr(keep[-2])
+    d.w_d, d.ld_d = _addr(keep[-1], Ocat - Od), Ocat
+    return d, keep
+
+
+def beam_stream_workspace_bytes(d) -> int:
+    n = _lib.lib().rnnt_hip_beam_stream_workspace_bytes(C.byref(d))
+    if n == 0:
+        raise ValueError("streaming beam search: invalid sizes or caps (all caps must be >= 1)")
+    return n
+
+
+def beam_stream_reset(d, rows: torch.Tensor, build_table: bool) -> None:
+    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to."""
+    _need_gpu(rows)
+    _check_buffer("rows", rows, (rows.numel(),), torch.int32, rows.device)
+    check(_lib.lib().rnnt_hip_beam_stream_reset(C.byref(d), _addr(rows), rows.numel(), int(build_table), _stream()),
+          "rnnt_hip_beam_stream_reset")
+
+
+def beam_stream_chunk(d, A: torch.Tensor, lens: torch.Tensor) -> None:
+    """One chunk: A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; the outputs d points to are written."""
+    _need_gpu(A, lens)
+    _check_buffer("A", A, (A.shape[0], d.B, d.V), torch.float32, A.device)
+    _check_buffer("lengths", lens, (d.B,), torch.int32, A.device)
+    d.T, d.A, d.lens = A.shape[0], _addr(A), _addr(lens)
+    try:
+        check(_lib.lib().rnnt_hip_beam_stream_chunk(C.byref(d), _stream()), "rnnt_hip_beam_stream_chunk")
+    finally:
+        d.T, d.A, d.lens = 0, None, None

@@ -11,6 +11,14 @@ order) the tokens agree wherever no two logits are within fp32 rounding of each 
     for chunk, lengths in feed:                  # chunk (B, T_c, F) on the GPU, lengths in [0, T_c] per stream
         new_tokens = jointnet.recognize_greedy_stream(chunk, lengths, state)
     state.reset([slot])                          # a new utterance in one slot; the other slots are not touched
+
+Streaming beam search (`JointNet.init_beam_stream` / `recognize_beams_stream`, csrc/beam_stream.hip) carries the search of
+`recognize_beams` the same way: after every chunk each stream's n-best is what `recognize_beams` gives for the frames fed so far.
+
+    state = jointnet.init_beam_stream(batch_size, blank, beam_widths=5, improved=True)
+    for chunk, lengths in feed:
+        nbest = jointnet.recognize_beams_stream(chunk, lengths, state)    # per stream: y_star lists, best first
+        partial = state.stable_prefix(0)                                  # the tokens of stream 0 no later chunk can change
 """
 from __future__ import annotations
 
@@ -19,7 +27,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import ops
-from ._lib import CELL_LSTM
+from ._lib import BEAM_NSTATS, BEAM_STATUS, CELL_LSTM, RnntHipError
 
 
 def host_lengths(chunk_lengths: Union[Sequence[int], torch.Tensor], B: int, T: int) -> List[int]:
@@ -121,3 +129,177 @@ class GreedyStreamState:
                                 dec.out_proj.weight, dec.out_proj.bias, self.blank, self.pred_h, self.pred_c, self.pred_joint,
                                 self.last_token)
         return self
+
+
+class BeamStreamState:
+    """Per-stream state of `JointNet.recognize_beams_stream`.  On the device:
+      enc_h / enc_c   (L_enc, B, H)   encoder state (enc_c None unless the encoder is an LSTM)
+      workspace       uint8           the carried search: the layer-0 input table of the prediction net, then per stream a
+                                      header (len(B), state slots, prefix nodes, committed length, status), the WHOLE last-frame
+                                      B set (fp64 score, prefix node, state slot, memo slot per entry), the prediction-net state
+                                      slots those entries reference and the prefix-tree nodes (include/rnnt_hip.h)
+      frames_seen     (B,) int64      frames consumed since the stream's last reset
+    On the host: the committed tokens per stream (`stable_prefix`) and the n-best list of the last chunk that fed it.
+    The search options and the caps are fixed here: they size the workspace and belong to the utterance.  The table is built
+    from the prediction net's weights when the state is opened, so the weights must not change while it is open (as
+    GreedyStreamState assumes for pred_joint).
+
+    Caps (`ops.beam_stream_caps`; each overflow raises RnntHipError naming it): max_pops = max(128, 4 * beam_widths) pops per
+    frame, max_candidates = max_pops * V, max_states = 3 * max_pops, max_nodes = 8192 live prefix nodes (the tree is collected
+    after every chunk), max_len = 256 uncommitted tokens of a y_star.  Bytes per stream (`bytes_per_stream`; all of them,
+    `workspace_bytes`): 32 * (max_candidates + max_pops) + 4 * max_states * (slot + 1) + 20 * max_nodes + 256 with slot =
+    L * Hp * (2 if LSTM else 1) + V floats; at Hp = 512, V = 72, one LSTM layer and beam 5 that is 2.15 MB (0.29 MB A entries,
+    1.69 MB state slots, 0.16 MB nodes) against about 20 MB for the offline defaults."""
+
+    def __init__(self, jointnet, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
+                 state_beam: float = 4.6, expand_beam: float = 2.3, device=None, **caps):
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        enc = jointnet.encoder.rnn
+        home = jointnet.fc.weight.device
+        device = torch.device(device) if device is not None else home
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device != home:
+            raise ValueError(f"init_beam_stream: device {device} is not the model's ({home}); the state lives beside the weights")
+        if not 0 <= blank_token_id < jointnet.num_classes:
+            raise ValueError(f"blank_token_id {blank_token_id} outside [0, {jointnet.num_classes})")
+        unknown = set(caps) - set(ops.BEAM_STREAM_CAPS)
+        if unknown:
+            raise TypeError(f"init_beam_stream: unknown keyword(s) {sorted(unknown)}; the caps are {ops.BEAM_STREAM_CAPS}")
+        self._net = jointnet
+        self.batch_size, self.blank = int(batch_size), int(blank_token_id)
+        self.beam, self.improved = int(beam_widths), bool(improved)
+        self.state_beam, self.expand_beam = float(state_beam), float(expand_beam)
+        self.caps = ops.beam_stream_caps(jointnet.num_classes, self.beam, **caps)
+        B = self.batch_size
+        z = lambda L, H: torch.zeros(L, B, H, device=device, dtype=torch.float32)
+        self.enc_h = z(enc.num_layers, enc.hidden_size)
+        self.enc_c = z(enc.num_layers, enc.hidden_size) if enc.CELL == CELL_LSTM else None
+        self.frames_seen = torch.zeros(B, device=device, dtype=torch.int64)
+        d, _ = self._descriptor(bare=True)
+        self.workspace_bytes = ops.beam_stream_workspace_bytes(d)
+        self.workspace = torch.zeros(self.workspace_bytes + 256, device=device, dtype=torch.uint8)
+        self._ws_off = -self.workspace.data_ptr() % 256
+        ngate = {0: 4, 1: 3}.get(jointnet.decoder.rnn.CELL, 1)
+        self._table_bytes = (jointnet.num_classes * ngate * jointnet.decoder.rnn.hidden_size * 4 + 255) // 256 * 256
+        self.bytes_per_stream = (self.workspace_bytes - self._table_bytes) // B
+        # outputs of a chunk: count | status | ncommit | stats rows, one transfer
+        self._small = torch.zeros(3 + BEAM_NSTATS, B, device=device, dtype=torch.int32)
+        self._tokens = torch.zeros(B, self.beam, self.caps["max_len"], device=device, dtype=torch.int32)
+        self._lens = torch.zeros(B, self.beam, device=device, dtype=torch.int32)
+        self._scores = torch.zeros(B, self.beam, device=device, dtype=torch.float64)
+        self._commit = torch.zeros(B, self.caps["max_nodes"], device=device, dtype=torch.int32)
+        self.committed: List[List[int]] = [[self.blank] for _ in range(B)]
+        self.nbest = [[([self.blank], 0.0)] for _ in range(B)]
+        self.failed = [False] * B
+        self.last_stats = torch.zeros(B, BEAM_NSTATS, dtype=torch.int32)   # of the last chunk: ops.beam_search's stats columns
+        self._reset(list(range(B)), build_table=True)
+
+    @property
+    def device(self) -> torch.device:
+        return self.enc_h.device
+
+    def _descriptor(self, bare: bool = False):
+        net, dec = self._net, self._net.decoder
+        d, keep = ops.beam_stream_desc(self.batch_size, net.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                                       dec.out_proj.weight, dec.out_proj.bias, self.blank, self.beam, self.improved,
+                                       self.state_beam, self.expand_beam, self.caps)
+        if not bare:
+            d.workspace, d.workspace_bytes = self.workspace.data_ptr() + self._ws_off, self.workspace_bytes
+            B = self.batch_size
+            d.tokens, d.out_lens, d.scores = self._tokens.data_ptr(), self._lens.data_ptr(), self._scores.data_ptr()
+            base = self._small.data_ptr()
+            d.count, d.status, d.ncommit, d.stats = base, base + 4 * B, base + 8 * B, base + 12 * B
+            d.commit = self._commit.data_ptr()
+        return d, keep
+
+    def workspace_row(self, b: int) -> torch.Tensor:
+        """The bytes of stream b's part of the workspace (a view)."""
+        lo = self._ws_off + self._table_bytes + b * self.bytes_per_stream
+        return self.workspace[lo:lo + self.bytes_per_stream]
+
+    def stable_prefix(self, b: int) -> List[int]:
+        """The committed tokens of stream b, leading blank included: the longest common prefix of the y_star of ALL carried
+        hypotheses.  Every hypothesis of any later frame extends one of those, so no later chunk can change it."""
+        return list(self.committed[b])
+
+    def check_fits(self, jointnet, B: int, device) -> None:
+        """ValueError unless this state was opened by `jointnet` for B streams on `device` and still has that layout."""
+        if self._net is not jointnet:
+            raise ValueError("this BeamStreamState was opened by another model: open one with this model's init_beam_stream")
+        if B != self.batch_size:
+            raise ValueError(f"a chunk of {B} streams for a state of {self.batch_size}")
+        if device != self.device:
+            raise ValueError(f"chunk on {device}, state on {self.device}")
+        enc = jointnet.encoder.rnn
+        want = [("enc_h", self.enc_h, (enc.num_layers, B, enc.hidden_size), torch.float32),
+                ("frames_seen", self.frames_seen, (B,), torch.int64),
+                ("workspace", self.workspace, (self.workspace_bytes + 256,), torch.uint8)]
+        if enc.CELL == CELL_LSTM:
+            want.append(("enc_c", self.enc_c, (enc.num_layers, B, enc.hidden_size), torch.float32))
+        for name, t, shape, dtype in want:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device \
+                    or not t.is_contiguous():
+                raise ValueError(f"state.{name} is not a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        if -self.workspace.data_ptr() % 256 != self._ws_off:
+            raise ValueError("state.workspace was replaced: its alignment offset no longer holds")
+
+    def check_feedable(self, lens: Sequence[int]) -> None:
+        bad = [b for b, n in enumerate(lens) if n > 0 and self.failed[b]]
+        if bad:
+            raise RnntHipError(f"streaming beam search: stream(s) {bad[:4]} exceeded a cap in an earlier chunk and must be reset "
+                               "(state.reset(rows)) before they are fed again")
+
+    @torch.no_grad()
+    def reset(self, rows) -> "BeamStreamState":
+        """Start a new utterance in the listed rows (zero encoder state, the hypothesis set {[blank], score 0, no state},
+        committed = [blank], frames_seen = 0).  Every other row is left bitwise as it is."""
+        rows = sorted({int(r) for r in (rows.tolist() if isinstance(rows, torch.Tensor) else rows)})
+        if any(not 0 <= r < self.batch_size for r in rows):
+            raise ValueError(f"reset: rows must lie in [0, {self.batch_size})")
+        if rows:
+            self._reset(rows, build_table=False)
+        return self
+
+    def _reset(self, rows: List[int], build_table: bool) -> None:
+        idx = torch.tensor(rows, device=self.device, dtype=torch.int64)
+        for t in (self.enc_h, self.enc_c):
+            if t is not None:
+                t.index_fill_(1, idx, 0.0)
+        self.frames_seen.index_fill_(0, idx, 0)
+        d, keep = self._descriptor()
+        ops.beam_stream_reset(d, idx.to(torch.int32), build_table)
+        for r in rows:
+            self.committed[r], self.nbest[r], self.failed[r] = [self.blank], [([self.blank], 0.0)], False
+
+    def results(self, return_scores: bool):
+        return [[(list(y), s) for y, s in hyps] if return_scores else [list(y) for y, _ in hyps] for hyps in self.nbest]
+
+    def run_chunk(self, A: torch.Tensor, lens_dev: torch.Tensor) -> None:
+        """The search over one chunk (A (T,B,V), lens_dev (B) int32): updates the workspace, `committed`, `nbest`,
+        `frames_seen`; raises RnntHipError for a stream that outgrew a cap, after every other stream has been updated."""
+        B = self.batch_size
+        d, keep = self._descriptor()
+        ops.beam_stream_chunk(d, A, lens_dev)
+        self.frames_seen += lens_dev
+        host = self._small.cpu()   # the host sync of the chunk; the result slices below are copied from an idle stream
+        count, status, ncommit = host[0].tolist(), host[1].tolist(), host[2].tolist()
+        self.last_stats = host[3:].reshape(B, BEAM_NSTATS)
+        ran = [b for b in range(B) if count[b] >= 0 and status[b] == 0]
+        if ran:
+            lens_h, scores_h = self._lens.cpu().tolist(), self._scores.cpu().tolist()
+            tok_h = self._tokens[:, :, :max(1, max(max(lens_h[b]) for b in ran))].cpu()
+            com_h = self._commit[:, :max(1, max(ncommit[b] for b in ran))].cpu()
+            for b in ran:
+                self.committed[b] += com_h[b, :ncommit[b]].tolist()
+                self.nbest[b] = [(self.committed[b] + tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])]
+        bad = [b for b in range(B) if status[b] != 0]
+        for b in bad:
+            self.failed[b] = True
+        if bad:
+            b = bad[0]
+            what, kw = BEAM_STATUS.get(status[b], ("unknown", "?"))
+            raise RnntHipError(f"streaming beam search: stream {b} exceeded the cap on {what} ({kw}={self.caps.get(kw)}); open the "
+                               f"state with a larger {kw}= keyword.  The other streams are unaffected; stream(s) {bad[:4]} must be "
+                               "reset (state.reset(rows)) before they are fed again")
