@@ -11,8 +11,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
-SOURCES = ["api.hip", "gemm.hip", "gemm_hp.hip", "loss.hip", "lstm.hip", "lstm5.hip", "decode.hip", "beam.hip", "frontend.hip",
-           "stream.hip", "beam_stream.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_hp.hip", "loss.hip", "lstm.hip", "lstm5.hip", "lstm_layer.hip", "colsum_embedding.hip",
+           "decode.hip", "beam.hip", "frontend.hip", "stream.hip", "beam_stream.hip"]
+HEADERS = ["common.hpp", "lstm_shared.hpp", "decode_shared.hpp", "beam_shared.hpp"]
 LIB = os.path.join(HERE, "librnnt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + HERE, "-Wno-unused-result"]
@@ -29,7 +30,7 @@ def source_digest() -> str:
     bench.py drops the stamped numbers when the sources have changed since)."""
     import hashlib
     h = hashlib.sha256()
-    for name in sorted(SOURCES + ["common.hpp", "lstm_shared.hpp", "decode_shared.hpp", "beam_shared.hpp"]):
+    for name in sorted(SOURCES + HEADERS):
         with open(os.path.join(HERE, name), "rb") as f:
             h.update(name.encode() + b"\0" + f.read())
     return h.hexdigest()[:16]
@@ -39,9 +40,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, "common.hpp"), os.path.join(HERE, "lstm_shared.hpp"),
-                                                         os.path.join(HERE, "decode_shared.hpp"), os.path.join(HERE, "beam_shared.hpp"),
-                                                         os.path.join(INCLUDE, "rnnt_hip.h")]
+    deps = [os.path.join(HERE, s) for s in SOURCES + HEADERS] + [os.path.join(INCLUDE, "rnnt_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

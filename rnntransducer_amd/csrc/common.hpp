@@ -44,14 +44,17 @@ struct ProfScope {
 };
 
 // Opt-in record of the persistent recurrence kernels launched (api.hip, rnnt_hip_lstm_launch_log_enable): the launch helpers of
-// lstm.hip / lstm5.hip call launch_log_note with the kernel's host pointer after each launch when g_launch_log_on is set (off: one
+// lstm.hip / lstm5.hip (lstm_shared.hpp) call launch_log_note with the kernel's host pointer after each launch when g_launch_log_on is set (off: one
 // branch per launch).
 extern std::atomic<bool> g_launch_log_on;
 void launch_log_note(const void* kernel, hipStream_t s);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// half-pair (hp) operands and the f16-MFMA GEMM on them (gemm_hp.hip); used by lstm.hip for its big products
+// deterministic two-stage column sums (colsum_embedding.hip): out[N] (+)= column sums of X (M, N); ws >= rnnt_hip_colsum_workspace_bytes
+int launch_colsum(const float* X, long M, long N, long ld, float* out, void* ws, size_t ws_bytes, hipStream_t s, int accumulate = 0);
+
+// half-pair (hp) operands and the f16-MFMA GEMM on them (gemm_hp.hip); used by lstm_layer.hip for its big products
 size_t hp_plane_bytes(int64_t rows, int64_t K);
 int hp_colmax(const float* x, int64_t rows, int64_t C, int64_t ld, uint32_t* amax, hipStream_t s);   // amax[C] of the columns
 // Ragged batches: `rowidx` / `kidx` (device tables, or nullptr) list the VALID rows of a padded (T*B, .) tensor in time-major order.

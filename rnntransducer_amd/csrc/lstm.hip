@@ -1233,230 +1233,13 @@ __global__ void __launch_bounds__(64 * NWV) lstm_bwd4_kernel(const LstmK p) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// small helpers
-// ------------------------------------------------------------------------------------------------
-// db[d][g*H + j] = sum over the direction's (group, row) table of part[(d*rows_per_dir + r)*4H + 4j+g], fixed order
-__global__ void db_reduce_kernel(const float* __restrict__ part, int rows_per_dir, int H, int ngate, float* __restrict__ o0,
-                                 float* __restrict__ o1, int accumulate, float* __restrict__ p0 = nullptr,
-                                 float* __restrict__ p1 = nullptr) {
-  const int c = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
-  if (c >= 4 * H || (c & 3) >= ngate) return;
-  const float* src = part + (long)d * rows_per_dir * 4 * H + c;
-  float s = 0.f;
-  for (int r = 0; r < rows_per_dir; ++r) s += src[(long)r * 4 * H];
-  float* o = (d ? o1 : o0) + (c & 3) * H + (c >> 2);
-  *o = accumulate ? *o + s : s;
-  float* q = d ? p1 : p0;  // optional second destination (LSTM / Elman: grad b_hh == grad b_ih)
-  if (q) {
-    q += (c & 3) * H + (c >> 2);
-    *q = accumulate ? *q + s : s;
-  }
-}
-// out[(d*4H + 4j+g)*I + k] = g < ngate ? w[d][(g*H + j)*I + k] : 0      (4 slots per unit whatever the cell type)
-__global__ void permute_w_kernel(const float* __restrict__ w0, const float* __restrict__ w1, int H, int I, int ngate,
-                                 float* __restrict__ out) {
-  const long per = (long)4 * H * I;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const int d = blockIdx.y;
-  if (idx >= per) return;
-  const int k = (int)(idx % I), r = (int)(idx / I);
-  const float* w = d ? w1 : w0;
-  out[d * per + idx] = (r & 3) < ngate ? w[(long)((r & 3) * H + (r >> 2)) * I + k] : 0.f;
-}
-// dX rows of padded frames (t >= lens[b]) under a ragged plan (rnnt_lstm_desc.row_idx): the products skip them (row-gathered dX) or
-// read dG rows the recurrence never wrote (dense dX), so they are set to exact zeros here, what the unplanned call leaves there.
-// One wavefront per time-major row, grid-stride; rows of valid frames are not touched.
-__global__ void __launch_bounds__(256) zero_padded_rows_kernel(float* __restrict__ x, const int* __restrict__ lens, int T, int B, int I) {
-  const int lane = threadIdx.x & 63;
-  const long nrow = (long)T * B;
-  const long nw = ((long)gridDim.x * blockDim.x) >> 6;
-  for (long r = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < nrow; r += nw) {
-    if ((int)(r / B) < lens[r % B]) continue;
-    float* row = x + r * I;
-    for (int i = lane; i < I; i += 64) row[i] = 0.f;
-  }
-}
-// inverse for gradients: dw[d][(g*H + j)*I + k] = in[(d*4H + 4j+g)*I + k]
-__global__ void unpermute_w_kernel(const float* __restrict__ in, int H, int I, long in_dir_stride, int ngate,
-                                   float* __restrict__ o0, float* __restrict__ o1, int accumulate, float* __restrict__ p0 = nullptr,
-                                   float* __restrict__ p1 = nullptr) {
-  const long per = (long)4 * H * I;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const int d = blockIdx.y;
-  if (idx >= per) return;
-  const int k = (int)(idx % I), r = (int)(idx / I);
-  float* o = d ? o1 : o0;
-  if ((r & 3) < ngate) {
-    const long off = (long)((r & 3) * H + (r >> 2)) * I + k;
-    const float v = in[d * in_dir_stride + idx];
-    o[off] = accumulate ? o[off] + v : v;
-    float* q = d ? p1 : p0;
-    if (q) q[off] = accumulate ? q[off] + v : v;
-  }
-}
-// bias folded into the hoisted input projection: b_ih + b_hh per slot; GRU keeps b_hn out (it sits inside r * (.))
-__global__ void permute_bias_kernel(const float* __restrict__ bi0, const float* __restrict__ bh0,
-                                    const float* __restrict__ bi1, const float* __restrict__ bh1, int H, int ngate,
-                                    int gru, float* __restrict__ out) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const int d = blockIdx.y;
-  if (idx >= 4 * H) return;
-  const int g = idx & 3, src = g * H + (idx >> 2);
-  float v = 0.f;
-  if (g < ngate) {
-    const float bi = d ? bi1[src] : bi0[src], bh = d ? bh1[src] : bh0[src];
-    v = (gru && g == 2) ? bi : bi + bh;
-  }
-  out[d * 4 * H + idx] = v;
-}
+}  // namespace
 
-// two-stage deterministic column sum.  stage 1: grid (ceil(N/64), RC): block (64 columns x 4 row lanes) sums its
-// row chunk into part[rc][n]; stage 2: out[n] = sum_rc part[rc][n] in fixed order.
-constexpr int COLSUM_RC_MAX = 128;
-inline int colsum_chunks(long M, long N) {
-  long want = ceil_div(2048, ceil_div(N, 64));  // ~2048 blocks in flight
-  const long by_m = ceil_div(M, 64);
-  if (want > by_m) want = by_m;
-  if (want > COLSUM_RC_MAX) want = COLSUM_RC_MAX;
-  return (int)(want < 1 ? 1 : want);
-}
-__global__ void __launch_bounds__(256) colsum_stage1_kernel(const float* __restrict__ X, long M, long N, long ld,
-                                                            long rows_per_chunk, float* __restrict__ part) {
-  __shared__ float red[4][64];
-  const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
-  const long n = (long)blockIdx.x * 64 + c;
-  const long m0 = (long)blockIdx.y * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
-  float s = 0.f;
-  if (n < N)
-    for (long m = m0 + r; m < m1; m += 4) s += X[m * ld + n];
-  red[r][c] = s;
-  __syncthreads();
-  if (r == 0 && n < N) part[(long)blockIdx.y * N + n] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
-}
-__global__ void __launch_bounds__(256) colsum_stage2_kernel(const float* __restrict__ part, long N, int rc,
-                                                            float* __restrict__ out, int accumulate) {
-  const long n = (long)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  float s = 0.f;
-  for (int k = 0; k < rc; ++k) s += part[(long)k * N + n];
-  out[n] = accumulate ? out[n] + s : s;
-}
-int launch_colsum(const float* X, long M, long N, long ld, float* out, void* ws, size_t ws_bytes, hipStream_t s,
-                  int accumulate = 0) {
-  const int rc = colsum_chunks(M, N);
-  RNNT_CHECK_ARG(ws && ws_bytes >= (size_t)rc * N * 4, "colsum: workspace too small (%zu < %zu)", ws_bytes, (size_t)rc * N * 4);
-  ProfScope prof(RNNT_K_MISC, 4.0 * (double)M * (double)N, s);
-  const long rows = ceil_div(M, rc);
-  hipLaunchKernelGGL(colsum_stage1_kernel, dim3((unsigned)ceil_div(N, 64), rc), dim3(256), 0, s, X, M, N, ld, rows, (float*)ws);
-  RNNT_CHECK_LAUNCH();
-  hipLaunchKernelGGL(colsum_stage2_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, s, (const float*)ws, N, rc, out, accumulate);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
+// host side ----------------------------------------------------------------------------------------------------
+// What each kernel generation of this file takes (make_plan*) and one pair of launch functions per generation (as lstm5.hip): the
+// layer code (lstm_layer.hip) resolves the plans once per call and names no kernel.
 
-__global__ void embedding_fwd_kernel(const float* __restrict__ W, const long* __restrict__ idx, long M, int H, int V,
-                                     float* __restrict__ out) {
-  const long total = M * H;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long m = i / H;
-    const int h = (int)(i % H);
-    const long v = idx[m];
-    out[i] = (v >= 0 && v < V) ? W[v * H + h] : 0.f;
-  }
-}
-
-__global__ void __launch_bounds__(256) embedding_bwd_kernel(const float* __restrict__ dE, const long* __restrict__ idx, long M, int H, int V,
-                                                            long pad, float* __restrict__ dW, int accumulate) {
-  // one workgroup per vocabulary row: the tokens that hit it are compacted IN ORDER (ballot prefix) into LDS, then summed in that
-  // fixed order (deterministic, no atomics) — the scan over all M tokens is done once per row, not once per feature
-  constexpr int CAP = 2048;
-  __shared__ int list[CAP];
-  __shared__ int wcnt[4], nlist;
-  const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (v == pad) return;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};   // features tid, tid + 256, ... (H <= 1024 keeps everything in registers; more: extra passes)
-  for (int h0 = 0; h0 < H; h0 += 1024) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = 0.f;
-    for (long mb = 0; mb < M; mb += CAP) {   // batches of CAP tokens
-      if (tid == 0) nlist = 0;
-      __syncthreads();
-      const long mend = min(M, mb + CAP);
-      for (long m0 = mb; m0 < mend; m0 += 256) {
-        const long m = m0 + tid;
-        const bool hit = m < mend && idx[m] == v;
-        const unsigned long long bal = __ballot(hit);
-        if (lane == 0) wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int base = nlist;
-        for (int w = 0; w < wave; ++w) base += wcnt[w];
-        if (hit) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int)(m - mb);
-        __syncthreads();
-        if (tid == 0) nlist += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
-      }
-      const int n = nlist;
-      for (int i = 0; i < n; ++i) {
-        const float* row = dE + (mb + list[i]) * H + h0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (h0 + tid + 256 * q < H) acc[q] += row[tid + 256 * q];
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int h = h0 + tid + 256 * q;
-      if (h < H) dW[(long)v * H + h] = accumulate ? dW[(long)v * H + h] + acc[q] : acc[q];
-    }
-  }
-}
-
-struct LstmWs {
-  unsigned* flags;  // [16 words: status at word 0] [D*NC step flags], zeroed per launch
-  size_t sync_bytes, nflags;
-  float* hx;
-  size_t hx_bytes;
-  float* wp;   // (D*4H, I) permuted input weights; reused as dW_ih' in backward
-  float* bp;   // (D*4H)
-  float* dwhh; // (D*4H, H) scratch for dW_hh'
-  unsigned long long* dbg;  // 256 workgroups x 8 phase counters (diagnostics)
-  float* dbp;   // v4 backward: per-(group, row) time sums of dG (input side | hidden side), (2, D*G*NBR, 4H)
-  size_t dbp_half;  // floats per side
-  void* scratch;  // split-K slabs of the weight-gradient GEMMs / column-sum partials
-  size_t scratch_bytes;
-  // half-pair operand planes of the big products (gemm_hp.hip); null when the shape stays on gemm.hip
-  bool hp;
-  char* hp_x;    // fwd: x (T*B, I)            bwd: x^T (I, T*B)
-  char* hp_w;    // fwd: W_ih' (D*4H, I)       bwd: W_ih'^T (I, D*4H)
-  char* hp_dg;   // bwd: dG (T*B, D*4H)
-  char* hp_dgt;  // bwd: dG^T (D*4H, T*B)
-  char* hp_yt;   // bwd: time-shifted h^T per direction (D, H, T*B)
-  uint32_t* hp_amax;  // per-row maxima of the operands: [M | N4 | M | N4 | I | I | D*H | N4] words (carve_lstm)
-  size_t total;
-};
-
-// the hp path pays for the big products only (the operand conversion passes are fixed costs)
-inline bool use_hp(int T, int B, int I, int H, int D) {
-  if (getenv("RNNT_GEMM_NO_HP")) return false;
-  const long M = (long)T * B, N4 = (long)D * 4 * H;
-  // gemm_hp.hip addresses an operand's planes with 32-bit buffer offsets: a shape with a plane of 4 GB or more (e.g. bi-H = 1024,
-  // B = 64, T = 2048) stays on gemm.hip.  The bound is evaluated with the widest input a layer of this stack can see (I or D*H),
-  // so the sizing query (rnnt_hip_lstm_workspace_bytes) and every layer's launch take the same decision.
-  const long Iw = I > D * H ? I : (long)D * H;
-  const size_t lim = (size_t)1 << 32;
-  if (hp_plane_bytes(M, Iw) >= lim || hp_plane_bytes(Iw, M) >= lim || hp_plane_bytes(M, N4) >= lim || hp_plane_bytes(N4, M) >= lim ||
-      hp_plane_bytes(H, M) >= lim)
-    return false;
-  return M >= 1024 && N4 >= 512 && H >= 128 && (getenv("RNNT_GEMM_FORCE_HP") || (M * N4 >= (1l << 22)));
-}
-
-struct Plan {
-  int Hs, NC, MT, NT, Bp, LDW, wgs_per_cu;
-  size_t lds_fwd, lds_bwd;
-};
-
+// v1: one 4- / 8- / 16-unit slice of all (padded) rows per workgroup.  Every layer call needs this plan to exist (the acceptance test).
 bool make_plan(int B, int H, int D, int cus, Plan* pl) {
   if (H < 4 || H % 4 != 0 || B < 1 || B > 64 || D < 1 || D > 2) return false;
   const int NT = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
@@ -1483,7 +1266,6 @@ bool make_plan(int B, int H, int D, int cus, Plan* pl) {
   }
   return false;
 }
-
 
 // v2 decomposition: largest hidden slice whose W_hh rows fit LDS (fewest workgroups per sync group), then as many
 // batch slices as the CUs allow.  Returns false when the shape does not fit (caller falls back to v1).
@@ -1516,8 +1298,8 @@ bool make_plan2(int B, int H, int D, int cus, Plan2* pl) {
 }
 
 // v3 / v4 (W_hh in registers, bf16 pieces): 16 units per workgroup, H a multiple of 128 with H/128 among the instantiated
-// k-step counts (H <= 640), no LDS constraint.
-bool make_plan3(int B, int H, int D, int cus, bool bwd, Plan2* pl) {
+// k-step counts (H <= 640), no LDS constraint.  The forward (v3) and the backward (v4) take the same plan; v5 (lstm5.hip) too.
+bool make_plan3(int B, int H, int D, int cus, Plan2* pl) {
   if (getenv("RNNT_LSTM_V1") || getenv("RNNT_LSTM_V2")) return false;
   if (H % 128 != 0 || B < 1 || D < 1 || D > 2) return false;
   const int nks = H / 128;
@@ -1527,7 +1309,6 @@ bool make_plan3(int B, int H, int D, int cus, bool bwd, Plan2* pl) {
   if (!(nks >= 1 && nks <= 6) && nks != 8) return false;
   // (its backward keeps one of the six output blocks' W_hh pieces in LDS: with all 216 operand registers per lane it spilled 66-80
   //  and lost to the 16-unit / 4-wave form, 66.0 vs 63.8 ms per c5 step; with 180 it takes 45.5)
-  (void)bwd;
   const bool h640 = nks == 5;
   const int MB = h640 ? 5 : 4, HS = 4 * MB;
   const int NC = H / HS;
@@ -1550,75 +1331,7 @@ bool make_plan3(int B, int H, int D, int cus, bool bwd, Plan2* pl) {
   return true;
 }
 
-LstmWs carve_lstm(void* ws, int T, int B, int I, int H, int D, const Plan& pl) {
-  LstmWs w;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  size_t nflags = (size_t)D * pl.NC;
-  size_t hxb = (size_t)2 * D * H * pl.Bp * 4 * 4;  // v1, sized for the backward exchange (B x 4H), fwd uses a quarter
-  {
-    Plan2 p2;
-    int cus = device_cus();
-    if (cus <= 0) cus = 256;
-    if (make_plan2(B, H, D, cus, &p2)) {
-      const size_t nf2 = (size_t)D * p2.G * p2.NC;
-      const size_t hx2 = (size_t)2 * D * p2.G * 4 * p2.BQ * 4 * p2.Kp * 4;
-      if (nf2 > nflags) nflags = nf2;
-      if (hx2 > hxb) hxb = hx2;
-    }
-    for (int bwd = 0; bwd < 2; ++bwd) {
-      if (!make_plan3(B, H, D, cus, bwd != 0, &p2)) continue;
-      const size_t nf3 = (size_t)D * p2.G * p2.NC;
-      const size_t hx3 = bwd ? (size_t)2 * D * p2.G * p2.NC * 4 * p2.BQ * p2.Kp * 4   // v4: per-producer partial dh, fp32
-                             : (size_t)2 * D * p2.G * 4 * p2.BQ * p2.Kp * 6;          // v3: three bf16 planes of h
-      if (nf3 > nflags) nflags = nf3;
-      if (hx3 > hxb) hxb = hx3;
-    }
-  }
-  w.nflags = nflags;
-  w.sync_bytes = align_up((2 * nflags + 16) * 4, 16);  // status block | step flags | XCC table
-  w.flags = reinterpret_cast<unsigned*>(take(w.sync_bytes));
-  w.hx_bytes = hxb;
-  w.hx = reinterpret_cast<float*>(take(w.hx_bytes));
-  w.wp = reinterpret_cast<float*>(take((size_t)D * 4 * H * I * 4));
-  w.bp = reinterpret_cast<float*>(take((size_t)D * 4 * H * 4));
-  w.dwhh = reinterpret_cast<float*>(take((size_t)D * 4 * H * H * 4));
-  w.dbg = reinterpret_cast<unsigned long long*>(take(512 * 8 * 8));
-  w.dbp_half = (size_t)D * (B + 64) * 4 * H;  // D*G*NBR <= D*(B + 4*G) rows of 4H
-  w.dbp = reinterpret_cast<float*>(take(2 * w.dbp_half * 4));
-  {
-    const int64_t M = (int64_t)T * B, N4 = (int64_t)D * 4 * H;
-    size_t sc = rnnt_hip_gemm_workspace_bytes(N4, I, M);
-    const size_t s2 = rnnt_hip_gemm_workspace_bytes(4 * H, H, M > B ? M - B : 1);
-    const size_t s3 = rnnt_hip_colsum_workspace_bytes(M, N4);
-    if (s2 > sc) sc = s2;
-    if (s3 > sc) sc = s3;
-    w.hp = use_hp(T, B, I, H, D);
-    if (w.hp) {
-      const size_t h1 = hp_gemm_workspace_bytes(N4, I, M), h2 = hp_gemm_workspace_bytes(4 * H, H, M);
-      if (h1 > sc) sc = h1;
-      if (h2 > sc) sc = h2;
-      const int64_t mn[3] = {N4 * I, (int64_t)4 * H * H, (int64_t)4 * H * H};   // the grouped launch keeps all slabs at once
-      const size_t h3 = HPQ_HEADER_BYTES + hp_gemm_grouped_workspace_bytes(mn, 1 + D);   // queue counters in front of the slabs
-      if (h3 > sc) sc = h3;
-    }
-    w.scratch_bytes = sc;
-    w.scratch = take(sc);
-    w.hp_x = w.hp_w = w.hp_dg = w.hp_dgt = w.hp_yt = nullptr;
-    w.hp_amax = nullptr;
-    if (w.hp) {
-      w.hp_amax = reinterpret_cast<uint32_t*>(take((size_t)(2 * M + 3 * N4 + 2 * I + (int64_t)D * H) * 4));
-      w.hp_x = take(hp_plane_bytes(M, I) > hp_plane_bytes(I, M) ? hp_plane_bytes(M, I) : hp_plane_bytes(I, M));
-      w.hp_w = take(hp_plane_bytes(N4, I) > hp_plane_bytes(I, N4) ? hp_plane_bytes(N4, I) : hp_plane_bytes(I, N4));
-      w.hp_dg = take(hp_plane_bytes(M, N4));
-      w.hp_dgt = take(hp_plane_bytes(N4, M));
-      w.hp_yt = take((size_t)D * hp_plane_bytes(H, M));
-    }
-  }
-  w.total = off;
-  return w;
-}
+namespace {
 
 template <typename K>
 int launch_persistent(K kernel, const LstmK& k, const Plan& pl, size_t lds, hipStream_t s, const char* what) {
@@ -1643,613 +1356,97 @@ int launch_persistent(K kernel, const LstmK& k, const Plan& pl, size_t lds, hipS
   return RNNT_OK;
 }
 
-int check_desc(const rnnt_lstm_desc* d, Plan* pl, LstmWs* w) {
-  RNNT_CHECK_ARG(d != nullptr, "lstm: null descriptor");
-  RNNT_CHECK_ARG(d->T >= 1 && d->I >= 1, "lstm: T and I must be positive (T=%d I=%d)", d->T, d->I);
-  const int cus = device_cus();
-  RNNT_CHECK_ARG(cus > 0, "lstm: no HIP device");
-  if (!make_plan(d->B, d->H, d->D, cus, pl)) {
-    set_error("lstm: unsupported configuration B=%d H=%d D=%d (need H%%4==0, 1<=B<=64, D in {1,2}, slice must fit %d CUs)",
-              d->B, d->H, d->D, cus);
-    return RNNT_ERR_UNSUPPORTED;
-  }
-  RNNT_CHECK_ARG(d->cell >= RNNT_CELL_LSTM && d->cell <= RNNT_CELL_RNN_RELU, "lstm: unknown cell type %d", d->cell);
-  RNNT_CHECK_ARG(d->lens && d->x && d->y && d->gates && (d->cst || d->cell != RNNT_CELL_LSTM), "lstm: null tensor");
-  for (int k = 0; k < d->D; ++k)
-    RNNT_CHECK_ARG(d->w_ih[k] && d->w_hh[k] && d->b_ih[k] && d->b_hh[k], "lstm: null weight (direction %d)", k);
-  RNNT_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "lstm: dropout_p must be in [0,1)");
-  RNNT_CHECK_ARG(d->dropout_p == 0.f || d->y_drop, "lstm: dropout_p > 0 needs y_drop");
-  RNNT_CHECK_ARG(d->x_abs_bound >= 0.f && d->x_abs_bound < 1e30f, "lstm: x_abs_bound must be 0 (measure) or a finite positive bound");
-  RNNT_CHECK_ARG(!d->row_idx || (d->n_rows >= 1 && d->n_rows <= (int64_t)d->T * d->B), "lstm: row_idx needs 1 <= n_rows <= T*B (got %d)", d->n_rows);
-  *w = carve_lstm(d->workspace, d->T, d->B, d->I, d->H, d->D, *pl);
-  RNNT_CHECK_ARG(d->workspace && d->workspace_bytes >= w->total, "lstm: workspace too small (%zu < %zu)",
-                 d->workspace_bytes, w->total);
-  RNNT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->gates) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->y) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(d->cst) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->aux) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0,
-                 "lstm: gates/y/cst must be 16-byte aligned, workspace 256-byte aligned");
-  return RNNT_OK;
-}
-
-void fill_kernel_args(const rnnt_lstm_desc* d, const Plan& pl, const LstmWs& w, LstmK* k) {
-  k->T = d->T; k->B = d->B; k->H = d->H; k->D = d->D;
-  k->Hs = pl.Hs; k->NC = pl.NC; k->Bp = pl.Bp; k->LDW = pl.LDW;
-  k->lens = d->lens; k->gates = d->gates; k->cst = d->cst; k->y = d->y;
-  k->ydrop = d->dropout_p > 0.f ? d->y_drop : nullptr;
-  k->keep_scale = d->dropout_p > 0.f ? 1.f / (1.f - d->dropout_p) : 1.f;
-  k->drop_thresh = (unsigned)((double)d->dropout_p * 4294967296.0);
-  k->seed = d->dropout_seed;
-  k->w_hh[0] = d->w_hh[0]; k->w_hh[1] = d->D > 1 ? d->w_hh[1] : d->w_hh[0];
-  // status word: the caller's sticky device word when given (never reset by the library: a raised status makes every later
-  // launch bail out at its first wait and stays visible until the caller reads it), else word 0 of the workspace (reset per launch)
-  k->hx = w.hx; k->status = d->status ? d->status : w.flags; k->flags = w.flags + 16;
-  k->dy = nullptr;
-  k->cell = d->cell;
-  k->b_hh[0] = d->b_hh[0]; k->b_hh[1] = d->D > 1 ? d->b_hh[1] : d->b_hh[0];
-  k->aux = d->aux;
-  k->G = 1; k->Bg = d->B; k->Kp = d->H; k->NGL = d->D;
-  k->dbp = w.dbp; k->dbhp = w.dbp + w.dbp_half;
-  k->dbg = getenv("RNNT_LSTM_DBG") ? w.dbg : nullptr;
-  k->xcc = w.flags + 16 + w.nflags;
-  k->allow_local = getenv("RNNT_LSTM_NO_XCD_LOCAL") ? 0 : 1;
-  k->hw_math = getenv("RNNT_LSTM_EXACT_MATH") ? 0 : 1;
-  k->pause = 0;
-  k->gbound = 0;
-  k->colmax = k->colmax_h = nullptr;
-  k->rowmax = nullptr;
-}
-
-// rnnt_lstm_desc.row_idx is honoured where EVERY consumer of the stash gathers the valid rows: v5 recurrences (group step bounds) with
-// the half-pair products (row gather in the operand fetch / k-gather in the transposed splits).  Same answer in the forward and the
-// backward call of a layer (it depends on the shape only).
-bool shape_takes_row_idx(int T, int B, int I, int H, int D, int cell, int cus) {
-  Plan2 p2;
-  return use_hp(T, B, I, H, D) && I >= 32 && T > 1 && make_plan3(B, H, D, cus, true, &p2) && lstm5_supported(T, B, H, D, cell);
-}
-// RNNT_PRECISION_F16 is honoured where the WHOLE layer runs the forms that have a one-product variant: v5 recurrences in both
-// directions of time and the half-pair products (gemm_hp.hip).  Everywhere else the layer computes in fp32, bitwise
-// what RNNT_PRECISION_FP32 computes.  Same answer in the forward and the backward call of a layer (it depends on the shape only).
-bool shape_takes_f16(int T, int B, int I, int H, int D, int cell, int cus) {
-  Plan2 pf, pb;
-  return use_hp(T, B, I, H, D) && make_plan3(B, H, D, cus, false, &pf) && make_plan3(B, H, D, cus, true, &pb) &&
-         lstm5_supported(T, B, H, D, cell);
-}
-bool ragged_plan(const rnnt_lstm_desc* d, const LstmWs& w, int cus) {
-  return d->row_idx && d->n_rows > 0 && d->n_rows < (int64_t)d->T * d->B && w.hp && d->x_sb == d->I && d->x_st == (int64_t)d->B * d->I &&
-         shape_takes_row_idx(d->T, d->B, d->I, d->H, d->D, d->cell, cus);
-}
-
 }  // namespace
-}  // namespace rnnt
 
-using namespace rnnt;
-
-extern "C" int32_t rnnt_hip_lstm_max_batch(int32_t H, int32_t D, int32_t cell) {
-  // largest per-call batch the persistent kernels take for this shape (callers split bigger batches along B:
-  // sequences are independent, weight gradients add)
-  int cus = device_cus();
-  if (cus <= 0) cus = 256;
-  int best = 0;
-  for (int B = 64; B >= 1; --B) {
-    Plan2 p2;
-    Plan p1;
-    // the backward decides: a batch both directions of the recurrence can take
-    if (make_plan3(B, H, D, cus, true, &p2) || make_plan2(B, H, D, cus, &p2) || (cell == RNNT_CELL_LSTM && make_plan(B, H, D, cus, &p1))) { best = B; break; }
-  }
-  return best;
+int lstm1_fwd_launch(const LstmK& k, const Plan& pl, hipStream_t s) {
+  return dispatch<1, 2, 4>(pl.MT, "lstm_fwd MT", [&](auto MT) {
+    return dispatch<1, 2, 4>(pl.NT, "lstm_fwd NT", [&](auto NT) {
+      return launch_persistent(lstm_fwd_kernel<MT, NT>, k, pl, pl.lds_fwd, s, "lstm_fwd");
+    });
+  });
 }
 
-// the placement rule shared by the backward (which XCDs its grouped products avoid) and the caller's decision to overlap at all
-static int recurrence_xcds(int T, int B, int H, int D, int cell, int cus) {
-  Plan2 p2;
-  if (!make_plan3(B, H, D, cus, true, &p2) || !lstm5_supported(T, B, H, D, cell)) return 8;
-  const int NG = D * p2.G;
-  return (NG <= 4 && p2.NC <= 32 && !getenv("RNNT_LSTM_NO_XCD_STRIDE")) ? NG : 8;   // launch_persistent2: stride 8, group g on XCD g
+int lstm1_bwd_launch(const LstmK& k, const Plan& pl, hipStream_t s) {
+  return dispatch<1, 2, 4>(pl.MT, "lstm_bwd MT", [&](auto MT) {
+    return dispatch<1, 2, 4>(pl.NT, "lstm_bwd NT", [&](auto NT) {
+      return launch_persistent(lstm_bwd_kernel<MT, NT>, k, pl, pl.lds_bwd, s, "lstm_bwd");
+    });
+  });
 }
 
-extern "C" int32_t rnnt_hip_lstm_takes_row_idx(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell) {
-  int cus = device_cus();
-  if (cus <= 0) cus = 256;
-  if (T < 1 || B < 1 || I < 1 || H < 4 || D < 1 || D > 2) return 0;
-  return shape_takes_row_idx(T, B, I, H, D, cell, cus) ? 1 : 0;
-}
-
-extern "C" int32_t rnnt_hip_lstm_takes_f16(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D, int32_t cell) {
-  int cus = device_cus();
-  if (cus <= 0) cus = 256;
-  if (T < 1 || B < 1 || I < 1 || H < 4 || D < 1 || D > 2) return 0;
-  return shape_takes_f16(T, B, I, H, D, cell, cus) ? 1 : 0;
-}
-
-extern "C" int32_t rnnt_hip_lstm_free_xcds(int32_t T, int32_t B, int32_t H, int32_t D, int32_t cell) {
-  int cus = device_cus();
-  if (cus <= 0) cus = 256;
-  if (T < 1 || B < 1 || H < 4 || D < 1 || D > 2) return 0;
-  return 8 - recurrence_xcds(T, B, H, D, cell, cus);
-}
-
-extern "C" size_t rnnt_hip_lstm_workspace_bytes(int32_t T, int32_t B, int32_t I, int32_t H, int32_t D) {
-  Plan pl;
-  int cus = device_cus();
-  if (cus <= 0) cus = 256;  // sizing query without a device: assume MI355X
-  if (T < 1 || I < 1 || !make_plan(B, H, D, cus, &pl)) return 0;
-  return carve_lstm(nullptr, T, B, I, H, D, pl).total;
-}
-
-static int lstm_fwd_impl(const rnnt_lstm_desc* d, uint32_t precision, void* stream) {
-  Plan pl;
-  LstmWs w;
-  if (int rc = check_desc(d, &pl, &w)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int H = d->H, D = d->D, I = d->I;
-  // one-product forms (RNNT_PRECISION_F16) where the whole layer has them, fp32 otherwise
-  const bool f16 = precision == RNNT_PRECISION_F16 && shape_takes_f16(d->T, d->B, I, H, D, d->cell, device_cus());
-  const unsigned hpf = f16 ? RNNT_GEMM_HP_F16 : 0u;
-  const int ngate = d->cell == RNNT_CELL_LSTM ? 4 : (d->cell == RNNT_CELL_GRU ? 3 : 1);
-  // 1. gate-adjacent copy of W_ih (both directions stacked) and of b_ih + b_hh
-  {
-    const long per = (long)4 * H * I;
-    hipLaunchKernelGGL(permute_w_kernel, dim3((unsigned)ceil_div(per, 256), D), dim3(256), 0, s, d->w_ih[0],
-                       D > 1 ? d->w_ih[1] : d->w_ih[0], H, I, ngate, w.wp);
-    RNNT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(permute_bias_kernel, dim3((unsigned)ceil_div(4 * H, 256), D), dim3(256), 0, s, d->b_ih[0], d->b_hh[0],
-                       D > 1 ? d->b_ih[1] : d->b_ih[0], D > 1 ? d->b_hh[1] : d->b_hh[0], H, ngate,
-                       d->cell == RNNT_CELL_GRU ? 1 : 0, w.bp);
-    RNNT_CHECK_LAUNCH();
-  }
-  // 2. hoisted input projection for all timesteps: gates[(t,b)][d*4H + 4j+g] = x(t,b,:) . W_ih'[.] + bias'
-  const bool x_plain = d->x_sb == I && d->x_st == (int64_t)d->B * I;
-  const bool ragged = ragged_plan(d, w, device_cus());   // valid frames only (rnnt_lstm_desc.row_idx)
-  if (w.hp && x_plain && I >= 32) {  // f16 matrix cores on half-pair operands (gemm_hp.hip)
-    const int64_t M = (int64_t)d->T * d->B, N4 = (int64_t)D * 4 * H;
-    const int64_t Mv = ragged ? d->n_rows : M;             // rows the product runs over
-    const int* ridx = ragged ? d->row_idx : nullptr;
-    uint32_t* ax = w.hp_amax, *aw = w.hp_amax + M;
-    if (int rc = hp_split(d->x, Mv, I, I, ax, w.hp_x, s, ridx)) return rc;   // planes / maxima of the valid rows, in place
-    if (int rc = hp_split(w.wp, N4, I, I, aw, w.hp_w, s)) return rc;
-    if (int rc = hp_gemm(w.hp_x, ax, w.hp_w, aw, Mv, N4, I, d->gates, 1, N4, 0, w.bp, hpf, nullptr, 0, s, ridx, M, ridx)) return rc;
-  } else {
-    rnnt_gemm_desc g = {};
-    g.M = (int64_t)d->T * d->B; g.N = (int64_t)D * 4 * H; g.K = I;
-    g.A = d->x; g.a_div = d->B; g.a_so = d->x_st; g.a_si = d->x_sb; g.a_sk = 1; g.a_mc = 0;
-    g.B = w.wp; g.b_sn = I; g.b_sk = 1;
-    g.C = d->gates; g.c_div = 1; g.c_so = g.N; g.c_si = 0;
-    g.bias = w.bp;
-    if (int rc = rnnt_hip_gemm_f32(&g, s)) return rc;
-  }
-  // 3. the recurrence
-  // sync block and exchange buffers are neighbours in the workspace (carve_lstm): one fill
-  RNNT_CHECK_HIP(hipMemsetAsync(w.flags, 0, (size_t)(reinterpret_cast<char*>(w.hx) - reinterpret_cast<char*>(w.flags)) + w.hx_bytes, s));
-  LstmK k;
-  fill_kernel_args(d, pl, w, &k);
-  k.gbound = ragged ? 1 : 0;
-  int rc = RNNT_OK;
-  Plan2 p2;
-  const int cus = device_cus();
-  auto adopt = [&](const Plan2& q) {
-    k.NC = q.NC; k.Hs = q.HS; k.G = q.G; k.Bg = q.Bg; k.Kp = q.Kp;
-  };
-  if (make_plan3(d->B, d->H, d->D, cus, false, &p2)) {
-    adopt(p2);
-    const int nks = p2.Kp / 128, c = cell_form(d->cell);
-    if (lstm5_supported(d->T, d->B, d->H, d->D, d->cell)) {  // v5: tagged-payload exchange, f16 matrix cores (lstm5.hip)
-      rc = lstm5_fwd_launch(k, p2, d->cell, s, f16);
-    } else if (p2.MB == 5) {  // H = 640: 5 blocks, 8 waves x 3 k-steps over K padded to 768
-      const size_t lds5 = p2.lds_fwd + 8 * 1 * 3 * 3 * 1024;  // one of the five blocks' pieces in LDS
-      rc = dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
-        return launch_persistent2(lstm_fwd3_kernel<3, C, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
-      });
-    } else if (nks == 4) {  // H = 512 forward: 8 waves x 2 k-steps (12.5 vs 13.1 ms per c2 step)
-      const size_t lds = (size_t)8 * 4 * 64 * 16 + 16;
-      rc = dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
-        return launch_persistent2(lstm_fwd3_kernel<2, C, 8>, k, p2, lds, s, "lstm_fwd3", 512);
-      });
-    } else if (nks <= 3) {
-      rc = dispatch<1, 2, 3>(nks, "lstm_fwd3 k-steps", [&](auto N) {
-        return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
-          return launch_persistent2(lstm_fwd3_kernel<N, C>, k, p2, p2.lds_fwd, s, "lstm_fwd3");
-        });
-      });
-    } else {  // H = 768 / 1024: 8 waves x 3 / 4 k-steps
-      rc = dispatch<3, 4>(p2.Kp / (32 * 8), "lstm_fwd3 k-steps", [&](auto N) {
-        const size_t lds8 = p2.lds_fwd + 8 * 1 * N * 3 * 1024;  // one of the four blocks' pieces in LDS
-        return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
-          return launch_persistent2(lstm_fwd3_kernel<N, C, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512);
-        });
-      });
-    }
-  } else if (make_plan2(d->B, d->H, d->D, cus, &p2)) {
-    adopt(p2);
-    rc = dispatch<4, 8, 16>(p2.HS, "lstm_fwd2 HS", [&](auto HS) {
-      return dispatch<1, 2, 4>(p2.BQ, "lstm_fwd2 BQ", [&](auto BQ) {
-        return dispatch<0, 1, 2>(cell_form(d->cell), "lstm_fwd2 cell", [&](auto C) {
-          return launch_persistent2(lstm_fwd2_kernel<HS, BQ, C>, k, p2, p2.lds_fwd, s, "lstm_fwd2");
-        });
+int lstm2_fwd_launch(const LstmK& k, const Plan2& p2, int cell, hipStream_t s) {
+  return dispatch<4, 8, 16>(p2.HS, "lstm_fwd2 HS", [&](auto HS) {
+    return dispatch<1, 2, 4>(p2.BQ, "lstm_fwd2 BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(cell_form(cell), "lstm_fwd2 cell", [&](auto C) {
+        return launch_persistent2(lstm_fwd2_kernel<HS, BQ, C>, k, p2, p2.lds_fwd, s, "lstm_fwd2");
       });
     });
-  } else if (d->cell == RNNT_CELL_LSTM) {
-    rc = dispatch<1, 2, 4>(pl.MT, "lstm_fwd MT", [&](auto MT) {
-      return dispatch<1, 2, 4>(pl.NT, "lstm_fwd NT", [&](auto NT) {
-        return launch_persistent(lstm_fwd_kernel<MT, NT>, k, pl, pl.lds_fwd, s, "lstm_fwd");
+  });
+}
+
+int lstm2_bwd_launch(const LstmK& k, const Plan2& p2, int cell, hipStream_t s) {
+  return dispatch<4, 8, 16>(p2.HS, "lstm_bwd2 HS", [&](auto HS) {
+    return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd2 BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(cell_form(cell), "lstm_bwd2 cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd2_kernel<HS, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd2");
       });
     });
-  } else {
-    set_error("rnn: GRU / Elman cells need the grouped decomposition (B/G <= 16 rows per group); B=%d H=%d does not fit", d->B, d->H);
-    rc = RNNT_ERR_UNSUPPORTED;
+  });
+}
+
+int lstm3_fwd_launch(const LstmK& k, const Plan2& p2, int cell, hipStream_t s) {
+  const int nks = p2.Kp / 128, c = cell_form(cell);
+  if (p2.MB == 5) {  // H = 640: 5 blocks, 8 waves x 3 k-steps over K padded to 768
+    const size_t lds5 = p2.lds_fwd + 8 * 1 * 3 * 3 * 1024;  // one of the five blocks' pieces in LDS
+    return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+      return launch_persistent2(lstm_fwd3_kernel<3, C, 8, 5, 1>, k, p2, lds5, s, "lstm_fwd3", 512);
+    });
   }
-  return rc;
+  if (nks == 4) {  // H = 512 forward: 8 waves x 2 k-steps (12.5 vs 13.1 ms per c2 step)
+    const size_t lds = (size_t)8 * 4 * 64 * 16 + 16;
+    return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+      return launch_persistent2(lstm_fwd3_kernel<2, C, 8>, k, p2, lds, s, "lstm_fwd3", 512);
+    });
+  }
+  if (nks <= 3)
+    return dispatch<1, 2, 3>(nks, "lstm_fwd3 k-steps", [&](auto N) {
+      return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+        return launch_persistent2(lstm_fwd3_kernel<N, C>, k, p2, p2.lds_fwd, s, "lstm_fwd3");
+      });
+    });
+  // H = 768 / 1024: 8 waves x 3 / 4 k-steps
+  return dispatch<3, 4>(p2.Kp / (32 * 8), "lstm_fwd3 k-steps", [&](auto N) {
+    const size_t lds8 = p2.lds_fwd + 8 * 1 * N * 3 * 1024;  // one of the four blocks' pieces in LDS
+    return dispatch<0, 1, 2>(c, "lstm_fwd3 cell", [&](auto C) {
+      return launch_persistent2(lstm_fwd3_kernel<N, C, 8, 4, 1>, k, p2, lds8, s, "lstm_fwd3", 512);
+    });
+  });
 }
 
-extern "C" int rnnt_hip_lstm_fwd(const rnnt_lstm_desc* d, void* stream) { return lstm_fwd_impl(d, RNNT_PRECISION_FP32, stream); }
-
-extern "C" int rnnt_hip_lstm_fwd_ex(const rnnt_lstm_desc* d, uint32_t precision, void* stream) {
-  RNNT_CHECK_ARG(precision == RNNT_PRECISION_FP32 || precision == RNNT_PRECISION_F16, "lstm_fwd_ex: precision must be 0 (fp32) or 1 (f16), got %u",
-                 precision);
-  return lstm_fwd_impl(d, precision, stream);
-}
-
-static int lstm_bwd_impl(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void* stream) {
-  RNNT_CHECK_ARG(bd != nullptr, "lstm_bwd: null descriptor");
-  const rnnt_lstm_desc* d = &bd->f;
-  Plan pl;
-  LstmWs w;
-  if (int rc = check_desc(d, &pl, &w)) return rc;
-  RNNT_CHECK_ARG(bd->dy, "lstm_bwd: null dy");
-  const int T = d->T, B = d->B, H = d->H, D = d->D, I = d->I;
-  // same decision as the forward call of the layer (shape only)
-  const bool f16 = precision == RNNT_PRECISION_F16 && shape_takes_f16(T, B, I, H, D, d->cell, device_cus());
-  const unsigned hpf = f16 ? RNNT_GEMM_HP_F16 : 0u;
-  const bool gru = d->cell == RNNT_CELL_GRU;
-  const int ngate = d->cell == RNNT_CELL_LSTM ? 4 : (gru ? 3 : 1);
-  RNNT_CHECK_ARG(!gru || d->aux, "lstm_bwd: GRU needs the aux buffer (T,B,D*4H)");
-  for (int k = 0; k < D; ++k) RNNT_CHECK_ARG(!gru || bd->db_hh[k], "lstm_bwd: GRU needs db_hh");
-  const int acc = bd->accumulate ? 1 : 0;       // += into dw_ih / dw_hh / db / db_hh (flat-gradient views) instead of =
-  // LSTM / Elman: grad b_hh == grad b_ih; when the caller also hands db_hh it receives the same values (second destination)
-  float* twin0 = gru ? nullptr : bd->db_hh[0];
-  float* twin1 = gru ? nullptr : (D > 1 ? bd->db_hh[1] : bd->db_hh[0]);
-  if (twin0 == bd->db[0]) twin0 = nullptr;
-  if (twin1 == (D > 1 ? bd->db[1] : bd->db[0])) twin1 = nullptr;
-  const float* ghid = gru ? d->aux : d->gates;  // hidden-side gate gradients (== input side except for GRU's n gate)
-  RNNT_CHECK_ARG(d->x_sb == I && d->x_st == (int64_t)B * I, "lstm_bwd: x must be time-major contiguous (T,B,I)");
-  for (int k = 0; k < D; ++k) RNNT_CHECK_ARG(bd->dw_ih[k] && bd->dw_hh[k] && bd->db[k], "lstm_bwd: null gradient output");
-  hipStream_t s = (hipStream_t)stream;
-  RNNT_CHECK_ARG(bd->phase >= RNNT_LSTM_BWD_ALL && bd->phase <= RNNT_LSTM_BWD_WEIGHTS, "lstm_bwd: phase must be 0, 1 or 2");
-  // phase 1 = steps 1-2 (the chain autograd waits for), phase 2 = steps 3-5 (weight / bias gradients: any stream ordered after phase 1)
-  const bool do_recur = bd->phase != RNNT_LSTM_BWD_WEIGHTS, do_weights = bd->phase != RNNT_LSTM_BWD_RECUR;
-
-  // 1. reverse-time recurrence: gates (activated) -> dG in place
-  if (do_recur)   // sync block and exchange buffers are neighbours in the workspace (carve_lstm): one fill
-    RNNT_CHECK_HIP(hipMemsetAsync(w.flags, 0, (size_t)(reinterpret_cast<char*>(w.hx) - reinterpret_cast<char*>(w.flags)) + w.hx_bytes, s));
-  LstmK k;
-  fill_kernel_args(d, pl, w, &k);
-  k.dy = bd->dy;
-  int rc = RNNT_OK;
-  Plan2 p2;
-  const int cus = device_cus();
-  const bool ragged = ragged_plan(d, w, cus);            // valid frames only (rnnt_lstm_desc.row_idx): as in the forward call
-  const int* ridx = ragged ? d->row_idx : nullptr;
-  k.gbound = ragged ? 1 : 0;
-  auto adopt = [&](const Plan2& q) {
-    k.NC = q.NC; k.Hs = q.HS; k.G = q.G; k.Bg = q.Bg; k.Kp = q.Kp;
-  };
-  bool fused_db = false, colmax_done = false, rowmax_done = false;
-  int db_rows = 0;
-  unsigned xcd_skip = 0;
-  if (make_plan3(d->B, d->H, d->D, cus, true, &p2)) {
-    adopt(p2);
-    fused_db = true;
-    db_rows = p2.G * 4 * p2.BQ;
-    const int c = cell_form(d->cell);
-    if (lstm5_supported(d->T, d->B, d->H, d->D, d->cell)) {  // v5 (lstm5.hip)
-      if (w.hp) {  // the recurrence also leaves the column maxima of dG (the scales of the half-pair dG^T planes): no extra pass
-        const int64_t Mr = (int64_t)T * B, N4r = (int64_t)D * 4 * H;
-        k.colmax = w.hp_amax + Mr + N4r + Mr;
-        k.colmax_h = w.hp_amax + 2 * Mr + 2 * N4r + 2 * I + (int64_t)D * H;
-        // LSTM / Elman layers that hand on dx: the recurrence also leaves the row maxima, and ONE pass over dG then writes both
-        // orientations of its planes (hp_split_both) instead of a row-major pass that measures each row first plus a transposed pass
-        unsigned* fill_from = k.colmax;
-        if (!gru && I >= 128 && bd->dx && !getenv("RNNT_GEMM_HP_NO_FUSED_SPLIT")) {
-          k.rowmax = w.hp_amax + Mr + N4r;   // = a_dgr below, directly in front of the column table
-          fill_from = k.rowmax;
-          rowmax_done = true;
-        }
-        if (do_recur)   // one fill from the first table to the end of the last (the tables in between are written later)
-          RNNT_CHECK_HIP(hipMemsetAsync(fill_from, 0, (size_t)(k.colmax_h + N4r - fill_from) * 4, s));
-        colmax_done = true;
-      }
-      if (do_recur) rc = lstm5_bwd_launch(k, p2, d->cell, s, f16);
-      // the weight-gradient products of THIS layer may run beside the recurrence of the next one (same shape): that one sits on
-      // XCDs 0 .. D*G-1 (launch_persistent2's stride-8 placement), the products keep to the others
-      if (bd->beside_recurrence) {
-        // (only on a device that exposes all 8 XCDs — the 256-CU SPX mode the placement rule was measured on; a partitioned device
-        //  runs the products on every XCD it has, and gemm_hp.hip's check kernel raises the status word if a launch left units undone)
-        const int used = recurrence_xcds(T, B, H, D, d->cell, cus);
-        if (used <= 4 && cus == 256) xcd_skip = (1u << used) - 1u;
-      }
-    } else if (!do_recur) {
-      // phase 2: nothing to launch here
-    } else if (p2.MB == 5) {  // H = 640: own 80 gate columns (3 k-steps), 48 output blocks over 8 waves
-      rc = dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+int lstm4_bwd_launch(const LstmK& k, const Plan2& p2, int cell, hipStream_t s) {
+  const int c = cell_form(cell);
+  if (p2.MB == 5)  // H = 640: own 80 gate columns (3 k-steps), 48 output blocks over 8 waves
+    return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd4_kernel<6, BQ, C, 8, 5, 1>, k, p2, p2.lds_bwd + 8 * 1 * 3 * 3 * 1024, s, "lstm_bwd4", 512);
+      });
+    });
+  if (p2.Kp <= 512)  // (H = 512 backward with 8 waves: 12.9 vs 11.9 ms per c2 step -> stays at 4)
+    return dispatch<2, 4, 6, 8>(p2.Kp / (16 * 4), "lstm_bwd4 output blocks", [&](auto NOB) {
+      return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
         return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
-          return launch_persistent2(lstm_bwd4_kernel<6, BQ, C, 8, 5, 1>, k, p2, p2.lds_bwd + 8 * 1 * 3 * 3 * 1024, s, "lstm_bwd4", 512);
+          return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd4");
         });
       });
-    } else if (p2.Kp <= 512) {  // (H = 512 backward with 8 waves: 12.9 vs 11.9 ms per c2 step -> stays at 4)
-      rc = dispatch<2, 4, 6, 8>(p2.Kp / (16 * 4), "lstm_bwd4 output blocks", [&](auto NOB) {
-        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
-          return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
-            return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd4");
-          });
-        });
+    });
+  // H = 768 / 1024: 8 waves, 6 / 8 output blocks each
+  return dispatch<6, 8>(p2.Kp / (16 * 8), "lstm_bwd4 output blocks", [&](auto NOB) {
+    return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
+      return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
+        return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C, 8, 4, 2>, k, p2, p2.lds_bwd + 8 * 2 * 2 * 3 * 1024, s, "lstm_bwd4", 512);
       });
-    } else {  // H = 768 / 1024: 8 waves, 6 / 8 output blocks each
-      rc = dispatch<6, 8>(p2.Kp / (16 * 8), "lstm_bwd4 output blocks", [&](auto NOB) {
-        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd4 BQ", [&](auto BQ) {
-          return dispatch<0, 1, 2>(c, "lstm_bwd4 cell", [&](auto C) {
-            return launch_persistent2(lstm_bwd4_kernel<NOB, BQ, C, 8, 4, 2>, k, p2, p2.lds_bwd + 8 * 2 * 2 * 3 * 1024, s, "lstm_bwd4", 512);
-          });
-        });
-      });
-    }
-  } else if (make_plan2(d->B, d->H, d->D, cus, &p2)) {
-    adopt(p2);
-    if (do_recur)
-      rc = dispatch<4, 8, 16>(p2.HS, "lstm_bwd2 HS", [&](auto HS) {
-        return dispatch<1, 2, 4>(p2.BQ, "lstm_bwd2 BQ", [&](auto BQ) {
-          return dispatch<0, 1, 2>(cell_form(d->cell), "lstm_bwd2 cell", [&](auto C) {
-            return launch_persistent2(lstm_bwd2_kernel<HS, BQ, C>, k, p2, p2.lds_bwd, s, "lstm_bwd2");
-          });
-        });
-      });
-  } else if (d->cell == RNNT_CELL_LSTM) {
-    if (do_recur)
-      rc = dispatch<1, 2, 4>(pl.MT, "lstm_bwd MT", [&](auto MT) {
-        return dispatch<1, 2, 4>(pl.NT, "lstm_bwd NT", [&](auto NT) {
-          return launch_persistent(lstm_bwd_kernel<MT, NT>, k, pl, pl.lds_bwd, s, "lstm_bwd");
-        });
-      });
-  } else {
-    set_error("rnn: GRU / Elman cells need the grouped decomposition; B=%d H=%d does not fit", d->B, d->H);
-    rc = RNNT_ERR_UNSUPPORTED;
-  }
-  if (rc) return rc;
-
-  const int64_t M = (int64_t)T * B, N4 = (int64_t)D * 4 * H;
-  const int64_t Mv = ragged ? d->n_rows : M;   // rows (row-major operands: gathered by the GEMM) / contraction length (transposed planes: packed)
-  const bool hp_in = w.hp && I >= 128;   // products with I as an output / contraction width on the f16 matrix cores
-  // per-row maxima: dG rows | dG columns | W_ih'^T rows | X^T rows | h^T rows
-  uint32_t* a_dgr = w.hp ? w.hp_amax + M + N4 : nullptr;
-  uint32_t* a_dgc = w.hp ? a_dgr + M : nullptr;
-  uint32_t* a_w = w.hp ? a_dgc + N4 : nullptr;
-  uint32_t* a_x = w.hp ? a_w + I : nullptr;
-  uint32_t* a_y = w.hp ? a_x + I : nullptr;
-  if (w.hp) {  // half-pair planes of dG in both orientations (gemm_hp.hip is NT-only: transposed operands are materialised)
-    const bool both = rowmax_done && colmax_done && hp_in && bd->dx;   // (same in both phases of a two-phase backward)
-    if (do_recur && hp_in && bd->dx) {
-      if (both) rc = hp_split_both(d->gates, Mv, N4, N4, a_dgr, a_dgc, w.hp_dg, w.hp_dgt, s, ridx);
-      else rc = hp_split(d->gates, Mv, N4, N4, a_dgr, w.hp_dg, s, ridx);
-      if (rc) return rc;
-    }
-    if (do_weights && !colmax_done)
-      if ((rc = hp_colmax(d->gates, M, N4, N4, a_dgc, s))) return rc;
-    if (do_weights && !both)
-      if ((rc = hp_split_t(d->gates, N4, Mv, N4, M, 0, a_dgc, w.hp_dgt, s, ridx))) return rc;
-  }
-  // 2. dX = dG . W_ih'   (needs the permuted weights: rebuild them, the forward copy may have been overwritten)
-  if (do_recur && bd->dx) {
-    const long per = (long)4 * H * I;
-    hipLaunchKernelGGL(permute_w_kernel, dim3((unsigned)ceil_div(per, 256), D), dim3(256), 0, s, d->w_ih[0],
-                       D > 1 ? d->w_ih[1] : d->w_ih[0], H, I, ngate, w.wp);
-    RNNT_CHECK_LAUNCH();
-    if (hp_in) {
-      if ((rc = hp_colmax(w.wp, N4, I, I, a_w, s))) return rc;
-      if ((rc = hp_split_t(w.wp, I, N4, I, N4, 0, a_w, w.hp_w, s))) return rc;   // W_ih'^T: (I, contraction N4)
-      if ((rc = hp_gemm(w.hp_dg, a_dgr, w.hp_w, a_w, Mv, I, N4, bd->dx, 1, I, 0, nullptr, hpf, nullptr, 0, s, ridx, M, ridx))) return rc;
-    } else {
-      rnnt_gemm_desc g = {};
-      g.M = M; g.N = I; g.K = N4;
-      g.A = d->gates; g.a_div = 1; g.a_so = N4; g.a_si = 0; g.a_sk = 1; g.a_mc = 0;
-      g.B = w.wp; g.b_sn = 1; g.b_sk = I;
-      g.C = bd->dx; g.c_div = 1; g.c_so = I; g.c_si = 0;
-      if ((rc = rnnt_hip_gemm_f32(&g, s))) return rc;
-    }
-    if (ragged) {
-      const long nrow = (long)T * B;
-      hipLaunchKernelGGL(zero_padded_rows_kernel, dim3((unsigned)(ceil_div(nrow, 4) < 2048 ? ceil_div(nrow, 4) : 2048)), dim3(256), 0, s, bd->dx, d->lens, T, B, I);
-      RNNT_CHECK_LAUNCH();
-    }
-  }
-  if (!do_weights) return RNNT_OK;
-  // All three weight-gradient products on the half-pair path (LSTM / Elman) beside a recurrence: their operand planes first, then
-  // ONE queue-driven launch (gemm_hp.hip) that stays off the recurrence's XCDs.
-  // (alone on the device three launches are faster: 1.13 vs 1.29 ms for a c2 layer, tools/gemm_hpq_bench.py — the queue form is for
-  // the overlapped case, where it keeps off the recurrence's XCDs)
-  const bool grouped = w.hp && hp_in && T > 1 && !gru && D <= 2 && (xcd_skip != 0u || getenv("RNNT_GEMM_HP_GROUP")) && !getenv("RNNT_GEMM_HP_NO_GROUP");
-  // 3. dW_ih' = dG^T . X  (both directions at once), un-permute rows into torch layout
-  {
-    // (a narrow input — the 80 mel bins of layer 0 — still goes to the half-pair kernel: one 256-wide tile column, split over K)
-    const bool x_plain = d->x_sb == I && d->x_st == (int64_t)B * I;
-    if (hp_in || (w.hp && I >= 32 && x_plain && !getenv("RNNT_GEMM_HP_NO_NARROW"))) {
-      if (d->x_abs_bound > 0.f) {   // bounded input (the dropped output of the layer below): its bound is the scale, no pass over x
-        uint32_t bits;
-        memcpy(&bits, &d->x_abs_bound, 4);
-        RNNT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)a_x, (int)bits, (size_t)I, s));
-      } else if ((rc = hp_colmax(d->x, M, I, I, a_x, s))) return rc;
-      if ((rc = hp_split_t(d->x, I, Mv, I, M, 0, a_x, w.hp_x, s, ridx))) return rc;     // X^T: (I, contraction over the (valid) frames)
-      if (!grouped)
-        if ((rc = hp_gemm(w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, 1, I, 0, nullptr, hpf, w.scratch, w.scratch_bytes, s))) return rc;
-    } else {
-      rnnt_gemm_desc g = {};
-      g.M = N4; g.N = I; g.K = M;
-      g.A = d->gates; g.a_mc = 1; g.a_sk = N4; g.a_div = 1;
-      g.B = d->x; g.b_sn = 1; g.b_sk = I;
-      g.C = w.wp; g.c_div = 1; g.c_so = I; g.c_si = 0;
-      g.workspace = w.scratch; g.workspace_bytes = w.scratch_bytes;
-      if ((rc = rnnt_hip_gemm_f32(&g, s))) return rc;
-    }
-    if (!grouped) {
-      const long per = (long)4 * H * I;
-      hipLaunchKernelGGL(unpermute_w_kernel, dim3((unsigned)ceil_div(per, 256), D), dim3(256), 0, s, w.wp, H, I, per, ngate,
-                         bd->dw_ih[0], D > 1 ? bd->dw_ih[1] : bd->dw_ih[0], acc);
-      RNNT_CHECK_LAUNCH();
-    }
-  }
-  // 4. dW_hh'[d] = sum_t dG[t]^T . h_prev(t): time-shifted views of dG and y (padded frames are zero in both)
-  if (w.hp && T > 1) {
-    if (d->cell != RNNT_CELL_RNN_RELU) {   // |h| < 1 for LSTM / GRU / tanh cells: the planes of h^T take 1.0 as their scale
-      RNNT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)a_y, 0x3f800000, (size_t)D * H, s));
-    } else if ((rc = hp_colmax(d->y, M, (int64_t)D * H, (int64_t)D * H, a_y, s))) return rc;
-    if (gru) {  // hidden-side gate gradients differ from the input-side ones in the n gate: their own transposed planes
-      if (colmax_done) a_dgc = a_y + (int64_t)D * H;   // left there by the v5 recurrence
-      else if ((rc = hp_colmax(ghid, M, N4, N4, a_dgc, s))) return rc;
-      if ((rc = hp_split_t(ghid, N4, Mv, N4, M, 0, a_dgc, w.hp_dgt, s, ridx))) return rc;
-    }
-    HpProblem pr[HP_GROUP_MAX];
-    int npr = 0;
-    if (grouped) pr[npr++] = HpProblem{w.hp_dgt, a_dgc, w.hp_x, a_x, N4, I, Mv, w.wp, I, hpf};
-    for (int dir = 0; dir < D; ++dir) {
-      // h_prev of frame t is y[t-1] (forward direction) / y[t+1] (reverse): plane row j, index k = y[k -/+ B][dir*H + j], zero outside
-      char* yt = w.hp_yt + (size_t)dir * hp_plane_bytes(H, M);
-      // (ragged batches: frame (t, b) of the packed contraction takes y of padded row (t -/+ 1, b), which is a valid frame or holds 0)
-      if ((rc = hp_split_t(d->y + (int64_t)dir * H, H, Mv, (int64_t)D * H, M, dir == 0 ? -B : B, a_y + (int64_t)dir * H, yt, s, ridx))) return rc;
-      const char* ag = w.hp_dgt + (size_t)dir * 4 * H * (size_t)ceil_div(Mv, 32) * 128;
-      if (grouped) {
-        pr[npr++] = HpProblem{ag, a_dgc + (int64_t)dir * 4 * H, yt, a_y + (int64_t)dir * H, 4 * H, H, Mv, w.dwhh + (int64_t)dir * 4 * H * H, H, hpf};
-        continue;
-      }
-      if ((rc = hp_gemm(ag, a_dgc + (int64_t)dir * 4 * H, yt, a_y + (int64_t)dir * H, 4 * H, H, Mv, w.dwhh + (int64_t)dir * 4 * H * H, 1, H, 0,
-                        nullptr, hpf, w.scratch, w.scratch_bytes, s)))
-        return rc;
-    }
-    if (grouped) {
-      if ((rc = hp_gemm_grouped(pr, npr, xcd_skip, reinterpret_cast<unsigned*>(w.scratch), (char*)w.scratch + HPQ_HEADER_BYTES,
-                                w.scratch_bytes - HPQ_HEADER_BYTES, s, k.status)))
-        return rc;
-      const long per = (long)4 * H * I;
-      hipLaunchKernelGGL(unpermute_w_kernel, dim3((unsigned)ceil_div(per, 256), D), dim3(256), 0, s, w.wp, H, I, per, ngate,
-                         bd->dw_ih[0], D > 1 ? bd->dw_ih[1] : bd->dw_ih[0], acc);
-      RNNT_CHECK_LAUNCH();
-    }
-  } else
-  for (int dir = 0; dir < D; ++dir) {
-    rnnt_gemm_desc g = {};
-    g.M = 4 * H; g.N = H; g.K = (int64_t)(T - 1) * B;
-    const int64_t shift_g = dir == 0 ? (int64_t)B * N4 : 0;           // dG rows t = 1..T-1 | 0..T-2
-    const int64_t shift_y = dir == 0 ? 0 : (int64_t)B * D * H;        // y  rows t = 0..T-2 | 1..T-1
-    g.A = ghid + shift_g + (int64_t)dir * 4 * H; g.a_mc = 1; g.a_sk = N4; g.a_div = 1;
-    g.B = d->y + shift_y + (int64_t)dir * H; g.b_sn = 1; g.b_sk = (int64_t)D * H;
-    g.C = w.dwhh + (int64_t)dir * 4 * H * H; g.c_div = 1; g.c_so = H; g.c_si = 0;
-    g.workspace = w.scratch; g.workspace_bytes = w.scratch_bytes;
-    if (g.K > 0) {
-      if ((rc = rnnt_hip_gemm_f32(&g, s))) return rc;
-    } else {
-      RNNT_CHECK_HIP(hipMemsetAsync(g.C, 0, (size_t)4 * H * H * 4, s));
-    }
-  }
-  {
-    const long per = (long)4 * H * H;
-    hipLaunchKernelGGL(unpermute_w_kernel, dim3((unsigned)ceil_div(per, 256), D), dim3(256), 0, s, w.dwhh, H, H, per, ngate,
-                       bd->dw_hh[0], D > 1 ? bd->dw_hh[1] : bd->dw_hh[0], acc);
-    RNNT_CHECK_LAUNCH();
-  }
-  // 5. bias gradient = column sums of dG, un-permuted (the v4 recurrence already summed its own cells over time)
-  if (fused_db) {
-    hipLaunchKernelGGL(db_reduce_kernel, dim3((unsigned)ceil_div(4 * H, 256), D), dim3(256), 0, s, k.dbp, db_rows, H, ngate, bd->db[0],
-                       D > 1 ? bd->db[1] : bd->db[0], acc, twin0, twin1);
-    RNNT_CHECK_LAUNCH();
-    if (gru) {
-      hipLaunchKernelGGL(db_reduce_kernel, dim3((unsigned)ceil_div(4 * H, 256), D), dim3(256), 0, s, k.dbhp, db_rows, H, ngate, bd->db_hh[0],
-                         D > 1 ? bd->db_hh[1] : bd->db_hh[0], acc);
-      RNNT_CHECK_LAUNCH();
-    }
-  } else {
-    if ((rc = launch_colsum(d->gates, (long)M, (long)N4, (long)N4, w.bp, w.scratch, w.scratch_bytes, s))) return rc;
-    hipLaunchKernelGGL(unpermute_w_kernel, dim3((unsigned)ceil_div(4 * H, 256), D), dim3(256), 0, s, w.bp, H, 1, (long)4 * H, ngate,
-                       bd->db[0], D > 1 ? bd->db[1] : bd->db[0], acc, twin0, twin1);
-    RNNT_CHECK_LAUNCH();
-    if (gru) {  // b_hh sees the hidden-side gradients (n gate scaled by r)
-      if ((rc = launch_colsum(ghid, (long)M, (long)N4, (long)N4, w.bp, w.scratch, w.scratch_bytes, s))) return rc;
-      hipLaunchKernelGGL(unpermute_w_kernel, dim3((unsigned)ceil_div(4 * H, 256), D), dim3(256), 0, s, w.bp, H, 1, (long)4 * H, ngate,
-                         bd->db_hh[0], D > 1 ? bd->db_hh[1] : bd->db_hh[0], acc);
-      RNNT_CHECK_LAUNCH();
-    }
-  }
-  return RNNT_OK;
+    });
+  });
 }
 
-extern "C" int rnnt_hip_lstm_bwd(const rnnt_lstm_bwd_desc* bd, void* stream) { return lstm_bwd_impl(bd, RNNT_PRECISION_FP32, stream); }
-
-extern "C" int rnnt_hip_lstm_bwd_ex(const rnnt_lstm_bwd_desc* bd, uint32_t precision, void* stream) {
-  RNNT_CHECK_ARG(precision == RNNT_PRECISION_FP32 || precision == RNNT_PRECISION_F16, "lstm_bwd_ex: precision must be 0 (fp32) or 1 (f16), got %u",
-                 precision);
-  return lstm_bwd_impl(bd, precision, stream);
-}
-
-extern "C" int rnnt_hip_lstm_check(const void* workspace, void* stream) {
-  // word 0 of the workspace is the persistent kernels' status word (0 = ok, 1 = an inter-CU wait gave up)
-  RNNT_CHECK_ARG(workspace != nullptr, "lstm_check: null workspace");
-  unsigned st = 0;
-  RNNT_CHECK_HIP(hipMemcpyAsync(&st, workspace, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  RNNT_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-  if (st != 0) {
-    set_error("persistent LSTM kernel abandoned an inter-workgroup wait (status %u)", st);
-    return RNNT_ERR_TIMEOUT;
-  }
-  return RNNT_OK;
-}
-
-extern "C" int rnnt_hip_lstm_debug_read(const void* workspace, int32_t T, int32_t B, int32_t I, int32_t H, int32_t D,
-                                        uint64_t* out, int32_t nwg, void* stream) {
-  Plan pl;
-  int cus = device_cus();
-  RNNT_CHECK_ARG(workspace && out && nwg >= 1 && nwg <= 512, "lstm_debug_read: bad arguments");
-  RNNT_CHECK_ARG(make_plan(B, H, D, cus, &pl), "lstm_debug_read: unsupported shape");
-  const LstmWs w = carve_lstm(const_cast<void*>(workspace), T, B, I, H, D, pl);
-  RNNT_CHECK_HIP(hipMemcpyAsync(out, w.dbg, (size_t)nwg * 8 * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  RNNT_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return RNNT_OK;
-}
-
-extern "C" size_t rnnt_hip_colsum_workspace_bytes(int64_t M, int64_t N) {
-  if (M < 0 || N < 1) return 0;
-  return (size_t)colsum_chunks((long)M, (long)N) * (size_t)N * 4;
-}
-
-extern "C" int rnnt_hip_colsum_f32(const float* X, int64_t M, int64_t N, int64_t ld, float* out, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  RNNT_CHECK_ARG(X && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
-  return launch_colsum(X, (long)M, (long)N, (long)ld, out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-extern "C" int rnnt_hip_colsum_f32_acc(const float* X, int64_t M, int64_t N, int64_t ld, float* out, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  RNNT_CHECK_ARG(X && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
-  return launch_colsum(X, (long)M, (long)N, (long)ld, out, workspace, workspace_bytes, (hipStream_t)stream, 1);
-}
-
-extern "C" int rnnt_hip_embedding_fwd(const float* W, const int64_t* idx, int64_t M, int32_t H, int32_t V, float* out,
-                                      void* stream) {
-  RNNT_CHECK_ARG(W && idx && out && M >= 0 && H >= 1 && V >= 1, "embedding_fwd: bad arguments");
-  if (M == 0) return RNNT_OK;
-  const long blocks = ceil_div(M * H, 256);
-  hipLaunchKernelGGL(embedding_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, W,
-                     (const long*)idx, (long)M, H, V, out);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-static int embedding_bwd_impl(const float* dE, const int64_t* idx, int64_t M, int32_t H, int32_t V, int64_t padding_idx,
-                              float* dW, int accumulate, void* stream) {
-  RNNT_CHECK_ARG(dE && idx && dW && M >= 0 && H >= 1 && V >= 1, "embedding_bwd: bad arguments");
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(V), dim3(256), 0, (hipStream_t)stream, dE, (const long*)idx, (long)M, H, V,
-                     (long)padding_idx, dW, accumulate);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-extern "C" int rnnt_hip_embedding_bwd(const float* dE, const int64_t* idx, int64_t M, int32_t H, int32_t V,
-                                      int64_t padding_idx, float* dW, void* stream) {
-  return embedding_bwd_impl(dE, idx, M, H, V, padding_idx, dW, 0, stream);
-}
-extern "C" int rnnt_hip_embedding_bwd_acc(const float* dE, const int64_t* idx, int64_t M, int32_t H, int32_t V,
-                                          int64_t padding_idx, float* dW, void* stream) {
-  return embedding_bwd_impl(dE, idx, M, H, V, padding_idx, dW, 1, stream);
-}
+}  // namespace rnnt

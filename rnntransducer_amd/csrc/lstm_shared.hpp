@@ -1,5 +1,7 @@
-// Shared by lstm.hip and lstm5.hip: kernel argument block, inter-workgroup protocol helpers and the grouped-launch helper of the
-// persistent recurrences (see the header comment of lstm.hip).  Everything here is per-translation-unit (anonymous namespace).
+// Shared by the recurrence kernels (lstm.hip: v1-v4, lstm5.hip: v5) and the layer code that chooses between them (lstm_layer.hip):
+// kernel argument block, the plans of the kernel generations with their launch functions, inter-workgroup protocol helpers and the
+// grouped-launch helper of the persistent recurrences (see the header comment of lstm.hip).  The helpers in the anonymous namespace
+// are per-translation-unit.
 #pragma once
 #include "common.hpp"
 
@@ -45,12 +47,31 @@ struct LstmK {
                    // IEEE-division form, which RNNT_LSTM_EXACT_MATH=1 selects)
 };
 
-struct Plan2 {
+struct Plan {   // v1: hidden slices of Hs units, all rows (padded to Bp) in every workgroup
+  int Hs, NC, MT, NT, Bp, LDW, wgs_per_cu;
+  size_t lds_fwd, lds_bwd;
+};
+
+struct Plan2 {  // v2 - v5: NC hidden slices of HS units x G batch groups of Bg rows per direction
   int HS, NC, G, Bg, BQ, Kp;
   int MB = 4;  // register-form kernels: 16-gate-column blocks per workgroup (HS = 4*MB)
   size_t lds_fwd, lds_bwd;
 };
 
+// What each generation takes (false: not this shape, or switched off by the environment) and its launches.  The launch functions
+// expect k.NC / Hs / G / Bg / Kp to come from the same plan.  Called from lstm_layer.hip only: resolve_plan / launch_recurrence.
+// v1 (lstm.hip): LSTM cells only
+bool make_plan(int B, int H, int D, int cus, Plan* pl);
+int lstm1_fwd_launch(const LstmK& k, const Plan& pl, hipStream_t s);
+int lstm1_bwd_launch(const LstmK& k, const Plan& pl, hipStream_t s);
+// v2 (lstm.hip): W_hh slice in LDS
+bool make_plan2(int B, int H, int D, int cus, Plan2* pl);
+int lstm2_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
+int lstm2_bwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
+// v3 forward / v4 backward (lstm.hip): W_hh in registers; v5 runs on the same plan
+bool make_plan3(int B, int H, int D, int cus, Plan2* pl);
+int lstm3_fwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
+int lstm4_bwd_launch(const LstmK& k, const Plan2& pl, int cell, hipStream_t s);
 // v5 recurrences (lstm5.hip)
 bool lstm5_supported(int T, int B, int H, int D, int cell);
 // f16: the one-product forms (hi.hi only, RNNT_PRECISION_F16); the exchange protocol is the same in both modes
