@@ -355,6 +355,35 @@ int rnnt_hip_loss_from_logits_fwd_bwd_ex(const void* logits, int32_t dtype, cons
                                          float gscale, float* nll, void* grad, void* workspace, size_t workspace_bytes,
                                          void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Forced alignment: the best (Viterbi) RNN-T path of a KNOWN transcript, per utterance, on the device.  No (B,T,U+1,V) tensor:
+ * the same two numbers per lattice cell as the loss, blk(t,u) = log p(blank | t,u) and emit(t,u) = log p(y_u | t,u), then the
+ * lattice sweep of the loss in the (max, +) semiring:
+ *   v(t,u) = max( v(t-1,u) + blk(t-1,u), v(t,u-1) + emit(t,u-1) ),  v(0,0) = 0,
+ *   score  = v(Tb-1,Ub) + blk(Tb-1,Ub)            (Tb = t_lens[b], Ub = u_lens[b]),
+ * accumulated in fp64 from the fp32 cell terms (an exact sum: no transcendental after the log-softmax).
+ * Tie rule: on exactly equal candidates the blank predecessor (t-1,u) wins; the label predecessor (t,u-1) is taken only when it
+ * is strictly greater.  The path is therefore a pure function of blk / emit.
+ * Outputs: frames (B,U) int32 (U = U1-1): frames[b][u] = the frame at which label u is emitted on the best path, for u < u_lens[b]
+ *   (non-decreasing in u, in [0, t_lens[b])); -1 for u >= u_lens[b].  score (B) fp64 = log-probability of the best path
+ *   (<= -nll of the loss, which sums over all paths).
+ * Limits and edge cases are the loss's: U1 <= 512, any V; t_lens[b] in [1,T]; t_lens[b] = 0 gives score[b] = -inf and frames -1
+ *   in row b and leaves every other row as it is without row b; u_lens[b] = 0 is the all-blank path (finite score, no frame);
+ *   T = 1 puts every label on frame 0.  Row b gives the same bits alone as inside any batch.  frames may be NULL when U1 = 1.
+ * The fused form takes the operands and strides of rnnt_hip_joint_loss_fwd_bwd (and picks its log-softmax kernel by the same
+ * vocabulary rule); the dense form takes logits (B,T,U1,V) stored as RNNT_DTYPE_F32 / _F16 / _BF16, as
+ * rnnt_hip_loss_from_logits_fwd_bwd_ex does.  Both use a workspace of rnnt_hip_joint_align_workspace_bytes (0 for invalid
+ * dims): 8 bytes + 1 bit per lattice cell.  Arguments are validated before any device work; nothing synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_joint_align_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V);
+int rnnt_hip_joint_align(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                         const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                         int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, int32_t* frames, double* score,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int rnnt_hip_align_from_logits_ex(const void* logits, int32_t dtype, const int32_t* labels, const int32_t* t_lens,
+                                  const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                  int32_t* frames, double* score, void* workspace, size_t workspace_bytes, void* stream);
+
 /* One fused AdamW step over FLAT fp32 buffers (all parameters / gradients / moments of the module laid out back to back):
  * replaces torch.optim.AdamW's multi-tensor kernels at model.py:111-115.  Same update as torch (decoupled weight decay,
  * bias corrections from `step` >= 1). */

@@ -366,6 +366,130 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// forced alignment: the alpha sweep above in the (max, +) semiring, one wavefront per utterance.
+//   v(t,u) = max( v(t-1,u) + blk(t-1,u), v(t,u-1) + emit(t,u-1) ),  v(0,0) = 0,  score = v(Tb-1,Ub) + blk(Tb-1,Ub)
+// fp64 sums of the fp32 cell terms, no transcendental: the score is exact.  TIE RULE: on exactly equal candidates the blank
+// predecessor (t-1,u) wins (the label predecessor is taken only when it is strictly greater), so the path is a pure function of
+// blk / emit.  Back-pointers: ONE BIT per cell (1 = came from (t,u-1), i.e. label u-1 is emitted at frame t), 32 consecutive frames
+// of one label row per word: bp[b][u][t >> 5] bit (t & 31).  A lane collects the bits of its K rows in registers and stores a word
+// when its row reaches the end of a 32-frame block or the utterance's last frame; like every memory operation of the loop the store
+// goes through a buffer resource with an out-of-range offset when there is nothing to store.
+// ------------------------------------------------------------------------------------------------
+template <int K>
+__global__ void __launch_bounds__(64) viterbi_kernel(const float* __restrict__ blk, const float* __restrict__ emit,
+                                                     const int* __restrict__ t_lens, const int* __restrict__ u_lens,
+                                                     int T, int U1, int NW, unsigned* __restrict__ bp,
+                                                     double* __restrict__ score) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  // valid cells: t < Tb, u <= Ub.  The lengths are the caller's: clamped into the lattice (as backtrace_kernel clamps them), so a wrong
+  // length can neither reach another label row through u * T + t nor leave score[b] unwritten
+  const int Tb = min(t_lens[b], T), Ub = max(min(u_lens[b], U1 - 1), 0);
+  const long rowbase = (long)b * U1 * T;
+  const int ulo = lane * K;
+  const int lastlane = Ub / K;
+  const int nsteps = Tb + lastlane;
+  const int cells = U1 * T;
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(blk + rowbase), 0, cells * 4, AB_RSRC);
+  const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(emit + rowbase), 0, cells * 4, AB_RSRC);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bp + (long)b * U1 * NW, 0, U1 * NW * 4, AB_RSRC);
+  auto cell = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u <= Ub) ? u * T + t : -1; };
+  auto ld = [&](const __amdgpu_buffer_rsrc_t& r, int c) -> float {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, c >= 0 ? c * 4 : AB_OOB, 0, 0));
+  };
+  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, rw, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
+  const int nrounds = (nsteps + PF - 1) / PF;
+  double best = NEG_INF;
+
+  double down[K];    // v[t-1][u] + blk[t-1][u]
+  unsigned bits[K];  // back-pointer bits of the current 32-frame block of row ulo + k
+#pragma unroll
+  for (int k = 0; k < K; ++k) { down[k] = NEG_INF; bits[k] = 0u; }
+  double eout = NEG_INF;  // v[t][uhi] + emit[t][uhi] of this lane's last cell at its current row
+  float pb[PF][K], pe[PF][K];
+#pragma unroll
+  for (int j = 0; j < PF; ++j)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int c = cell(ulo + k, j - lane);
+      pb[j][k] = ld(rb, c);
+      pe[j][k] = ld(re, c);
+    }
+  for (int r = 0; r < nrounds; ++r) {
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int t = r * PF + j - lane;
+      const double carry = shfl_up1(eout, lane);
+      float cb[K], ce[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) { cb[k] = pb[j][k]; ce[k] = pe[j][k]; }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int c = cell(ulo + k, t + PF);
+        pb[j][k] = ld(rb, c);
+        pe[j][k] = ld(re, c);
+      }
+      const bool row = t >= 0 && t < Tb;
+      const int sh = t & 31;
+      const bool flush = sh == 31 || t == Tb - 1;
+      double left = carry;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int u = ulo + k;
+        const bool ok = row && u <= Ub;
+        const bool from_label = left > down[k];   // strict: a tie keeps the blank predecessor; (0,0) and u = 0 see left = -inf
+        const double v = (t == 0 && u == 0) ? 0.0 : (from_label ? left : down[k]);
+        const unsigned nb = (sh == 0 ? 0u : bits[k]) | ((unsigned)from_label << sh);
+        bits[k] = ok ? nb : bits[k];
+        stw(nb, (ok && flush) ? u * NW + (t >> 5) : -1);
+        const double nd = v + (double)cb[k];
+        down[k] = ok ? nd : down[k];
+        left = ok ? ((u < Ub) ? v + (double)ce[k] : NEG_INF) : left;
+        best = (ok && t == Tb - 1 && u == Ub) ? nd : best;
+      }
+      eout = row ? left : eout;
+    }
+  }
+  if (lane == lastlane) score[b] = best;   // the lane that owns cell (Tb - 1, Ub); -inf when the utterance has no frame
+}
+
+// Back-trace from (Tb-1, Ub) to label row 0: one workgroup per utterance.  A zero word (below the current frame) is 32 blank steps
+// at once, a set bit is found by a leading-zero count: about U + T/32 dependent loads instead of T + U.  The utterance's part of the
+// table is first copied to LDS (coalesced) when the whole table of the call fits there; otherwise the walk reads the workspace.
+// frames[b][u] = frame at which label u is emitted (u < Ub), -1 beyond (and everywhere when the utterance has no frame).
+__global__ void __launch_bounds__(256) backtrace_kernel(const unsigned* __restrict__ bp, const int* __restrict__ t_lens,
+                                                        const int* __restrict__ u_lens, int T, int U1, int NW, int in_lds,
+                                                        int* __restrict__ frames) {
+  extern __shared__ unsigned bt_tab[];
+  const int b = blockIdx.x, tid = threadIdx.x, U = U1 - 1;
+  const int Tb = min(t_lens[b], T), Ub = max(min(u_lens[b], U), 0);   // (lengths are the caller's: clamped so no access leaves the row)
+  int* fr = frames + (long)b * U;
+  const int nlab = Tb >= 1 ? Ub : 0;   // labels that receive a frame
+  for (int i = nlab + tid; i < U; i += 256) fr[i] = -1;
+  if (nlab == 0) return;   // (uniform)
+  const unsigned* tp = bp + (long)b * U1 * NW;
+  int stride = NW;
+  if (in_lds) {
+    const int nwb = ((Tb - 1) >> 5) + 1;   // words per row this utterance wrote
+    for (int i = tid; i < (Ub + 1) * nwb; i += 256) bt_tab[i] = tp[(i / nwb) * NW + i % nwb];
+    __syncthreads();
+    tp = bt_tab;
+    stride = nwb;
+  }
+  if (tid != 0) return;
+  int t = Tb - 1, u = Ub;
+  while (u > 0 && t >= 0) {
+    const unsigned w = tp[u * stride + (t >> 5)] & (0xffffffffu >> (31 - (t & 31)));   // frames <= t of the block
+    if (w == 0u) {
+      t = (t & ~31) - 1;
+    } else {
+      t = (t & ~31) + 31 - __clz(w);
+      fr[--u] = t;
+    }
+  }
+  while (u > 0) fr[--u] = -1;   // (only with -inf cell terms: no finite path)
+}
+
+// ------------------------------------------------------------------------------------------------
 // per-cell scalars for the gradient: occupancy w, row lse, blank- and label-transition posteriors
 // ------------------------------------------------------------------------------------------------
 struct CellS {
@@ -790,6 +914,63 @@ int launch_alphabeta(const LossWs& w, const int* t_lens, const int* u_lens, int 
   return RNNT_OK;
 }
 
+// forced alignment: blk / emit as the loss lays them out, then the back-pointer table bp[B][U1][ceil(T/32)] (one bit per cell)
+struct AlignWs {
+  float *blk, *emit;
+  unsigned* bp;
+  int nw;
+  size_t total;
+};
+
+AlignWs carve_align(void* ws, int B, int T, int U1) {
+  AlignWs w;
+  const size_t cells = (size_t)B * T * U1;
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
+  w.blk = reinterpret_cast<float*>(take(cells * 4));
+  w.emit = reinterpret_cast<float*>(take(cells * 4));
+  w.nw = (int)ceil_div(T, 32);
+  w.bp = reinterpret_cast<unsigned*>(take((size_t)B * U1 * w.nw * 4));
+  w.total = off;
+  return w;
+}
+
+int check_align(const void* labels, const void* t_lens, const void* u_lens, int B, int T, int U1, int V, int blank,
+                const void* frames, const void* score) {
+  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, score)) return rc;
+  RNNT_CHECK_ARG(U1 == 1 || frames, "rnnt align: null frames");
+  return RNNT_OK;
+}
+
+int launch_viterbi(const AlignWs& w, const int* t_lens, const int* u_lens, int B, int T, int U1, int* frames, double* score,
+                   hipStream_t s) {
+  const int K = (int)ceil_div(U1, 64);
+  // one scope over BOTH launches (sweep: read blk + emit, write one bit per cell; back-trace: read the bits back), booked under the
+  // lattice-sweep kind of the loss: the profiler's kinds are part of the ABI (rnnt_hip_prof_collect), which this feature leaves as it
+  // is, so a process that trains and aligns sees both sweeps summed in that slot
+  ProfScope prof(RNNT_K_ALPHABETA, (8.0 + 0.25) * (double)B * T * U1, s);
+  dim3 grid(B), block(64);
+#define VT(KK) hipLaunchKernelGGL((viterbi_kernel<KK>), grid, block, 0, s, w.blk, w.emit, t_lens, u_lens, T, U1, w.nw, w.bp, score)
+  switch (K) {
+    case 1: VT(1); break;
+    case 2: VT(2); break;
+    case 3: VT(3); break;
+    case 4: VT(4); break;
+    default: VT(8); break;
+  }
+#undef VT
+  RNNT_CHECK_LAUNCH();
+  constexpr size_t LDS_MAX = 160 * 1024;
+  const size_t lds = (size_t)U1 * w.nw * 4;   // U+1 = 512 label rows by T = 2560 frames fit
+  const int in_lds = lds <= LDS_MAX;
+  if (in_lds && lds > 64 * 1024)
+    RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)backtrace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(backtrace_kernel, grid, dim3(256), in_lds ? lds : 0, s, w.bp, t_lens, u_lens, T, U1, w.nw, in_lds, frames);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
 }  // namespace
 }  // namespace rnnt
 
@@ -800,6 +981,25 @@ using namespace rnnt;
 static bool large_vocab(int V) {
   if (getenv("RNNT_LOSS_SMALLV_KERNELS")) return false;
   return V >= 256 || getenv("RNNT_LOSS_LARGEV_KERNELS") != nullptr;
+}
+
+// blk / emit of every lattice cell from the separable operands (the loss and the alignment share it)
+static int launch_lse_sep(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su, const float* bias,
+                          const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float* blk, float* emit,
+                          hipStream_t s) {
+  const int ntiles = (int)ceil_div(T, TT);
+  const double cells = (double)B * T * U1;
+  {
+  ProfScope prof(RNNT_K_LSE, 4.0 * ((double)B * T * V + (double)B * U1 * V) + 8.0 * cells, s);
+  if (large_vocab(V))
+    hipLaunchKernelGGL(lse_sepv_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSV_UT), B), dim3(256), 0, s, A, C, bias, labels,
+                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, blk, emit);
+  else
+    hipLaunchKernelGGL(lse_sep_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSE_UT), B), dim3(256), 0, s, A, C, bias, labels,
+                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, blk, emit);
+  }
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
 }
 
 static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
@@ -864,19 +1064,7 @@ extern "C" int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t
   const LossWs w = carve(workspace, B, T, U1, V, true);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_loss: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
-  const int ntiles = (int)ceil_div(T, TT);
-
-  const double cells = (double)B * T * U1;
-  {
-  ProfScope prof(RNNT_K_LSE, 4.0 * ((double)B * T * V + (double)B * U1 * V) + 8.0 * cells, s);
-  if (large_vocab(V))
-    hipLaunchKernelGGL(lse_sepv_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSV_UT), B), dim3(256), 0, s, A, C, bias, labels,
-                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, w.blk, w.emit);
-  else
-    hipLaunchKernelGGL(lse_sep_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSE_UT), B), dim3(256), 0, s, A, C, bias, labels,
-                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, w.blk, w.emit);
-  }
-  RNNT_CHECK_LAUNCH();
+  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
   if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
   hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
   RNNT_CHECK_LAUNCH();
@@ -922,6 +1110,21 @@ extern "C" int rnnt_hip_joint_logits_fwd(const float* A, int64_t a_sb, int64_t a
   return RNNT_OK;
 }
 
+// blk / emit of every lattice cell from dense logits in fp32 / f16 / bf16 storage (the loss and the alignment share it)
+static unsigned dense_grid(long ncell) { return (unsigned)(ceil_div(ncell, 4) < 16384 ? ceil_div(ncell, 4) : 16384); }
+
+template <typename TZ>
+static int launch_lse_dense(const void* logits, const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                            float* blk, float* emit, hipStream_t s) {
+  const long ncell = (long)B * T * U1;
+  {
+  ProfScope prof(RNNT_K_LSE, (double)sizeof(TZ) * (double)ncell * V + 8.0 * (double)ncell, s);
+  hipLaunchKernelGGL((lse_dense_kernel<TZ>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V, blank, blk, emit);
+  }
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
 template <typename TZ>
 static int loss_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
                                  int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float* nll,
@@ -932,12 +1135,8 @@ static int loss_from_logits_impl(const void* logits, const int32_t* labels, cons
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "loss_from_logits: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
   const long ncell = (long)B * T * U1;
-  const unsigned grid = (unsigned)(ceil_div(ncell, 4) < 16384 ? ceil_div(ncell, 4) : 16384);
-  {
-  ProfScope prof(RNNT_K_LSE, (double)sizeof(TZ) * (double)ncell * V + 8.0 * (double)ncell, s);
-  hipLaunchKernelGGL((lse_dense_kernel<TZ>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V, blank, w.blk, w.emit);
-  }
-  RNNT_CHECK_LAUNCH();
+  const unsigned grid = dense_grid(ncell);
+  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
   if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
   hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
   RNNT_CHECK_LAUNCH();
@@ -973,4 +1172,52 @@ extern "C" int rnnt_hip_loss_from_logits_fwd_bwd(const float* logits, const int3
                                                  size_t workspace_bytes, void* stream) {
   return rnnt_hip_loss_from_logits_fwd_bwd_ex(logits, RNNT_DTYPE_F32, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nll, grad,
                                               workspace, workspace_bytes, stream);
+}
+
+/* ---- forced alignment (include/rnnt_hip.h): lse kernels of the loss, max-plus sweep, back-trace ---- */
+extern "C" size_t rnnt_hip_joint_align_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
+  if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
+  return carve_align(nullptr, B, T, U1).total;
+}
+
+extern "C" int rnnt_hip_joint_align(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                    const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                    int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, int32_t* frames, double* score,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_align(labels, t_lens, u_lens, B, T, U1, V, blank, frames, score)) return rc;
+  RNNT_CHECK_ARG(A && C && bias, "joint_align: null A/C/bias");
+  const AlignWs w = carve_align(workspace, B, T, U1);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_align: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
+  return launch_viterbi(w, t_lens, u_lens, B, T, U1, frames, score, s);
+}
+
+template <typename TZ>
+static int align_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
+                                  int32_t T, int32_t U1, int32_t V, int32_t blank, int32_t* frames, double* score, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  if (int rc = check_align(labels, t_lens, u_lens, B, T, U1, V, blank, frames, score)) return rc;
+  RNNT_CHECK_ARG(logits, "align_from_logits: null logits");
+  const AlignWs w = carve_align(workspace, B, T, U1);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "align_from_logits: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
+  return launch_viterbi(w, t_lens, u_lens, B, T, U1, frames, score, s);
+}
+
+extern "C" int rnnt_hip_align_from_logits_ex(const void* logits, int32_t dtype, const int32_t* labels, const int32_t* t_lens,
+                                             const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                             int32_t* frames, double* score, void* workspace, size_t workspace_bytes, void* stream) {
+  switch (dtype) {
+    case RNNT_DTYPE_F32:
+      return align_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
+    case RNNT_DTYPE_F16:
+      return align_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
+    case RNNT_DTYPE_BF16:
+      return align_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
+    default:
+      set_error("align_from_logits: unknown dtype code %d", dtype);
+      return RNNT_ERR_INVALID;
+  }
 }

@@ -7,7 +7,7 @@ difference), or (B,) for reduction="none".
 import torch
 import torch.nn as nn
 
-from .ops import RnntLossFromLogitsFn
+from .ops import Alignment, RnntLossFromLogitsFn, align_from_logits
 
 
 class RNNTLoss(nn.Module):
@@ -27,3 +27,14 @@ class RNNTLoss(nn.Module):
         if self.reduction == "sum":
             return nll.sum()
         return nll
+
+
+@torch.no_grad()
+def rnnt_align(logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor, target_lengths: torch.Tensor,
+               blank: int = 0) -> Alignment:
+    """Forced alignment on dense logits (B, T, U+1, V), arguments as RNNTLoss.forward: the best path of `targets` per utterance.
+    Returns an ops.Alignment (`frames` (B,U) int32: the frame at which each label is emitted, -1 past target_lengths[b];
+    `score` (B,) float64: the path's log-probability; `token_frames(b)`).  On exactly equal candidates blank wins."""
+    if logits.dim() != 4:
+        raise ValueError("logits must be (B, T, U+1, V)")
+    return align_from_logits(logits, targets, logit_lengths, target_lengths, blank)

@@ -120,6 +120,13 @@ class RNNTransducer(_Base):
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}
 
+    def align(self, batch):
+        """JointNet.align on the 7-tuple batch of training_step with this model's blank: per utterance the frame at which each
+        label of the transcript is emitted on the best path, and that path's score (ops.Alignment)."""
+        input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
+        return self.jointnet.align(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
+                                   audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None)
+
     def init_stream(self, batch_size: int, device=None):
         """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
         return self.jointnet.init_stream(batch_size, self.blank_token_id, device)

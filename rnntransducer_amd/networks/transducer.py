@@ -15,6 +15,8 @@ prefix tree for y_star; LM and hotword rescoring (pyctcdecode / KenLM) stay out 
 prediction-net and search state carried between chunks (rnntransducer_amd/streaming.py, csrc/stream.hip).
 `init_beam_stream` / `recognize_beams_stream` do the same for the beam search: the whole hypothesis set is carried on the device
 (csrc/beam_stream.hip, the offline kernel's frame loop), with the stable prefix of every stream exposed after each chunk.
+`align` returns the best path of a known transcript (the frame at which every label is emitted, and the path's score) from the
+fused loss's per-cell terms: the loss's lattice sweep in the (max, +) semiring (csrc/loss.hip).
 """
 import torch
 import torch.nn as nn
@@ -92,6 +94,44 @@ class JointNet(nn.Module):
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
         out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction)
         return out if inv is None else out.index_select(0, inv)
+
+    @torch.no_grad()
+    def align(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, audio_lengths=None):
+        """Forced alignment: the best RNN-T path of the KNOWN transcript `targets` per utterance (csrc/loss.hip: the loss's
+        log-softmax kernels, then its lattice sweep in the (max, +) semiring with one back-pointer bit per cell; no (B,T,U+1,V)
+        tensor).  Arguments as `loss`, with the same ragged handling under `audio_lengths` (results come back in the caller's row
+        order).  Returns an ops.Alignment: `frames` (B,U) int32 — the frame at which each label is emitted, -1 past
+        target_lengths[b] —, `score` (B,) float64 — the log-probability of that path, <= -loss —, and `token_frames(b)`, the
+        un-padded list of one utterance after one host copy.  Frames count encoder output frames.  On exactly equal candidates
+        the path stays on a frame (blank) rather than emit.  eval() mode only, like recognize_greedy."""
+        from ..ops import Alignment, _joint_ac, _need_gpu, joint_align
+        if self.training:
+            raise RuntimeError("align expects eval() mode (dropout inactive), like recognize_greedy")
+        _need_gpu(input_audios, input_texts, targets)
+        dev = input_audios.device
+        t_lens = lengths_to_device(tensor_audio_lengths, dev)
+        u_lens = lengths_to_device(target_lengths, dev)
+        enc_lens, inv = t_lens, None
+        T, B = input_audios.size(1), input_audios.size(0)
+        if audio_lengths is not None and len(audio_lengths) == B and B > 1 and min(audio_lengths) < T:
+            from ..ops import RaggedPlan
+            host = [int(n) for n in audio_lengths]
+            order = sorted(range(B), key=lambda b: (-host[b], b))
+            if order != list(range(B)):   # length-sorted rows, as in loss(); frames and scores are un-sorted below
+                perm = torch.tensor(order, dtype=torch.int64, device=dev)
+                input_audios, input_texts, targets = (x.index_select(0, perm) for x in (input_audios, input_texts, targets))
+                t_lens, u_lens = t_lens.index_select(0, perm), u_lens.index_select(0, perm)
+                host = [host[b] for b in order]
+                inv = torch.empty_like(perm)
+                inv[perm] = torch.arange(B, dtype=torch.int64, device=dev)
+            enc_lens = RaggedPlan(host, T, dev)
+        enc = self.encoder.forward_time_major(input_audios, enc_lens)
+        dec = self.decoder.forward_time_major(input_texts, u_lens + 1)
+        A, Cm = _joint_ac(enc, dec, self.fc.weight, self.enc_out, self.dec_out, self.num_classes)
+        res = joint_align(A, Cm, self.fc.bias, targets, t_lens, u_lens, blank)
+        if inv is None:
+            return res
+        return Alignment(res.frames.index_select(0, inv), res.score.index_select(0, inv), u_lens.index_select(0, inv))
 
     @torch.no_grad()
     def recognize_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, max_iters: int = 3,

@@ -758,6 +758,99 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------------------
+# forced alignment (include/rnnt_hip.h: rnnt_hip_joint_align / rnnt_hip_align_from_logits_ex): best path of a known transcript
+# --------------------------------------------------------------------------------------------------
+class Alignment:
+    """Result of an alignment call, on the device: `frames` (B,U) int32 — frames[b, u] = the frame at which label u of
+    utterance b is emitted on the best path, -1 for u >= target_lengths[b] — and `score` (B,) float64, the log-probability of
+    that path (-inf, frames -1, for an utterance without frames).  Nothing here has synchronised with the host yet;
+    `token_frames(b)` does, once, for the whole batch."""
+
+    def __init__(self, frames: torch.Tensor, score: torch.Tensor, u_lens: torch.Tensor):
+        self.frames, self.score, self.target_lengths = frames, score, u_lens
+        self._host = None
+
+    def token_frames(self, b: int) -> List[int]:
+        """The un-padded list of emission frames of utterance b (one host copy of the batch on first use)."""
+        if self._host is None:
+            self._host = (self.frames.tolist(), self.target_lengths.tolist())
+        rows, n = self._host
+        return rows[b][:n[b]]
+
+
+def _align_buffers(B, U1, device, frames, score):
+    frames = torch.empty(B, U1 - 1, device=device, dtype=torch.int32) if frames is None else frames
+    score = torch.empty(B, device=device, dtype=torch.float64) if score is None else score
+    _check_buffer("frames", frames, (B, U1 - 1), torch.int32, device)
+    _check_buffer("score", score, (B,), torch.float64, device)
+    return frames, score
+
+
+def _align_lengths(labels, t_lens, u_lens, B, U1):
+    for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32, got {t.dtype}")
+    if labels.shape != (B, U1 - 1) or t_lens.shape != (B,) or u_lens.shape != (B,):
+        raise ValueError(f"targets must be (B, U) = ({B}, {U1 - 1}) and both lengths (B,), got {tuple(labels.shape)}, "
+                         f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
+    return labels.contiguous(), t_lens.contiguous(), u_lens.contiguous()
+
+
+def align_workspace_bytes(B: int, T: int, U1: int, V: int) -> int:
+    n = _lib.lib().rnnt_hip_joint_align_workspace_bytes(B, T, U1, V)
+    if n == 0:
+        raise ValueError(f"alignment: dims must be positive (B={B} T={T} U1={U1} V={V})")
+    return n
+
+
+def joint_align(A: torch.Tensor, Cm: torch.Tensor, bias: torch.Tensor, labels: torch.Tensor, t_lens: torch.Tensor,
+                u_lens: torch.Tensor, blank: int, *, batch_first: bool = False, workspace: Optional[torch.Tensor] = None,
+                frames: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None) -> Alignment:
+    """Best RNN-T path per utterance for logits[b,t,u,:] = A[b,t,:] + C[b,u,:] + bias, never built.  A (T,B,V) and Cm (U1,B,V)
+    time-major as the joint's pre-GEMMs leave them (batch_first=True: (B,T,V) and (B,U1,V)), fp32 contiguous; labels (B,U),
+    t_lens, u_lens int32.  `workspace` (uint8, >= align_workspace_bytes), `frames`, `score`: the caller's buffers, allocated
+    here when None.  No host synchronisation."""
+    _need_gpu(A, Cm, bias, labels, t_lens, u_lens, workspace, frames, score)
+    A, Cm, bias = _f32c(A, "A"), _f32c(Cm, "C"), _f32c(bias, "bias")
+    if A.dim() != 3 or Cm.dim() != 3:
+        raise ValueError("joint_align takes A (T,B,V) and C (U1,B,V) (or batch-first with batch_first=True)")
+    (B, T, V), U1 = (A.shape, Cm.shape[1]) if batch_first else ((A.shape[1], A.shape[0], A.shape[2]), Cm.shape[0])
+    if Cm.shape != ((B, U1, V) if batch_first else (U1, B, V)) or bias.shape != (V,):
+        raise ValueError(f"shape mismatch: A {tuple(A.shape)} C {tuple(Cm.shape)} bias {tuple(bias.shape)}")
+    labels, t_lens, u_lens = _align_lengths(labels, t_lens, u_lens, B, U1)
+    frames, score = _align_buffers(B, U1, A.device, frames, score)
+    nws = align_workspace_bytes(B, T, U1, V)
+    ws = torch.empty(nws, device=A.device, dtype=torch.uint8) if workspace is None else workspace
+    a_sb, a_st, c_sb, c_su = (T * V, V, U1 * V, V) if batch_first else (V, B * V, V, B * V)
+    check(_lib.lib().rnnt_hip_joint_align(_addr(A), a_sb, a_st, _addr(Cm), c_sb, c_su, _addr(bias), _addr(labels), _addr(t_lens),
+                                          _addr(u_lens), B, T, U1, V, int(blank), _addr(frames), _addr(score), _addr(ws),
+                                          ws.numel() * ws.element_size(), _stream()), "rnnt_hip_joint_align")
+    return Alignment(frames, score, u_lens)
+
+
+def align_from_logits(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.Tensor, u_lens: torch.Tensor, blank: int, *,
+                      workspace: Optional[torch.Tensor] = None, frames: Optional[torch.Tensor] = None,
+                      score: Optional[torch.Tensor] = None) -> Alignment:
+    """joint_align for dense logits (B,T,U1,V) in float32, float16 or bfloat16 (arithmetic fp32 / fp64 whatever the storage)."""
+    _need_gpu(logits, labels, t_lens, u_lens, workspace, frames, score)
+    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    if logits.dtype not in codes:
+        raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    if logits.dim() != 4:
+        raise ValueError("logits must be (B, T, U+1, V)")
+    logits = logits if logits.is_contiguous() else logits.contiguous()
+    B, T, U1, V = logits.shape
+    labels, t_lens, u_lens = _align_lengths(labels, t_lens, u_lens, B, U1)
+    frames, score = _align_buffers(B, U1, logits.device, frames, score)
+    nws = align_workspace_bytes(B, T, U1, V)
+    ws = torch.empty(nws, device=logits.device, dtype=torch.uint8) if workspace is None else workspace
+    check(_lib.lib().rnnt_hip_align_from_logits_ex(_addr(logits), codes[logits.dtype], _addr(labels), _addr(t_lens), _addr(u_lens),
+                                                   B, T, U1, V, int(blank), _addr(frames), _addr(score), _addr(ws),
+                                                   ws.numel() * ws.element_size(), _stream()), "rnnt_hip_align_from_logits_ex")
+    return Alignment(frames, score, u_lens)
+
+
+# --------------------------------------------------------------------------------------------------
 # greedy decoding (replaces the host loop of transducer.py:95-145)
 # --------------------------------------------------------------------------------------------------
 def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
