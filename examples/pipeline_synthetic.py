@@ -75,6 +75,12 @@ def main(argv=None):
     ep = model.validation_epoch_end([out])
     print(f"loss {first:.3f} -> {loss.item():.3f} after {a.steps} steps; validation loss {ep['val_loss'].item():.3f}, "
           f"token error rate {ep['val_ter'].item():.3f}")
+    # where the recognised tokens of the first utterance are, in seconds, and how sure the model was of each
+    n0 = int(batch[2][0])
+    timed = model.eval().jointnet.recognize_greedy(batch[0][:1, :n0], batch[2][:1], 0, 3, return_timing=True)
+    secs = frontend.frame_seconds(timed.frames).tolist()
+    print("utterance 0: " + " ".join(f"{k}@{t:.2f}s(p={math.exp(lp):.2f})"
+                                       for k, t, lp in zip(timed.tokens.tolist(), secs, timed.logp.tolist())))
     return first, loss.item(), ep
 
 

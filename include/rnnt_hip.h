@@ -594,7 +594,7 @@ int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, const int32_t
  *
  * The workspace IS the carried state.  It starts with the layer-0 input table (V, G*Hp) (built by the reset entry when
  * build_table != 0: the weights must not change while a state is open), followed per stream by a 256-byte header of int32
- * { len(B), state slots in use, prefix nodes in use, committed length, RNNT_BEAM_ST_* status }, the A and B entries, the state
+ * { len(B), state slots in use, prefix nodes in use, committed length, RNNT_BEAM_ST_* status, frames consumed }, the A and B entries, the state
  * slots, the slot remap table, the prefix nodes and a node remap table.
  *
  * Chunk call, one workgroup per stream, one launch: load the header; run frames t < lens[b] of A (from
@@ -644,6 +644,46 @@ size_t rnnt_hip_beam_stream_workspace_bytes(const rnnt_beam_stream_desc* d);  /*
 int rnnt_hip_beam_stream_reset(const rnnt_beam_stream_desc* d, const int32_t* rows, int32_t n_rows, int32_t build_table,
                                void* stream);
 int rnnt_hip_beam_stream_chunk(const rnnt_beam_stream_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Token timestamps and confidences: what the four searches know at the moment they emit.  Each *_timed entry takes the
+ * descriptor of its untimed entry (unchanged layout) plus a small struct of extra outputs, runs the SAME kernel (the extra
+ * pointers are null in the untimed launch and are the only switch) and returns, besides, bitwise what the untimed entry
+ * returns.  A null struct or a null output pointer is RNNT_ERR_INVALID.
+ *
+ * Greedy (rnnt_hip_greedy_decode_timed, rnnt_hip_stream_greedy_timed): for every token that is APPENDED (entry i of tokens[b])
+ *   frames[b,i] = the encoder frame t at which it was chosen;
+ *   logp[b,i]   = the log-softmax of the joint at that evaluation, at the chosen token: z[tok] - lse_v(z), z[v] = A[t,b,v] + C[v].
+ * A symbol equal to the last appended one advances the prediction net without being appended and gets no entry.  Entries
+ * past max_out are dropped exactly as tokens are.  The reduction behind lse is fp32 in an order fixed by (thread, lane, wave)
+ * alone (a strided pass per thread, a wave butterfly, the waves in order): it depends neither on B, T nor on chunk
+ * boundaries, and it runs only when a token is appended, never per blank evaluation.  Streaming: frames are absolute,
+ * frame_base[b] + t with frame_base (B) int64 on the device = the frames stream b consumed since its last reset BEFORE this
+ * chunk (NULL: 0); the offline entry ignores frame_base.  Frames are int32 (the low 32 bits of frame_base[b] + t): a stream
+ * must be reset before it has consumed 2^31 frames.
+ *
+ * Beam (rnnt_hip_beam_search_timed, rnnt_hip_beam_stream_chunk_timed): every prefix-tree node carries the frame at which it
+ * was created (the pop that materialises its token; -1 for the leading blank), so frames (B, beam, max_len) is aligned with
+ * tokens: the frame at which each token of that y_star was appended.  Streaming: node frames are absolute (the stream's
+ * consumed-frame count is one more int32 of the workspace header, zeroed by the reset entry and advanced by every chunk,
+ * timed or not); frames holds the tail's frames beside the tail's tokens and commit_frames (B, max_nodes) the committed
+ * tokens' frames beside commit.  Collection and compaction move the frame with its node.  No per-token confidence here: a
+ * hypothesis has its score.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_greedy_timing {
+  int32_t* frames;           /* (B,max_out) */
+  float* logp;               /* (B,max_out) */
+  const int64_t* frame_base; /* (B) device or NULL; streaming only */
+} rnnt_greedy_timing;
+int rnnt_hip_greedy_decode_timed(const rnnt_decode_desc* d, const rnnt_greedy_timing* timing, void* stream);
+int rnnt_hip_stream_greedy_timed(const rnnt_stream_greedy_desc* d, const rnnt_greedy_timing* timing, void* stream);
+
+typedef struct rnnt_beam_timing {
+  int32_t* frames;        /* (B, beam, max_len) beside tokens */
+  int32_t* commit_frames; /* (B, max_nodes) beside commit; streaming only */
+} rnnt_beam_timing;
+int rnnt_hip_beam_search_timed(const rnnt_beam_desc* d, const rnnt_beam_timing* timing, void* stream);
+int rnnt_hip_beam_stream_chunk_timed(const rnnt_beam_stream_desc* d, const rnnt_beam_timing* timing, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).

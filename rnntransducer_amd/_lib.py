@@ -125,6 +125,14 @@ class BeamStreamDesc(C.Structure):
                 ("ncommit", C.c_void_p), ("stats", C.c_void_p)]
 
 
+class GreedyTiming(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("logp", C.c_void_p), ("frame_base", C.c_void_p)]
+
+
+class BeamTiming(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("commit_frames", C.c_void_p)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -198,6 +206,10 @@ SYMBOLS = {
     "rnnt_hip_beam_stream_workspace_bytes": (C.c_size_t, [C.POINTER(BeamStreamDesc)]),
     "rnnt_hip_beam_stream_reset": (C.c_int, [C.POINTER(BeamStreamDesc), C.c_void_p, c_i32, c_i32, C.c_void_p]),
     "rnnt_hip_beam_stream_chunk": (C.c_int, [C.POINTER(BeamStreamDesc), C.c_void_p]),
+    "rnnt_hip_greedy_decode_timed": (C.c_int, [C.POINTER(DecodeDesc), C.POINTER(GreedyTiming), C.c_void_p]),
+    "rnnt_hip_stream_greedy_timed": (C.c_int, [C.POINTER(StreamGreedyDesc), C.POINTER(GreedyTiming), C.c_void_p]),
+    "rnnt_hip_beam_search_timed": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_stream_chunk_timed": (C.c_int, [C.POINTER(BeamStreamDesc), C.POINTER(BeamTiming), C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
 }

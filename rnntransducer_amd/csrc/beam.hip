@@ -31,7 +31,8 @@ extern "C" size_t rnnt_hip_beam_workspace_bytes(const rnnt_beam_desc* d) {
   return l.table_bytes + l.stride * (size_t)d->B;
 }
 
-extern "C" int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream) {
+// both entries: `timing` null = the untimed search (the kernel's frames pointer is null, nothing else differs)
+static int beam_search_launch(const rnnt_beam_desc* d, const rnnt_beam_timing* timing, void* stream) {
   int rc = beam_check_dims(d, "beam_search", 1);
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->A && d->lens, "beam_search: null pointer");
@@ -39,6 +40,7 @@ extern "C" int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream) {
   if ((rc = beam_fill_common(d, k, "beam_search")) != RNNT_OK) return rc;
   k.t_lens = d->t_lens;
   k.lens = d->lens;
+  k.frames = timing ? timing->frames : nullptr;
   const BeamLayout l = beam_layout(d);
   RNNT_CHECK_ARG(d->workspace && (reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0 &&
                  d->workspace_bytes >= l.table_bytes + l.stride * (size_t)d->B,
@@ -54,4 +56,11 @@ extern "C" int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream) {
   hipLaunchKernelGGL(beam_search_kernel<false>, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_beam_search(const rnnt_beam_desc* d, void* stream) { return beam_search_launch(d, nullptr, stream); }
+
+extern "C" int rnnt_hip_beam_search_timed(const rnnt_beam_desc* d, const rnnt_beam_timing* timing, void* stream) {
+  RNNT_CHECK_ARG(timing != nullptr && timing->frames, "beam_search_timed: null timing output (frames)");
+  return beam_search_launch(d, timing, stream);
 }

@@ -21,7 +21,7 @@ struct Hyp {       // an A or B entry (32 bytes)
 };
 
 // per-stream header of the streaming workspace (ints at the start of a stream's workspace; STREAM only)
-enum { BS_NB = 0, BS_NSLOTS = 1, BS_NNODES = 2, BS_ROOT_LEN = 3, BS_STATUS = 4, BS_HEADER_BYTES = 256 };
+enum { BS_NB = 0, BS_NSLOTS = 1, BS_NNODES = 2, BS_ROOT_LEN = 3, BS_STATUS = 4, BS_FRAMES = 5, BS_HEADER_BYTES = 256 };
 
 struct BeamK {
   int T, B, V, Hp, O, L, cell, blank, beam, improved;
@@ -51,6 +51,9 @@ struct BeamK {
   int* commit;         // STREAM: (B, max_nodes) tokens committed by this chunk's collection
   int* ncommit;        // STREAM: (B)
   const int* rows;     // stream reset: the rows to seed
+  int* frames;         // timed entries: (B, beam, max_len) frame at which each y_star token was appended (-1: the leading
+                       // blank), beside `tokens`; null otherwise
+  int* commit_frames;  // STREAM, timed entry: (B, max_nodes) beside `commit`; null otherwise
 };
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -125,7 +128,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
   Hyp* bents = reinterpret_cast<Hyp*>(ws + p.off_b);
   float* slots = reinterpret_cast<float*>(ws + p.off_slots);
   int* remap = reinterpret_cast<int*>(ws + p.off_remap);
-  int4* nodes = reinterpret_cast<int4*>(ws + p.off_nodes);  // (parent, token, len, -)
+  int4* nodes = reinterpret_cast<int4*>(ws + p.off_nodes);  // (parent, token, len, frame of creation: -1 for [blank])
   int* hdr = reinterpret_cast<int*>(ws);                    // STREAM only
   const int SF = p.slot_floats;
 
@@ -189,6 +192,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
 
   int nB, nslots, nnodes;
   int root_len = 0;   // STREAM: tokens committed so far = length of the root's y_star; offline the root is written out too
+  int t_base = 0;     // STREAM: frames the stream consumed before this chunk (node frames are absolute)
   int Tb = p.t_lens ? p.t_lens[b] : p.T;
   Tb = Tb < 0 ? 0 : (Tb > p.T ? p.T : Tb);
   if constexpr (STREAM) {
@@ -201,10 +205,11 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
     __syncthreads();
     if (st != RNNT_BEAM_ST_OK) { fail(st); return; }
     nB = hdr[BS_NB]; nslots = hdr[BS_NSLOTS]; nnodes = hdr[BS_NNODES]; root_len = hdr[BS_ROOT_LEN];
+    t_base = hdr[BS_FRAMES];
   } else {
     // y_star = [blank], state None (transducer.py:276-284)
     if (tid == 0) {
-      nodes[0] = make_int4(-1, p.blank, 1, 0);
+      nodes[0] = make_int4(-1, p.blank, 1, -1);
       Hyp r0;
       r0.score = 0.0; r0.node = 0; r0.tok = -1; r0.state = -1; r0.memo = -1; r0.live = 1; r0.pad = 0;
       bents[0] = r0;
@@ -276,7 +281,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       if (a.tok >= 0) {
         if (nnodes >= p.max_nodes) { fail(RNNT_BEAM_ST_NODES); return; }
         const int len = nodes[a.node].z + 1;
-        if (tid == 0) nodes[nnodes] = make_int4(a.node, a.tok, len, 0);
+        if (tid == 0) nodes[nnodes] = make_int4(a.node, a.tok, len, t_base + t);
         node = nnodes++;
         last = a.tok;
       } else {
@@ -392,10 +397,12 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       const int lenR = nodes[R].z, nnew = lenR - root_len;
       if (tid == 0) {
         int* out = p.commit + (long)b * p.max_nodes;   // nnew < nnodes <= max_nodes
+        int* outf = p.commit_frames ? p.commit_frames + (long)b * p.max_nodes : nullptr;
         int n = R;
         for (int j = nnew - 1; j >= 0; --j) {
           const int4 nd = nodes[n];
           out[j] = nd.y;
+          if (outf) outf[j] = nd.w;
           n = nd.x;
         }
         p.ncommit[b] = nnew;
@@ -449,10 +456,12 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
     if (tid == 0) {
       bents[ib].live = 0;
       int* out = p.tokens + ((long)b * p.beam + r) * p.max_len;
+      int* outf = p.frames ? p.frames + ((long)b * p.beam + r) * p.max_len : nullptr;
       int n = e.node;
       for (int j = len - 1; j >= root_len; --j) {  // offline: len steps, the root has length 1; STREAM: the tail below the root
         const int4 nd = nodes[n];
         out[j - root_len] = nd.y;
+        if (outf) outf[j - root_len] = nd.w;
         n = nd.x;
       }
       p.lens[(long)b * p.beam + r] = len - root_len;
@@ -471,6 +480,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
     }
     if constexpr (STREAM) {
       hdr[BS_NB] = nB; hdr[BS_NSLOTS] = nslots; hdr[BS_NNODES] = nnodes; hdr[BS_ROOT_LEN] = root_len;
+      hdr[BS_FRAMES] = t_base + Tb;
     }
   }
 }
@@ -493,7 +503,7 @@ static int beam_fill_common(const D* d, BeamK& k, const char* who) {
   }
   k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
   k.tokens = d->tokens; k.scores = d->scores; k.count = d->count; k.status = d->status; k.stats = d->stats;
-  k.commit = nullptr; k.ncommit = nullptr; k.rows = nullptr;
+  k.commit = nullptr; k.ncommit = nullptr; k.rows = nullptr; k.frames = nullptr; k.commit_frames = nullptr;
   return RNNT_OK;
 }
 

@@ -9,7 +9,8 @@
 namespace rnnt {
 namespace {
 
-// rows[blockIdx.x] starts a new utterance: y_star = [blank], state None (transducer.py:276-284), committed = [blank]
+// rows[blockIdx.x] starts a new utterance: y_star = [blank], state None (transducer.py:276-284), committed = [blank], no
+// frames consumed (header word BS_FRAMES = 0)
 __global__ void __launch_bounds__(64) beam_stream_reset_kernel(const BeamK p) {
   const int b = p.rows[blockIdx.x];
   if (b < 0 || b >= p.B) return;
@@ -18,7 +19,7 @@ __global__ void __launch_bounds__(64) beam_stream_reset_kernel(const BeamK p) {
   const int i = threadIdx.x;
   if (i < BS_HEADER_BYTES / 4) hdr[i] = i == BS_NB || i == BS_NNODES || i == BS_ROOT_LEN ? 1 : 0;
   if (i == 0) {
-    reinterpret_cast<int4*>(ws + p.off_nodes)[0] = make_int4(-1, p.blank, 1, 0);
+    reinterpret_cast<int4*>(ws + p.off_nodes)[0] = make_int4(-1, p.blank, 1, -1);
     Hyp r0;
     r0.score = 0.0; r0.node = 0; r0.tok = -1; r0.state = -1; r0.memo = -1; r0.live = 1; r0.pad = 0;
     reinterpret_cast<Hyp*>(ws + p.off_b)[0] = r0;
@@ -75,10 +76,12 @@ extern "C" int rnnt_hip_beam_stream_reset(const rnnt_beam_stream_desc* d, const 
   return RNNT_OK;
 }
 
-extern "C" int rnnt_hip_beam_stream_chunk(const rnnt_beam_stream_desc* d, void* stream) {
+// both entries: `timing` null = the untimed search (the kernel's two frame pointers are null, nothing else differs)
+static int beam_stream_chunk_launch(const rnnt_beam_stream_desc* d, const rnnt_beam_timing* timing, void* stream) {
   BeamK k;
   const int rc = stream_fill(d, k, "beam_stream_chunk");
   if (rc != RNNT_OK) return rc;
+  if (timing) { k.frames = timing->frames; k.commit_frames = timing->commit_frames; }
   RNNT_CHECK_ARG(d->T >= 1 && d->A && d->lens, "beam_stream_chunk: needs T >= 1 frames, A and lens");
   const size_t lds = beam_lds_bytes(d->L, d->Hp, d->O, d->V);
   if (lds > 64 * 1024)
@@ -87,4 +90,14 @@ extern "C" int rnnt_hip_beam_stream_chunk(const rnnt_beam_stream_desc* d, void* 
   hipLaunchKernelGGL(beam_search_kernel<true>, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_beam_stream_chunk(const rnnt_beam_stream_desc* d, void* stream) {
+  return beam_stream_chunk_launch(d, nullptr, stream);
+}
+
+extern "C" int rnnt_hip_beam_stream_chunk_timed(const rnnt_beam_stream_desc* d, const rnnt_beam_timing* timing, void* stream) {
+  RNNT_CHECK_ARG(timing != nullptr && timing->frames && timing->commit_frames,
+                 "beam_stream_chunk_timed: null timing outputs (frames, commit_frames)");
+  return beam_stream_chunk_launch(d, timing, stream);
 }

@@ -33,6 +33,8 @@ struct DecodeK {
   long ld_d;
   long long* tokens;  // (B, max_out)
   int* ntok;          // (B)
+  int* frames;        // (B, max_out) frame of each appended token, or null (the untimed entry)
+  float* logp;        // (B, max_out) log-softmax of the joint at the appended token; with frames
 };
 
 // dynamic LDS: h[L][Hp] | c[L][Hp] | gi[4Hp] | gh[4Hp] | x[Hp] | dec[O] | Cv[V] | red (2 * 16 floats/ints) | ctl[4]
@@ -102,6 +104,13 @@ __global__ void __launch_bounds__(DEC_THREADS) greedy_decode_kernel(const Decode
       const int tok = frame_argmax(t);
       if (tok == p.blank) break;
       if (last != tok) {
+        if (p.frames && n < p.max_out) {  // timed entry: one more V-wide reduction per appended token
+          const float lp = token_logp(p.A + ((long)t * p.B + b) * V, Cv, V, tok, redv);
+          if (tid == 0) {
+            p.frames[(long)b * p.max_out + n] = t;
+            p.logp[(long)b * p.max_out + n] = lp;
+          }
+        }
         if (n < p.max_out && tid == 0) p.tokens[(long)b * p.max_out + n] = tok;
         ++n;
         last = tok;
@@ -159,7 +168,8 @@ __global__ void __launch_bounds__(DEC_THREADS) prednet_step_kernel(const StepK p
 
 using namespace rnnt;
 
-extern "C" int rnnt_hip_greedy_decode(const rnnt_decode_desc* d, void* stream) {
+// both entries: `timing` null = the untimed search (the kernel's frames pointer is null, nothing else differs)
+static int greedy_decode_launch(const rnnt_decode_desc* d, const rnnt_greedy_timing* timing, void* stream) {
   RNNT_CHECK_ARG(d != nullptr, "greedy_decode: null descriptor");
   RNNT_CHECK_ARG(d->T >= 1 && d->B >= 1 && d->V >= 1 && d->Hp >= 4 && d->Hp % 4 == 0 && d->O >= 4 && d->O % 4 == 0,
                  "greedy_decode: bad dims (hidden and output sizes must be multiples of 4)");
@@ -178,6 +188,8 @@ extern "C" int rnnt_hip_greedy_decode(const rnnt_decode_desc* d, void* stream) {
   }
   k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
   k.tokens = (long long*)d->tokens; k.ntok = d->ntok;
+  k.frames = timing ? timing->frames : nullptr;
+  k.logp = timing ? timing->logp : nullptr;
   const size_t lds = ((size_t)2 * d->L * d->Hp + 8 * d->Hp + d->Hp + d->O + d->V + 32 + 8) * 4;
   RNNT_CHECK_ARG(lds <= 160 * 1024, "greedy_decode: state needs %zu B of LDS (> 160 KiB)", lds);
   if (lds > 64 * 1024)
@@ -186,6 +198,13 @@ extern "C" int rnnt_hip_greedy_decode(const rnnt_decode_desc* d, void* stream) {
   hipLaunchKernelGGL(greedy_decode_kernel, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_greedy_decode(const rnnt_decode_desc* d, void* stream) { return greedy_decode_launch(d, nullptr, stream); }
+
+extern "C" int rnnt_hip_greedy_decode_timed(const rnnt_decode_desc* d, const rnnt_greedy_timing* timing, void* stream) {
+  RNNT_CHECK_ARG(timing != nullptr && timing->frames && timing->logp, "greedy_decode_timed: null timing outputs (frames, logp)");
+  return greedy_decode_launch(d, timing, stream);
 }
 
 extern "C" int rnnt_hip_prednet_step(const rnnt_prednet_step_desc* d, void* stream) {

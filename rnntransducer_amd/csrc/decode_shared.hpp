@@ -96,4 +96,24 @@ __device__ __forceinline__ void prednet_joint_half(const P& p, const float* h_la
   __syncthreads();
 }
 
+// log-softmax of one joint evaluation at the token the argmax chose: z[tok] - lse_v(z) with z[v] = a[v] + Cv[v], fp32.  tok is
+// the argmax, so z[tok] is the maximum and lse = z[tok] + log(sum_v exp(z[v] - z[tok])): one V-wide reduction.  Its order is
+// fixed by (tid, lane, wave) alone: a strided pass per thread, the wave butterfly (a + b == b + a: every lane holds the same
+// sum), then the waves in order; nothing depends on B, T or a chunk boundary.  All threads call it; red is DEC_THREADS / 64
+// floats of LDS nobody reads at the call; every thread returns the value.  Ends with a barrier.
+__device__ __forceinline__ float token_logp(const float* __restrict__ a, const float* __restrict__ Cv, int V, int tok, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float zt = a[tok] + Cv[tok];
+  float s = 0.f;
+  for (int v = tid; v < V; v += DEC_THREADS) s += expf((a[v] + Cv[v]) - zt);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  float r = red[0];
+  for (int w = 1; w < DEC_THREADS / 64; ++w) r += red[w];
+  __syncthreads();
+  return -logf(r);
+}
+
 }  // namespace rnnt

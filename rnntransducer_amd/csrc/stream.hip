@@ -268,6 +268,9 @@ struct StreamGreedyK {
   long long* last;   // (B)
   long long* tokens; // (B,max_out)
   int* ntok;         // (B)
+  int* frames;       // (B,max_out) absolute frame of each appended token, or null (the untimed entry)
+  float* logp;       // (B,max_out) with frames
+  const long long* frame_base;  // (B) frames the stream consumed before this chunk, or null (0)
 };
 
 // dynamic LDS as greedy_decode_kernel: h[L][Hp] | c[L][Hp] | gi[4Hp] | gh[4Hp] | x[Hp] | dec[O] | Cv[V] | red | ctl
@@ -365,11 +368,19 @@ __global__ void __launch_bounds__(DEC_THREADS) stream_greedy_kernel(const Stream
 
   int n = 0;
   long long last = p.last[b];
+  const int t_base = p.frames && p.frame_base ? (int)p.frame_base[b] : 0;   // frames are int32: reset before 2^31 frames
   for (int t = 0; t < Tb; ++t) {
     for (int u = 0; u < p.max_iters; ++u) {
       const int tok = frame_argmax(t);
       if (tok == p.blank) break;
       if (last != tok) {
+        if (p.frames && n < p.max_out) {  // timed entry (as greedy_decode_kernel)
+          const float lp = token_logp(p.A + ((long)t * p.B + b) * V, s.Cv, V, tok, s.redv);
+          if (tid == 0) {
+            p.frames[(long)b * p.max_out + n] = t_base + t;
+            p.logp[(long)b * p.max_out + n] = lp;
+          }
+        }
         if (n < p.max_out && tid == 0) p.tokens[(long)b * p.max_out + n] = tok;
         ++n;
         last = tok;
@@ -439,6 +450,7 @@ int fill_greedy(const rnnt_stream_greedy_desc* d, StreamGreedyK& k, const char* 
   k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
   k.h = d->h; k.c = d->c; k.Cs = d->C; k.last = (long long*)d->last;
   k.tokens = (long long*)d->tokens; k.ntok = d->ntok;
+  k.frames = nullptr; k.logp = nullptr; k.frame_base = nullptr;
   return RNNT_OK;
 }
 
@@ -530,11 +542,13 @@ extern "C" int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, co
   return RNNT_OK;
 }
 
-extern "C" int rnnt_hip_stream_greedy(const rnnt_stream_greedy_desc* d, void* stream) {
+// both entries: `timing` null = the untimed search (the kernel's frames pointer is null, nothing else differs)
+static int stream_greedy_launch(const rnnt_stream_greedy_desc* d, const rnnt_greedy_timing* timing, void* stream) {
   RNNT_CHECK_ARG(d != nullptr, "stream_greedy: null descriptor");
   StreamGreedyK k;
   const int rc = fill_greedy(d, k, "stream_greedy");
   if (rc != RNNT_OK) return rc;
+  if (timing) { k.frames = timing->frames; k.logp = timing->logp; k.frame_base = (const long long*)timing->frame_base; }
   RNNT_CHECK_ARG(d->T >= 1 && d->max_iters >= 1 && d->max_out >= 1, "stream_greedy: bad T / max_iters / max_out");
   RNNT_CHECK_ARG(d->A && d->lens && d->tokens && d->ntok, "stream_greedy: null pointer");
   const size_t lds = greedy_lds_bytes(d);
@@ -544,4 +558,11 @@ extern "C" int rnnt_hip_stream_greedy(const rnnt_stream_greedy_desc* d, void* st
   hipLaunchKernelGGL(stream_greedy_kernel, dim3(d->B), dim3(DEC_THREADS), lds, (hipStream_t)stream, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_stream_greedy(const rnnt_stream_greedy_desc* d, void* stream) { return stream_greedy_launch(d, nullptr, stream); }
+
+extern "C" int rnnt_hip_stream_greedy_timed(const rnnt_stream_greedy_desc* d, const rnnt_greedy_timing* timing, void* stream) {
+  RNNT_CHECK_ARG(timing != nullptr && timing->frames && timing->logp, "stream_greedy_timed: null timing outputs (frames, logp)");
+  return stream_greedy_launch(d, timing, stream);
 }

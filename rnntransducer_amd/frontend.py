@@ -56,6 +56,15 @@ class LogMelFrontend(nn.Module):
     def num_frames(self, n_samples: int) -> int:
         return 1 + n_samples // self.hop
 
+    def frame_seconds(self, frames):
+        """Frame indices (a tensor, a list or a number; e.g. the `frames` of recognize_greedy(return_timing=True)) -> seconds:
+        frames * hop / sample_rate.  With center=True frame k is centred on sample k * hop, and the encoder does not subsample."""
+        if isinstance(frames, torch.Tensor):
+            return frames.to(torch.float64) * (self.hop / self.sample_rate)
+        if isinstance(frames, (list, tuple)):
+            return [f * self.hop / self.sample_rate for f in frames]
+        return frames * self.hop / self.sample_rate
+
     @torch.no_grad()
     def forward(self, wav: torch.Tensor, lengths: Union[Sequence[int], torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """wav (B, L_max) float32 on the GPU (anything beyond lengths[b] is ignored), lengths in samples ->

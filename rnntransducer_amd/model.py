@@ -131,9 +131,10 @@ class RNNTransducer(_Base):
         """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
         return self.jointnet.init_stream(batch_size, self.blank_token_id, device)
 
-    def recognize_greedy_stream(self, chunk, chunk_lengths, state, max_iters: int = 3):
-        """JointNet.recognize_greedy_stream: the tokens each stream appends during this chunk of features."""
-        return self.jointnet.recognize_greedy_stream(chunk, chunk_lengths, state, max_iters)
+    def recognize_greedy_stream(self, chunk, chunk_lengths, state, max_iters: int = 3, return_timing: bool = False):
+        """JointNet.recognize_greedy_stream: the tokens each stream appends during this chunk of features (with
+        return_timing, their absolute frames and log-probabilities too)."""
+        return self.jointnet.recognize_greedy_stream(chunk, chunk_lengths, state, max_iters, return_timing=return_timing)
 
     def init_beam_stream(self, batch_size: int, beam_widths: int = 100, improved: bool = False, state_beam: float = 4.6,
                          expand_beam: float = 2.3, device=None, **caps):
@@ -141,9 +142,11 @@ class RNNTransducer(_Base):
         return self.jointnet.init_beam_stream(batch_size, self.blank_token_id, beam_widths, improved, state_beam, expand_beam,
                                               device, **caps)
 
-    def recognize_beams_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False):
-        """JointNet.recognize_beams_stream: per stream the n-best list for the frames fed so far."""
-        return self.jointnet.recognize_beams_stream(chunk, chunk_lengths, state, return_scores=return_scores)
+    def recognize_beams_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False, return_frames: bool = False):
+        """JointNet.recognize_beams_stream: per stream the n-best list for the frames fed so far (with return_frames, the
+        frame at which every token was appended too)."""
+        return self.jointnet.recognize_beams_stream(chunk, chunk_lengths, state, return_scores=return_scores,
+                                                    return_frames=return_frames)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):

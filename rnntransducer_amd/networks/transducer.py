@@ -21,7 +21,7 @@ fused loss's per-cell terms: the loss's lattice sweep in the (max, +) semiring (
 import torch
 import torch.nn as nn
 
-from ..ops import JointLogitsFn, JointLossFn, beam_search, greedy_decode, stream_greedy
+from ..ops import JointLogitsFn, JointLossFn, TimedTokens, beam_search, greedy_decode, stream_greedy
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -135,23 +135,32 @@ class JointNet(nn.Module):
 
     @torch.no_grad()
     def recognize_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, max_iters: int = 3,
-                         visit_padded_frames: bool = False):
+                         visit_padded_frames: bool = False, return_timing: bool = False, max_out=None):
         """Greedy search, same result as transducer.py:95-145: per frame up to `max_iters` non-blank symbols, a symbol
         equal to the previously appended one is dropped (but still advances the prediction net).  Returns a LongTensor
         (1, n) for a single utterance, as the reference's `torch.stack` does.  For B > 1 (where the reference's stack
         raises on ragged outputs) a list of B 1-D LongTensors, each equal to what the reference returns for that
         utterance decoded alone; `visit_padded_frames=True` instead walks all max(lengths) frames for every utterance,
-        which is what the reference's loop bound (transducer.py:115,121) does inside a batched call."""
+        which is what the reference's loop bound (transducer.py:115,121) does inside a batched call.
+        return_timing=True returns per utterance an ops.TimedTokens (tokens int64, frames int32, logp float32), three 1-D
+        tensors of equal length, instead of the tokens alone (one tuple for a single utterance, else a list): for every
+        appended token the encoder frame at which the search chose it and the log-softmax of the joint at that evaluation,
+        at that token (fp32).  A symbol dropped as a repeat has no entry.  `LogMelFrontend.frame_seconds` turns frames into
+        seconds.  max_out caps the entries kept per utterance (default: max_iters per frame, which never truncates)."""
         if self.training:
             raise RuntimeError("recognize_greedy expects eval() mode (dropout inactive), like the reference's validation_step")
         dev = inputs.device
         t_lens = lengths_to_device(inputs_lengths, dev)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         dec = self.decoder
-        tokens, ntok = greedy_decode(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(),
-                                     dec.rnn.CELL, dec.out_proj.weight, dec.out_proj.bias, blank_token_id, max_iters,
-                                     None if visit_padded_frames else t_lens)
+        res = greedy_decode(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(),
+                            dec.rnn.CELL, dec.out_proj.weight, dec.out_proj.bias, blank_token_id, max_iters,
+                            None if visit_padded_frames else t_lens, timing=return_timing, max_out=max_out)
+        tokens, ntok = res[0], res[1]
         n = ntok.tolist()  # the only host sync of the decode
+        if return_timing:
+            outs = [TimedTokens(tokens[b, :n[b]], res[2][b, :n[b]], res[3][b, :n[b]]) for b in range(tokens.shape[0])]
+            return outs[0] if len(outs) == 1 else outs
         outs = [tokens[b, :n[b]] for b in range(tokens.shape[0])]
         return outs[0].unsqueeze(0) if len(outs) == 1 else outs
 
@@ -159,7 +168,7 @@ class JointNet(nn.Module):
     def recognize_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 100,
                         improved: bool = False, state_beam: float = 4.6, expand_beam: float = 2.3, lm=None, tokenizer=None,
                         hotwords=None, hotword_weight: float = 10.0, *, visit_padded_frames: bool = False,
-                        return_scores: bool = False, **caps):
+                        return_scores: bool = False, return_frames: bool = False, **caps):
         """Beam search, same result as transducer.py:215-361 with lm=None and hotwords=None: a list of up to `beam_widths`
         y_star token lists (leading blank included), best first by asr_score / len(y_star), duplicates kept.  `tokenizer` is
         accepted and ignored: without an LM or hotwords the reference only uses it for lm_score, which never decides anything.
@@ -169,6 +178,8 @@ class JointNet(nn.Module):
         walks all max(lengths) frames for every utterance.  return_scores=True returns (y_star, asr_score) pairs instead
         (fp64 scores).  `caps`: max_pops / max_candidates / max_states / max_nodes / max_len of ops.beam_search; a search that
         outgrows one raises RnntHipError naming it (the reference's loop is unbounded there).
+        return_frames=True returns (y_star, frames) pairs, (y_star, frames, asr_score) with return_scores as well: frames is a
+        list aligned with y_star, the encoder frame at which the search appended each token (-1 for the leading blank).
         Divergence: where the reference's max() over an empty A raises ValueError (improved mode) the frame ends instead."""
         if lm is not None or hotwords is not None:
             raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
@@ -181,8 +192,11 @@ class JointNet(nn.Module):
         dec = self.decoder
         res = beam_search(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
                           dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
-                          expand_beam, None if visit_padded_frames else t_lens, **caps)
-        outs = [hyps if return_scores else [y for y, _ in hyps] for hyps in res]
+                          expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, **caps)
+        if return_frames:
+            outs = [[(y, f, s) if return_scores else (y, f) for y, s, f in hyps] for hyps in res]
+        else:
+            outs = [hyps if return_scores else [y for y, _ in hyps] for hyps in res]
         return outs[0] if len(outs) == 1 else outs
 
     def init_stream(self, batch_size: int, blank_token_id: int, device=None):
@@ -194,12 +208,15 @@ class JointNet(nn.Module):
         return GreedyStreamState(self, batch_size, blank_token_id, device)
 
     @torch.no_grad()
-    def recognize_greedy_stream(self, chunk: torch.Tensor, chunk_lengths, state, max_iters: int = 3):
+    def recognize_greedy_stream(self, chunk: torch.Tensor, chunk_lengths, state, max_iters: int = 3, return_timing: bool = False):
         """Greedy search over the next chunk of every stream: chunk (B,T_c,F) fp32 on the GPU, chunk_lengths B values in
         [0,T_c] (frames past a stream's length are ignored; a stream with 0 frames is left bitwise unchanged), `state` from
         this model's init_stream, updated in place.  Returns a list of B 1-D LongTensors: the tokens appended during this chunk.
         The per-frame rule is recognize_greedy's; any chunking of an utterance gives the same bits as one chunk holding all of
         it, and the tokens of recognize_greedy wherever no two logits are within fp32 rounding of each other.
+        return_timing=True returns ops.TimedTokens (tokens, frames, logp) per stream instead, as recognize_greedy does, with
+        absolute frames: counted from the stream's last reset (the base is state.frames_seen, read on the device; still one
+        host sync per chunk).  Frames and logp are chunk-invariant bit for bit like the tokens.
         Unidirectional encoders only; fp32 whatever compute_precision says."""
         from ..streaming import GreedyStreamState, host_lengths
         self.encoder.check_streamable("recognize_greedy_stream")
@@ -213,17 +230,23 @@ class JointNet(nn.Module):
         lens = host_lengths(chunk_lengths, B, T)
         T_run = max(lens)
         if T_run == 0:
-            return [torch.empty(0, dtype=torch.int64, device=chunk.device) for _ in range(B)]
+            empty = lambda dt: torch.empty(0, dtype=dt, device=chunk.device)
+            if return_timing:
+                return [TimedTokens(empty(torch.int64), empty(torch.int32), empty(torch.float32)) for _ in range(B)]
+            return [empty(torch.int64) for _ in range(B)]
         lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)   # one copy, shared by both launches' reads
         enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
         A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
                                       (self.fc.weight, self.fc.bias))
         dec = self.decoder
-        tokens, ntok = stream_greedy(A, lens_dev, self.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-                                     dec.out_proj.weight, dec.out_proj.bias, state.blank, max_iters, state.pred_h, state.pred_c,
-                                     state.pred_joint, state.last_token)
-        state.frames_seen += lens_dev
+        res = stream_greedy(A, lens_dev, self.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                            dec.out_proj.weight, dec.out_proj.bias, state.blank, max_iters, state.pred_h, state.pred_c,
+                            state.pred_joint, state.last_token, frame_base=state.frames_seen if return_timing else None)
+        tokens, ntok = res[0], res[1]
+        state.frames_seen += lens_dev   # after the search's launch on this stream: the kernel read the count before the chunk
         n = ntok.tolist()  # the only host sync of the chunk
+        if return_timing:
+            return [TimedTokens(tokens[b, :n[b]], res[2][b, :n[b]], res[3][b, :n[b]]) for b in range(B)]
         return [tokens[b, :n[b]] for b in range(B)]
 
     def init_beam_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
@@ -239,7 +262,8 @@ class JointNet(nn.Module):
         return BeamStreamState(self, batch_size, blank_token_id, beam_widths, improved, state_beam, expand_beam, device, **caps)
 
     @torch.no_grad()
-    def recognize_beams_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False):
+    def recognize_beams_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False,
+                               return_frames: bool = False):
         """Beam search over the next chunk of every stream: chunk (B,T_c,F) fp32 on the GPU, chunk_lengths B values in [0,T_c],
         `state` from this model's init_beam_stream, updated in place.  Returns a list of B n-best lists, each what
         recognize_beams returns for the frames that stream has been fed so far (transducer.py:215-361 with lm=None: full y_star
@@ -247,6 +271,9 @@ class JointNet(nn.Module):
         return_scores=True), whatever the chunking: same tokens, bitwise the same fp64 scores.  A stream that has seen no
         frames returns [[blank]]; a stream with 0 frames in this chunk is left bitwise unchanged and returns its previous list.
         `state.stable_prefix(b)` is the part of stream b's answer that no later chunk can change.
+        return_frames=True returns (y_star, frames) pairs ((y_star, frames, asr_score) with return_scores), frames as in
+        recognize_beams but absolute: counted from the stream's last reset.  Ask for them from a stream's first chunk after a
+        reset on: a chunk fed without them leaves that stream's frames unknown (ValueError) until its next reset.
         One launch for the search and one host sync per call.  A stream that outgrows a cap raises RnntHipError naming it after
         the other streams have been updated; it must be reset before it is fed again.
         Unidirectional encoders only; fp32 whatever compute_precision says."""
@@ -259,11 +286,13 @@ class JointNet(nn.Module):
         state.check_fits(self, B, chunk.device)
         lens = host_lengths(chunk_lengths, B, T)
         state.check_feedable(lens)
+        if return_frames:
+            state.check_frames_known()   # before the encoder runs: a refused call leaves the state untouched
         T_run = max(lens)
         if T_run > 0:
             lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
             enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
             A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
                                           (self.fc.weight, self.fc.bias))
-            state.run_chunk(A, lens_dev)
-        return state.results(return_scores)
+            state.run_chunk(A, lens_dev, return_frames)
+        return state.results(return_scores, return_frames)

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -853,12 +853,21 @@ def align_from_logits(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.
 # --------------------------------------------------------------------------------------------------
 # greedy decoding (replaces the host loop of transducer.py:95-145)
 # --------------------------------------------------------------------------------------------------
+class TimedTokens(NamedTuple):
+    """One utterance's greedy result with timing: three 1-D tensors of equal length."""
+    tokens: torch.Tensor   # int64
+    frames: torch.Tensor   # int32: the encoder frame each token was chosen at (streaming: counted from the stream's last reset)
+    logp: torch.Tensor     # float32: log-softmax of the joint at that evaluation, at the chosen token
+
+
 def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                   cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, max_iters: int,
-                  t_lens: Optional[torch.Tensor] = None):
+                  t_lens: Optional[torch.Tensor] = None, timing: bool = False, max_out: Optional[int] = None):
     """enc_tm (T,B,Oe) encoder outputs (time-major) -> (tokens (B, T*max_iters) int64, ntok (B,) int32), all on device.
     rnn_weights: [w_ih, w_hh, b_ih, b_hh] per prediction-net layer; t_lens (B) int32 on device = frames visited per
-    utterance (None: all T)."""
+    utterance (None: all T).  timing=True (rnnt_hip_greedy_decode_timed, the same kernel) -> (tokens, ntok, frames (B,
+    max_out) int32, logp (B, max_out) float32): per appended token the frame it was chosen at and the log-softmax of the
+    joint there.  max_out (default T*max_iters, which never truncates) caps the stored entries per utterance."""
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
     T, B, Oe = enc_tm.shape
@@ -876,7 +885,9 @@ def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, 
         raise ValueError(f"greedy decode: blank {blank} outside [0,{V}) or max_iters {max_iters} < 1")
     A = torch.empty(T, B, V, device=enc_tm.device, dtype=torch.float32)
     gemm(T * B, V, Oe, enc_tm, fc_w, A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
-    max_out = T * max_iters
+    max_out = T * max_iters if max_out is None else int(max_out)
+    if max_out < 1:
+        raise ValueError(f"greedy decode: max_out {max_out} < 1")
     tokens = torch.full((B, max_out), blank, device=enc_tm.device, dtype=torch.int64)
     ntok = torch.zeros(B, device=enc_tm.device, dtype=torch.int32)
     d = _lib.DecodeDesc()
@@ -891,6 +902,12 @@ def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, 
     d.w_o, d.b_o = _addr(out_w), _addr(out_b)
     d.w_d, d.ld_d = _addr(fc_w, Oe), Ocat
     d.tokens, d.ntok = _addr(tokens), _addr(ntok)
+    if timing:
+        frames = torch.full((B, max_out), -1, device=enc_tm.device, dtype=torch.int32)
+        logp = torch.zeros(B, max_out, device=enc_tm.device, dtype=torch.float32)
+        tm = _lib.GreedyTiming(_addr(frames), _addr(logp), None)
+        check(_lib.lib().rnnt_hip_greedy_decode_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_greedy_decode_timed")
+        return tokens, ntok, frames, logp
     check(_lib.lib().rnnt_hip_greedy_decode(C.byref(d), _stream()), "rnnt_hip_greedy_decode")
     return tokens, ntok
 
@@ -944,14 +961,16 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
                 cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam: int, improved: bool = False,
                 state_beam: float = 4.6, expand_beam: float = 2.3, t_lens: Optional[torch.Tensor] = None, *,
                 max_pops: int = 1024, max_candidates: Optional[int] = None, max_states: Optional[int] = None,
-                max_nodes: int = 1 << 18, max_len: Optional[int] = None, stats: bool = False):
+                max_nodes: int = 1 << 18, max_len: Optional[int] = None, stats: bool = False, frames: bool = False):
     """enc_tm (T,B,Oe) encoder outputs (time-major) -> per utterance the n-best list [(y_star, asr_score), ...] of
     transducer.py:215-361 (lm=None), one kernel launch for the batch (csrc/beam.hip) and one host sync.
     t_lens (B) int32 on device = frames visited per utterance (None: all T).  Caps (each raises RnntHipError naming it):
     max_pops = pops per frame, max_candidates = A entries per frame (default max_pops * V), max_states = live prediction-net
     states (default 3 * max_pops: a frame carries at most 2 per B entry and adds 1 per pop), max_nodes = y_star prefix nodes
     per utterance, max_len = tokens of a returned y_star (default 4 T + 64).  stats=True also returns a (B, 6) int tensor:
-    pops, prediction-net steps run, max pops in a frame, max A entries in a frame, max live states, prefix nodes."""
+    pops, prediction-net steps run, max pops in a frame, max A entries in a frame, max live states, prefix nodes.
+    frames=True (rnnt_hip_beam_search_timed, the same kernel): every entry is (y_star, asr_score, frames) with frames aligned
+    with y_star: the frame at which each token was appended, -1 for the leading blank."""
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
     T, B, Oe = enc_tm.shape
@@ -996,7 +1015,12 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     d.w_d, d.ld_d = _addr(fc_w, Oe), Ocat
     d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
     d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
-    check(_lib.lib().rnnt_hip_beam_search(C.byref(d), _stream()), "rnnt_hip_beam_search")
+    if frames:
+        fr = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
+        tm = _lib.BeamTiming(_addr(fr), None)
+        check(_lib.lib().rnnt_hip_beam_search_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_beam_search_timed")
+    else:
+        check(_lib.lib().rnnt_hip_beam_search(C.byref(d), _stream()), "rnnt_hip_beam_search")
     host = small.cpu()   # the only host sync of the search
     count, status = host.reshape(-1)[:B].tolist(), host.reshape(-1)[B:2 * B].tolist()
     for b, st in enumerate(status):
@@ -1009,6 +1033,9 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     lens_h, scores_h = lens.cpu().tolist(), scores.cpu().tolist()
     tok_h = tokens[:, :, :max(1, max(max(r) for r in lens_h))].cpu()
     out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if frames:
+        fr_h = fr[:, :, :tok_h.shape[2]].cpu()
+        out = [[(y, s, fr_h[b, r, :len(y)].tolist()) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
     if stats:
         return out, host.reshape(-1)[2 * B:].reshape(B, _lib.BEAM_NSTATS)
     return out
@@ -1139,9 +1166,11 @@ def stream_greedy_reset(rows: torch.Tensor, fc_w, emb_w, rnn_weights, cell: int,
 
 
 def stream_greedy(A: torch.Tensor, lens: torch.Tensor, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, max_iters: int,
-                  h, c, Cs, last):
+                  h, c, Cs, last, frame_base: Optional[torch.Tensor] = None):
     """Greedy search over one chunk from carried state.  A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; h / c / Cs /
-    last updated in place -> (tokens (B, T*max_iters) int64, ntok (B,) int32) appended in this chunk."""
+    last updated in place -> (tokens (B, T*max_iters) int64, ntok (B,) int32) appended in this chunk.  With frame_base ((B,)
+    int64 on device: the frames every stream consumed before this chunk; rnnt_hip_stream_greedy_timed, the same kernel) ->
+    (tokens, ntok, frames (B, T*max_iters) int32 absolute, logp float32)."""
     _need_gpu(A, lens, fc_w, emb_w, h, Cs, last)
     T, B = A.shape[0], A.shape[1]
     d, keep = _stream_greedy_desc(T, B, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, h, c, Cs, last)
@@ -1154,6 +1183,13 @@ def stream_greedy(A: torch.Tensor, lens: torch.Tensor, fc_w, emb_w, rnn_weights,
     ntok = torch.zeros(B, device=A.device, dtype=torch.int32)
     d.max_iters, d.max_out = max_iters, max_out
     d.A, d.lens, d.tokens, d.ntok = _addr(A), _addr(lens), _addr(tokens), _addr(ntok)
+    if frame_base is not None:
+        _check_buffer("frame_base", frame_base, (B,), torch.int64, fc_w.device)
+        frames = torch.full((B, max_out), -1, device=A.device, dtype=torch.int32)
+        logp = torch.zeros(B, max_out, device=A.device, dtype=torch.float32)
+        tm = _lib.GreedyTiming(_addr(frames), _addr(logp), _addr(frame_base))
+        check(_lib.lib().rnnt_hip_stream_greedy_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_stream_greedy_timed")
+        return tokens, ntok, frames, logp
     check(_lib.lib().rnnt_hip_stream_greedy(C.byref(d), _stream()), "rnnt_hip_stream_greedy")
     return tokens, ntok
 
@@ -1226,13 +1262,22 @@ def beam_stream_reset(d, rows: torch.Tensor, build_table: bool) -> None:
           "rnnt_hip_beam_stream_reset")
 
 
-def beam_stream_chunk(d, A: torch.Tensor, lens: torch.Tensor) -> None:
-    """One chunk: A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; the outputs d points to are written."""
+def beam_stream_chunk(d, A: torch.Tensor, lens: torch.Tensor, frames: Optional[torch.Tensor] = None,
+                      commit_frames: Optional[torch.Tensor] = None) -> None:
+    """One chunk: A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; the outputs d points to are written.  With
+    frames (B, beam, max_len) and commit_frames (B, max_nodes), int32 on device: rnnt_hip_beam_stream_chunk_timed, the same
+    kernel, which also writes the tail's and the committed tokens' absolute frames."""
     _need_gpu(A, lens)
     _check_buffer("A", A, (A.shape[0], d.B, d.V), torch.float32, A.device)
     _check_buffer("lengths", lens, (d.B,), torch.int32, A.device)
     d.T, d.A, d.lens = A.shape[0], _addr(A), _addr(lens)
     try:
-        check(_lib.lib().rnnt_hip_beam_stream_chunk(C.byref(d), _stream()), "rnnt_hip_beam_stream_chunk")
+        if frames is not None:
+            _check_buffer("frames", frames, (d.B, d.beam, d.max_len), torch.int32, A.device)
+            _check_buffer("commit_frames", commit_frames, (d.B, d.max_nodes), torch.int32, A.device)
+            tm = _lib.BeamTiming(_addr(frames), _addr(commit_frames))
+            check(_lib.lib().rnnt_hip_beam_stream_chunk_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_beam_stream_chunk_timed")
+        else:
+            check(_lib.lib().rnnt_hip_beam_stream_chunk(C.byref(d), _stream()), "rnnt_hip_beam_stream_chunk")
     finally:
         d.T, d.A, d.lens = 0, None, None

@@ -190,6 +190,12 @@ class BeamStreamState:
         self._lens = torch.zeros(B, self.beam, device=device, dtype=torch.int32)
         self._scores = torch.zeros(B, self.beam, device=device, dtype=torch.float64)
         self._commit = torch.zeros(B, self.caps["max_nodes"], device=device, dtype=torch.int32)
+        # the timed chunk entry's outputs, made by the first chunk that asks for frames
+        self._frames: Optional[torch.Tensor] = None
+        self._commit_frames: Optional[torch.Tensor] = None
+        # frames beside `committed` / `nbest` (per stream; None: a chunk was fed without return_frames since the last reset)
+        self.committed_frames: List[Optional[List[int]]] = [[-1] for _ in range(B)]
+        self.nbest_frames: List[Optional[List[List[int]]]] = [[[-1]] for _ in range(B)]
         self.committed: List[List[int]] = [[self.blank] for _ in range(B)]
         self.nbest = [[([self.blank], 0.0)] for _ in range(B)]
         self.failed = [False] * B
@@ -219,10 +225,15 @@ class BeamStreamState:
         lo = self._ws_off + self._table_bytes + b * self.bytes_per_stream
         return self.workspace[lo:lo + self.bytes_per_stream]
 
-    def stable_prefix(self, b: int) -> List[int]:
+    def stable_prefix(self, b: int, return_frames: bool = False):
         """The committed tokens of stream b, leading blank included: the longest common prefix of the y_star of ALL carried
-        hypotheses.  Every hypothesis of any later frame extends one of those, so no later chunk can change it."""
-        return list(self.committed[b])
+        hypotheses.  Every hypothesis of any later frame extends one of those, so no later chunk can change it.
+        return_frames=True: (tokens, frames), frames aligned with the tokens (absolute; -1 for the leading blank)."""
+        if not return_frames:
+            return list(self.committed[b])
+        if self.committed_frames[b] is None:
+            raise ValueError(f"stream {b} was fed a chunk without return_frames=True since its last reset: its frames are unknown")
+        return list(self.committed[b]), list(self.committed_frames[b])
 
     def check_fits(self, jointnet, B: int, device) -> None:
         """ValueError unless this state was opened by `jointnet` for B streams on `device` and still has that layout."""
@@ -244,6 +255,15 @@ class BeamStreamState:
                 raise ValueError(f"state.{name} is not a contiguous {dtype} tensor of shape {shape} on {self.device}")
         if -self.workspace.data_ptr() % 256 != self._ws_off:
             raise ValueError("state.workspace was replaced: its alignment offset no longer holds")
+
+    def check_frames_known(self) -> None:
+        """ValueError if a stream took a chunk without return_frames=True since its last reset (a call that returns frames
+        returns them for every stream).  Called before anything is launched, like every guard of a chunk: a refused call
+        leaves the state bitwise as it is."""
+        unknown = [b for b, f in enumerate(self.committed_frames) if f is None]
+        if unknown:
+            raise ValueError(f"stream(s) {unknown[:4]} were fed a chunk without return_frames=True since their last reset: "
+                             "their frames are unknown")
 
     def check_feedable(self, lens: Sequence[int]) -> None:
         bad = [b for b, n in enumerate(lens) if n > 0 and self.failed[b]]
@@ -272,16 +292,31 @@ class BeamStreamState:
         ops.beam_stream_reset(d, idx.to(torch.int32), build_table)
         for r in rows:
             self.committed[r], self.nbest[r], self.failed[r] = [self.blank], [([self.blank], 0.0)], False
+            self.committed_frames[r], self.nbest_frames[r] = [-1], [[-1]]
 
-    def results(self, return_scores: bool):
-        return [[(list(y), s) for y, s in hyps] if return_scores else [list(y) for y, _ in hyps] for hyps in self.nbest]
+    def results(self, return_scores: bool, return_frames: bool = False):
+        if not return_frames:
+            return [[(list(y), s) for y, s in hyps] if return_scores else [list(y) for y, _ in hyps] for hyps in self.nbest]
+        unknown = [b for b, f in enumerate(self.nbest_frames) if f is None]
+        if unknown:
+            raise ValueError(f"stream(s) {unknown[:4]} were fed a chunk without return_frames=True since their last reset: their "
+                             "frames are unknown")
+        return [[(list(y), list(f), s) if return_scores else (list(y), list(f)) for (y, s), f in zip(hyps, frs)]
+                for hyps, frs in zip(self.nbest, self.nbest_frames)]
 
-    def run_chunk(self, A: torch.Tensor, lens_dev: torch.Tensor) -> None:
-        """The search over one chunk (A (T,B,V), lens_dev (B) int32): updates the workspace, `committed`, `nbest`,
-        `frames_seen`; raises RnntHipError for a stream that outgrew a cap, after every other stream has been updated."""
+    def run_chunk(self, A: torch.Tensor, lens_dev: torch.Tensor, timed: bool = False) -> None:
+        """The search over one chunk (A (T,B,V), lens_dev (B) int32; `timed` after check_frames_known): updates the workspace,
+        `committed`, `nbest`, `frames_seen` and, with `timed`, their frames (the timed entry; without it the fed streams'
+        frames become unknown); raises RnntHipError for a stream that outgrew a cap, after every other stream has been updated."""
         B = self.batch_size
         d, keep = self._descriptor()
-        ops.beam_stream_chunk(d, A, lens_dev)
+        if timed:
+            if self._frames is None:
+                self._frames = torch.zeros_like(self._tokens)
+                self._commit_frames = torch.zeros_like(self._commit)
+            ops.beam_stream_chunk(d, A, lens_dev, self._frames, self._commit_frames)
+        else:
+            ops.beam_stream_chunk(d, A, lens_dev)
         self.frames_seen += lens_dev
         host = self._small.cpu()   # the host sync of the chunk; the result slices below are copied from an idle stream
         count, status, ncommit = host[0].tolist(), host[1].tolist(), host[2].tolist()
@@ -291,9 +326,16 @@ class BeamStreamState:
             lens_h, scores_h = self._lens.cpu().tolist(), self._scores.cpu().tolist()
             tok_h = self._tokens[:, :, :max(1, max(max(lens_h[b]) for b in ran))].cpu()
             com_h = self._commit[:, :max(1, max(ncommit[b] for b in ran))].cpu()
+            if timed:
+                fr_h, cfr_h = self._frames[:, :, :tok_h.shape[2]].cpu(), self._commit_frames[:, :com_h.shape[1]].cpu()
             for b in ran:
                 self.committed[b] += com_h[b, :ncommit[b]].tolist()
                 self.nbest[b] = [(self.committed[b] + tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])]
+                if timed:
+                    self.committed_frames[b] += cfr_h[b, :ncommit[b]].tolist()
+                    self.nbest_frames[b] = [self.committed_frames[b] + fr_h[b, r, :lens_h[b][r]].tolist() for r in range(count[b])]
+                else:
+                    self.committed_frames[b], self.nbest_frames[b] = None, None
         bad = [b for b in range(B) if status[b] != 0]
         for b in bad:
             self.failed[b] = True

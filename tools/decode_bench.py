@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-utts", type=int, default=1)
     ap.add_argument("--blank-bias", type=float, default=0.0, help="added to fc.bias[blank]: fewer emitted symbols per frame")
+    ap.add_argument("--timing", action="store_true", help="time recognize_greedy(return_timing=True): frames and logp per token")
     a = ap.parse_args()
     from oracle.rnnt_oracle import OracleJointNet
     from rnntransducer_amd import _lib
@@ -48,7 +49,7 @@ def main():
     lib.rnnt_hip_prof_enable(1)
     t0 = time.perf_counter()
     for _ in range(a.reps):
-        net.recognize_greedy(dev_audio, lens, 0, 3)
+        net.recognize_greedy(dev_audio, lens, 0, 3, return_timing=a.timing)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.reps
     import ctypes as C
@@ -66,7 +67,7 @@ def main():
     got = out if isinstance(out, list) else [out[0]]
     agree = sum(int(got[b].tolist() == want[b]) for b in range(a.cpu_utts))
     print(json.dumps({"metric": "greedy decode utterances/sec", "value": round(a.batch / dt, 2), "ms_per_batch": round(dt * 1e3, 2),
-                      "batch": a.batch, "frames": a.frames, "blank_bias": a.blank_bias, "tokens_per_utt": sum(ntok) / len(ntok),
+                      "batch": a.batch, "frames": a.frames, "blank_bias": a.blank_bias, "timing": a.timing, "tokens_per_utt": sum(ntok) / len(ntok),
                       "kernel_ms_per_batch": per_kind,
                       "cpu_baseline": {"value": round(a.cpu_utts / cpu_dt, 3), "unit": "utterances/sec", "kind": "port",
                                        "sample": f"{a.cpu_utts} utterance(s), torch CPU host loop", "cores": torch.get_num_threads()},

@@ -39,7 +39,7 @@ def make_net(V: int, device="cuda"):
     return net.to(device).eval(), tn["num_layers"]
 
 
-def run_point(B: int, Tc: int, V: int, chunks: int, warmup: int) -> dict:
+def run_point(B: int, Tc: int, V: int, chunks: int, warmup: int, timing: bool = False) -> dict:
     net, L_enc = make_net(V)
     state = net.init_stream(B, 0)
     g = torch.Generator(device="cuda").manual_seed(B * 1000 + Tc)
@@ -49,12 +49,12 @@ def run_point(B: int, Tc: int, V: int, chunks: int, warmup: int) -> dict:
     for i in range(warmup + chunks):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-        out = net.recognize_greedy_stream(feats[i % len(feats)], lens, state)
+        out = net.recognize_greedy_stream(feats[i % len(feats)], lens, state, return_timing=timing)
         e.record()
         e.synchronize()
         if i >= warmup:
             times.append(s.elapsed_time(e) * 1e3)
-            ntok += sum(t.numel() for t in out)
+            ntok += sum((t.tokens if timing else t).numel() for t in out)
     us = statistics.median(times)
     # the encoder alone (recurrence + out_proj, forward_stream) on the same chunks: the rest is the joint half and the search
     enc_times, enc_state = [], None
@@ -66,7 +66,7 @@ def run_point(B: int, Tc: int, V: int, chunks: int, warmup: int) -> dict:
         e.synchronize()
         if i >= warmup:
             enc_times.append(s.elapsed_time(e) * 1e3)
-    return dict(B=B, T_c=Tc, V=V, enc="4x512 lstm uni", pred="1x512 lstm", us_per_chunk=round(us, 1),
+    return dict(B=B, T_c=Tc, V=V, timing=timing, enc="4x512 lstm uni", pred="1x512 lstm", us_per_chunk=round(us, 1),
                 us_min=round(min(times), 1), us_max=round(max(times), 1), encoder_us=round(statistics.median(enc_times), 1), chunks=chunks,
                 library_launches_per_chunk=Tc + L_enc + 3, tokens_per_chunk=round(ntok / chunks, 2),
                 rtf=round(us / (Tc * FRAME_MS * 1e3), 5))
@@ -77,13 +77,14 @@ def main():
     ap.add_argument("--chunks", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", default="", help="B:Tc:V,... (default: the sweep of the module docstring)")
+    ap.add_argument("--timing", action="store_true", help="time recognize_greedy_stream(return_timing=True)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench needs the GPU")
     points = [tuple(int(v) for v in p.split(":")) for p in a.points.split(",")] if a.points else DEFAULT_POINTS
     with torch.no_grad():
         for B, Tc, V in points:
-            print(json.dumps(run_point(B, Tc, V, a.chunks, a.warmup)), flush=True)
+            print(json.dumps(run_point(B, Tc, V, a.chunks, a.warmup, a.timing)), flush=True)
 
 
 if __name__ == "__main__":
