@@ -116,6 +116,25 @@ typedef struct rnnt_gemm_desc {
 size_t rnnt_hip_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream);
 
+/* What rnnt_hip_gemm_f32 would launch for this descriptor (read-only: no launch, no device access; the operand pointers are looked
+ * at for their alignment only).  Both entries take their decisions from the same function, and the descriptor is validated as the
+ * launch validates it.  An empty output (M or N zero) gives tiles = 0 and tile_m = tile_n = 0: nothing is launched.
+ *   mode: 6 split-bf16 with six products (default), 3 first-order split-bf16, 0 f32-input MFMA (RNNT_GEMM_EXACT_F32 / RNNT_GEMM_MODE).
+ *   tile_m x tile_n: 128x128 or 128x256 (256 threads), 256x256 (512 threads, mode 6 only).
+ *   a_kc / b_kc: the operand's rows are k-contiguous (a_mc == 0 / b_sk == 1).  vec: 16-byte operand loads, else scalar ones.
+ *   splits > 1: split-K into `splits` slabs of `kchunk` k each in the workspace, summed in fixed order by a second kernel that also
+ *   applies bias, the C row map, MUL_DGELU and ACCUM.  tiles: workgroups per slab.
+ * Used by the tests that pin which kernel instance a shape runs. */
+typedef struct rnnt_gemm_plan {
+  int32_t mode;
+  int32_t tile_m, tile_n;
+  int32_t a_kc, b_kc;
+  int32_t vec;
+  int32_t tiles;
+  int32_t splits, kchunk;
+} rnnt_gemm_plan;
+int rnnt_hip_gemm_plan(const rnnt_gemm_desc* d, rnnt_gemm_plan* out);
+
 /* ------------------------------------------------------------------------------------------------
  * fp32 GEMM on the f16 matrix cores through "half-pair" (hp) operands — the form the BIG products of the hot path use
  * inside rnnt_hip_lstm_fwd / _bwd (hoisted input projection of nn.LSTM, networks/encoder.py:67-75,99, and its backward
@@ -342,7 +361,7 @@ int rnnt_hip_loss_from_logits_fwd_bwd(const float* logits, const int32_t* labels
                                       size_t workspace_bytes, void* stream);
 
 /* Embedding forward (networks/decoder.py:69,102): out[m,:] = W[idx[m],:]  (row padding_idx of W is zero by
- * construction, nn.Embedding(padding_idx=blank)). */
+ * construction, nn.Embedding(padding_idx=blank)).  Ids outside [0, V) give zero rows.  M == 0 does nothing (idx and out may be NULL). */
 int rnnt_hip_embedding_fwd(const float* W, const int64_t* idx, int64_t M, int32_t H, int32_t V, float* out, void* stream);
 
 /* Same, for logits/grad stored as fp16 or bf16 (torchaudio's RNNTLoss takes half logits: model.py:28-31); the
@@ -396,7 +415,7 @@ int rnnt_hip_adamw_step_ex(float* p, const float* g, float* m, float* v, int64_t
                            float weight_decay, int64_t step, float grad_scale, const uint32_t* guard, void* stream);
 
 /* column sums: out[n] = sum_m X[m*ld + n]  (bias gradients: fc.bias, out_proj.bias, LSTM biases).
- * Two-stage fixed-order reduction; workspace = rnnt_hip_colsum_workspace_bytes(M, N) bytes. */
+ * Two-stage fixed-order reduction; workspace = rnnt_hip_colsum_workspace_bytes(M, N) bytes.  M == 0 gives zeros (X may be NULL). */
 size_t rnnt_hip_colsum_workspace_bytes(int64_t M, int64_t N);
 int rnnt_hip_colsum_f32(const float* X, int64_t M, int64_t N, int64_t ld, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
@@ -405,7 +424,8 @@ int rnnt_hip_colsum_f32_acc(const float* X, int64_t M, int64_t N, int64_t ld, fl
                             size_t workspace_bytes, void* stream);
 
 /* Embedding backward (networks/decoder.py:69,102): dW[idx[m]] += dE[m] for idx[m] != padding_idx. dW (V,H)
- * must be zeroed by the caller. */
+ * must be zeroed by the caller.  Ids outside [0, V) are ignored; the hits of a row are added in token order (a fixed-order fp32
+ * sum).  M == 0: dE and idx may be NULL. */
 int rnnt_hip_embedding_bwd(const float* dE, const int64_t* idx, int64_t M, int32_t H, int32_t V, int64_t padding_idx,
                            float* dW, void* stream);
 /* dW[v] += sum (row padding_idx untouched): accumulation into an existing gradient */

@@ -31,6 +31,11 @@ class GemmDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GemmPlan(C.Structure):
+    _fields_ = [("mode", c_i32), ("tile_m", c_i32), ("tile_n", c_i32), ("a_kc", c_i32), ("b_kc", c_i32), ("vec", c_i32),
+                ("tiles", c_i32), ("splits", c_i32), ("kchunk", c_i32)]
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("T", c_i32), ("B", c_i32), ("I", c_i32), ("H", c_i32), ("D", c_i32), ("cell", c_i32), ("lens", C.c_void_p),
                 ("x", C.c_void_p), ("x_st", c_i64), ("x_sb", c_i64), ("w_ih", C.c_void_p * 2),
@@ -144,6 +149,7 @@ SYMBOLS = {
     "rnnt_hip_lstm_launch_log": (c_i64, [C.c_char_p, C.c_size_t]),
     "rnnt_hip_gemm_workspace_bytes": (C.c_size_t, [c_i64, c_i64, c_i64]),
     "rnnt_hip_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), C.c_void_p]),
+    "rnnt_hip_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlan)]),
     "rnnt_hip_hp_bytes": (C.c_size_t, [c_i64, c_i64]),
     "rnnt_hip_hp_split": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, c_i32, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i32, C.c_void_p]),
     "rnnt_hip_gemm_hp_workspace_bytes": (C.c_size_t, [c_i64, c_i64, c_i64]),

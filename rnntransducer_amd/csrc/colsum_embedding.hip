@@ -123,18 +123,18 @@ extern "C" size_t rnnt_hip_colsum_workspace_bytes(int64_t M, int64_t N) {
 
 extern "C" int rnnt_hip_colsum_f32(const float* X, int64_t M, int64_t N, int64_t ld, float* out, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  RNNT_CHECK_ARG(X && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
+  RNNT_CHECK_ARG((X || M == 0) && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
   return launch_colsum(X, (long)M, (long)N, (long)ld, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 extern "C" int rnnt_hip_colsum_f32_acc(const float* X, int64_t M, int64_t N, int64_t ld, float* out, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  RNNT_CHECK_ARG(X && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
+  RNNT_CHECK_ARG((X || M == 0) && out && M >= 0 && N >= 1 && ld >= N, "colsum: bad arguments");
   return launch_colsum(X, (long)M, (long)N, (long)ld, out, workspace, workspace_bytes, (hipStream_t)stream, 1);
 }
 
 extern "C" int rnnt_hip_embedding_fwd(const float* W, const int64_t* idx, int64_t M, int32_t H, int32_t V, float* out,
                                       void* stream) {
-  RNNT_CHECK_ARG(W && idx && out && M >= 0 && H >= 1 && V >= 1, "embedding_fwd: bad arguments");
+  RNNT_CHECK_ARG(M >= 0 && W && ((idx && out) || M == 0) && H >= 1 && V >= 1, "embedding_fwd: bad arguments");
   if (M == 0) return RNNT_OK;
   const long blocks = ceil_div(M * H, 256);
   hipLaunchKernelGGL(embedding_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, W,
@@ -145,7 +145,7 @@ extern "C" int rnnt_hip_embedding_fwd(const float* W, const int64_t* idx, int64_
 
 static int embedding_bwd_impl(const float* dE, const int64_t* idx, int64_t M, int32_t H, int32_t V, int64_t padding_idx,
                               float* dW, int accumulate, void* stream) {
-  RNNT_CHECK_ARG(dE && idx && dW && M >= 0 && H >= 1 && V >= 1, "embedding_bwd: bad arguments");
+  RNNT_CHECK_ARG(M >= 0 && ((dE && idx) || M == 0) && dW && H >= 1 && V >= 1, "embedding_bwd: bad arguments");
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(V), dim3(256), 0, (hipStream_t)stream, dE, (const long*)idx, (long)M, H, V,
                      (long)padding_idx, dW, accumulate);
   RNNT_CHECK_LAUNCH();

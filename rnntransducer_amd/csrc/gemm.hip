@@ -712,11 +712,26 @@ extern "C" size_t rnnt_hip_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K)
   return best >= 2 ? (size_t)best * M * N * 4 : 0;
 }
 
-extern "C" int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream) {
-  using namespace rnnt;
+// Every decision of one rnnt_hip_gemm_f32 call, made in one place from the descriptor alone: arithmetic mode, tiling, operand
+// layouts, vector or scalar loads, split-K.  rnnt_hip_gemm_f32 launches what this says; rnnt_hip_gemm_plan reports it.
+namespace rnnt {
+namespace {
+
+struct GemmPlan {
+  int mode;        // 6 = split-bf16 (six products), 3 = first-order split-bf16, 0 = f32-input MFMA
+  bool big;        // 256x256 tile, 512 threads
+  int bn;          // tile width of the 128-row tilings (128 / 256); 256 with big
+  bool a_kc, b_kc; // operand rows k-contiguous
+  bool vec;        // 16-byte operand loads
+  int tiles;       // workgroups per K slab; 0 = empty output, nothing is launched
+  int splits, kchunk;
+};
+
+int make_gemm_plan(const rnnt_gemm_desc* d, GemmPlan& pl) {
   RNNT_CHECK_ARG(d != nullptr, "gemm: null descriptor");
   RNNT_CHECK_ARG(d->M >= 0 && d->N >= 0 && d->K >= 0, "gemm: negative dims");
   RNNT_CHECK_ARG(d->M < (1ll << 31) && d->N < (1ll << 31) && d->K < (1ll << 31), "gemm: dims must fit int32");
+  pl = GemmPlan{};
   if (d->M == 0 || d->N == 0) return RNNT_OK;
   RNNT_CHECK_ARG(d->A && d->B && d->C, "gemm: null operand");
   RNNT_CHECK_ARG(d->c_div >= 1, "gemm: c_div must be >= 1");
@@ -730,20 +745,15 @@ extern "C" int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream) {
   } else {
     RNNT_CHECK_ARG(d->a_rowidx == nullptr, "gemm: a_rowidx only with k-contiguous A");
   }
-
-  GemmK k;
-  k.M = (int)d->M; k.N = (int)d->N; k.K = (int)d->K;
-  k.A = d->A; k.a_div = (int)(d->a_div < 1 ? 1 : (d->a_div > 0x7fffffff ? 0x7fffffff : d->a_div));
-  k.a_so = d->a_so; k.a_si = d->a_si; k.a_sk = d->a_sk; k.a_rowidx = (const long*)d->a_rowidx;
-  k.B = d->B; k.b_sn = d->b_sn; k.b_sk = d->b_sk;
-  k.C = d->C; k.c_div = (int)(d->c_div > 0x7fffffff ? 0x7fffffff : d->c_div); k.c_so = d->c_so; k.c_si = d->c_si;
-  k.bias = d->bias; k.aux = d->aux; k.flags = d->flags;
+  pl.a_kc = a_kc;
+  pl.b_kc = b_kc;
 
   bool vec = aligned16(d->A) && aligned16(d->B);
   if (a_kc) vec = vec && (d->a_si % 4 == 0) && (d->a_rowidx || d->a_so % 4 == 0);
   else vec = vec && (d->a_sk % 4 == 0);
   if (b_kc) vec = vec && (d->b_sn % 4 == 0);
   else vec = vec && (d->b_sk % 4 == 0);
+  pl.vec = vec;
 
   const int mode = (d->flags & RNNT_GEMM_EXACT_F32) ? 0 : gemm_mode();
   const int bks = BK;  // (a K-tile depth of 32 with 128x128 tiles was measured slower: DESIGN.md 4.4; the kernel template still takes it)
@@ -778,8 +788,54 @@ extern "C" int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream) {
     if (want > 64) want = 64;
     if (want >= 2) splits = (int)want;
   }
-  k.kchunk = splits > 1 ? (int)(ceil_div(ceil_div(d->K, splits), bks) * bks) : (int)(d->K > 0 ? d->K : 1);
-  if (splits > 1) splits = (int)ceil_div(d->K, k.kchunk);
+  pl.kchunk = splits > 1 ? (int)(ceil_div(ceil_div(d->K, splits), bks) * bks) : (int)(d->K > 0 ? d->K : 1);
+  if (splits > 1) splits = (int)ceil_div(d->K, pl.kchunk);
+  pl.mode = mode;
+  pl.big = big;
+  pl.bn = big ? 256 : bn;
+  pl.tiles = tiles;
+  pl.splits = splits;
+  return RNNT_OK;
+}
+
+}  // namespace
+}  // namespace rnnt
+
+extern "C" int rnnt_hip_gemm_plan(const rnnt_gemm_desc* d, rnnt_gemm_plan* out) {
+  using namespace rnnt;
+  RNNT_CHECK_ARG(out != nullptr, "gemm_plan: null plan");
+  GemmPlan pl;
+  const int rc = make_gemm_plan(d, pl);
+  if (rc != RNNT_OK) return rc;
+  out->mode = pl.mode;
+  out->tile_m = pl.tiles == 0 ? 0 : (pl.big ? 256 : BM);
+  out->tile_n = pl.tiles == 0 ? 0 : pl.bn;
+  out->a_kc = pl.a_kc;
+  out->b_kc = pl.b_kc;
+  out->vec = pl.vec;
+  out->tiles = pl.tiles;
+  out->splits = pl.splits;
+  out->kchunk = pl.kchunk;
+  return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_gemm_f32(const rnnt_gemm_desc* d, void* stream) {
+  using namespace rnnt;
+  GemmPlan pl;
+  const int rc = make_gemm_plan(d, pl);
+  if (rc != RNNT_OK) return rc;
+  if (pl.tiles == 0) return RNNT_OK;
+  const bool a_kc = pl.a_kc, b_kc = pl.b_kc, vec = pl.vec, big = pl.big;
+  const int mode = pl.mode, bks = BK, bn = pl.bn, tiles = pl.tiles, splits = pl.splits;
+
+  GemmK k;
+  k.M = (int)d->M; k.N = (int)d->N; k.K = (int)d->K;
+  k.A = d->A; k.a_div = (int)(d->a_div < 1 ? 1 : (d->a_div > 0x7fffffff ? 0x7fffffff : d->a_div));
+  k.a_so = d->a_so; k.a_si = d->a_si; k.a_sk = d->a_sk; k.a_rowidx = (const long*)d->a_rowidx;
+  k.B = d->B; k.b_sn = d->b_sn; k.b_sk = d->b_sk;
+  k.C = d->C; k.c_div = (int)(d->c_div > 0x7fffffff ? 0x7fffffff : d->c_div); k.c_so = d->c_so; k.c_si = d->c_si;
+  k.bias = d->bias; k.aux = d->aux; k.flags = d->flags;
+  k.kchunk = pl.kchunk;
   k.splits = splits;
   k.slab = (float*)d->workspace;
   dim3 grid(tiles, splits), block(256);

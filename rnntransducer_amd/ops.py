@@ -89,13 +89,11 @@ def lstm_status_check(device=None) -> None:
 # --------------------------------------------------------------------------------------------------
 # raw GEMM
 # --------------------------------------------------------------------------------------------------
-def gemm(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, *, a_off=0, a_div=BIG, a_so=0,
-         a_si=None, a_sk=1, a_mc=False, a_rowidx=None, b_off=0, b_sn=None, b_sk=1, c_off=0, c_div=BIG, c_so=0, c_si=None,
-         bias=None, aux=None, flags=0, split_k=None) -> None:
-    """C(m,n) = sum_k A(m,k) B(k,n) (+bias) — see include/rnnt_hip.h for the operand maps.
-    split_k=True hands the kernel a slab workspace so small-output / deep-K products (weight gradients) fill the chip;
-    None (default): do so when the output is small (<= 2^21 elements: the prediction net's and the joint's products)."""
-    _need_gpu(A, B, Cout)
+def _gemm_desc(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, *, a_off=0, a_div=BIG, a_so=0,
+               a_si=None, a_sk=1, a_mc=False, a_rowidx=None, b_off=0, b_sn=None, b_sk=1, c_off=0, c_div=BIG, c_so=0, c_si=None,
+               bias=None, aux=None, flags=0, split_k=None, need_ws=True):
+    """The descriptor of one gemm() call and the tensor that owns its split-K workspace (None without one).  need_ws=False: only
+    the workspace's size is entered (rnnt_hip_gemm_plan reads the size and whether the pointer is null, never the memory)."""
     d = GemmDesc()
     ws = None
     if split_k is None:
@@ -103,7 +101,7 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.T
     if split_k:
         nws = _lib.lib().rnnt_hip_gemm_workspace_bytes(M, N, K)
         if nws:
-            ws = torch.empty(nws, device=Cout.device, dtype=torch.uint8)
+            ws = torch.empty(nws if need_ws else 16, device=Cout.device, dtype=torch.uint8)
             d.workspace, d.workspace_bytes = _addr(ws), nws
     d.M, d.N, d.K = M, N, K
     d.A = _addr(A, a_off)
@@ -115,9 +113,42 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.T
     d.C = _addr(Cout, c_off)
     d.c_div, d.c_so, d.c_si = c_div, c_so, (N if c_si is None else c_si)
     d.bias = _addr(bias)
-    d.aux = _addr(aux)
+    d.aux = _addr(aux, c_off)   # aux is laid out like C: element (m, n) of both sits at the same mapped offset behind c_off
     d.flags = flags
+    return d, ws
+
+
+def gemm(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, **kw) -> None:
+    """C(m,n) = sum_k A(m,k) B(k,n) (+bias) — see include/rnnt_hip.h for the operand maps.  Keywords: a_off=0, a_div=BIG, a_so=0,
+    a_si=K, a_sk=1, a_mc=False, a_rowidx=None, b_off=0, b_sn=K, b_sk=1, c_off=0, c_div=BIG, c_so=0, c_si=N, bias=None, aux=None,
+    flags=0, split_k=None.
+    split_k=True hands the kernel a slab workspace so small-output / deep-K products (weight gradients) fill the chip;
+    None (default): do so when the output is small (<= 2^21 elements: the prediction net's and the joint's products)."""
+    _need_gpu(A, B, Cout)
+    d, ws = _gemm_desc(M, N, K, A, B, Cout, **kw)
     check(_lib.lib().rnnt_hip_gemm_f32(C.byref(d), _stream()), "rnnt_hip_gemm_f32")
+
+
+class GemmPlan(NamedTuple):
+    """What one gemm() call launches (rnnt_hip_gemm_plan): arithmetic mode (6 / 3 / 0), tile (rows, columns), operand layouts,
+    vector or scalar operand loads, workgroups per K slab, split-K slab count (1 = no split) and depth."""
+    mode: int
+    tile: Tuple[int, int]
+    a_kc: bool
+    b_kc: bool
+    vec: bool
+    tiles: int
+    splits: int
+    kchunk: int
+
+
+def gemm_plan(M: int, N: int, K: int, A: torch.Tensor, B: torch.Tensor, Cout: torch.Tensor, **kw) -> GemmPlan:
+    """The plan of the gemm() call with these arguments, from the function that call takes its decisions from; launches nothing
+    (the tensors are looked at for their addresses only, so any device serves)."""
+    d, ws = _gemm_desc(M, N, K, A, B, Cout, need_ws=False, **kw)
+    p = _lib.GemmPlan()
+    check(_lib.lib().rnnt_hip_gemm_plan(C.byref(d), C.byref(p)), "rnnt_hip_gemm_plan")
+    return GemmPlan(p.mode, (p.tile_m, p.tile_n), bool(p.a_kc), bool(p.b_kc), bool(p.vec), p.tiles, p.splits, p.kchunk)
 
 
 # --------------------------------------------------------------------------------------------------

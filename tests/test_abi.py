@@ -147,3 +147,33 @@ def test_lstm_launch_record_entry_points():
     with lstm_launch_record() as rec:
         pass
     assert rec.symbols == [] and rec.instances == []
+
+
+def test_gemm_plan_entry_point():
+    """rnnt_hip_gemm_plan: host-only, reads the descriptor and the operand addresses' alignment, launches nothing.  The rules it shares
+    with the launch (csrc/gemm.hip, make_gemm_plan): 128x128 tiles unless N is a multiple of 256 with >= 64 tiles of 128x256; 256x256
+    tiles from 64 (tiles x split-K slabs) on; scalar loads for a stride or an address off 16 bytes; split-K only with a workspace;
+    the launch's own argument checks."""
+    import ctypes as C
+    from rnntransducer_amd import _lib
+    from rnntransducer_amd.ops import gemm_plan
+    L = _lib.lib()
+    plan = _lib.GemmPlan()
+    assert L.rnnt_hip_gemm_plan(None, C.byref(plan)) == -1 and b"null" in L.rnnt_hip_last_error()
+    a = torch.zeros(64)
+    kw = dict(split_k=False)
+    p = gemm_plan(130, 70, 33, a, a, a, a_si=36, b_sn=36, **kw)
+    assert (p.mode, p.tile, p.a_kc, p.b_kc, p.vec, p.tiles, p.splits, p.kchunk) == (6, (128, 128), True, True, True, 2, 1, 33)
+    assert not gemm_plan(130, 70, 33, a, a, a, **kw).vec                               # row stride 33
+    assert not gemm_plan(130, 70, 33, a, a, a, a_si=36, b_sn=36, b_off=7, **kw).vec    # address off 16 bytes
+    p = gemm_plan(130, 70, 33, a, a, a, a_mc=True, a_sk=132, b_sn=1, b_sk=72, flags=_lib.GEMM_EXACT_F32, **kw)
+    assert (p.mode, p.a_kc, p.b_kc, p.vec) == (0, False, False, True)
+    assert gemm_plan(3970, 512, 40, a, a, a, **kw).tile == (128, 256) and gemm_plan(3970, 520, 40, a, a, a, **kw).tile == (128, 128)
+    assert gemm_plan(2100, 1800, 40, a, a, a, **kw).tile == (256, 256) and gemm_plan(2100, 1500, 40, a, a, a, **kw).tile == (128, 128)
+    p = gemm_plan(515, 515, 1030, a, a, a, split_k=True)
+    assert (p.tile, p.tiles, p.splits, p.kchunk) == ((256, 256), 9, 8, 144)
+    assert gemm_plan(515, 515, 1030, a, a, a, **kw).splits == 1
+    p = gemm_plan(0, 70, 33, a, a, a, **kw)
+    assert p.tiles == 0 and p.tile == (0, 0)
+    with pytest.raises(ValueError):
+        gemm_plan(4, 4, 4, a, a, a, b_sn=2, b_sk=2)
