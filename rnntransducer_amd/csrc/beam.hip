@@ -47,7 +47,7 @@ static int beam_search_launch(const rnnt_beam_desc* d, const rnnt_beam_timing* t
                  "beam_search: workspace must be 256-byte aligned and hold rnnt_hip_beam_workspace_bytes() bytes");
   beam_set_layout(k, d->workspace, l);
   const size_t lds = beam_lds_bytes(d->L, d->Hp, d->O, d->V);
-  RNNT_CHECK_ARG(lds <= 160 * 1024, "beam_search: state needs %zu B of LDS (> 160 KiB)", lds);
+  RNNT_CHECK_ARG(lds <= DEC_MAX_LDS, "beam_search: state needs %zu B of LDS (> 160 KiB)", lds);
   if (lds > 64 * 1024)
     RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)beam_search_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V, (hipStream_t)stream);

@@ -23,21 +23,12 @@ struct Hyp {       // an A or B entry (32 bytes)
 // per-stream header of the streaming workspace (ints at the start of a stream's workspace; STREAM only)
 enum { BS_NB = 0, BS_NSLOTS = 1, BS_NNODES = 2, BS_ROOT_LEN = 3, BS_STATUS = 4, BS_FRAMES = 5, BS_HEADER_BYTES = 256 };
 
-struct BeamK {
-  int T, B, V, Hp, O, L, cell, blank, beam, improved;
-  double state_beam, expand_beam;
+struct BeamK : PredNet {
+  int T, B, beam, improved;
   int max_cands, max_pops, max_states, max_nodes, max_len;
+  double state_beam, expand_beam;
   const float* A;
   const int* t_lens;
-  const float* emb;
-  const float* w_ih[DEC_MAX_LAYERS];
-  const float* w_hh[DEC_MAX_LAYERS];
-  const float* b_ih[DEC_MAX_LAYERS];
-  const float* b_hh[DEC_MAX_LAYERS];
-  const float* w_o;
-  const float* b_o;
-  const float* w_d;
-  long ld_d;
   const float* table;  // (V, G*Hp) layer-0 input projection
   char* ws;            // per-utterance workspaces, `ws_stride` bytes each
   size_t ws_stride, off_a, off_b, off_slots, off_remap, off_nodes, off_nmap;
@@ -485,23 +476,18 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
   }
 }
 
-// copies the descriptor fields both searches share (D: rnnt_beam_desc or rnnt_beam_stream_desc); t_lens, lens and the
-// workspace layout are the caller's
+// checks and copies the descriptor fields both searches share (D: rnnt_beam_desc or rnnt_beam_stream_desc); t_lens, lens and
+// the workspace layout are the caller's
 template <class D>
 static int beam_fill_common(const D* d, BeamK& k, const char* who) {
-  RNNT_CHECK_ARG(d->emb && d->w_o && d->b_o && d->w_d && d->tokens && d->scores && d->count && d->status,
-                 "%s: null pointer", who);
-  RNNT_CHECK_ARG(d->ld_d % 4 == 0 && (reinterpret_cast<uintptr_t>(d->w_d) & 15) == 0, "%s: fc slice must be 16-byte aligned", who);
-  k.T = d->T; k.B = d->B; k.V = d->V; k.Hp = d->Hp; k.O = d->O; k.L = d->L; k.cell = d->cell; k.blank = d->blank;
+  RNNT_CHECK_ARG(d->tokens && d->scores && d->count && d->status, "%s: null pointer", who);
+  const int rc = fill_prednet<true>(d, k, who);
+  if (rc != RNNT_OK) return rc;
+  k.T = d->T; k.B = d->B;
   k.beam = d->beam; k.improved = d->improved ? 1 : 0; k.state_beam = d->state_beam; k.expand_beam = d->expand_beam;
   k.max_cands = d->max_candidates; k.max_pops = d->max_pops; k.max_states = d->max_states; k.max_nodes = d->max_nodes;
   k.max_len = d->max_len;
-  k.A = d->A; k.emb = d->emb;
-  for (int i = 0; i < d->L; ++i) {
-    RNNT_CHECK_ARG(d->w_ih[i] && d->w_hh[i] && d->b_ih[i] && d->b_hh[i], "%s: null weight (layer %d)", who, i);
-    k.w_ih[i] = d->w_ih[i]; k.w_hh[i] = d->w_hh[i]; k.b_ih[i] = d->b_ih[i]; k.b_hh[i] = d->b_hh[i];
-  }
-  k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
+  k.A = d->A;
   k.tokens = d->tokens; k.scores = d->scores; k.count = d->count; k.status = d->status; k.stats = d->stats;
   k.commit = nullptr; k.ncommit = nullptr; k.rows = nullptr; k.frames = nullptr; k.commit_frames = nullptr;
   return RNNT_OK;
@@ -518,10 +504,9 @@ static inline void beam_set_layout(BeamK& k, void* workspace, const BeamLayout& 
 template <class D>
 static int beam_check_dims(const D* d, const char* who, int min_T) {
   RNNT_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  RNNT_CHECK_ARG(d->T >= min_T && d->B >= 1 && d->V >= 2 && d->Hp >= 4 && d->Hp % 4 == 0 && d->O >= 4 && d->O % 4 == 0,
-                 "%s: bad dims (V >= 2; hidden and output sizes must be multiples of 4)", who);
-  RNNT_CHECK_ARG(d->L >= 1 && d->L <= DEC_MAX_LAYERS, "%s: 1..%d prediction-net layers", who, DEC_MAX_LAYERS);
-  RNNT_CHECK_ARG(d->cell >= RNNT_CELL_LSTM && d->cell <= RNNT_CELL_RNN_RELU, "%s: unknown cell type", who);
+  RNNT_CHECK_ARG(d->T >= min_T && d->B >= 1 && d->V >= 2, "%s: bad dims (V >= 2)", who);
+  const int rc = prednet_check_dims<true>(d, who, RNNT_ERR_INVALID);
+  if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->blank >= 0 && d->blank < d->V && d->beam >= 1, "%s: bad blank / beam width", who);
   RNNT_CHECK_ARG(d->max_candidates >= 1 && d->max_pops >= 1 && d->max_states >= 1 && d->max_nodes >= 1 && d->max_len >= 1,
                  "%s: caps must be >= 1", who);

@@ -42,7 +42,7 @@ int stream_fill(const rnnt_beam_stream_desc* d, BeamK& k, const char* who) {
                  "%s: workspace must be 256-byte aligned and hold rnnt_hip_beam_stream_workspace_bytes() bytes", who);
   beam_set_layout(k, d->workspace, l);
   const size_t lds = beam_lds_bytes(d->L, d->Hp, d->O, d->V);
-  RNNT_CHECK_ARG(lds <= 160 * 1024, "%s: state needs %zu B of LDS (> 160 KiB)", who, lds);
+  RNNT_CHECK_ARG(lds <= DEC_MAX_LDS, "%s: state needs %zu B of LDS (> 160 KiB)", who, lds);
   return RNNT_OK;
 }
 

@@ -1,5 +1,8 @@
-// Prediction-net step pieces shared by the search kernels (decode.hip: greedy search and the batched step; beam.hip: beam
-// search).  One workgroup of DEC_THREADS threads owns one utterance; state vectors live in LDS, weights are streamed.
+// What the search kernels share (decode.hip: offline greedy search and the batched step; stream.hip: streaming greedy search;
+// beam_shared.hpp: both beam searches).  One workgroup of DEC_THREADS threads owns one utterance; state vectors live in LDS,
+// weights are streamed.  Here: the prediction-net block of every kernel-parameter struct (PredNet) with its one host-side
+// check and fill, the prediction-net step pieces, and THE greedy search: its parameter struct (GreedyK), its LDS carve-up and
+// size (GreedyLds, greedy_lds_bytes) and its frame loop (greedy_frames), which the offline and the streaming kernel both run.
 #pragma once
 #include "common.hpp"
 
@@ -7,6 +10,60 @@ namespace rnnt {
 
 constexpr int DEC_THREADS = 1024;
 constexpr int DEC_MAX_LAYERS = RNNT_DECODE_MAX_LAYERS;
+constexpr size_t DEC_MAX_LDS = 160 * 1024;
+
+// The prediction net and its half of the joint as the kernels read them; every search's parameter struct derives from it.
+// `blank` belongs to the block (every search but the batched step reads it), and it makes the ints six: 24 bytes, so `emb`
+// follows them at an 8-byte boundary and the struct has no hole.  A derived struct's own members start after `ld_d`, at the
+// end of this block.  (With five ints, and the 4-byte hole before `emb`, this toolchain's resource report showed the two
+// greedy kernels with 12-16 more bytes of scratch per lane; nothing relies on that.)
+struct PredNet {
+  int V, Hp, O, L, cell, blank;
+  const float* emb;  // (V, Hp)
+  const float* w_ih[DEC_MAX_LAYERS];
+  const float* w_hh[DEC_MAX_LAYERS];
+  const float* b_ih[DEC_MAX_LAYERS];
+  const float* b_hh[DEC_MAX_LAYERS];
+  const float* w_o;  // (O, Hp)
+  const float* b_o;  // (O)
+  const float* w_d;  // fc.weight[:, O_enc:] : (V, O) with row stride ld_d
+  long ld_d;
+};
+
+// Sizes of a descriptor's prediction net (D: any rnnt_*_desc that carries one).  JOINT = false: the batched step, whose
+// descriptor has no out_proj / fc half.  A layer count outside the limit returns `layers_rc`: the entries differ in it.
+template <bool JOINT, class D>
+int prednet_check_dims(const D* d, const char* who, int layers_rc) {
+  bool ok = d->Hp >= 4 && d->Hp % 4 == 0;
+  if constexpr (JOINT) ok = ok && d->O >= 4 && d->O % 4 == 0;
+  RNNT_CHECK_ARG(ok, "%s: bad dims (hidden and output sizes must be multiples of 4)", who);
+  if (d->L < 1 || d->L > DEC_MAX_LAYERS) {
+    set_error("%s: %d prediction-net layers (RNNT_DECODE_MAX_LAYERS = %d)", who, d->L, DEC_MAX_LAYERS);
+    return layers_rc;
+  }
+  RNNT_CHECK_ARG(d->cell >= RNNT_CELL_LSTM && d->cell <= RNNT_CELL_RNN_RELU, "%s: unknown cell type", who);
+  return RNNT_OK;
+}
+
+// Null, alignment and per-layer weight checks of a descriptor's prediction net, and its copy into k.  After
+// prednet_check_dims (d->L indexes the weight arrays).
+template <bool JOINT, class D>
+int fill_prednet(const D* d, PredNet& k, const char* who) {
+  RNNT_CHECK_ARG(d->emb, "%s: null pointer", who);
+  k.Hp = d->Hp; k.L = d->L; k.cell = d->cell; k.emb = d->emb;
+  if constexpr (JOINT) {
+    RNNT_CHECK_ARG(d->w_o && d->b_o && d->w_d, "%s: null pointer", who);
+    RNNT_CHECK_ARG(d->ld_d % 4 == 0 && (reinterpret_cast<uintptr_t>(d->w_d) & 15) == 0, "%s: fc slice must be 16-byte aligned", who);
+    k.V = d->V; k.O = d->O; k.blank = d->blank; k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
+  } else {
+    k.V = 0; k.O = 0; k.blank = 0; k.w_o = k.b_o = k.w_d = nullptr; k.ld_d = 0;
+  }
+  for (int l = 0; l < d->L; ++l) {   // last, as every entry always had it: after the other pointers and the alignment
+    RNNT_CHECK_ARG(d->w_ih[l] && d->w_hh[l] && d->b_ih[l] && d->b_hh[l], "%s: null weight (layer %d)", who, l);
+    k.w_ih[l] = d->w_ih[l]; k.w_hh[l] = d->w_hh[l]; k.b_ih[l] = d->b_ih[l]; k.b_hh[l] = d->b_hh[l];
+  }
+  return RNNT_OK;
+}
 
 // y[r] = dot(W[r, :cols], x) (+ bias[r]) for r in [0, rows): one wave per group of RU rows (lanes along the contiguous k),
 // 16 waves per pass.  All RU rows' loads are issued before any is consumed: a single row per wave keeps only 2 KB in
@@ -114,6 +171,114 @@ __device__ __forceinline__ float token_logp(const float* __restrict__ a, const f
   for (int w = 1; w < DEC_THREADS / 64; ++w) r += red[w];
   __syncthreads();
   return -logf(r);
+}
+
+// ---- greedy search ----------------------------------------------------------------------------------------------------
+// Per utterance, for t in 0..Tb-1: up to `max_iters` times { tok = argmax_v (A[t] + C); if tok == blank: stop this frame;
+// append tok unless it equals the last appended token; advance the prediction net with tok }.  The offline search
+// (decode.hip) starts from the primed state; the streaming search (stream.hip) from the state the last chunk left.
+struct GreedyK : PredNet {
+  int T, B, max_iters, max_out;
+  const float* A;      // (T,B,V) time-major, bias included
+  const int* lens;     // (B) frames to visit per utterance; offline: or null (= T)
+  const int* rows;     // prime: the rows to (re)initialise
+  float* h;            // carried state, null offline: (L,B,Hp)
+  float* c;            //   (L,B,Hp) LSTM only
+  float* Cs;           //   (B,V) joint half of the current state
+  long long* last;     //   (B) last appended token
+  long long* tokens;   // (B,max_out)
+  int* ntok;           // (B)
+  int* frames;         // (B,max_out) frame of each appended token, or null (the untimed entries)
+  float* logp;         // (B,max_out) log-softmax of the joint at the appended token; with frames
+  const long long* frame_base;  // streaming: (B) frames the stream consumed before this chunk, or null (0)
+};
+
+// dynamic LDS of the greedy kernels: h[L][Hp] | c[L][Hp] | gi[4Hp] | gh[4Hp] | x[Hp] | dec[O] | Cv[V] | redv[16] redi[16] | ctl[8]
+struct GreedyLds {
+  float *h, *c, *gi, *gh, *x, *dec, *Cv, *redv;
+  int *redi, *ctl;  // ctl[0] = token chosen this evaluation
+  __device__ GreedyLds(char* smem, int L, int Hp, int O, int V) {
+    h = reinterpret_cast<float*>(smem);
+    c = h + L * Hp;
+    gi = c + L * Hp;
+    gh = gi + 4 * Hp;
+    x = gh + 4 * Hp;
+    dec = x + Hp;
+    Cv = dec + O;
+    redv = Cv + V;
+    redi = reinterpret_cast<int*>(redv + 16);
+    ctl = redi + 16;
+  }
+};
+inline size_t greedy_lds_bytes(int L, int Hp, int O, int V) {
+  return ((size_t)2 * L * Hp + 8 * Hp + Hp + O + V + 32 + 8) * 4;
+}
+
+// frame number reported for a chunk's frame 0: what the stream consumed before (timed streaming entry), else 0
+__device__ __forceinline__ int greedy_frame_base(const GreedyK& p, int b) {
+  return p.frames && p.frame_base ? (int)p.frame_base[b] : 0;   // frames are int32: reset before 2^31 frames
+}
+
+// one prediction-net step with input token `tok`, then C = gelu(out_proj(h_last)) . W_d^T
+__device__ __forceinline__ void prednet_step_lds(const GreedyK& p, GreedyLds& s, int tok) {
+  for (int i = threadIdx.x; i < p.Hp; i += DEC_THREADS) s.x[i] = p.emb[(long)tok * p.Hp + i];
+  __syncthreads();
+  prednet_cells(p, s.h, s.c, s.gi, s.gh, s.x, nullptr);
+  prednet_joint_half(p, s.h + (p.L - 1) * p.Hp, s.dec, s.Cv);
+}
+
+// tok = argmax_v (a[v] + Cv[v]); lowest index among equal maxima (torch.argmax on a 1-D tensor).  Every thread returns it.
+__device__ __forceinline__ int frame_argmax(const float* a, const float* Cv, int V, GreedyLds& s) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float best = -__builtin_huge_valf();
+  int bi = 0x7fffffff;
+  for (int v = tid; v < V; v += DEC_THREADS) {
+    const float z = a[v] + Cv[v];
+    if (z > best || (z == best && v < bi)) { best = z; bi = v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  if (lane == 0) { s.redv[wave] = best; s.redi[wave] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < DEC_THREADS / 64; ++w)
+      if (s.redv[w] > best || (s.redv[w] == best && s.redi[w] < bi)) { best = s.redv[w]; bi = s.redi[w]; }
+    s.ctl[0] = bi;
+  }
+  __syncthreads();
+  const int tok = s.ctl[0];
+  __syncthreads();
+  return tok;
+}
+
+// The frame loop of utterance b over frames [0, Tb) of p.A, from the state in `s` (h, c, Cv), the last appended token `last`
+// and n tokens appended so far; frame t is reported as t_base + t.  Leaves the state after the last step in `s`.
+__device__ __forceinline__ void greedy_frames(const GreedyK& p, GreedyLds& s, int b, int Tb, int t_base, long long& last, int& n) {
+  const int tid = threadIdx.x, V = p.V;
+  for (int t = 0; t < Tb; ++t) {
+    for (int u = 0; u < p.max_iters; ++u) {
+      const float* a = p.A + ((long)t * p.B + b) * V;
+      const int tok = frame_argmax(a, s.Cv, V, s);
+      if (tok == p.blank) break;
+      if (last != tok) {
+        if (p.frames && n < p.max_out) {  // timed entries: one more V-wide reduction per appended token
+          const float lp = token_logp(a, s.Cv, V, tok, s.redv);
+          if (tid == 0) {
+            p.frames[(long)b * p.max_out + n] = t_base + t;
+            p.logp[(long)b * p.max_out + n] = lp;
+          }
+        }
+        if (n < p.max_out && tid == 0) p.tokens[(long)b * p.max_out + n] = tok;
+        ++n;
+        last = tok;
+      }
+      prednet_step_lds(p, s, tok);
+    }
+  }
 }
 
 }  // namespace rnnt

@@ -12,10 +12,11 @@
 //     of a wave accumulates k = i, i + 64, ... with fmaf, then a fixed butterfly adds the 64 lane partials.
 //  2. stream_gemm_kernel: out_proj of the top layer and the encoder half of the joint, A = gelu(enc) W_e^T + bias.  Every
 //     output element is one k-ordered fmaf chain from k = 0 (the tiling only decides which thread runs it), bias added last.
-//  3. stream_greedy_kernel: the greedy search of decode.hip continued from carried state (prediction-net h / c, the joint
-//     half C of that state, the last appended token) instead of priming; stream_prime_kernel primes listed rows as
-//     transducer.py:116-119 does (zero state, one blank step).  Both use decode_shared.hpp, so a step is the same code as
-//     in the offline search.
+//  3. stream_greedy_kernel: the greedy search continued from carried state (prediction-net h / c, the joint half C of that
+//     state, the last appended token) instead of priming; stream_prime_kernel primes listed rows as transducer.py:116-119
+//     does (zero state, one blank step).  The search loop is greedy_frames of decode_shared.hpp, the one the offline
+//     kernel (decode.hip) runs, on the same parameter struct and LDS carve-up: this file only loads and stores the state
+//     around it.
 #include "decode_shared.hpp"
 
 namespace rnnt {
@@ -248,57 +249,7 @@ __global__ void __launch_bounds__(SR_THREADS) stream_gemm_kernel(const StreamGem
   }
 }
 
-struct StreamGreedyK {
-  int T, B, V, Hp, O, L, cell, blank, max_iters, max_out;
-  const float* A;    // (T,B,V)
-  const int* lens;   // (B)
-  const int* rows;   // prime: the rows to (re)initialise
-  const float* emb;
-  const float* w_ih[DEC_MAX_LAYERS];
-  const float* w_hh[DEC_MAX_LAYERS];
-  const float* b_ih[DEC_MAX_LAYERS];
-  const float* b_hh[DEC_MAX_LAYERS];
-  const float* w_o;
-  const float* b_o;
-  const float* w_d;
-  long ld_d;
-  float* h;          // (L,B,Hp)
-  float* c;          // (L,B,Hp) LSTM only
-  float* Cs;         // (B,V) joint half of the current state
-  long long* last;   // (B)
-  long long* tokens; // (B,max_out)
-  int* ntok;         // (B)
-  int* frames;       // (B,max_out) absolute frame of each appended token, or null (the untimed entry)
-  float* logp;       // (B,max_out) with frames
-  const long long* frame_base;  // (B) frames the stream consumed before this chunk, or null (0)
-};
-
-// dynamic LDS as greedy_decode_kernel: h[L][Hp] | c[L][Hp] | gi[4Hp] | gh[4Hp] | x[Hp] | dec[O] | Cv[V] | red | ctl
-struct GreedyLds {
-  float *h, *c, *gi, *gh, *x, *dec, *Cv, *redv;
-  int *redi, *ctl;
-  __device__ GreedyLds(char* smem, int L, int Hp, int O, int V) {
-    h = reinterpret_cast<float*>(smem);
-    c = h + L * Hp;
-    gi = c + L * Hp;
-    gh = gi + 4 * Hp;
-    x = gh + 4 * Hp;
-    dec = x + Hp;
-    Cv = dec + O;
-    redv = Cv + V;
-    redi = reinterpret_cast<int*>(redv + 16);
-    ctl = redi + 16;
-  }
-};
-
-__device__ __forceinline__ void prednet_step_lds(const StreamGreedyK& p, GreedyLds& s, int tok) {
-  for (int i = threadIdx.x; i < p.Hp; i += DEC_THREADS) s.x[i] = p.emb[(long)tok * p.Hp + i];
-  __syncthreads();
-  prednet_cells(p, s.h, s.c, s.gi, s.gh, s.x, nullptr);
-  prednet_joint_half(p, s.h + (p.L - 1) * p.Hp, s.dec, s.Cv);
-}
-
-__device__ __forceinline__ void state_out(const StreamGreedyK& p, const GreedyLds& s, int b) {
+__device__ __forceinline__ void state_out(const GreedyK& p, const GreedyLds& s, int b) {
   const int Hp = p.Hp;
   for (int i = threadIdx.x; i < p.L * Hp; i += DEC_THREADS) {
     const int l = i / Hp, j = i - l * Hp;
@@ -309,7 +260,7 @@ __device__ __forceinline__ void state_out(const StreamGreedyK& p, const GreedyLd
 }
 
 // rows[blockIdx.x]: zero state, one prediction-net step on blank (transducer.py:116-119), last token = blank
-__global__ void __launch_bounds__(DEC_THREADS) stream_prime_kernel(const StreamGreedyK p) {
+__global__ void __launch_bounds__(DEC_THREADS) stream_prime_kernel(const GreedyK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   GreedyLds s(smem, p.L, p.Hp, p.O, p.V);
   const int b = p.rows[blockIdx.x];
@@ -320,10 +271,11 @@ __global__ void __launch_bounds__(DEC_THREADS) stream_prime_kernel(const StreamG
   if (threadIdx.x == 0) p.last[b] = p.blank;
 }
 
-__global__ void __launch_bounds__(DEC_THREADS) stream_greedy_kernel(const StreamGreedyK p) {
+// continues the search of decode_shared.hpp from the carried state over this chunk's frames
+__global__ void __launch_bounds__(DEC_THREADS) stream_greedy_kernel(const GreedyK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   GreedyLds s(smem, p.L, p.Hp, p.O, p.V);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, Hp = p.Hp, V = p.V;
+  const int tid = threadIdx.x, b = blockIdx.x, Hp = p.Hp, V = p.V;
   int Tb = p.lens[b];
   Tb = Tb < 0 ? 0 : (Tb > p.T ? p.T : Tb);
   if (Tb == 0) {   // no frames: the state stays bitwise as it is
@@ -337,57 +289,9 @@ __global__ void __launch_bounds__(DEC_THREADS) stream_greedy_kernel(const Stream
   }
   for (int v = tid; v < V; v += DEC_THREADS) s.Cv[v] = p.Cs[(long)b * V + v];
   __syncthreads();
-
-  // tok = argmax_v (A[t,b,v] + Cv[v]), lowest index among equal maxima (as greedy_decode_kernel)
-  auto frame_argmax = [&](int t) -> int {
-    const float* a = p.A + ((long)t * p.B + b) * V;
-    float best = -__builtin_huge_valf();
-    int bi = 0x7fffffff;
-    for (int v = tid; v < V; v += DEC_THREADS) {
-      const float z = a[v] + s.Cv[v];
-      if (z > best || (z == best && v < bi)) { best = z; bi = v; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { s.redv[wave] = best; s.redi[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < DEC_THREADS / 64; ++w)
-        if (s.redv[w] > best || (s.redv[w] == best && s.redi[w] < bi)) { best = s.redv[w]; bi = s.redi[w]; }
-      s.ctl[0] = bi;
-    }
-    __syncthreads();
-    const int tok = s.ctl[0];
-    __syncthreads();
-    return tok;
-  };
-
   int n = 0;
   long long last = p.last[b];
-  const int t_base = p.frames && p.frame_base ? (int)p.frame_base[b] : 0;   // frames are int32: reset before 2^31 frames
-  for (int t = 0; t < Tb; ++t) {
-    for (int u = 0; u < p.max_iters; ++u) {
-      const int tok = frame_argmax(t);
-      if (tok == p.blank) break;
-      if (last != tok) {
-        if (p.frames && n < p.max_out) {  // timed entry (as greedy_decode_kernel)
-          const float lp = token_logp(p.A + ((long)t * p.B + b) * V, s.Cv, V, tok, s.redv);
-          if (tid == 0) {
-            p.frames[(long)b * p.max_out + n] = t_base + t;
-            p.logp[(long)b * p.max_out + n] = lp;
-          }
-        }
-        if (n < p.max_out && tid == 0) p.tokens[(long)b * p.max_out + n] = tok;
-        ++n;
-        last = tok;
-      }
-      prednet_step_lds(p, s, tok);
-    }
-  }
+  greedy_frames(p, s, b, Tb, greedy_frame_base(p, b), last, n);
   state_out(p, s, b);
   if (tid == 0) {
     p.last[b] = last;
@@ -419,35 +323,21 @@ int launch_gemm(const StreamGemmK& p, hipStream_t s) {
   return RNNT_OK;
 }
 
-size_t greedy_lds_bytes(const rnnt_stream_greedy_desc* d) {
-  return ((size_t)2 * d->L * d->Hp + 8 * d->Hp + d->Hp + d->O + d->V + 32 + 8) * 4;
-}
-
-int fill_greedy(const rnnt_stream_greedy_desc* d, StreamGreedyK& k, const char* who) {
-  RNNT_CHECK_ARG(d->B >= 1 && d->V >= 1 && d->Hp >= 4 && d->Hp % 4 == 0 && d->O >= 4 && d->O % 4 == 0,
-                 "%s: bad dims (hidden and output sizes must be multiples of 4)", who);
-  if (d->L < 1 || d->L > DEC_MAX_LAYERS) {
-    set_error("%s: %d prediction-net layers (RNNT_DECODE_MAX_LAYERS = %d)", who, d->L, DEC_MAX_LAYERS);
-    return RNNT_ERR_UNSUPPORTED;
-  }
-  RNNT_CHECK_ARG(d->cell >= RNNT_CELL_LSTM && d->cell <= RNNT_CELL_RNN_RELU, "%s: unknown cell type", who);
+// checks and copies what the reset and the chunk entries share; A, lens, the outputs and max_iters / max_out are the chunk's
+int fill_greedy(const rnnt_stream_greedy_desc* d, GreedyK& k, const char* who) {
+  RNNT_CHECK_ARG(d->B >= 1 && d->V >= 1, "%s: bad dims", who);
+  int rc = prednet_check_dims<true>(d, who, RNNT_ERR_UNSUPPORTED);
+  if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->blank >= 0 && d->blank < d->V, "%s: blank outside [0, V)", who);
-  RNNT_CHECK_ARG(d->emb && d->w_o && d->b_o && d->w_d && d->h && d->C && d->last && (d->c || d->cell != RNNT_CELL_LSTM),
-                 "%s: null pointer", who);
-  RNNT_CHECK_ARG(d->ld_d % 4 == 0 && (reinterpret_cast<uintptr_t>(d->w_d) & 15) == 0, "%s: fc slice must be 16-byte aligned", who);
-  const size_t lds = greedy_lds_bytes(d);
-  if (lds > SR_MAX_LDS) {
+  RNNT_CHECK_ARG(d->h && d->C && d->last && (d->c || d->cell != RNNT_CELL_LSTM), "%s: null pointer", who);
+  if ((rc = fill_prednet<true>(d, k, who)) != RNNT_OK) return rc;
+  const size_t lds = greedy_lds_bytes(d->L, d->Hp, d->O, d->V);
+  if (lds > DEC_MAX_LDS) {
     set_error("%s: prediction-net state and joint row need %zu B of LDS (limit 160 KiB)", who, lds);
     return RNNT_ERR_UNSUPPORTED;
   }
-  k.T = d->T; k.B = d->B; k.V = d->V; k.Hp = d->Hp; k.O = d->O; k.L = d->L; k.cell = d->cell; k.blank = d->blank;
-  k.max_iters = d->max_iters; k.max_out = d->max_out;
-  k.A = d->A; k.lens = d->lens; k.rows = nullptr; k.emb = d->emb;
-  for (int l = 0; l < d->L; ++l) {
-    RNNT_CHECK_ARG(d->w_ih[l] && d->w_hh[l] && d->b_ih[l] && d->b_hh[l], "%s: null weight (layer %d)", who, l);
-    k.w_ih[l] = d->w_ih[l]; k.w_hh[l] = d->w_hh[l]; k.b_ih[l] = d->b_ih[l]; k.b_hh[l] = d->b_hh[l];
-  }
-  k.w_o = d->w_o; k.b_o = d->b_o; k.w_d = d->w_d; k.ld_d = d->ld_d;
+  k.T = d->T; k.B = d->B; k.max_iters = d->max_iters; k.max_out = d->max_out;
+  k.A = d->A; k.lens = d->lens; k.rows = nullptr;
   k.h = d->h; k.c = d->c; k.Cs = d->C; k.last = (long long*)d->last;
   k.tokens = (long long*)d->tokens; k.ntok = d->ntok;
   k.frames = nullptr; k.logp = nullptr; k.frame_base = nullptr;
@@ -527,13 +417,13 @@ extern "C" int rnnt_hip_stream_rnn_chunk(const rnnt_stream_rnn_desc* d, void* st
 
 extern "C" int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, const int32_t* rows, int32_t n_rows, void* stream) {
   RNNT_CHECK_ARG(d != nullptr, "stream_greedy_reset: null descriptor");
-  StreamGreedyK k;
+  GreedyK k;
   const int rc = fill_greedy(d, k, "stream_greedy_reset");
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(n_rows >= 0 && (rows || n_rows == 0), "stream_greedy_reset: bad row list");
   if (n_rows == 0) return RNNT_OK;
   k.rows = rows;
-  const size_t lds = greedy_lds_bytes(d);
+  const size_t lds = greedy_lds_bytes(d->L, d->Hp, d->O, d->V);
   if (lds > 64 * 1024)
     RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)stream_prime_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)n_rows * d->V, (hipStream_t)stream);
@@ -545,13 +435,13 @@ extern "C" int rnnt_hip_stream_greedy_reset(const rnnt_stream_greedy_desc* d, co
 // both entries: `timing` null = the untimed search (the kernel's frames pointer is null, nothing else differs)
 static int stream_greedy_launch(const rnnt_stream_greedy_desc* d, const rnnt_greedy_timing* timing, void* stream) {
   RNNT_CHECK_ARG(d != nullptr, "stream_greedy: null descriptor");
-  StreamGreedyK k;
+  GreedyK k;
   const int rc = fill_greedy(d, k, "stream_greedy");
   if (rc != RNNT_OK) return rc;
   if (timing) { k.frames = timing->frames; k.logp = timing->logp; k.frame_base = (const long long*)timing->frame_base; }
   RNNT_CHECK_ARG(d->T >= 1 && d->max_iters >= 1 && d->max_out >= 1, "stream_greedy: bad T / max_iters / max_out");
   RNNT_CHECK_ARG(d->A && d->lens && d->tokens && d->ntok, "stream_greedy: null pointer");
-  const size_t lds = greedy_lds_bytes(d);
+  const size_t lds = greedy_lds_bytes(d->L, d->Hp, d->O, d->V);
   if (lds > 64 * 1024)
     RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)stream_greedy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V, (hipStream_t)stream);

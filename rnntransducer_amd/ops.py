@@ -891,6 +891,52 @@ class TimedTokens(NamedTuple):
     logp: torch.Tensor     # float32: log-softmax of the joint at that evaluation, at the chosen token
 
 
+def _check_rnn_weights(rnn_weights, cell: int, I0: int, H: int, what: str) -> None:
+    """Shapes of a uni-directional stack's [w_ih, w_hh, b_ih, b_hh] per layer (layer 0 reads I0 inputs, the others H)."""
+    ngate = {0: 4, 1: 3, 2: 1, 3: 1}.get(cell)
+    if ngate is None or not rnn_weights or len(rnn_weights) % 4 != 0:
+        raise ValueError(f"{what}: cell {cell!r} / {len(rnn_weights)} weight tensors")
+    for i, w in enumerate(rnn_weights):
+        want = [(ngate * H, I0 if i < 4 else H), (ngate * H, H), (ngate * H,), (ngate * H,)][i % 4]
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want:
+            raise ValueError(f"{what} weight #{i}: expected shape {want}, "
+                             f"got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+
+
+def _fill_prednet_weights(d, emb_w, rnn_weights, cell: int, what: str) -> list:
+    """The prediction net of a search or step descriptor: checks the layer limit and every weight shape against the embedding
+    width (the kernels index raw pointers), fills d.Hp, d.L, d.cell, d.emb and the per-layer weights.  -> tensors to keep alive."""
+    Hp, L = emb_w.shape[1], len(rnn_weights) // 4
+    if L > _lib.DECODE_MAX_LAYERS:
+        raise ValueError(f"{what}: {L} prediction-net layers (RNNT_DECODE_MAX_LAYERS = {_lib.DECODE_MAX_LAYERS})")
+    _check_rnn_weights(rnn_weights, cell, Hp, Hp, "prediction net")
+    keep = [_f32c(t, "prediction-net weight") for t in rnn_weights] + [_f32c(emb_w, "embedding")]
+    d.Hp, d.L, d.cell, d.emb = Hp, L, cell, _addr(keep[-1])
+    for l in range(L):
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
+    return keep
+
+
+def _fill_prednet(d, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, what: str) -> list:
+    """The prediction net and its half of the joint of a search descriptor (greedy or beam, offline or streaming): fc, out_proj
+    and embedding checked against each other (a row of the embedding per fc output: the kernels read emb[tok] for any tok < V),
+    0 <= blank < V, then _fill_prednet_weights; fills d.V, d.O, d.blank, d.w_o, d.b_o and the fc slice d.w_d / d.ld_d, whose
+    offset Oe = Ocat - Od is the encoder's share of the joint input.  -> tensors to keep alive."""
+    V, Ocat = fc_w.shape
+    Od, Hp = out_w.shape[0], emb_w.shape[1]
+    if not 1 <= Od < Ocat or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or emb_w.shape[0] < V:
+        raise ValueError(f"{what}: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding {tuple(emb_w.shape)} "
+                         "do not fit together (the embedding needs a row per fc output)")
+    if not 0 <= blank < V:
+        raise ValueError(f"{what}: blank {blank} outside [0,{V})")
+    keep = _fill_prednet_weights(d, emb_w, rnn_weights, cell, what)
+    keep += [_f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias"), _f32c(fc_w, "fc weight")]
+    d.V, d.O, d.blank = V, Od, blank
+    d.w_o, d.b_o = _addr(keep[-3]), _addr(keep[-2])
+    d.w_d, d.ld_d = _addr(keep[-1], Ocat - Od), Ocat
+    return keep
+
+
 def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                   cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, max_iters: int,
                   t_lens: Optional[torch.Tensor] = None, timing: bool = False, max_out: Optional[int] = None):
@@ -903,35 +949,22 @@ def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, 
     enc_tm = _f32c(enc_tm, "encoder outputs")
     T, B, Oe = enc_tm.shape
     V, Ocat = fc_w.shape
-    Od = Ocat - Oe
-    Hp = emb_w.shape[1]
-    L = len(rnn_weights) // 4
-    if L > _lib.DECODE_MAX_LAYERS:
-        raise ValueError(f"greedy decode supports at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
-    _check_prednet_weights(rnn_weights, cell, Hp)
-    if Od < 1 or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or tuple(fc_b.shape) != (V,) or emb_w.shape[0] < 1:
-        raise ValueError(f"greedy decode: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding {tuple(emb_w.shape)} "
-                         f"do not fit encoder width {Oe}")
-    if not 0 <= blank < V or max_iters < 1:
-        raise ValueError(f"greedy decode: blank {blank} outside [0,{V}) or max_iters {max_iters} < 1")
+    d = _lib.DecodeDesc()
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "greedy decode")
+    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
+        raise ValueError(f"greedy decode: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
+                         f"encoder width {Oe}")
+    if max_iters < 1:
+        raise ValueError(f"greedy decode: max_iters {max_iters} < 1")
     A = torch.empty(T, B, V, device=enc_tm.device, dtype=torch.float32)
-    gemm(T * B, V, Oe, enc_tm, fc_w, A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
     max_out = T * max_iters if max_out is None else int(max_out)
     if max_out < 1:
         raise ValueError(f"greedy decode: max_out {max_out} < 1")
     tokens = torch.full((B, max_out), blank, device=enc_tm.device, dtype=torch.int64)
     ntok = torch.zeros(B, device=enc_tm.device, dtype=torch.int32)
-    d = _lib.DecodeDesc()
-    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell = T, B, V, Hp, Od, L, cell
-    d.blank, d.max_iters, d.max_out = blank, max_iters, max_out
-    d.A, d.t_lens, d.emb = _addr(A), _addr(t_lens), _addr(emb_w)
-    keep = []
-    for l in range(L):
-        w = [_f32c(t, "prediction-net weight") for t in rnn_weights[4 * l:4 * l + 4]]
-        keep.append(w)
-        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in w)
-    d.w_o, d.b_o = _addr(out_w), _addr(out_b)
-    d.w_d, d.ld_d = _addr(fc_w, Oe), Ocat
+    d.T, d.B, d.max_iters, d.max_out = T, B, max_iters, max_out
+    d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.ntok = _addr(tokens), _addr(ntok)
     if timing:
         frames = torch.full((B, max_out), -1, device=enc_tm.device, dtype=torch.int32)
@@ -943,41 +976,21 @@ def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, 
     return tokens, ntok
 
 
-def _check_prednet_weights(rnn_weights, cell: int, H: int) -> None:
-    """Host-side shape check of a uni-directional prediction-net stack (input width == hidden width): the decode kernels
-    index raw pointers."""
-    ngate = {0: 4, 1: 3, 2: 1, 3: 1}.get(cell)
-    if ngate is None or len(rnn_weights) % 4 != 0 or not rnn_weights:
-        raise ValueError(f"prediction net: cell {cell!r} / {len(rnn_weights)} weight tensors")
-    for i, w in enumerate(rnn_weights):
-        want = [(ngate * H, H), (ngate * H, H), (ngate * H,), (ngate * H,)][i % 4]
-        if tuple(w.shape) != want:
-            raise ValueError(f"prediction-net weight #{i}: expected {want}, got {tuple(w.shape)}")
-
-
 def prednet_step(tokens: torch.Tensor, emb_w: torch.Tensor, rnn_weights, cell: int, h_in=None, c_in=None):
     """One prediction-net step for a batch with carried state (decoder.py:121-123).  tokens (B,) int64; h_in / c_in (L,B,H)
     or None (zeros) -> (h_out, c_out) with c_out None unless LSTM; the layer output is h_out[-1]."""
     _need_gpu(tokens, emb_w)
     L = len(rnn_weights) // 4
     B, H = tokens.numel(), emb_w.shape[1]
-    if L > _lib.DECODE_MAX_LAYERS:
-        raise ValueError(f"at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
-    _check_prednet_weights(rnn_weights, cell, H)
+    d = _lib.PrednetStepDesc()
+    keep = _fill_prednet_weights(d, emb_w, rnn_weights, cell, "prediction-net step")
     for name, t in (("h_in", h_in), ("c_in", c_in)):
         if t is not None and tuple(t.shape) != (L, B, H):
             raise ValueError(f"{name} must be (L,B,H) = ({L},{B},{H}), got {tuple(t.shape)}")
     tokens = tokens.reshape(-1).to(torch.int64).contiguous()
     h_out = torch.empty(L, B, H, device=emb_w.device, dtype=torch.float32)
     c_out = torch.empty_like(h_out) if cell == _lib.CELL_LSTM else None
-    d = _lib.PrednetStepDesc()
-    d.B, d.Hp, d.L, d.cell = B, H, L, cell
-    d.tokens, d.emb = _addr(tokens), _addr(emb_w)
-    keep = []
-    for l in range(L):
-        w = [_f32c(t, "prediction-net weight") for t in rnn_weights[4 * l:4 * l + 4]]
-        keep.append(w)
-        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in w)
+    d.B, d.tokens = B, _addr(tokens)
     h_in = None if h_in is None else _f32c(h_in, "h_in")
     c_in = None if c_in is None else _f32c(c_in, "c_in")
     d.h_in, d.c_in, d.h_out, d.c_out = _addr(h_in), _addr(c_in), _addr(h_out), _addr(c_out)
@@ -1006,29 +1019,24 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     enc_tm = _f32c(enc_tm, "encoder outputs")
     T, B, Oe = enc_tm.shape
     V, Ocat = fc_w.shape
-    Od = Ocat - Oe
-    Hp = emb_w.shape[1]
-    L = len(rnn_weights) // 4
-    if L > _lib.DECODE_MAX_LAYERS:
-        raise ValueError(f"beam search supports at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
-    _check_prednet_weights(rnn_weights, cell, Hp)
-    if Od < 1 or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or tuple(fc_b.shape) != (V,) or emb_w.shape[0] < V:
-        raise ValueError(f"beam search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding {tuple(emb_w.shape)} "
-                         f"do not fit encoder width {Oe}")
-    if not 0 <= blank < V or V < 2 or beam < 1:
-        raise ValueError(f"beam search: blank {blank} outside [0,{V}), V {V} < 2 or beam {beam} < 1")
+    d = _lib.BeamDesc()
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "beam search")
+    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
+        raise ValueError(f"beam search: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
+                         f"encoder width {Oe}")
+    if V < 2 or beam < 1:
+        raise ValueError(f"beam search: V {V} < 2 or beam {beam} < 1")
     max_candidates = max_pops * V if max_candidates is None else max_candidates
     max_states = 3 * max_pops if max_states is None else max_states
     max_len = 4 * T + 64 if max_len is None else max_len
     dev = enc_tm.device
     A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
-    gemm(T * B, V, Oe, enc_tm, fc_w, A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
     tokens = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
     lens = torch.empty(B, beam, device=dev, dtype=torch.int32)
     scores = torch.empty(B, beam, device=dev, dtype=torch.float64)
     small = torch.empty(B, 2 + _lib.BEAM_NSTATS, device=dev, dtype=torch.int32)   # count | status | stats: one transfer
-    d = _lib.BeamDesc()
-    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = T, B, V, Hp, Od, L, cell, blank
+    d.T, d.B = T, B
     d.beam, d.improved, d.state_beam, d.expand_beam = beam, int(bool(improved)), float(state_beam), float(expand_beam)
     d.max_candidates, d.max_pops, d.max_states, d.max_nodes, d.max_len = max_candidates, max_pops, max_states, max_nodes, max_len
     ws_bytes = _lib.lib().rnnt_hip_beam_workspace_bytes(C.byref(d))
@@ -1036,14 +1044,7 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
         raise ValueError("beam search: invalid sizes or caps (all caps must be >= 1)")
     ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
     d.workspace, d.workspace_bytes = (_addr(ws) + 255) // 256 * 256, ws_bytes
-    d.A, d.t_lens, d.emb = _addr(A), _addr(t_lens), _addr(emb_w)
-    keep = []
-    for l in range(L):
-        w = [_f32c(t, "prediction-net weight") for t in rnn_weights[4 * l:4 * l + 4]]
-        keep.append(w)
-        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in w)
-    d.w_o, d.b_o = _addr(out_w), _addr(out_b)
-    d.w_d, d.ld_d = _addr(fc_w, Oe), Ocat
+    d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
     d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
     if frames:
@@ -1083,18 +1084,6 @@ def _check_buffer(name: str, t: Optional[torch.Tensor], shape, dtype, device) ->
         got = (tuple(t.shape), t.dtype, str(t.device), "contiguous" if t.is_contiguous() else "strided") \
             if isinstance(t, torch.Tensor) else type(t).__name__
         raise ValueError(f"{name}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got {got}")
-
-
-def _check_rnn_weights(rnn_weights, cell: int, I0: int, H: int, what: str) -> None:
-    """Shapes of a uni-directional stack's [w_ih, w_hh, b_ih, b_hh] per layer (layer 0 reads I0 inputs, the others H)."""
-    ngate = {0: 4, 1: 3, 2: 1, 3: 1}.get(cell)
-    if ngate is None or not rnn_weights or len(rnn_weights) % 4 != 0:
-        raise ValueError(f"{what}: cell {cell!r} / {len(rnn_weights)} weight tensors")
-    for i, w in enumerate(rnn_weights):
-        want = [(ngate * H, I0 if i < 4 else H), (ngate * H, H), (ngate * H,), (ngate * H,)][i % 4]
-        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want:
-            raise ValueError(f"{what} weight #{i}: expected shape {want}, "
-                             f"got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
 
 
 def stream_rnn_chunk(chunk: torch.Tensor, lens: torch.Tensor, rnn_weights, cell: int, h: torch.Tensor, c: Optional[torch.Tensor],
@@ -1156,32 +1145,15 @@ def stream_rnn_chunk(chunk: torch.Tensor, lens: torch.Tensor, rnn_weights, cell:
 
 def _stream_greedy_desc(T: int, B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, h, c, Cs, last):
     """Descriptor of the streaming search; every weight and state shape checked against the others (raw pointers)."""
-    V, Ocat = fc_w.shape
-    Od = out_w.shape[0]
-    Hp, L = emb_w.shape[1], len(rnn_weights) // 4
-    if L > _lib.DECODE_MAX_LAYERS:
-        raise RnntHipError(f"streaming greedy search: {L} prediction-net layers (RNNT_DECODE_MAX_LAYERS = {_lib.DECODE_MAX_LAYERS})")
-    _check_prednet_weights(rnn_weights, cell, Hp)
-    if not 1 <= Od < Ocat or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or emb_w.shape[0] < V:
-        raise ValueError(f"streaming greedy search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding "
-                         f"{tuple(emb_w.shape)} do not fit together (the embedding needs a row per fc output)")
-    if not 0 <= blank < V:
-        raise ValueError(f"streaming greedy search: blank {blank} outside [0,{V})")
-    dev = fc_w.device
+    d = _lib.StreamGreedyDesc()
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "streaming greedy search")
+    V, Hp, L, dev = d.V, d.Hp, d.L, fc_w.device
     _check_buffer("prediction-net h", h, (L, B, Hp), torch.float32, dev)
     if cell == _lib.CELL_LSTM:
         _check_buffer("prediction-net c", c, (L, B, Hp), torch.float32, dev)
     _check_buffer("prediction-net joint half", Cs, (B, V), torch.float32, dev)
     _check_buffer("last token", last, (B,), torch.int64, dev)
-    d = _lib.StreamGreedyDesc()
-    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = T, B, V, Hp, Od, L, cell, blank
-    keep = [_f32c(t, "prediction-net weight") for t in rnn_weights]
-    keep += [_f32c(emb_w, "embedding"), _f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias"), _f32c(fc_w, "fc weight")]
-    d.emb = _addr(keep[-4])
-    for l in range(L):
-        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
-    d.w_o, d.b_o = _addr(keep[-3]), _addr(keep[-2])
-    d.w_d, d.ld_d = _addr(keep[-1], Ocat - Od), Ocat
+    d.T, d.B = T, B
     d.h, d.c, d.C, d.last = _addr(h), _addr(c), _addr(Cs), _addr(last)
     return d, keep
 
@@ -1252,29 +1224,14 @@ def beam_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, 
     """Descriptor of the streaming beam search with every weight shape checked against the others (raw pointers); the
     workspace, A, lens and the outputs are the caller's to fill.  -> (descriptor, tensors to keep alive)."""
     _need_gpu(fc_w, emb_w)
-    V, Ocat = fc_w.shape
-    Od = out_w.shape[0]
-    Hp, L = emb_w.shape[1], len(rnn_weights) // 4
-    if L > _lib.DECODE_MAX_LAYERS:
-        raise ValueError(f"beam search supports at most {_lib.DECODE_MAX_LAYERS} prediction-net layers")
-    _check_prednet_weights(rnn_weights, cell, Hp)
-    if not 1 <= Od < Ocat or tuple(out_w.shape) != (Od, Hp) or tuple(out_b.shape) != (Od,) or emb_w.shape[0] < V:
-        raise ValueError(f"streaming beam search: fc {tuple(fc_w.shape)} / out_proj {tuple(out_w.shape)} / embedding "
-                         f"{tuple(emb_w.shape)} do not fit together (the embedding needs a row per fc output)")
-    if not 0 <= blank < V or V < 2 or beam < 1 or B < 1:
-        raise ValueError(f"streaming beam search: blank {blank} outside [0,{V}), V {V} < 2, beam {beam} < 1 or {B} streams")
     d = _lib.BeamStreamDesc()
-    d.T, d.B, d.V, d.Hp, d.O, d.L, d.cell, d.blank = 0, B, V, Hp, Od, L, cell, blank
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "streaming beam search")
+    if d.V < 2 or beam < 1 or B < 1:
+        raise ValueError(f"streaming beam search: V {d.V} < 2, beam {beam} < 1 or {B} streams")
+    d.T, d.B = 0, B
     d.beam, d.improved, d.state_beam, d.expand_beam = beam, int(bool(improved)), float(state_beam), float(expand_beam)
     d.max_candidates, d.max_pops, d.max_states, d.max_nodes, d.max_len = (caps[k] for k in ("max_candidates", "max_pops",
                                                                                            "max_states", "max_nodes", "max_len"))
-    keep = [_f32c(t, "prediction-net weight") for t in rnn_weights]
-    keep += [_f32c(emb_w, "embedding"), _f32c(out_w, "out_proj weight"), _f32c(out_b, "out_proj bias"), _f32c(fc_w, "fc weight")]
-    d.emb = _addr(keep[-4])
-    for l in range(L):
-        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = (_addr(t) for t in keep[4 * l:4 * l + 4])
-    d.w_o, d.b_o = _addr(keep[-3]), _addr(keep[-2])
-    d.w_d, d.ld_d = _addr(keep[-1], Ocat - Od), Ocat
     return d, keep
 
 

@@ -184,3 +184,16 @@ def test_prednet_step_branch_and_1d_joint_match_oracle(cell, layers):
         assert z.shape == (10,) and (z.cpu() - z_ref).abs().max() < 2e-5
     with pytest.raises(RuntimeError):
         net.decoder(nxt.cuda(), prev_hidden_state=st)  # inference-only: needs no_grad
+
+
+def test_greedy_decode_refuses_an_embedding_with_fewer_rows_than_outputs():
+    """The kernel reads emb[tok] for any tok < V: an embedding of V - 1 rows is refused on the host, before anything is launched."""
+    from rnntransducer_amd import ops
+    T, B, V, Hp, O, Oe = 3, 2, 20, 8, 8, 8
+    z = lambda *shape: torch.zeros(*shape, device="cuda")  # noqa: E731
+    rnn = [z(4 * Hp, Hp), z(4 * Hp, Hp), z(4 * Hp), z(4 * Hp)]
+    args = (z(T, B, Oe), z(V, Oe + O), z(V))
+    with pytest.raises(ValueError, match="embedding"):
+        ops.greedy_decode(*args, z(V - 1, Hp), rnn, 0, z(O, Hp), z(O), 0, 2)
+    tokens, ntok = ops.greedy_decode(*args, z(V, Hp), rnn, 0, z(O, Hp), z(O), 0, 2)   # a row per output: accepted
+    assert tokens.shape == (B, T * 2) and ntok.tolist() == [0, 0]

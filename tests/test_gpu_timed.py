@@ -267,3 +267,65 @@ def test_stream_beam_collection_moves_frames_with_their_nodes():
     assert small == want and live <= cap
     assert grew >= 1 and max(len(state.stable_prefix(b)) for b in range(B)) >= 2   # a frame really was committed by a chunk
     assert [state.stable_prefix(b, return_frames=True) for b in range(B)] == [ref.stable_prefix(b) for b in range(B)]
+
+
+# 7. the offline and the streaming greedy entries on the same A: one loop, the same bits ----------------------------------
+def _ops_greedy_net(cell, L, V, Hp, O, Oe, seed):
+    """Random prediction net / joint weights at the ops level, scaled so that the argmax is rarely the blank."""
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *shape, scale=1.0: (scale * torch.randn(*shape, generator=g)).cuda()  # noqa: E731
+    G = {0: 4, 1: 3, 2: 1}[cell]
+    rnn = []
+    for _ in range(L):
+        rnn += [r(G * Hp, Hp, scale=0.3), r(G * Hp, Hp, scale=0.3), r(G * Hp, scale=0.3), r(G * Hp, scale=0.3)]
+    return dict(fc_w=r(V, Oe + O, scale=0.5), fc_b=r(V, scale=0.1), emb_w=r(V, Hp), rnn=rnn, out_w=r(O, Hp, scale=0.3),
+                out_b=r(O, scale=0.1))
+
+
+@pytest.mark.parametrize("cell,L", [(0, 2), (1, 1), (2, 1)], ids=["lstm-2", "gru-1", "rnn_tanh-1"])
+def test_offline_and_stream_greedy_entries_same_bits_on_the_same_A(cell, L):
+    """ops.greedy_decode(timing=True), ops.stream_greedy on the whole A in one chunk and on A[:5] / A[5:] run the same frame
+    loop (csrc/decode_shared.hpp) on the same A: tokens, counts, frames and logp are bitwise equal; a row without frames keeps
+    the state its reset left, bitwise.  V = 1100: more than one pass of the 1024 threads and no multiple of 64."""
+    from rnntransducer_amd import ops
+    B, T, V, Hp, O, Oe, max_iters, blank = 4, 12, 1100, 32, 24, 16, 3, 0
+    t_list = [12, 7, 0, 1]
+    w = _ops_greedy_net(cell, L, V, Hp, O, Oe, 40 + cell)
+    enc = (2.0 * torch.randn(T, B, Oe, generator=torch.Generator().manual_seed(7))).cuda()
+    dev = enc.device
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)  # noqa: E731
+    tok0, n0, fr0, lp0 = ops.greedy_decode(enc, w["fc_w"], w["fc_b"], w["emb_w"], w["rnn"], cell, w["out_w"], w["out_b"], blank,
+                                           max_iters, t_lens=i32(t_list), timing=True)
+    n0 = n0.tolist()
+    assert sum(n0) > 10 and n0[2] == 0
+    # the A greedy_decode computed: the same deterministic GEMM call on the same operands
+    A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
+    ops.gemm(T * B, V, Oe, enc, w["fc_w"], A, b_sn=Oe + O, b_sk=1, bias=w["fc_b"], flags=ops.GEMM_GELU_A)
+    h = torch.zeros(L, B, Hp, device=dev)
+    c = torch.zeros(L, B, Hp, device=dev) if cell == 0 else None
+    Cs, last = torch.zeros(B, V, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)
+    net = (w["fc_w"], w["emb_w"], w["rnn"], cell, w["out_w"], w["out_b"], blank)
+
+    def run(chunks):
+        """reset every row, feed the chunks [(A_chunk, lens, frame_base)] -> per row (tokens, frames, logp) concatenated"""
+        ops.stream_greedy_reset(i32(list(range(B))), *net, h, c, Cs, last)
+        carried = [t for t in (h, c) if t is not None]
+        primed = [t[:, 2].clone() for t in carried] + [Cs[2].clone(), last[2].clone()]
+        out = [[[], [], []] for _ in range(B)]
+        for a, lens, base in chunks:
+            tok, n, fr, lp = ops.stream_greedy(a.contiguous(), i32(lens), *net, max_iters, h, c, Cs, last,
+                                               frame_base=torch.tensor(base, dtype=torch.int64, device=dev))
+            for b, k in enumerate(n.tolist()):
+                for dst, src in zip(out[b], (tok, fr, lp)):
+                    dst.append(src[b, :k])
+        assert all(torch.equal(a, w) for a, w in zip([t[:, 2] for t in carried] + [Cs[2], last[2]], primed))
+        return [[torch.cat(part) for part in row] for row in out]
+
+    one = run([(A, t_list, [0] * B)])
+    two = run([(A[:5], [min(t, 5) for t in t_list], [0] * B),
+               (A[5:], [max(t - 5, 0) for t in t_list], [min(t, 5) for t in t_list])])
+    for b in range(B):
+        want = (tok0[b, :n0[b]], fr0[b, :n0[b]], lp0[b, :n0[b]])
+        for got in (one[b], two[b]):
+            assert len(got[0]) == n0[b]
+            assert all(torch.equal(x, y) for x, y in zip(got, want)), b
