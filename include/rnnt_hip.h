@@ -166,6 +166,48 @@ int rnnt_hip_gemm_hp(const void* A, const uint32_t* a_amax, const void* B, const
                      float* C, int64_t ldc, const float* bias, uint32_t flags, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* The arguments the ragged (variable-length) batches of rnnt_hip_lstm_fwd / _bwd run these kernels with, exposed for tests; the
+ * entries above are these with no index table and the plain C map.  Every index table is a DEVICE array of int32 whose values the
+ * caller guarantees to lie inside the tensors they address (they are not read on the host).
+ * rnnt_hip_hp_split_ex: idx (or NULL).  transpose == 0: `rows` listed source rows, each converted IN PLACE (source row idx[i] ->
+ *   plane row idx[i] and amax[idx[i]]; other plane rows and amax words are not touched).  transpose == 1: K listed source rows,
+ *   packed along the contraction: plane row r, index k holds x[idx[k] + shift][r] (0 where idx[k] + shift is outside [0, src_rows)).
+ *   Without amax_given the column maxima are still taken over all src_rows.
+ * rnnt_hip_hp_split_both_ex: rowidx (or NULL), M = its length: source row rowidx[i] -> row-major plane row rowidx[i] (in place, scale
+ *   from rowmax[rowidx[i]]) and index i of the transposed planes (packed, contraction length M).
+ * rnnt_hip_hp_colmax: amax[c] = max_r |x[r * ld + c]| over a (rows x C) view, as fp32 bit patterns (0 for an empty view).
+ * rnnt_hip_gemm_hp_ex: C(m, n) [+]= sum_k A(a_rowidx ? a_rowidx[m] : m, k) B(n, k) + bias[n], written to
+ *   C[(mo / c_div) * c_so + (mo % c_div) * c_si + n] with mo = c_rowidx ? c_rowidx[m] : m  (rnnt_hip_gemm_hp: c_div = 1, c_so = ldc,
+ *   c_si = 0).  a_rowidx gathers plane rows AND amax words of A, whose planes hold a_plane_rows >= M rows (0 without a_rowidx).
+ * rnnt_hip_gemm_hp_plan: what rnnt_hip_gemm_hp / _ex launch for (M, N, K) and a workspace of workspace_bytes (0: none) — no launch,
+ *   no device access; the launch and rnnt_hip_gemm_hp_workspace_bytes take their decisions from the same function.  tiles_m x tiles_n
+ *   tiles of 256 x 256, walked in bands of group_m tile rows; splits > 1: split-K over `splits` slabs of kt_per_split K-tiles (32 k
+ *   each; the last slab takes what is left), summed in fixed order; workspace_bytes_wanted = rnnt_hip_gemm_hp_workspace_bytes. */
+int rnnt_hip_hp_split_ex(const float* x, int64_t rows, int64_t K, int64_t ld, int32_t transpose, int64_t src_rows, int64_t shift,
+                         void* planes, uint32_t* amax, int32_t amax_given, const int32_t* idx, void* stream);
+int rnnt_hip_hp_split_both_ex(const float* x, int64_t M, int64_t C, int64_t ld, const uint32_t* rowmax, const uint32_t* colmax,
+                              void* planes_rm, void* planes_t, const int32_t* rowidx, void* stream);
+int rnnt_hip_hp_colmax(const float* x, int64_t rows, int64_t C, int64_t ld, uint32_t* amax, void* stream);
+typedef struct rnnt_hp_gemm_desc {
+  const void* A; const uint32_t* a_amax;   /* planes of a_plane_rows (a_rowidx) or M rows x K + their row maxima */
+  const void* B; const uint32_t* b_amax;   /* (N x K) */
+  int64_t M, N, K;
+  float* C;
+  int64_t c_div, c_so, c_si;
+  const float* bias;                       /* (N) or NULL */
+  uint32_t flags;                          /* RNNT_GEMM_ACCUM, RNNT_GEMM_HP_F16 */
+  void* workspace; size_t workspace_bytes; /* optional split-K slabs */
+  const int32_t* a_rowidx; int64_t a_plane_rows;
+  const int32_t* c_rowidx;
+} rnnt_hp_gemm_desc;
+int rnnt_hip_gemm_hp_ex(const rnnt_hp_gemm_desc* d, void* stream);
+typedef struct rnnt_hp_gemm_plan {
+  int32_t tiles_m, tiles_n, group_m;
+  int32_t splits, kt_per_split;
+  size_t workspace_bytes_wanted;
+} rnnt_hp_gemm_plan;
+int rnnt_hip_gemm_hp_plan(int64_t M, int64_t N, int64_t K, size_t workspace_bytes, rnnt_hp_gemm_plan* out);
+
 /* Up to 4 such products in ONE queue-driven launch: 256 resident workgroups draw (problem, tile, K-split) units until none is left
  * (one launch tail instead of one per product).  xcd_skip: bit x set = workgroups that find themselves on XCD x leave at once, the
  * other XCDs do all the work — for products that run on a second stream beside a persistent recurrence (rnnt_lstm_bwd_desc.phase).

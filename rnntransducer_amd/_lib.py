@@ -57,6 +57,18 @@ class HpProblem(C.Structure):
                 ("K", c_i64), ("C", C.c_void_p), ("ldc", c_i64), ("flags", C.c_uint32)]
 
 
+class HpGemmDesc(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("a_amax", C.c_void_p), ("B", C.c_void_p), ("b_amax", C.c_void_p), ("M", c_i64), ("N", c_i64),
+                ("K", c_i64), ("C", C.c_void_p), ("c_div", c_i64), ("c_so", c_i64), ("c_si", c_i64), ("bias", C.c_void_p),
+                ("flags", C.c_uint32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("a_rowidx", C.c_void_p),
+                ("a_plane_rows", c_i64), ("c_rowidx", C.c_void_p)]
+
+
+class HpGemmPlan(C.Structure):
+    _fields_ = [("tiles_m", c_i32), ("tiles_n", c_i32), ("group_m", c_i32), ("splits", c_i32), ("kt_per_split", c_i32),
+                ("workspace_bytes_wanted", C.c_size_t)]
+
+
 DECODE_MAX_LAYERS = 8
 
 
@@ -156,6 +168,13 @@ SYMBOLS = {
     "rnnt_hip_gemm_hp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p,
                                   C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnnt_hip_hp_split_both": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnnt_hip_hp_split_ex": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, c_i32, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i32, C.c_void_p,
+                                      C.c_void_p]),
+    "rnnt_hip_hp_split_both_ex": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "rnnt_hip_hp_colmax": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "rnnt_hip_gemm_hp_ex": (C.c_int, [C.POINTER(HpGemmDesc), C.c_void_p]),
+    "rnnt_hip_gemm_hp_plan": (C.c_int, [c_i64, c_i64, c_i64, C.c_size_t, C.POINTER(HpGemmPlan)]),
     "rnnt_hip_gemm_hp_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(HpProblem), c_i32]),
     "rnnt_hip_gemm_hp_grouped": (C.c_int, [C.POINTER(HpProblem), c_i32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnnt_hip_lstm_workspace_bytes": (C.c_size_t, [c_i32] * 5),

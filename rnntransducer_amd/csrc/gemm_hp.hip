@@ -13,7 +13,8 @@
 //   precision whatever the other rows hold; inside a row, values more than 2^17 below the row's amax lose relative (not absolute)
 //   precision: |e| <= 2^-40 amax_r — below the fp32 rounding of any sum the row's large elements take part in.  a.b ~= s_a^-1 s_b^-1 (a_lo b_hi + a_hi b_lo + a_hi b_hi): the dropped a_lo b_lo is
 // <= 2^-22 |a b|, typically 2^-25; products and sums are exact / fp32-accumulated in the MFMA.  Measured against fp64:
-// tests/test_gpu_gemm.py::test_gemm_hp_*.
+// tests/test_gpu_gemm.py::test_gemm_hp_*; the format restated on the CPU and compared bitwise, and every index table / C map of the
+// ragged batches per element: tests/test_gpu_gemm_hp_forms.py.
 //
 // Kernel (NT form only: both operands k-contiguous; transposed operands are produced as such by the split kernels):
 //   256 x 256 x 32 tile, 512 threads = 8 waves as 2 (M) x 4 (N), 128 x 64 of C per wave = 8 x 4 blocks of 16 x 16,
@@ -565,15 +566,40 @@ int hp_split_both(const float* x, int64_t M, int64_t C, int64_t ld, const uint32
   return RNNT_OK;
 }
 
-size_t hp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  const long tiles = ceil_div(M, HP_BM) * ceil_div(N, HP_BN);
+// The ONE place that decides how a product is cut up: tiles, band height of the tile walk and the split-K slabs.  hp_gemm launches what
+// this says, hp_gemm_workspace_bytes asks it how many slabs it would like, rnnt_hip_gemm_hp_plan reports it.  M, N, K >= 1.
+// workspace_bytes = 0: no workspace (one pass).
+struct HpGemmPlan {
+  int tiles_m, tiles_n, group_m, splits, kt_per_split;
+  size_t workspace_bytes_wanted;
+};
+static HpGemmPlan hp_gemm_plan(int64_t M, int64_t N, int64_t K, size_t workspace_bytes) {
+  HpGemmPlan pl;
+  pl.tiles_m = (int)ceil_div(M, HP_BM); pl.tiles_n = (int)ceil_div(N, HP_BN);
+  const long tiles = (long)pl.tiles_m * pl.tiles_n;
   const long nkt = ceil_div(K, HP_BK);
-  if (tiles >= 192 || nkt < 64) return 0;
-  long want = ceil_div(256, tiles);
-  if (want > nkt / 32) want = nkt / 32;
-  if (want > 32) want = 32;
-  return want >= 2 ? (size_t)want * M * N * 4 : 0;
+  {  // band height of the tile walk: 8 x 4 tiles in flight per XCD when an XCD's share is >= 32 tiles, 4 x 2 for the small outputs
+    static const int env_gm = getenv("RNNT_GEMM_HP_GROUP_M") ? atoi(getenv("RNNT_GEMM_HP_GROUP_M")) : -1;
+    pl.group_m = env_gm >= 0 ? env_gm : (tiles >= 256 ? 8 : 4);
+  }
+  long want = 1;
+  if (tiles < 192 && nkt >= 64) {  // too few tiles for 256 CUs and a deep contraction (weight gradients): split K
+    want = ceil_div(256, tiles);
+    if (want > nkt / 32) want = nkt / 32;
+    if (want > 32) want = 32;
+    if (want < 2) want = 1;
+  }
+  const size_t slab = (size_t)M * (size_t)N * 4;
+  pl.workspace_bytes_wanted = want >= 2 ? (size_t)want * slab : 0;
+  const size_t by_ws = workspace_bytes / slab;
+  long splits = (size_t)want > by_ws ? (long)by_ws : want;
+  if (splits < 2) splits = 1;
+  pl.kt_per_split = (int)ceil_div(nkt, splits);
+  pl.splits = (int)ceil_div(nkt, pl.kt_per_split);
+  return pl;
 }
+
+size_t hp_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) { return hp_gemm_plan(M, N, K, 0).workspace_bytes_wanted; }
 
 int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t* b_amax, int64_t M, int64_t N, int64_t K, float* C,
             int64_t c_div, int64_t c_so, int64_t c_si, const float* bias, unsigned flags, void* workspace, size_t workspace_bytes,
@@ -594,24 +620,10 @@ int hp_gemm(const void* A, const uint32_t* a_amax, const void* B, const uint32_t
   k.bias = bias; k.flags = flags;
   k.a_rowidx = a_rowidx; k.c_rowidx = c_rowidx;
   const bool f16 = (flags & RNNT_GEMM_HP_F16) != 0u;
-  k.tiles_m = (int)ceil_div(M, HP_BM); k.tiles_n = (int)ceil_div(N, HP_BN);
-  const int tiles = k.tiles_m * k.tiles_n;
-  {  // band height of the tile walk: 8 x 4 tiles in flight per XCD when an XCD's share is >= 32 tiles, 4 x 2 for the small outputs
-    static const int env_gm = getenv("RNNT_GEMM_HP_GROUP_M") ? atoi(getenv("RNNT_GEMM_HP_GROUP_M")) : -1;
-    k.group_m = env_gm >= 0 ? env_gm : (tiles >= 256 ? 8 : 4);
-  }
-  int splits = 1;
-  if (workspace && tiles < 192 && k.nkt >= 64) {  // too few tiles for 256 CUs and a deep contraction (weight gradients): split K
-    long want = ceil_div(256, tiles);
-    const long by_ws = (long)(workspace_bytes / ((size_t)M * N * 4));
-    if (want > k.nkt / 32) want = k.nkt / 32;
-    if (want > by_ws) want = by_ws;
-    if (want > 32) want = 32;
-    if (want >= 2) splits = (int)want;
-  }
-  k.kt_per_split = (int)ceil_div(k.nkt, splits);
-  splits = (int)ceil_div(k.nkt, k.kt_per_split);
-  k.splits = splits;
+  const HpGemmPlan pl = hp_gemm_plan(M, N, K, workspace ? workspace_bytes : 0);
+  k.tiles_m = pl.tiles_m; k.tiles_n = pl.tiles_n; k.group_m = pl.group_m;
+  k.splits = pl.splits; k.kt_per_split = pl.kt_per_split;
+  const int tiles = k.tiles_m * k.tiles_n, splits = k.splits;
   k.slab = (float*)workspace;
   if (f16) RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
   else RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_hp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HP_STAGE));
@@ -721,25 +733,57 @@ extern "C" size_t rnnt_hip_hp_bytes(int64_t rows, int64_t K) {
   return hp_plane_bytes(rows, K);
 }
 
-extern "C" int rnnt_hip_hp_split(const float* x, int64_t rows, int64_t K, int64_t ld, int32_t transpose, int64_t src_rows, int64_t shift,
-                                 void* planes, uint32_t* amax, int32_t amax_given, void* stream) {
+extern "C" int rnnt_hip_hp_split_ex(const float* x, int64_t rows, int64_t K, int64_t ld, int32_t transpose, int64_t src_rows, int64_t shift,
+                                    void* planes, uint32_t* amax, int32_t amax_given, const int32_t* idx, void* stream) {
   RNNT_CHECK_ARG(x && planes && amax && rows >= 0 && K >= 0, "hp_split: bad arguments");
+  RNNT_CHECK_ARG(rows < (1ll << 31) && K < (1ll << 31), "hp_split: dims must fit 31 bits");
   RNNT_CHECK_ARG((reinterpret_cast<uintptr_t>(planes) & 127) == 0, "hp_split: planes must be 128-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   if (!transpose) {
     RNNT_CHECK_ARG(ld >= K, "hp_split: ld < K");
     RNNT_CHECK_ARG(!amax_given, "hp_split: the row-major split computes its row maxima itself");
-    return hp_split(x, rows, K, ld, amax, planes, s);
+    return hp_split(x, rows, K, ld, amax, planes, s, idx);
   }
   RNNT_CHECK_ARG(ld >= rows && src_rows >= 1, "hp_split: transposed source is (src_rows x >= rows), ld >= rows");
+  RNNT_CHECK_ARG(src_rows < (1ll << 31) && shift > -(1ll << 31) && shift < (1ll << 31), "hp_split: src_rows and shift must fit 31 bits");
   if (!amax_given)
     if (int rc = hp_colmax(x, src_rows, rows, ld, amax, s)) return rc;
-  return hp_split_t(x, rows, K, ld, src_rows, shift, amax, planes, s);
+  return hp_split_t(x, rows, K, ld, src_rows, shift, amax, planes, s, idx);
+}
+
+extern "C" int rnnt_hip_hp_split(const float* x, int64_t rows, int64_t K, int64_t ld, int32_t transpose, int64_t src_rows, int64_t shift,
+                                 void* planes, uint32_t* amax, int32_t amax_given, void* stream) {
+  return rnnt_hip_hp_split_ex(x, rows, K, ld, transpose, src_rows, shift, planes, amax, amax_given, nullptr, stream);
+}
+
+extern "C" int rnnt_hip_hp_colmax(const float* x, int64_t rows, int64_t C, int64_t ld, uint32_t* amax, void* stream) {
+  RNNT_CHECK_ARG(amax && rows >= 0 && C >= 0 && C < (1ll << 31), "hp_colmax: bad arguments");
+  RNNT_CHECK_ARG(x || rows == 0 || C == 0, "hp_colmax: null source");
+  RNNT_CHECK_ARG(ld >= C, "hp_colmax: ld < C");
+  return hp_colmax(x, rows, C, ld, amax, (hipStream_t)stream);
 }
 
 extern "C" size_t rnnt_hip_gemm_hp_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M < 1 || N < 1 || K < 1) return 0;
   return hp_gemm_workspace_bytes(M, N, K);
+}
+
+extern "C" int rnnt_hip_gemm_hp_plan(int64_t M, int64_t N, int64_t K, size_t workspace_bytes, rnnt_hp_gemm_plan* out) {
+  RNNT_CHECK_ARG(out != nullptr, "gemm_hp_plan: null plan");
+  RNNT_CHECK_ARG(M >= 1 && N >= 1 && K >= 1 && M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "gemm_hp_plan: bad dims");
+  const HpGemmPlan pl = hp_gemm_plan(M, N, K, workspace_bytes);
+  out->tiles_m = pl.tiles_m; out->tiles_n = pl.tiles_n; out->group_m = pl.group_m;
+  out->splits = pl.splits; out->kt_per_split = pl.kt_per_split;
+  out->workspace_bytes_wanted = pl.workspace_bytes_wanted;
+  return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_gemm_hp_ex(const rnnt_hp_gemm_desc* d, void* stream) {
+  RNNT_CHECK_ARG(d != nullptr, "gemm_hp: null descriptor");
+  RNNT_CHECK_ARG(d->a_rowidx || d->a_plane_rows == 0, "gemm_hp: a_plane_rows given without a_rowidx");
+  RNNT_CHECK_ARG(d->workspace || d->workspace_bytes == 0, "gemm_hp: workspace_bytes given without a workspace");
+  return hp_gemm(d->A, d->a_amax, d->B, d->b_amax, d->M, d->N, d->K, d->C, d->c_div, d->c_so, d->c_si, d->bias, d->flags, d->workspace,
+                 d->workspace_bytes, (hipStream_t)stream, d->a_rowidx, d->a_plane_rows, d->c_rowidx);
 }
 
 extern "C" int rnnt_hip_gemm_hp(const void* A, const uint32_t* a_amax, const void* B, const uint32_t* b_amax, int64_t M, int64_t N,
@@ -772,10 +816,15 @@ extern "C" int rnnt_hip_gemm_hp_grouped(const rnnt_hp_problem* problems, int32_t
                          (hipStream_t)stream);
 }
 
-extern "C" int rnnt_hip_hp_split_both(const float* x, int64_t M, int64_t C, int64_t ld, const uint32_t* rowmax, const uint32_t* colmax,
-                                      void* planes_rm, void* planes_t, void* stream) {
+extern "C" int rnnt_hip_hp_split_both_ex(const float* x, int64_t M, int64_t C, int64_t ld, const uint32_t* rowmax, const uint32_t* colmax,
+                                         void* planes_rm, void* planes_t, const int32_t* rowidx, void* stream) {
   RNNT_CHECK_ARG(x && rowmax && colmax && planes_rm && planes_t && M >= 0 && C >= 0 && ld >= C, "hp_split_both: bad arguments");
   RNNT_CHECK_ARG(M < (1ll << 31) && C < (1ll << 31), "hp_split_both: dims must fit 31 bits");
   RNNT_CHECK_ARG(((reinterpret_cast<uintptr_t>(planes_rm) | reinterpret_cast<uintptr_t>(planes_t)) & 127) == 0, "hp_split_both: planes must be 128-byte aligned");
-  return hp_split_both(x, M, C, ld, rowmax, colmax, planes_rm, planes_t, (hipStream_t)stream);
+  return hp_split_both(x, M, C, ld, rowmax, colmax, planes_rm, planes_t, (hipStream_t)stream, rowidx);
+}
+
+extern "C" int rnnt_hip_hp_split_both(const float* x, int64_t M, int64_t C, int64_t ld, const uint32_t* rowmax, const uint32_t* colmax,
+                                      void* planes_rm, void* planes_t, void* stream) {
+  return rnnt_hip_hp_split_both_ex(x, M, C, ld, rowmax, colmax, planes_rm, planes_t, nullptr, stream);
 }

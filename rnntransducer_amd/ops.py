@@ -206,28 +206,36 @@ def gemm_hp(a: HpTensor, b: HpTensor, out: Optional[torch.Tensor] = None, bias: 
     return out
 
 
-def gemm_hp_grouped(pairs, outs=None, accumulate: bool = False, xcd_skip: int = 0, check: bool = False, f16: bool = False):
+def gemm_hp_grouped(pairs, outs=None, accumulate=False, xcd_skip: int = 0, check: bool = False, f16: bool = False,
+                    workspace_bytes: Optional[int] = None):
     """[C_i (M_i, N_i) [+]= A_i . B_i^T] for up to 4 (A, B) pairs of hp operands in ONE queue-driven launch; `xcd_skip`: bit mask of
     XCDs whose workgroups leave at once (the launch then runs on the other XCDs only).  `check`: read back (synchronising) the
     launch's self-check — word 9 of the workspace is 1 when units were left undone because the mask named XCDs the device does not
-    expose (include/rnnt_hip.h) — and raise RnntHipError in that case.  f16=True: every product in the one-product form (as gemm_hp)."""
+    expose (include/rnnt_hip.h) — and raise RnntHipError in that case.  f16=True: every product in the one-product form (as gemm_hp).
+    outs[i] may be a column block of a wider matrix (unit column stride, row stride ldc >= N_i); `accumulate` may be one flag per
+    problem; `workspace_bytes`: hand the launch this much instead of what rnnt_hip_gemm_hp_grouped_workspace_bytes asks for (>= 256:
+    the split-K slabs shrink to fit)."""
     n = len(pairs)
     if not 1 <= n <= 4:
         raise ValueError("1..4 products per grouped launch")
+    acc = list(accumulate) if isinstance(accumulate, (list, tuple)) else [bool(accumulate)] * n
+    if len(acc) != n:
+        raise ValueError("one accumulate flag per problem")
     pr = (_lib.HpProblem * n)()
     res = []
     for i, (a, b) in enumerate(pairs):
         if a.K != b.K:
             raise ValueError(f"contraction lengths differ: {a.K} vs {b.K}")
         out = outs[i] if outs is not None else torch.empty(a.rows, b.rows, device=a.planes.device, dtype=torch.float32)
-        if tuple(out.shape) != (a.rows, b.rows) or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError(f"out[{i}] must be a contiguous float32 ({a.rows}, {b.rows}) tensor")
+        if tuple(out.shape) != (a.rows, b.rows) or out.dtype != torch.float32 or (b.rows > 1 and out.stride(1) != 1) \
+                or (a.rows > 1 and out.stride(0) < b.rows):
+            raise ValueError(f"out[{i}] must be a float32 ({a.rows}, {b.rows}) tensor with unit column stride and row stride >= {b.rows}")
         pr[i].A, pr[i].a_amax, pr[i].B, pr[i].b_amax = _addr(a.planes), _addr(a.amax), _addr(b.planes), _addr(b.amax)
-        pr[i].M, pr[i].N, pr[i].K, pr[i].C, pr[i].ldc = a.rows, b.rows, a.K, _addr(out), b.rows
-        pr[i].flags = (GEMM_ACCUM if accumulate else 0) | (GEMM_HP_F16 if f16 else 0)
+        pr[i].M, pr[i].N, pr[i].K, pr[i].C, pr[i].ldc = a.rows, b.rows, a.K, _addr(out), max(out.stride(0), b.rows)
+        pr[i].flags = (GEMM_ACCUM if acc[i] else 0) | (GEMM_HP_F16 if f16 else 0)
         res.append(out)
-    nws = _lib.lib().rnnt_hip_gemm_hp_grouped_workspace_bytes(pr, n)
-    ws = torch.empty(nws, device=res[0].device, dtype=torch.uint8)
+    nws = _lib.lib().rnnt_hip_gemm_hp_grouped_workspace_bytes(pr, n) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nws, 256), device=res[0].device, dtype=torch.uint8)
     _lib.check(_lib.lib().rnnt_hip_gemm_hp_grouped(pr, n, int(xcd_skip), _addr(ws), nws, _stream()), "rnnt_hip_gemm_hp_grouped")
     if check:
         words = ws[:64].view(torch.int32).tolist()
@@ -235,6 +243,76 @@ def gemm_hp_grouped(pairs, outs=None, accumulate: bool = False, xcd_skip: int = 
             raise RnntHipError(f"grouped half-pair GEMM left units undone ({words[8]} drawn): xcd_skip = {xcd_skip:#x} names XCDs this "
                                "device does not expose")
     return res
+
+
+# The index tables and the C map the ragged batches of the LSTM layers run these kernels with (rnnt_hip_*_ex, include/rnnt_hip.h), on
+# caller-owned buffers: for the tests that poison everything a call does not own.  `off`: element offset of the view into `x` / `out`.
+def hp_split_ex(x: torch.Tensor, rows: int, K: int, ld: int, planes: torch.Tensor, amax: torch.Tensor, *, off: int = 0,
+                transpose: bool = False, src_rows: int = 0, shift: int = 0, idx: Optional[torch.Tensor] = None,
+                amax_given: bool = False) -> None:
+    """rnnt_hip_hp_split_ex: idx (int32, device) = rowidx of the row-major form (length rows) / kidx of the transposed form (length K)."""
+    _need_gpu(x, planes, amax, idx)
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != (K if transpose else rows)):
+        raise ValueError("idx must be int32 with one entry per listed row")
+    check(_lib.lib().rnnt_hip_hp_split_ex(_addr(x, off), rows, K, ld, 1 if transpose else 0, src_rows, int(shift), _addr(planes),
+                                          _addr(amax), 1 if amax_given else 0, _addr(idx), _stream()), "rnnt_hip_hp_split_ex")
+
+
+def hp_split_both_ex(x: torch.Tensor, M: int, Cc: int, ld: int, rowmax: torch.Tensor, colmax: torch.Tensor, planes_rm: torch.Tensor,
+                     planes_t: torch.Tensor, *, off: int = 0, rowidx: Optional[torch.Tensor] = None) -> None:
+    _need_gpu(x, rowmax, colmax, planes_rm, planes_t, rowidx)
+    if rowidx is not None and (rowidx.dtype != torch.int32 or rowidx.numel() != M):
+        raise ValueError("rowidx must be int32 with M entries")
+    check(_lib.lib().rnnt_hip_hp_split_both_ex(_addr(x, off), M, Cc, ld, _addr(rowmax), _addr(colmax), _addr(planes_rm), _addr(planes_t),
+                                               _addr(rowidx), _stream()), "rnnt_hip_hp_split_both_ex")
+
+
+def hp_colmax(x: torch.Tensor, rows: int, Cc: int, ld: int, amax: torch.Tensor, *, off: int = 0) -> None:
+    """amax[c] (int32 words: fp32 bit patterns) = max_r |x[off + r * ld + c]|."""
+    _need_gpu(x, amax)
+    check(_lib.lib().rnnt_hip_hp_colmax(_addr(x, off), rows, Cc, ld, _addr(amax), _stream()), "rnnt_hip_hp_colmax")
+
+
+class HpGemmPlan(NamedTuple):
+    """What one gemm_hp / gemm_hp_ex call launches (rnnt_hip_gemm_hp_plan): 256 x 256 tiles, band height of the tile walk, split-K
+    slabs (1 = one pass), K-tiles of 32 per slab, and the workspace the launch would like."""
+    tiles_m: int
+    tiles_n: int
+    group_m: int
+    splits: int
+    kt_per_split: int
+    workspace_bytes_wanted: int
+
+
+def gemm_hp_plan(M: int, N: int, K: int, workspace_bytes: Optional[int] = None) -> HpGemmPlan:
+    """workspace_bytes=None: a workspace of the size the query asks for (what gemm_hp(split_k=True) hands over); 0: none."""
+    if workspace_bytes is None:
+        workspace_bytes = _lib.lib().rnnt_hip_gemm_hp_workspace_bytes(M, N, K)
+    p = _lib.HpGemmPlan()
+    check(_lib.lib().rnnt_hip_gemm_hp_plan(M, N, K, int(workspace_bytes), C.byref(p)), "rnnt_hip_gemm_hp_plan")
+    return HpGemmPlan(p.tiles_m, p.tiles_n, p.group_m, p.splits, p.kt_per_split, p.workspace_bytes_wanted)
+
+
+def gemm_hp_ex(a_planes: torch.Tensor, a_amax: torch.Tensor, b_planes: torch.Tensor, b_amax: torch.Tensor, M: int, N: int, K: int,
+               out: torch.Tensor, *, c_off: int = 0, c_div: int = 1, c_so: Optional[int] = None, c_si: int = 0,
+               bias: Optional[torch.Tensor] = None, flags: int = 0, a_rowidx: Optional[torch.Tensor] = None, a_plane_rows: int = 0,
+               c_rowidx: Optional[torch.Tensor] = None, workspace_bytes: Optional[int] = None) -> None:
+    """rnnt_hip_gemm_hp_ex on caller-owned buffers.  workspace_bytes as in gemm_hp_plan."""
+    _need_gpu(a_planes, a_amax, b_planes, b_amax, out, bias, a_rowidx, c_rowidx)
+    for t in (a_rowidx, c_rowidx):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != M):
+            raise ValueError("row index tables must be int32 with M entries")
+    if workspace_bytes is None:
+        workspace_bytes = _lib.lib().rnnt_hip_gemm_hp_workspace_bytes(M, N, K)
+    ws = torch.empty(workspace_bytes, device=out.device, dtype=torch.uint8) if workspace_bytes else None
+    d = _lib.HpGemmDesc()
+    d.A, d.a_amax, d.B, d.b_amax = _addr(a_planes), _addr(a_amax), _addr(b_planes), _addr(b_amax)
+    d.M, d.N, d.K, d.C = M, N, K, _addr(out, c_off)
+    d.c_div, d.c_so, d.c_si = c_div, (N if c_so is None else c_so), c_si
+    d.bias, d.flags = _addr(bias), flags
+    d.workspace, d.workspace_bytes = _addr(ws), int(workspace_bytes)
+    d.a_rowidx, d.a_plane_rows, d.c_rowidx = _addr(a_rowidx), a_plane_rows, _addr(c_rowidx)
+    check(_lib.lib().rnnt_hip_gemm_hp_ex(C.byref(d), _stream()), "rnnt_hip_gemm_hp_ex")
 
 
 def colsum(X: torch.Tensor, M: int, N: int, ld: Optional[int] = None, into: Optional[torch.Tensor] = None):

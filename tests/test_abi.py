@@ -35,6 +35,64 @@ def test_argument_validation_happens_before_any_device_work():
     assert L.rnnt_hip_lstm_workspace_bytes(10, 2, 80, 128, 2) > 0
     rc = L.rnnt_hip_loss_from_logits_fwd_bwd(None, None, None, None, 1, 1, 600, 3, 0, 1.0, None, None, None, 0, None)
     assert rc == -1
+    # half-pair entry points that take index tables and a C map: refused on the host, with addresses that are never dereferenced
+    import ctypes as C
+    P, Q = 0x10000, 0x20000                                            # 128-byte aligned stand-ins for device pointers
+
+    def hp_desc(**kw):
+        d = _lib.HpGemmDesc()
+        d.A, d.a_amax, d.B, d.b_amax, d.C = P, Q, P, Q, Q
+        d.M, d.N, d.K, d.c_div, d.c_so, d.c_si = 8, 8, 32, 1, 8, 0
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return C.byref(d)
+    assert L.rnnt_hip_gemm_hp_ex(None, None) == -1 and b"null" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(a_rowidx=P, a_plane_rows=7), None) == -1 and b"row count" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(a_rowidx=P), None) == -1                      # a_plane_rows left at 0
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(a_plane_rows=8), None) == -1 and b"without a_rowidx" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(c_div=0), None) == -1 and b"c_div" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(workspace_bytes=4096), None) == -1 and b"workspace" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(a_amax=None), None) == -1
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(A=P + 64), None) == -1 and b"aligned" in L.rnnt_hip_last_error()
+    assert L.rnnt_hip_gemm_hp_ex(hp_desc(M=0), None) == -1
+    plan = _lib.HpGemmPlan()
+    assert L.rnnt_hip_gemm_hp_plan(8, 8, 32, 0, None) == -1
+    assert L.rnnt_hip_gemm_hp_plan(0, 8, 32, 0, C.byref(plan)) == -1 and L.rnnt_hip_gemm_hp_plan(8, 8, 1 << 31, 0, C.byref(plan)) == -1
+    assert L.rnnt_hip_hp_split_ex(P, 8, 32, 32, 0, 0, 0, P, Q, 1, Q, None) == -1       # row-major: the maxima are computed, never given
+    assert L.rnnt_hip_hp_split_ex(P, 8, 32, 31, 0, 0, 0, P, Q, 0, Q, None) == -1       # ld < K
+    assert L.rnnt_hip_hp_split_ex(P, 8, 32, 7, 1, 40, 0, P, Q, 1, Q, None) == -1       # transposed: ld < rows
+    assert L.rnnt_hip_hp_split_ex(P, 8, 32, 8, 1, 0, 0, P, Q, 1, Q, None) == -1        # no source rows
+    assert L.rnnt_hip_hp_split_ex(P, 8, 32, 32, 0, 0, 0, P + 64, Q, 0, None, None) == -1
+    assert L.rnnt_hip_hp_split_ex(None, 8, 32, 32, 0, 0, 0, P, Q, 0, None, None) == -1
+    assert L.rnnt_hip_hp_split_both_ex(P, 8, 32, 31, Q, Q, P, P, Q, None) == -1
+    assert L.rnnt_hip_hp_split_both_ex(P, 8, 32, 32, None, Q, P, P, Q, None) == -1
+    assert L.rnnt_hip_hp_split_both_ex(P, 8, 32, 32, Q, Q, P, P + 64, None, None) == -1
+    assert L.rnnt_hip_hp_colmax(None, 8, 32, 32, Q, None) == -1 and L.rnnt_hip_hp_colmax(P, 8, 32, 32, None, None) == -1
+    assert L.rnnt_hip_hp_colmax(P, 8, 32, 31, Q, None) == -1 and L.rnnt_hip_hp_colmax(P, -1, 32, 32, Q, None) == -1
+
+
+def test_gemm_hp_plan_is_the_workspace_query():
+    """rnnt_hip_gemm_hp_plan (host only): the split rule at the shapes the GPU tests name, and its agreement with
+    rnnt_hip_gemm_hp_workspace_bytes — both read the one function the launch takes its decisions from."""
+    from rnntransducer_amd import _lib
+    from rnntransducer_amd.ops import gemm_hp_plan
+    L = _lib.lib()
+    slab = 70 * 40 * 4
+    assert gemm_hp_plan(70, 40, 2061)[:5] == (1, 1, 4, 2, 33)                          # 65 K-tiles: 33 + 32
+    assert gemm_hp_plan(70, 40, 4100)[:5] == (1, 1, 4, 4, 33)                          # 129 K-tiles: 33 + 33 + 33 + 30
+    assert gemm_hp_plan(70, 40, 4100, 2 * slab)[:5] == (1, 1, 4, 2, 65)
+    assert gemm_hp_plan(70, 40, 4100, 2 * slab - 1).splits == 1 and gemm_hp_plan(70, 40, 4100, 0)[:5] == (1, 1, 4, 1, 129)
+    assert gemm_hp_plan(1300, 300, 40)[:5] == (6, 2, 4, 1, 2) and gemm_hp_plan(1, 1, 1)[:5] == (1, 1, 4, 1, 1)
+    assert gemm_hp_plan(70, 40, 2016).splits == 1 and gemm_hp_plan(49000, 768, 2048).splits == 1   # 63 K-tiles; >= 192 tiles
+    assert gemm_hp_plan(5381, 3328, 40).group_m == 8                                   # 22 x 13 tiles
+    for M, N, K in [(70, 40, 2061), (70, 40, 4100), (512, 260, 5000), (4096, 1024, 20000), (300, 257, 96), (1, 1, 1 << 20)]:
+        p = gemm_hp_plan(M, N, K, 1 << 40)
+        want = L.rnnt_hip_gemm_hp_workspace_bytes(M, N, K)
+        assert p.workspace_bytes_wanted == want and gemm_hp_plan(M, N, K, 0).workspace_bytes_wanted == want
+        assert gemm_hp_plan(M, N, K, want) == p                                        # what the query asks for is enough for the full split
+        assert (p.splits > 1) == (want > 0) and p.splits * M * N * 4 <= max(want, M * N * 4)
+        nkt = -(-K // 32)
+        assert (p.splits - 1) * p.kt_per_split < nkt <= p.splits * p.kt_per_split      # every slab has work, the last takes the rest
 
 
 def test_module_surface_mirrors_reference_and_fails_loudly_on_cpu():
