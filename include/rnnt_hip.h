@@ -445,6 +445,38 @@ int rnnt_hip_align_from_logits_ex(const void* logits, int32_t dtype, const int32
                                   const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
                                   int32_t* frames, double* score, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTC loss on per-frame logits (the auxiliary loss on the encoder's output) and the greedy CTC decode.  csrc/ctc.hip, DESIGN.md §16.
+ * logits(b,t,v) = logits[b*z_sb + t*z_st + v], finite fp32 (batch-major and time-major buffers both work, the inner stride is 1;
+ * z_st >= V).  labels (B,U) int32, t_lens (B) int32 in [1,T], u_lens (B) int32 in [0,U]; U <= 511, any V, U = 0 allowed (labels may
+ * then be NULL).  The blank is an ordinary vocabulary entry, blank in [0,V); a blank inside labels[b,:u_lens[b]] is not checked.
+ * Logits of frames t >= t_lens[b] and labels at k >= u_lens[b] are never read.
+ *   extended sequence l' of 2 u_lens[b] + 1 states (blank, y_0, blank, y_1, ..., blank), lp = log-softmax of a frame,
+ *   alpha_t(s) = lp[t,l'_s] + logsumexp(alpha_{t-1}(s), alpha_{t-1}(s-1), [l'_s != blank and l'_s != l'_{s-2}] alpha_{t-1}(s-2)),
+ *   nll[b] = -logaddexp(alpha_{T_b-1}(S-1), alpha_{T_b-1}(S-2)); fp32 per-frame terms, fp64 lattice sums, fixed summation order.
+ * A row with no path (t_lens[b] < u_lens[b] + number of k with y_k = y_{k+1}; also t_lens[b] = 0) gives nll[b] = +inf and an exactly
+ * zero row of dlogits; every other row is bitwise what it is alone.
+ * rnnt_hip_ctc_loss_fwd leaves the per-frame terms, alpha, beta and log Z in `workspace` (rnnt_hip_ctc_loss_workspace_bytes; 0 for
+ * B, T or V < 1 or U < 0); rnnt_hip_ctc_loss_bwd, on the SAME operands and that workspace, writes
+ *   dlogits(b,t,v) = gscale * gvec[b*gvec_stride] * (softmax(logits[b,t,:])[v] - sum_{s: l'_s = v} occ_t(s))   for t < t_lens[b],
+ * exact zeros for t_lens[b] <= t < T, with the logits' strides (gvec device, gvec_stride 1 = one value per utterance, 0 = ONE scalar
+ * for all, as in rnnt_hip_joint_loss_bwd; NULL = ones).  Repeated labels are summed in label order: no float atomics, the same bits
+ * on every call.  Arguments are validated before any device work; nothing allocates or synchronises.
+ * rnnt_hip_ctc_greedy: per frame the argmax over v (ties go to the LOWEST index); frame t's token is kept when it is not the blank
+ * and differs from frame t-1's argmax.  tokens (B,T) int32: the first counts[b] entries of row b are the kept tokens (the rest of the
+ * row is not written); counts (B) int32; frames (B,T) int32 or NULL: the first frame of each kept token's run.  One launch.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_ctc_loss_workspace_bytes(int32_t B, int32_t T, int32_t U, int32_t V);
+int rnnt_hip_ctc_loss_fwd(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
+                          const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, float* nll,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int rnnt_hip_ctc_loss_bwd(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
+                          const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, float gscale,
+                          const float* gvec, int32_t gvec_stride, float* dlogits, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T, int32_t V,
+                        int32_t blank, int32_t* tokens, int32_t* counts, int32_t* frames, void* stream);
+
 /* One fused AdamW step over FLAT fp32 buffers (all parameters / gradients / moments of the module laid out back to back):
  * replaces torch.optim.AdamW's multi-tensor kernels at model.py:111-115.  Same update as torch (decoupled weight decay,
  * bias corrections from `step` >= 1). */

@@ -210,6 +210,13 @@ SYMBOLS = {
                                        C.c_size_t, C.c_void_p]),
     "rnnt_hip_align_from_logits_ex": (C.c_int, [C.c_void_p, c_i32, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32,
                                                 c_i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_ctc_loss_workspace_bytes": (C.c_size_t, [c_i32] * 4),
+    "rnnt_hip_ctc_loss_fwd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32,
+                                        c_i32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_ctc_loss_bwd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32,
+                                        c_i32, C.c_float, C.c_void_p, c_i32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_ctc_greedy": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "rnnt_hip_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_float, c_i64, C.c_void_p]),
     "rnnt_hip_adamw_step_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_float, C.c_float, C.c_float,

@@ -16,6 +16,7 @@
 //   reduce_dc_kernel                  : fixed-order sum of the slabs (bitwise reproducible, no float atomics)
 //   grad_dense_kernel                 : warp-transducer-shaped d/d logits for rnnt_hip_loss_from_logits_*
 #include "common.hpp"
+#include "lattice_shared.hpp"
 
 #include <stdlib.h>
 
@@ -35,19 +36,6 @@ __device__ __forceinline__ float ldf(const __hip_bfloat16* p, long i) { return _
 __device__ __forceinline__ void stf(float* p, long i, float v) { p[i] = v; }
 __device__ __forceinline__ void stf(__half* p, long i, float v) { p[i] = __float2half(v); }
 __device__ __forceinline__ void stf(__hip_bfloat16* p, long i, float v) { p[i] = __float2bfloat16(v); }
-constexpr double NEG_INF = -__builtin_huge_val();
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 // ------------------------------------------------------------------------------------------------
 // per-cell log-sum-exp, separable logits.  grid (ceil(T/32), ceil(U1/8), B), 256 threads = 32 t x 8 u
 // ------------------------------------------------------------------------------------------------
@@ -210,32 +198,8 @@ __global__ void __launch_bounds__(256) lse_dense_kernel(const TZ* __restrict__ Z
 
 // ------------------------------------------------------------------------------------------------
 // alpha / beta: one wavefront per (b, which).  fp64 accumulation, fp32 correction term.
+// (logaddexp_d, the DPP hand-off shfl_up1 / shfl_down1, PF and AB_RSRC / AB_OOB are in lattice_shared.hpp, shared with ctc.hip)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double logaddexp_d(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == NEG_INF) return NEG_INF;
-  const float d = (float)(fmin(a, b) - m);  // <= 0, -inf allowed
-  // fp32 correction term in [0, ln 2]: hardware exp/log (abs err ~1e-7) -- the fp64 running sums keep the lattice exact
-  return m + (double)__logf(1.0f + __expf(d));
-}
-// neighbour hand-off across the whole wavefront by DPP (wave_shr:1 / wave_shl:1): two moves per fp64, no LDS permute
-__device__ __forceinline__ double shfl_up1(double x, int lane) {
-  const long long b = __builtin_bit_cast(long long, x);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x138, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x138, 0xf, 0xf, false);
-  const double y = __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-  return lane == 0 ? NEG_INF : y;
-}
-__device__ __forceinline__ double shfl_down1(double x, int lane) {
-  const long long b = __builtin_bit_cast(long long, x);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, 0x130, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x130, 0xf, 0xf, false);
-  const double y = __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-  return lane == 63 ? NEG_INF : y;
-}
-
-constexpr int PF = 8;  // rows of blk/emit in flight per lane (register ring)
-constexpr int AB_RSRC = 0x00027000, AB_OOB = 0x7ffffff0;
 // The sweep is a chain of ~T + U dependent steps (one anti-diagonal each).  Every memory operation of the loop goes through a buffer
 // resource with an out-of-range offset for lanes / steps that have no cell (loads return 0, stores are dropped): the loop body has NO
 // branch around a memory operation, so hipcc counts how many younger operations may stay in flight when it waits for a ring slot

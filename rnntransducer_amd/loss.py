@@ -3,11 +3,13 @@
 model.py:57 as `loss(logits, targets, logit_lengths, target_lengths)`, on the HIP alpha/beta kernels.
 Returns a 0-d tensor for "mean"/"sum" (the warp-transducer build returns shape (1,), model.py:83-88; documented
 difference), or (B,) for reduction="none".
+
+CTCLoss — the CTC loss on per-frame logits (the auxiliary loss on the encoder's output, csrc/ctc.hip), same call shape.
 """
 import torch
 import torch.nn as nn
 
-from .ops import Alignment, RnntLossFromLogitsFn, align_from_logits
+from .ops import Alignment, CtcLossFn, RnntLossFromLogitsFn, align_from_logits
 
 
 class RNNTLoss(nn.Module):
@@ -27,6 +29,28 @@ class RNNTLoss(nn.Module):
         if self.reduction == "sum":
             return nll.sum()
         return nll
+
+
+class CTCLoss(nn.Module):
+    """CTC negative log-likelihood of `targets` given per-frame `logits` (raw, the log-softmax is fused), on the HIP kernels of
+    csrc/ctc.hip: `loss(logits (B,T,V) fp32, targets (B,U) int32, logit_lengths (B,) int32, target_lengths (B,) int32)`.
+    reduction "none" gives (B,); "sum" and "mean" are reductions over the BATCH, exactly like RNNTLoss here: "mean" is
+    sum_b NLL_b / B.  It is NOT torch.nn.CTCLoss's "mean", which first divides each NLL by its target length.
+    An utterance with fewer frames than its transcript needs (labels + adjacent repeats) has NLL +inf, or 0 with
+    zero_infinity=True; its gradient row is exactly zero in both cases (torch gives NaN there).  U <= 511.  Same bits on every call."""
+
+    def __init__(self, blank: int = 0, reduction: str = "mean", zero_infinity: bool = False):
+        super().__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
+        self.blank, self.reduction, self.zero_infinity = int(blank), reduction, bool(zero_infinity)
+
+    def forward(self, logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor,
+                target_lengths: torch.Tensor) -> torch.Tensor:
+        if logits.dim() != 3:
+            raise ValueError("logits must be (B, T, V)")
+        return CtcLossFn.apply(logits, targets, logit_lengths, target_lengths, self.blank, torch.is_grad_enabled(), self.reduction,
+                               False, self.zero_infinity)
 
 
 @torch.no_grad()

@@ -11,6 +11,9 @@ Differences, all inside the hot path:
   * blank/pad id comes from `args.blank_token_id` / `prednet_params["pad_token_id"]` (default 0, as in the shipped
     config.json:37,40) instead of loading a tokenizer (model.py:24-26): tokenizer and WER/CER are validation-side
     and out of scope.
+  * `jointnet_params["aux_ctc"] = True` adds a CTC head on the encoder (JointNet.ctc_head) and `args.ctc_weight` (default 0.0) the
+    auxiliary CTC loss of joint CTC + transducer training to `training_step`: loss = rnnt + ctc_weight * ctc.  Both are off by
+    default; the reference has neither.
   * `validation_step` stays on the GPU (the reference moves the module to the CPU at model.py:65-72 because its
     decode is a host loop): fused loss + on-device greedy search; it returns token ids, and texts only if a
     tokenizer object was attached as `self.tokenizer`.
@@ -53,6 +56,9 @@ class RNNTransducer(_Base):
         self.jointnet.set_compute_precision(cp)
         # model.py:28-39 picks torchaudio (precision 16) or warp-transducer; both are this one HIP module here
         self.rnnt_loss = RNNTLoss(blank=self.blank_token_id, reduction="mean")
+        self.ctc_weight = float(getattr(args, "ctc_weight", 0.0) or 0.0)
+        if self.ctc_weight > 0.0 and not self.jointnet.aux_ctc:
+            raise ValueError("args.ctc_weight > 0 needs the CTC head: set jointnet_params['aux_ctc'] = True")
 
     def forward(self, input_audios, audio_lengths, input_texts, text_lengths):
         # the reference hands these two as python lists (dataloader.py:20,37): validating them costs no device sync
@@ -72,11 +78,21 @@ class RNNTransducer(_Base):
         with torch.serialization.safe_globals([Namespace]):
             return torch.load(path, map_location="cpu", weights_only=True)
 
+    AUX_KEYS = ("jointnet.ctc_head.weight", "jointnet.ctc_head.bias")   # what the reference's model does not have
+
     def load_reference_checkpoint(self, path: str, strict: bool = True):
-        """Loads the `state_dict` (keys `jointnet.*`) of a reference-written Lightning .ckpt into this module."""
+        """Loads the `state_dict` (keys `jointnet.*`) of a reference-written Lightning .ckpt into this module.
+        A model with the CTC head tolerates exactly the two `jointnet.ctc_head.*` keys missing from the file (the head keeps
+        its initialisation); anything else missing or unexpected still raises under strict=True."""
         blob = self.read_reference_checkpoint(path)
-        sd = blob.get("state_dict", blob)
-        return self.load_state_dict({k: v for k, v in sd.items() if k.startswith("jointnet.")}, strict=strict)
+        sd = {k: v for k, v in blob.get("state_dict", blob).items() if k.startswith("jointnet.")}
+        if not (self.jointnet.aux_ctc and strict and not any(k in sd for k in self.AUX_KEYS)):
+            return self.load_state_dict(sd, strict=strict)
+        res = self.load_state_dict(sd, strict=False)
+        missing = [k for k in res.missing_keys if k not in self.AUX_KEYS]
+        if missing or res.unexpected_keys:
+            raise RuntimeError(f"load_reference_checkpoint: missing keys {missing}, unexpected keys {list(res.unexpected_keys)}")
+        return res
 
     @classmethod
     def from_reference_checkpoint(cls, path: str, **overrides):
@@ -90,17 +106,28 @@ class RNNTransducer(_Base):
         model.load_state_dict({k: v for k, v in sd.items() if k.startswith("jointnet.")})
         return model
 
-    def save_reference_checkpoint(self, path: str, epoch: int = 0, global_step: int = 0, optimizer=None) -> None:
+    def save_reference_checkpoint(self, path: str, epoch: int = 0, global_step: int = 0, optimizer=None,
+                                  include_aux: bool = False) -> None:
         """Writes a Lightning-1.8-shaped .ckpt the reference's `load_from_checkpoint` / `--resume_from_checkpoint` accept:
         `state_dict` (CPU tensors, keys `jointnet.*`), `hyper_parameters` = what model.py:22 saves (three dicts + the
-        Namespace), epoch / global_step, `optimizer_states` in torch's format when an optimizer is given."""
+        Namespace), epoch / global_step, `optimizer_states` in torch's format when an optimizer is given.
+        include_aux=False (default) drops the `jointnet.ctc_head.*` tensors, the `aux_ctc` entry of jointnet_params and a positive
+        args.ctc_weight, so the reference's strict loader (and a model without the head) still accepts the file;
+        include_aux=True keeps them (for `from_reference_checkpoint` of a model with the head)."""
         jp = dict(self._ctor_args["jointnet_params"])
+        args = self._ctor_args["args"]
+        sd = self.state_dict()
+        if not include_aux:
+            jp.pop("aux_ctc", None)
+            sd = {k: v for k, v in sd.items() if k not in self.AUX_KEYS}
+            if getattr(args, "ctc_weight", 0.0):
+                args = Namespace(**{**vars(args), "ctc_weight": 0.0})
         blob = {
             "epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": "1.8.0",
-            "state_dict": {k: v.detach().cpu().clone() for k, v in self.state_dict().items()},
+            "state_dict": {k: v.detach().cpu().clone() for k, v in sd.items()},
             "hyper_parameters": {"prednet_params": dict(self._ctor_args["prednet_params"]),
                                  "transnet_params": dict(self._ctor_args["transnet_params"]), "jointnet_params": jp,
-                                 "args": self._ctor_args["args"]},
+                                 "args": args},
             "hparams_name": "kwargs",
         }
         if optimizer is not None:
@@ -115,7 +142,8 @@ class RNNTransducer(_Base):
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
-                                  audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None)
+                                  audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None,
+                                  ctc_weight=self.ctc_weight)
         if pl is not None and getattr(self, "_trainer", None) is not None:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}
@@ -126,6 +154,10 @@ class RNNTransducer(_Base):
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         return self.jointnet.align(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
                                    audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None)
+
+    def recognize_ctc_greedy(self, inputs, inputs_lengths, return_frames: bool = False):
+        """JointNet.recognize_ctc_greedy with this model's blank: the encoder-only greedy decode through the CTC head."""
+        return self.jointnet.recognize_ctc_greedy(inputs, inputs_lengths, self.blank_token_id, return_frames)
 
     def init_stream(self, batch_size: int, device=None):
         """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
@@ -151,19 +183,29 @@ class RNNTransducer(_Base):
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
         """model.py:62-79: loss + greedy search (max 3 symbols per frame).  `pred_tokens` is a list of B 1-D LongTensors
-        (each what the reference's batch-1 recognize_greedy returns for that utterance), `label_tokens` the un-padded targets."""
+        (each what the reference's batch-1 recognize_greedy returns for that utterance), `label_tokens` the un-padded targets.
+        A model with the CTC head adds `ctc_loss` (the mean CTC term; `loss` stays the RNN-T loss) and `ctc_pred_tokens` (the
+        encoder-only greedy decode, a list like `pred_tokens`)."""
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
-        nll = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id)
+        aux = self.jointnet.aux_ctc
+        nll = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
+                                 return_parts=aux)
+        if aux:
+            _, nll, ctc_nll = nll
         was_training = self.jointnet.training
         self.jointnet.eval()
         try:
             pred = self.jointnet.recognize_greedy(input_audios, tensor_audio_lengths, self.blank_token_id, 3)
+            if aux:
+                ctc_pred = self.jointnet.recognize_ctc_greedy(input_audios, tensor_audio_lengths, self.blank_token_id)
         finally:
             self.jointnet.train(was_training)
         pred = [p for p in pred] if isinstance(pred, list) else [pred[0]]
         u = target_lengths.tolist() if isinstance(target_lengths, torch.Tensor) else list(target_lengths)
         labels = [targets[b, :u[b]].long() for b in range(targets.size(0))]
         out = {"loss": nll.mean(), "pred_tokens": pred, "label_tokens": labels}
+        if aux:
+            out["ctc_loss"], out["ctc_pred_tokens"] = ctc_nll.mean(), ctc_pred
         tok = getattr(self, "tokenizer", None)
         if tok is not None:
             out["pred_texts"] = tok.batch_decode([p.tolist() for p in pred])

@@ -17,18 +17,21 @@ prediction-net and search state carried between chunks (rnntransducer_amd/stream
 (csrc/beam_stream.hip, the offline kernel's frame loop), with the stable prefix of every stream exposed after each chunk.
 `align` returns the best path of a known transcript (the frame at which every label is emitted, and the path's score) from the
 fused loss's per-cell terms: the loss's lattice sweep in the (max, +) semiring (csrc/loss.hip).
+`aux_ctc=True` adds `ctc_head`, a Linear(O_e -> V) on the encoder's output, for the auxiliary CTC loss of joint CTC + transducer
+training (`loss(..., ctc_weight=w)`, `ctc_loss` for CTC pre-training of the encoder) and an encoder-only greedy decode
+(`recognize_ctc_greedy`); csrc/ctc.hip.  Off by default: parameters, their initialisation and every result stay as without it.
 """
 import torch
 import torch.nn as nn
 
-from ..ops import JointLogitsFn, JointLossFn, TimedTokens, beam_search, greedy_decode, stream_greedy
+from ..ops import CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, ctc_greedy, greedy_decode, stream_greedy
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
 
 
 class JointNet(nn.Module):
-    def __init__(self, transnet_params: dict, prednet_params: dict, num_classes: int):
+    def __init__(self, transnet_params: dict, prednet_params: dict, num_classes: int, aux_ctc: bool = False):
         super().__init__()
         self.encoder = AudioTransNet(**transnet_params)
         self.decoder = TextPredNet(**prednet_params)
@@ -37,6 +40,35 @@ class JointNet(nn.Module):
         self.dec_out = prednet_params["output_size"]
         # parameter container only: fc is applied inside the fused kernels (A/C pre-GEMMs), never as one Linear
         self.fc = HipLinear(self.enc_out + self.dec_out, num_classes)
+        # created LAST: under a given seed every other parameter initialises to the same bits as without the head
+        self.aux_ctc = bool(aux_ctc)
+        if self.aux_ctc:
+            self.ctc_head = HipLinear(self.enc_out, num_classes)
+
+    def _need_ctc_head(self, what: str) -> None:
+        if not self.aux_ctc:
+            raise ValueError(f"{what} needs the CTC head: build the JointNet with aux_ctc=True (jointnet_params['aux_ctc'])")
+
+    @staticmethod
+    def _ragged_rows(audio_lengths, T, B, dev, t_lens, u_lens, rows, want_inv):
+        """The ragged handling of loss(): with the collate's python list of frame counts, rows sorted by descending length (the
+        per-row tensors `rows` and both length tensors follow) and an ops.RaggedPlan for the encoder; `inv` restores the
+        caller's row order.  -> rows, t_lens, u_lens, enc_lens, inv"""
+        enc_lens, inv = t_lens, None
+        if audio_lengths is not None and len(audio_lengths) == B and B > 1 and min(audio_lengths) < T:
+            from ..ops import RaggedPlan
+            host = [int(n) for n in audio_lengths]
+            order = sorted(range(B), key=lambda b: (-host[b], b))
+            if order != list(range(B)):   # length-sorted rows (encoder.py:94-96); the small per-utterance tensors follow, nll is un-sorted below
+                perm = torch.tensor(order, dtype=torch.int64, device=dev)
+                rows = tuple(x.index_select(0, perm) for x in rows)
+                t_lens, u_lens = t_lens.index_select(0, perm), u_lens.index_select(0, perm)
+                host = [host[b] for b in order]
+                if want_inv:
+                    inv = torch.empty_like(perm)
+                    inv[perm] = torch.arange(B, dtype=torch.int64, device=dev)
+            enc_lens = RaggedPlan(host, T, dev)
+        return rows, t_lens, u_lens, enc_lens, inv
 
     def set_compute_precision(self, p: str):
         """"fp32" | "fp16" for every recurrent stack below this module (HipLSTM.compute_precision); returns self."""
@@ -64,36 +96,67 @@ class JointNet(nn.Module):
         return JointLogitsFn.apply(enc, dec, self.fc.weight, self.fc.bias)
 
     def loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int,
-             reduction: str = "none", audio_lengths=None) -> torch.Tensor:
+             reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False):
         """-log P(y|x) through the fused path (no (B,T,U+1,V) tensor): per utterance, shape (B,) (reduction "none"), or the 0-d
         "mean" / "sum" over the batch (model.py:39 builds the reference's loss with reduction="mean").
         `audio_lengths`: the python list of frame counts the reference's collate hands over next to the tensor (dataloader.py:20,49).
         With it a ragged batch is handled as the reference handles it (networks/encoder.py:93-96: sort by length, pack): rows are
         sorted by descending length so that the recurrences' sync groups are length-homogeneous, and a valid-frame table lets the
         big products and the recurrences skip the padding (ops.RaggedPlan) — all planned on the host, no device synchronisation.
-        Results do not depend on it."""
+        Results do not depend on it.
+        `ctc_weight` != 0 (aux_ctc=True only): the result is rnnt + ctc_weight * ctc under the same reduction, the CTC term
+        being the CTC loss of `targets` on ctc_head(encoder output); ONE encoder forward feeds both.  return_parts=True returns
+        (total, rnnt, ctc); with ctc_weight = 0 the CTC part is then computed without a graph and total is the RNN-T loss.
+        With ctc_weight = 0 and return_parts=False the head is not touched: same bits as a model without it."""
+        with_ctc = ctc_weight != 0.0 or return_parts
+        if with_ctc:
+            self._need_ctc_head("loss(ctc_weight != 0 or return_parts=True)")
         dev = input_audios.device
         t_lens = lengths_to_device(tensor_audio_lengths, dev)
         u_lens = lengths_to_device(target_lengths, dev)
-        enc_lens, inv = t_lens, None
         T, B = input_audios.size(1), input_audios.size(0)
-        if audio_lengths is not None and len(audio_lengths) == B and B > 1 and min(audio_lengths) < T:
-            from ..ops import RaggedPlan
-            host = [int(n) for n in audio_lengths]
-            order = sorted(range(B), key=lambda b: (-host[b], b))
-            if order != list(range(B)):   # length-sorted rows (encoder.py:94-96); the small per-utterance tensors follow, nll is un-sorted below
-                perm = torch.tensor(order, dtype=torch.int64, device=dev)
-                input_audios, input_texts, targets = (x.index_select(0, perm) for x in (input_audios, input_texts, targets))
-                t_lens, u_lens = t_lens.index_select(0, perm), u_lens.index_select(0, perm)
-                host = [host[b] for b in order]
-                if reduction == "none":
-                    inv = torch.empty_like(perm)
-                    inv[perm] = torch.arange(B, dtype=torch.int64, device=dev)
-            enc_lens = RaggedPlan(host, T, dev)
+        (input_audios, input_texts, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), reduction == "none")
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
         out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction)
+        out = out if inv is None else out.index_select(0, inv)
+        if not with_ctc:
+            return out
+        track = ctc_weight != 0.0 and torch.is_grad_enabled()
+        with torch.set_grad_enabled(track):
+            ctc = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, track, reduction, True)
+        ctc = ctc if inv is None else ctc.index_select(0, inv)
+        total = out + ctc_weight * ctc if ctc_weight != 0.0 else out
+        return (total, out, ctc) if return_parts else total
+
+    def ctc_loss(self, input_audios, tensor_audio_lengths, targets, target_lengths, blank: int, reduction: str = "none",
+                 audio_lengths=None) -> torch.Tensor:
+        """The CTC term alone (CTC pre-training of the encoder): the CTC loss of `targets` on ctc_head(encoder output); the
+        prediction net and the joint are not run.  Arguments, reductions and the ragged handling as in `loss`."""
+        self._need_ctc_head("ctc_loss")
+        dev = input_audios.device
+        t_lens = lengths_to_device(tensor_audio_lengths, dev)
+        u_lens = lengths_to_device(target_lengths, dev)
+        T, B = input_audios.size(1), input_audios.size(0)
+        (input_audios, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, targets), reduction == "none")
+        enc = self.encoder.forward_time_major(input_audios, enc_lens)
+        out = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction, True)
         return out if inv is None else out.index_select(0, inv)
+
+    @torch.no_grad()
+    def recognize_ctc_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, return_frames: bool = False):
+        """Encoder-only greedy decode through the CTC head: per frame the argmax of ctc_head(encoder output) (ties to the lowest
+        index), repeats collapsed, blanks dropped; one launch and one host sync (csrc/ctc.hip).  Returns a list of B 1-D
+        LongTensors; with return_frames a list of (tokens, frames) pairs, frames int32: the encoder frame at which each token's
+        run starts.  Works with bidirectional encoders.  eval() mode only, like recognize_greedy."""
+        self._need_ctc_head("recognize_ctc_greedy")
+        if self.training:
+            raise RuntimeError("recognize_ctc_greedy expects eval() mode (dropout inactive), like recognize_greedy")
+        t_lens = lengths_to_device(inputs_lengths, inputs.device)
+        enc = self.encoder.forward_time_major(inputs, t_lens)
+        return ctc_greedy(self.ctc_head(enc), t_lens, blank_token_id, time_major=True, return_frames=return_frames)
 
     @torch.no_grad()
     def align(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, audio_lengths=None):

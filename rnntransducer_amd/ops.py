@@ -867,6 +867,96 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------------------
+# CTC loss on per-frame logits and the greedy CTC decode (include/rnnt_hip.h: rnnt_hip_ctc_*, csrc/ctc.hip)
+# --------------------------------------------------------------------------------------------------
+def _ctc_strides(logits: torch.Tensor, time_major: bool):
+    """(B, T, V) and the element strides over b and t of a contiguous (B,T,V) or, time_major, (T,B,V) tensor."""
+    if logits.dim() != 3:
+        raise ValueError("logits must be (B, T, V), or (T, B, V) with time_major=True")
+    if time_major:
+        T, B, V = logits.shape
+        return B, T, V, V, B * V
+    B, T, V = logits.shape
+    return B, T, V, T * V, V
+
+
+class CtcLossFn(torch.autograd.Function):
+    """logits (B,T,V) (time_major: (T,B,V)) fp32 -> per-utterance CTC NLL (B,), or its "sum" / "mean" over the batch (0-d).
+    forward: per-frame terms + alpha/beta (kept in a workspace); backward: the gradient kernel with the upstream gradient folded
+    in (1/B under "mean").  Under torch.no_grad() nothing is kept.  A row without any path has NLL +inf (0 with zero_infinity)
+    and an exactly zero gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", time_major=False, zero_infinity=False):
+        _need_gpu(logits, labels, t_lens, u_lens)
+        logits = _f32c(logits, "logits")
+        for name, t in (("targets", labels), ("logit lengths", t_lens), ("target lengths", u_lens)):
+            if t.dtype != torch.int32:
+                raise ValueError(f"{name} must be int32, got {t.dtype}")
+        B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+        if labels.dim() != 2 or labels.shape[0] != B or t_lens.shape != (B,) or u_lens.shape != (B,):
+            raise ValueError(f"targets must be (B, U) with B = {B} and both lengths (B,), got {tuple(labels.shape)}, "
+                             f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
+        labels, t_lens, u_lens = labels.contiguous(), t_lens.contiguous(), u_lens.contiguous()
+        U = labels.shape[1]
+        L = _lib.lib()
+        nll = torch.empty(B, device=logits.device, dtype=torch.float32)
+        nws = L.rnnt_hip_ctc_loss_workspace_bytes(B, T, U, V)
+        ws = torch.empty(max(nws, 16), device=logits.device, dtype=torch.uint8)
+        check(L.rnnt_hip_ctc_loss_fwd(_addr(logits), z_sb, z_st, _addr(labels) if U else None, _addr(t_lens), _addr(u_lens), B, T, U, V,
+                                      int(blank), _addr(nll), _addr(ws), nws, _stream()), "rnnt_hip_ctc_loss_fwd")
+        if want_grad and ctx.needs_input_grad[0]:   # want_grad: the caller's torch.is_grad_enabled() (always off in here)
+            ctx.save_for_backward(logits, labels, t_lens, u_lens, ws)
+            ctx.dims = (B, T, U, V, z_sb, z_st, int(blank), nws)
+        if zero_infinity:   # (the row's gradient is zero either way)
+            nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
+        ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
+        if ctx.red_scale is None:
+            return nll
+        out = torch.empty((), device=logits.device, dtype=torch.float32)
+        check(L.rnnt_hip_scaled_sum_f32(_addr(nll), B, ctx.red_scale, _addr(out), _stream()), "rnnt_hip_scaled_sum_f32")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, t_lens, u_lens, ws = ctx.saved_tensors
+        B, T, U, V, z_sb, z_st, blank, nws = ctx.dims
+        gvec = _f32c(g.to(torch.float32), "grad of the loss")
+        scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
+        dlogits = torch.empty_like(logits)
+        check(_lib.lib().rnnt_hip_ctc_loss_bwd(_addr(logits), z_sb, z_st, _addr(labels) if U else None, _addr(t_lens), _addr(u_lens),
+                                               B, T, U, V, blank, ctx.red_scale if scalar else 1.0, _addr(gvec), 0 if scalar else 1,
+                                               _addr(dlogits), _addr(ws), nws, _stream()), "rnnt_hip_ctc_loss_bwd")
+        return dlogits, None, None, None, None, None, None, None, None
+
+
+@torch.no_grad()
+def ctc_greedy(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, *, time_major: bool = False, return_frames: bool = False):
+    """Greedy CTC decode of logits (B,T,V) (time_major: (T,B,V)) fp32, t_lens (B,) int32: per frame the argmax (ties to the
+    lowest index), repeats collapsed, blanks dropped.  One launch, then one host copy (the counts).  Returns a list of B 1-D
+    LongTensors; with return_frames a list of (tokens, frames) pairs, frames int32: the first frame of each token's run."""
+    _need_gpu(logits, t_lens)
+    logits = _f32c(logits, "logits")
+    if t_lens.dtype != torch.int32:
+        raise ValueError(f"logit lengths must be int32, got {t_lens.dtype}")
+    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    if t_lens.shape != (B,):
+        raise ValueError(f"logit lengths must be (B,) = ({B},), got {tuple(t_lens.shape)}")
+    t_lens = t_lens.contiguous()
+    tokens = torch.empty(B, T, device=logits.device, dtype=torch.int32)
+    counts = torch.empty(B, device=logits.device, dtype=torch.int32)
+    frames = torch.empty(B, T, device=logits.device, dtype=torch.int32) if return_frames else None
+    check(_lib.lib().rnnt_hip_ctc_greedy(_addr(logits), z_sb, z_st, _addr(t_lens), B, T, V, int(blank), _addr(tokens), _addr(counts),
+                                         _addr(frames), _stream()), "rnnt_hip_ctc_greedy")
+    n = counts.tolist()   # the only host sync of the decode
+    if return_frames:
+        return [(tokens[b, :n[b]].long(), frames[b, :n[b]]) for b in range(B)]
+    return [tokens[b, :n[b]].long() for b in range(B)]
+
+
+# --------------------------------------------------------------------------------------------------
 # forced alignment (include/rnnt_hip.h: rnnt_hip_joint_align / rnnt_hip_align_from_logits_ex): best path of a known transcript
 # --------------------------------------------------------------------------------------------------
 class Alignment:
