@@ -780,6 +780,48 @@ int rnnt_hip_beam_search_timed(const rnnt_beam_desc* d, const rnnt_beam_timing* 
 int rnnt_hip_beam_stream_chunk_timed(const rnnt_beam_stream_desc* d, const rnnt_beam_timing* timing, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Beam search with token-level fusion: hotword boosting and token / grapheme LM tables.  The reference's lm= / hotwords= branch
+ * (networks/transducer.py:147-213, 253-264, 352-361; inference.py:56-64) ranks hypotheses by "lm_score" = asr_score plus a
+ * score that depends on the decoded y_star alone; it computes that score with pyctcdecode and KenLM over text.  Here the score
+ * is that of a weighted DETERMINISTIC AUTOMATON over token ids, held as dense tables on the device:
+ *   next  (S, V) int32    next[s*V + k]: the state after appending token k in state s, in [0, S) (values outside are clamped)
+ *   arc   (S, V) float32  the score added by that append
+ *   final (S)    float32  added once, only when a hypothesis is ranked for output
+ * State 0 is the start state: it belongs to y_star = [blank].  total(y) = sum_i arc[s_{i-1}, y_i] over the tokens after the
+ * leading blank, accumulated in fp64 in append order.  The automaton advances only when a token is APPENDED: a blank child and
+ * a child whose token equals y_star[-1] (the dedupe rule, :337, :345) keep state and total.
+ * Every comparison the reference makes on compare_key uses key = asr_score + total: the pop argmax over A (:285-288), the best
+ * of B (:293), the improved early-out (:295), the stop test (:355-358); the result is the last frame's B stable-sorted by
+ * (asr_score + total + final[state]) / len(y_star) (:360).  The prune test stays on the fp32 ASR log-probabilities (:336).
+ * `final` is never stored back, so the streaming search keeps "after every chunk the n-best is the offline result for the
+ * frames so far".  scores still returns asr_score; fused_scores returns asr_score + total + final[state].
+ * With positive arcs a frame's pop loop need not end (a hypothesis that keeps earning more than its log-probability falls; the
+ * reference has the same hazard with hotwords): max_pops bounds it, status RNNT_BEAM_ST_POPS.
+ *
+ * The fused entries take the descriptor of their unfused entry (unchanged layout), the fusion struct, and a timing struct that
+ * may be NULL (no frames).  They run the FUSED instance of the one kernel template (csrc/beam_shared.hpp); the unfused entries
+ * are untouched.  The workspace is the unfused one followed, per utterance, by the total (fp64) and state (int32) of every A
+ * and B entry: 12 * (max_candidates + max_pops) bytes rounded up to 256 twice; query it with the *_fused_workspace_bytes
+ * entries.  A stream's automaton is fixed by rnnt_hip_beam_stream_reset_fused (which also seeds state 0, total 0): pass the
+ * same tables to every chunk.  All argument checks (a NULL table, n_states < 1, n_states * V > 2^27, a misaligned or short
+ * workspace) happen on the host before any device work.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_fusion {
+  const int32_t* next;   /* (S, V) device */
+  const float* arc;      /* (S, V) device */
+  const float* final;    /* (S) device */
+  int32_t n_states;      /* S >= 1, S * V <= 2^27 */
+  double* fused_scores;  /* (B, beam) device, beside scores: asr_score + total + final[state] */
+} rnnt_beam_fusion;
+size_t rnnt_hip_beam_fused_workspace_bytes(const rnnt_beam_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_search_fused(const rnnt_beam_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_timing* timing, void* stream);
+size_t rnnt_hip_beam_stream_fused_workspace_bytes(const rnnt_beam_stream_desc* d);
+int rnnt_hip_beam_stream_reset_fused(const rnnt_beam_stream_desc* d, const rnnt_beam_fusion* fusion, const int32_t* rows,
+                                     int32_t n_rows, int32_t build_table, void* stream);
+int rnnt_hip_beam_stream_chunk_fused(const rnnt_beam_stream_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_timing* timing,
+                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

@@ -150,6 +150,11 @@ class BeamTiming(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("commit_frames", C.c_void_p)]
 
 
+class BeamFusion(C.Structure):
+    _fields_ = [("next", C.c_void_p), ("arc", C.c_void_p), ("final", C.c_void_p), ("n_states", c_i32),
+                ("fused_scores", C.c_void_p)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -242,6 +247,13 @@ SYMBOLS = {
     "rnnt_hip_stream_greedy_timed": (C.c_int, [C.POINTER(StreamGreedyDesc), C.POINTER(GreedyTiming), C.c_void_p]),
     "rnnt_hip_beam_search_timed": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(BeamTiming), C.c_void_p]),
     "rnnt_hip_beam_stream_chunk_timed": (C.c_int, [C.POINTER(BeamStreamDesc), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_fused_workspace_bytes": (C.c_size_t, [C.POINTER(BeamDesc)]),
+    "rnnt_hip_beam_search_fused": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(BeamFusion), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_stream_fused_workspace_bytes": (C.c_size_t, [C.POINTER(BeamStreamDesc)]),
+    "rnnt_hip_beam_stream_reset_fused": (C.c_int, [C.POINTER(BeamStreamDesc), C.POINTER(BeamFusion), C.c_void_p, c_i32, c_i32,
+                                                  C.c_void_p]),
+    "rnnt_hip_beam_stream_chunk_fused": (C.c_int, [C.POINTER(BeamStreamDesc), C.POINTER(BeamFusion), C.POINTER(BeamTiming),
+                                                  C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
 }

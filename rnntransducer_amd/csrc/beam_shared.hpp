@@ -4,6 +4,12 @@
 // n-best selection are the same statements for both, so the two searches cannot drift apart.  STREAM only adds what lies
 // around them: load the per-stream header instead of seeding [blank], collect the prefix tree after the last frame of the
 // chunk, write y_star tails relative to the committed root, store the header.
+//
+// FUSED (the rnnt_hip_beam_*_fused entries; token-level fusion, include/rnnt_hip.h): every hypothesis also carries the state of
+// a dense deterministic automaton over token ids and the fp64 total of the arc scores its y_star collected, and every place
+// the reference switches compare_key to "lm_score" (networks/transducer.py:253-256, 285-295, 355-360) ranks by asr_score +
+// total.  The two fields live in side arrays beside A and B, so Hyp stays 32 bytes and the unfused layout does not move; with
+// FUSED = false every fused statement is compiled out and the kernel is statement for statement the unfused one.
 #pragma once
 #include "decode_shared.hpp"
 
@@ -45,19 +51,26 @@ struct BeamK : PredNet {
   int* frames;         // timed entries: (B, beam, max_len) frame at which each y_star token was appended (-1: the leading
                        // blank), beside `tokens`; null otherwise
   int* commit_frames;  // STREAM, timed entry: (B, max_nodes) beside `commit`; null otherwise
+  // FUSED only (null / 0 otherwise)
+  const int* fnext;      // (S, V) state after appending token k in state s
+  const float* farc;     // (S, V) score of that append
+  const float* ffinal;   // (S) added once, inside the n-best selection only
+  int n_states;          // S
+  double* fused_scores;  // (B, beam) asr_score + total + final, beside `scores`
+  size_t off_fa, off_fb; // side arrays of A and B: total[n] (double) | fstate[n] (int)
 };
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Per-utterance workspace: [header (stream only)] | A entries | B entries | state slots | slot remap | prefix nodes
-// | [node remap (stream only)]
+// | [node remap (stream only)] | [fusion side arrays of A, of B (fused only): total (double) per entry, then fstate (int)]
 struct BeamLayout {
-  size_t table_bytes, off_a, off_b, off_slots, off_remap, off_nodes, off_nmap, stride;
+  size_t table_bytes, off_a, off_b, off_slots, off_remap, off_nodes, off_nmap, off_fa, off_fb, stride;
   int slot_floats;
 };
 
 static BeamLayout beam_layout(int V, int Hp, int L, int cell, int max_candidates, int max_pops, int max_states, int max_nodes,
-                              bool stream) {
+                              bool stream, bool fused = false) {
   BeamLayout l;
   const int NG = cell == RNNT_CELL_LSTM ? 4 : (cell == RNNT_CELL_GRU ? 3 : 1);
   l.table_bytes = align256((size_t)V * NG * Hp * sizeof(float));
@@ -69,6 +82,12 @@ static BeamLayout beam_layout(int V, int Hp, int L, int cell, int max_candidates
   l.off_nodes = l.off_remap + align256((size_t)max_states * sizeof(int));
   l.off_nmap = l.off_nodes + align256((size_t)max_nodes * sizeof(int4));
   l.stride = l.off_nmap + (stream ? align256((size_t)max_nodes * sizeof(int)) : 0);
+  l.off_fa = l.off_fb = 0;
+  if (fused) {   // after everything else: the offsets above are the unfused ones
+    l.off_fa = l.stride;
+    l.off_fb = l.off_fa + align256((size_t)max_candidates * (sizeof(double) + sizeof(int)));
+    l.stride = l.off_fb + align256((size_t)max_pops * (sizeof(double) + sizeof(int)));
+  }
   return l;
 }
 
@@ -92,7 +111,7 @@ __device__ __forceinline__ bool better(double s, int i, double bs, int bi) { ret
 
 // dynamic LDS: redd[16] ctld[4] (double) | redi[16] ctl[16] (int) | redf[16] | h[L*Hp] | c[L*Hp] | gi[4Hp] | gh[4Hp] | x[Hp]
 //              | dec[O] | Cv[V] | logp[V]
-template <bool STREAM>
+template <bool STREAM, bool FUSED>
 __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* redd = reinterpret_cast<double*>(smem);
@@ -122,6 +141,13 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
   int4* nodes = reinterpret_cast<int4*>(ws + p.off_nodes);  // (parent, token, len, frame of creation: -1 for [blank])
   int* hdr = reinterpret_cast<int*>(ws);                    // STREAM only
   const int SF = p.slot_floats;
+  // FUSED: fusion total and automaton state of A entry i (ftA, fsA) and of B entry i (ftB, fsB); they describe the entry's
+  // full y_star, pending `tok` included
+  double* ftA = nullptr; int* fsA = nullptr; double* ftB = nullptr; int* fsB = nullptr;
+  if constexpr (FUSED) {
+    ftA = reinterpret_cast<double*>(ws + p.off_fa); fsA = reinterpret_cast<int*>(ftA + p.max_cands);
+    ftB = reinterpret_cast<double*>(ws + p.off_fb); fsB = reinterpret_cast<int*>(ftB + p.max_pops);
+  }
 
   // block-wide argmax of (key desc, index asc); every thread returns the winner (index -1: no candidate)
   auto block_argmax = [&](double key, int idx, double& best) -> int {
@@ -204,6 +230,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       Hyp r0;
       r0.score = 0.0; r0.node = 0; r0.tok = -1; r0.state = -1; r0.memo = -1; r0.live = 1; r0.pad = 0;
       bents[0] = r0;
+      if constexpr (FUSED) { ftB[0] = 0.0; fsB[0] = 0; }   // state 0 belongs to y_star = [blank]
     }
     __syncthreads();
     nB = 1; nslots = 0; nnodes = 1;
@@ -221,6 +248,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       e.tok = -1;
       e.live = 1;
       cands[i] = e;
+      if constexpr (FUSED) { ftA[i] = ftB[i]; fsA[i] = fsB[i]; }
       if (e.state >= 0) remap[e.state] = 1;
       if (e.memo >= 0) remap[e.memo] = 1;
     }
@@ -256,8 +284,16 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       double abest;
       double key = -__builtin_huge_val();
       int idx = 0x7fffffff;
-      for (int i = tid; i < nA; i += DEC_THREADS)
-        if (cands[i].live && better(cands[i].score, i, key, idx)) { key = cands[i].score; idx = i; }
+      if constexpr (FUSED) {   // compare_key = "lm_score" (:285-288): asr_score + fusion total
+        for (int i = tid; i < nA; i += DEC_THREADS)
+          if (cands[i].live) {
+            const double k = cands[i].score + ftA[i];
+            if (better(k, i, key, idx)) { key = k; idx = i; }
+          }
+      } else {
+        for (int i = tid; i < nA; i += DEC_THREADS)
+          if (cands[i].live && better(cands[i].score, i, key, idx)) { key = cands[i].score; idx = i; }
+      }
       const int ia = block_argmax(key, idx, abest);
       if (ia < 0) break;  // A empty (transducer.py:286; after a pop the reference's max(A) would raise here instead)
       if (npops > 0 && nB >= p.beam && bestB > abest) break;  // :355-358
@@ -266,6 +302,9 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
 
       // ---- pop (transducer.py:304) ----
       const Hyp a = cands[ia];
+      double a_ft = 0.0;   // FUSED: the popped entry's total and state, uniform across the workgroup
+      int a_fs = 0;
+      if constexpr (FUSED) { a_ft = ftA[ia]; a_fs = fsA[ia]; }
       __syncthreads();
       if (tid == 0) cands[ia].live = 0;
       int node = a.node, last;
@@ -327,8 +366,10 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
         Hyp e;
         e.score = sb; e.node = node; e.tok = -1; e.state = a.state; e.memo = S; e.live = 0; e.pad = 0;
         bents[nB] = e;  // nB == npops < max_pops
+        if constexpr (FUSED) { ftB[nB] = a_ft; fsB[nB] = a_fs; }   // a blank appends nothing: state and total as popped
       }
-      bestB = (nB == 0 || sb > bestB) ? sb : bestB;
+      const double sbk = FUSED ? sb + a_ft : sb;   // a_ft is 0.0 and unused without fusion: sbk is sb itself
+      bestB = (nB == 0 || sbk > bestB) ? sbk : bestB;
       ++nB;
       int base = nA;
       for (int k0 = 0; k0 < V; k0 += DEC_THREADS) {
@@ -341,6 +382,17 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
           e.score = a.score + (double)logp[k];
           e.node = node; e.tok = k == last ? -1 : k; e.state = S; e.memo = -1; e.live = 1; e.pad = 0;
           cands[pos] = e;
+          if constexpr (FUSED) {   // threads run along k: both loads are coalesced; no barrier inside this divergent region
+            double ft = a_ft;
+            int fs = a_fs;
+            if (k != last) {       // the dedupe child appends nothing (:337, :345)
+              const long at = (long)a_fs * V + k;
+              const int ns = p.fnext[at];
+              fs = ns < 0 ? 0 : (ns >= p.n_states ? p.n_states - 1 : ns);   // a table out of range cannot index out of bounds
+              ft = a_ft + (double)p.farc[at];
+            }
+            ftA[pos] = ft; fsA[pos] = fs;
+          }
         }
         base += total;
         __syncthreads();
@@ -436,7 +488,9 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
     int idx = 0x7fffffff;
     for (int i = tid; i < nB; i += DEC_THREADS)
       if (bents[i].live) {
-        const double k = bents[i].score / (double)nodes[bents[i].node].z;
+        double k;
+        if constexpr (FUSED) k = (bents[i].score + ftB[i] + (double)p.ffinal[fsB[i]]) / (double)nodes[bents[i].node].z;
+        else k = bents[i].score / (double)nodes[bents[i].node].z;
         if (better(k, i, key, idx)) { key = k; idx = i; }
       }
     double kbest;
@@ -457,6 +511,8 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_search_kernel(const BeamK p)
       }
       p.lens[(long)b * p.beam + r] = len - root_len;
       p.scores[(long)b * p.beam + r] = e.score;
+      if constexpr (FUSED)   // `final` is applied here only and never stored back: the carried B set stays chunk-invariant
+        p.fused_scores[(long)b * p.beam + r] = e.score + ftB[ib] + (double)p.ffinal[fsB[ib]];
     }
     __syncthreads();
   }
@@ -490,6 +546,7 @@ static int beam_fill_common(const D* d, BeamK& k, const char* who) {
   k.A = d->A;
   k.tokens = d->tokens; k.scores = d->scores; k.count = d->count; k.status = d->status; k.stats = d->stats;
   k.commit = nullptr; k.ncommit = nullptr; k.rows = nullptr; k.frames = nullptr; k.commit_frames = nullptr;
+  k.fnext = nullptr; k.farc = nullptr; k.ffinal = nullptr; k.n_states = 0; k.fused_scores = nullptr; k.off_fa = k.off_fb = 0;
   return RNNT_OK;
 }
 
@@ -497,8 +554,20 @@ static inline void beam_set_layout(BeamK& k, void* workspace, const BeamLayout& 
   k.table = reinterpret_cast<const float*>(workspace);
   k.ws = reinterpret_cast<char*>(workspace) + l.table_bytes;
   k.ws_stride = l.stride; k.off_a = l.off_a; k.off_b = l.off_b; k.off_slots = l.off_slots; k.off_remap = l.off_remap;
-  k.off_nodes = l.off_nodes; k.off_nmap = l.off_nmap;
+  k.off_nodes = l.off_nodes; k.off_nmap = l.off_nmap; k.off_fa = l.off_fa; k.off_fb = l.off_fb;
   k.slot_floats = l.slot_floats;
+}
+
+// the fused entries' extra struct, checked on the host before any device work; copies it into the kernel's descriptor
+static int beam_fill_fusion(const rnnt_beam_fusion* f, int V, BeamK& k, const char* who) {
+  RNNT_CHECK_ARG(f != nullptr, "%s: null fusion struct", who);
+  RNNT_CHECK_ARG(f->n_states >= 1, "%s: fusion needs n_states >= 1", who);
+  RNNT_CHECK_ARG((int64_t)f->n_states * V <= ((int64_t)1 << 27), "%s: fusion tables hold n_states * V <= 2^27 entries", who);
+  RNNT_CHECK_ARG(f->next && f->arc && f->final, "%s: null fusion table (next, arc, final) with n_states %d", who,
+                 f->n_states);
+  RNNT_CHECK_ARG(f->fused_scores, "%s: null fused_scores output", who);
+  k.fnext = f->next; k.farc = f->arc; k.ffinal = f->final; k.n_states = f->n_states; k.fused_scores = f->fused_scores;
+  return RNNT_OK;
 }
 
 template <class D>

@@ -169,10 +169,11 @@ class RNNTransducer(_Base):
         return self.jointnet.recognize_greedy_stream(chunk, chunk_lengths, state, max_iters, return_timing=return_timing)
 
     def init_beam_stream(self, batch_size: int, beam_widths: int = 100, improved: bool = False, state_beam: float = 4.6,
-                         expand_beam: float = 2.3, device=None, **caps):
-        """JointNet.init_beam_stream with this model's blank: per-stream state for recognize_beams_stream."""
+                         expand_beam: float = 2.3, device=None, fusion=None, **caps):
+        """JointNet.init_beam_stream with this model's blank: per-stream state for recognize_beams_stream (fusion: a
+        TokenFusion, fixed for the life of the state)."""
         return self.jointnet.init_beam_stream(batch_size, self.blank_token_id, beam_widths, improved, state_beam, expand_beam,
-                                              device, **caps)
+                                              device, fusion=fusion, **caps)
 
     def recognize_beams_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False, return_frames: bool = False):
         """JointNet.recognize_beams_stream: per stream the n-best list for the frames fed so far (with return_frames, the

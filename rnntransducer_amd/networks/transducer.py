@@ -10,7 +10,8 @@ with A = gelu(enc) W_e^T, C = gelu(dec) W_d^T (GELU is element-wise, fc is linea
 `recognize_greedy` (transducer.py:95-145) runs as ONE kernel launch (a workgroup per utterance, csrc/decode.hip) instead of
 a host loop with a device sync per symbol.  `recognize_beams` (transducer.py:215-361, lm=None / hotwords=None) is one persistent
 launch too (csrc/beam.hip): the reference's pop / expand / prune / stop decisions, with memoised prediction-net steps and a
-prefix tree for y_star; LM and hotword rescoring (pyctcdecode / KenLM) stay out of scope.
+prefix tree for y_star; LM and hotword rescoring over text (pyctcdecode / KenLM) stay out of scope, their mechanism is `fusion=`:
+a weighted automaton over token ids (hotword boosting, token LM tables; rnntransducer_amd/fusion.py) that the same kernel walks.
 `init_stream` / `recognize_greedy_stream` run the same greedy search over a batch of streams fed in chunks, with the encoder,
 prediction-net and search state carried between chunks (rnntransducer_amd/streaming.py, csrc/stream.hip).
 `init_beam_stream` / `recognize_beams_stream` do the same for the beam search: the whole hypothesis set is carried on the device
@@ -24,7 +25,8 @@ training (`loss(..., ctc_weight=w)`, `ctc_loss` for CTC pre-training of the enco
 import torch
 import torch.nn as nn
 
-from ..ops import CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, ctc_greedy, greedy_decode, stream_greedy
+from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, check_fusion, ctc_greedy, greedy_decode,
+                   stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -231,7 +233,7 @@ class JointNet(nn.Module):
     def recognize_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 100,
                         improved: bool = False, state_beam: float = 4.6, expand_beam: float = 2.3, lm=None, tokenizer=None,
                         hotwords=None, hotword_weight: float = 10.0, *, visit_padded_frames: bool = False,
-                        return_scores: bool = False, return_frames: bool = False, **caps):
+                        return_scores: bool = False, return_frames: bool = False, fusion=None, **caps):
         """Beam search, same result as transducer.py:215-361 with lm=None and hotwords=None: a list of up to `beam_widths`
         y_star token lists (leading blank included), best first by asr_score / len(y_star), duplicates kept.  `tokenizer` is
         accepted and ignored: without an LM or hotwords the reference only uses it for lm_score, which never decides anything.
@@ -243,23 +245,32 @@ class JointNet(nn.Module):
         outgrows one raises RnntHipError naming it (the reference's loop is unbounded there).
         return_frames=True returns (y_star, frames) pairs, (y_star, frames, asr_score) with return_scores as well: frames is a
         list aligned with y_star, the encoder frame at which the search appended each token (-1 for the leading blank).
-        Divergence: where the reference's max() over an empty A raises ValueError (improved mode) the frame ends instead."""
+        Divergence: where the reference's max() over an empty A raises ValueError (improved mode) the frame ends instead.
+        fusion (a TokenFusion on the model's device; rnntransducer_amd/fusion.py): the mechanism of the reference's lm= /
+        hotwords= branch (transducer.py:253-256, 285-295, 355-360) over token ids instead of text.  Every comparison of the
+        search uses asr_score + the automaton's total for the hypothesis' y_star, the n-best is sorted by (asr_score + total +
+        final) / len(y_star), the prune test stays on the ASR log-probabilities.  With return_scores each hypothesis carries
+        asr_score (what it is without fusion: the sum of the ASR log-probabilities) and then fused_score = asr_score + total +
+        final, both fp64.  A positive bonus can make a frame's pop loop run away (so can the reference's hotwords): the
+        max_pops cap ends it in RnntHipError naming max_pops, and the next call succeeds."""
         if lm is not None or hotwords is not None:
             raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
-                                      "lm=None and hotwords=None")
+                                      "lm=None and hotwords=None, and give token-level hotwords or an LM table as fusion= "
+                                      "(rnntransducer_amd.TokenFusion.from_hotwords / from_bigram)")
         if self.training:
             raise RuntimeError("recognize_beams expects eval() mode (dropout inactive), like the reference's inference script")
+        check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams")   # before anything is launched
         dev = inputs.device
         t_lens = lengths_to_device(inputs_lengths, dev)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         dec = self.decoder
         res = beam_search(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
                           dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
-                          expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, **caps)
-        if return_frames:
-            outs = [[(y, f, s) if return_scores else (y, f) for y, s, f in hyps] for hyps in res]
+                          expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, fusion=fusion, **caps)
+        if return_frames:   # an entry is (y_star, asr_score[, fused_score], frames)
+            outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
         else:
-            outs = [hyps if return_scores else [y for y, _ in hyps] for hyps in res]
+            outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
         return outs[0] if len(outs) == 1 else outs
 
     def init_stream(self, batch_size: int, blank_token_id: int, device=None):
@@ -313,16 +324,20 @@ class JointNet(nn.Module):
         return [tokens[b, :n[b]] for b in range(B)]
 
     def init_beam_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
-                         state_beam: float = 4.6, expand_beam: float = 2.3, device=None, **caps):
+                         state_beam: float = 4.6, expand_beam: float = 2.3, device=None, fusion=None, **caps):
         """A streaming.BeamStreamState for `batch_size` streams, each starting as recognize_beams starts an utterance
         (transducer.py:276-284): y_star = [blank], score 0, no prediction-net state.  The search options are fixed here: they
         size the workspace and belong to the utterance.  `caps`: max_pops / max_candidates / max_states / max_nodes / max_len as
         in ops.beam_search, with streaming defaults (ops.beam_stream_caps; max_nodes bounds the LIVE prefix tree, max_len the
         uncommitted tail of a y_star); `state.workspace_bytes` / `state.bytes_per_stream` tell what they cost.  `device`, if
-        given, must be the model's.  The weights must not change while the state is open."""
+        given, must be the model's.  The weights must not change while the state is open.
+        fusion (a TokenFusion on the model's device): the streams search as recognize_beams(fusion=...) does; the automaton is
+        fixed here, its state and total are carried with every hypothesis, and recognize_beams_stream(return_scores=True)
+        returns asr_score and then fused_score per hypothesis."""
         from ..streaming import BeamStreamState
         self.encoder.check_streamable("init_beam_stream")
-        return BeamStreamState(self, batch_size, blank_token_id, beam_widths, improved, state_beam, expand_beam, device, **caps)
+        return BeamStreamState(self, batch_size, blank_token_id, beam_widths, improved, state_beam, expand_beam, device,
+                               fusion=fusion, **caps)
 
     @torch.no_grad()
     def recognize_beams_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False,

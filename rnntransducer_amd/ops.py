@@ -1167,13 +1167,33 @@ def prednet_step(tokens: torch.Tensor, emb_w: torch.Tensor, rnn_weights, cell: i
 
 
 # --------------------------------------------------------------------------------------------------
-# beam search (replaces the host loop of transducer.py:215-361 with lm=None, hotwords=None)
+# beam search (replaces the host loop of transducer.py:215-361 with lm=None, hotwords=None; with fusion=, the lm_score branch
+# over a token automaton: fusion.py)
 # --------------------------------------------------------------------------------------------------
+def check_fusion(fusion, V: int, device, what: str) -> None:
+    """ValueError unless `fusion` is None or a TokenFusion over V tokens on `device`: before anything is launched."""
+    if fusion is None:
+        return
+    from .fusion import TokenFusion
+    if not isinstance(fusion, TokenFusion):
+        raise ValueError(f"{what}: fusion must be a rnntransducer_amd.TokenFusion, got {type(fusion).__name__}")
+    if fusion.vocab_size != V:
+        raise ValueError(f"{what}: the fusion automaton is over {fusion.vocab_size} tokens, the model's joint over {V}")
+    if fusion.device != device:
+        raise ValueError(f"{what}: the fusion tables are on {fusion.device}, the search runs on {device}; use fusion.to(device)")
+
+
+def fusion_struct(fusion, fused_scores: torch.Tensor):
+    """rnnt_beam_fusion of a checked TokenFusion (raw pointers: the caller keeps `fusion` and `fused_scores` alive)."""
+    return _lib.BeamFusion(_addr(fusion.next), _addr(fusion.arc), _addr(fusion.final), fusion.n_states, _addr(fused_scores))
+
+
 def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                 cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam: int, improved: bool = False,
                 state_beam: float = 4.6, expand_beam: float = 2.3, t_lens: Optional[torch.Tensor] = None, *,
                 max_pops: int = 1024, max_candidates: Optional[int] = None, max_states: Optional[int] = None,
-                max_nodes: int = 1 << 18, max_len: Optional[int] = None, stats: bool = False, frames: bool = False):
+                max_nodes: int = 1 << 18, max_len: Optional[int] = None, stats: bool = False, frames: bool = False,
+                fusion=None):
     """enc_tm (T,B,Oe) encoder outputs (time-major) -> per utterance the n-best list [(y_star, asr_score), ...] of
     transducer.py:215-361 (lm=None), one kernel launch for the batch (csrc/beam.hip) and one host sync.
     t_lens (B) int32 on device = frames visited per utterance (None: all T).  Caps (each raises RnntHipError naming it):
@@ -1182,7 +1202,10 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     per utterance, max_len = tokens of a returned y_star (default 4 T + 64).  stats=True also returns a (B, 6) int tensor:
     pops, prediction-net steps run, max pops in a frame, max A entries in a frame, max live states, prefix nodes.
     frames=True (rnnt_hip_beam_search_timed, the same kernel): every entry is (y_star, asr_score, frames) with frames aligned
-    with y_star: the frame at which each token was appended, -1 for the leading blank."""
+    with y_star: the frame at which each token was appended, -1 for the leading blank.
+    fusion (a fusion.TokenFusion on enc_tm's device; rnnt_hip_beam_search_fused, the FUSED instance of the same kernel): the
+    search ranks by asr_score + the automaton's total, and every entry is (y_star, asr_score, fused_score[, frames]) with
+    fused_score = asr_score + total + final, fp64.  Positive arcs can make a frame's pop loop run away: max_pops bounds it."""
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
     T, B, Oe = enc_tm.shape
@@ -1194,6 +1217,7 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
                          f"encoder width {Oe}")
     if V < 2 or beam < 1:
         raise ValueError(f"beam search: V {V} < 2 or beam {beam} < 1")
+    check_fusion(fusion, V, enc_tm.device, "beam search")
     max_candidates = max_pops * V if max_candidates is None else max_candidates
     max_states = 3 * max_pops if max_states is None else max_states
     max_len = 4 * T + 64 if max_len is None else max_len
@@ -1207,7 +1231,8 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     d.T, d.B = T, B
     d.beam, d.improved, d.state_beam, d.expand_beam = beam, int(bool(improved)), float(state_beam), float(expand_beam)
     d.max_candidates, d.max_pops, d.max_states, d.max_nodes, d.max_len = max_candidates, max_pops, max_states, max_nodes, max_len
-    ws_bytes = _lib.lib().rnnt_hip_beam_workspace_bytes(C.byref(d))
+    ws_query = _lib.lib().rnnt_hip_beam_workspace_bytes if fusion is None else _lib.lib().rnnt_hip_beam_fused_workspace_bytes
+    ws_bytes = ws_query(C.byref(d))
     if ws_bytes == 0:
         raise ValueError("beam search: invalid sizes or caps (all caps must be >= 1)")
     ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
@@ -1215,9 +1240,16 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
     d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
+    tm = None
     if frames:
         fr = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
         tm = _lib.BeamTiming(_addr(fr), None)
+    if fusion is not None:
+        fused = torch.empty(B, beam, device=dev, dtype=torch.float64)
+        fs = fusion_struct(fusion, fused)
+        check(_lib.lib().rnnt_hip_beam_search_fused(C.byref(d), C.byref(fs), C.byref(tm) if frames else None, _stream()),
+              "rnnt_hip_beam_search_fused")
+    elif frames:
         check(_lib.lib().rnnt_hip_beam_search_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_beam_search_timed")
     else:
         check(_lib.lib().rnnt_hip_beam_search(C.byref(d), _stream()), "rnnt_hip_beam_search")
@@ -1233,9 +1265,12 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     lens_h, scores_h = lens.cpu().tolist(), scores.cpu().tolist()
     tok_h = tokens[:, :, :max(1, max(max(r) for r in lens_h))].cpu()
     out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if fusion is not None:
+        fused_h = fused.cpu().tolist()
+        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
     if frames:
         fr_h = fr[:, :, :tok_h.shape[2]].cpu()
-        out = [[(y, s, fr_h[b, r, :len(y)].tolist()) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
+        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
     if stats:
         return out, host.reshape(-1)[2 * B:].reshape(B, _lib.BEAM_NSTATS)
     return out
@@ -1403,35 +1438,48 @@ def beam_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, 
     return d, keep
 
 
-def beam_stream_workspace_bytes(d) -> int:
-    n = _lib.lib().rnnt_hip_beam_stream_workspace_bytes(C.byref(d))
+def beam_stream_workspace_bytes(d, fused: bool = False) -> int:
+    """Bytes of the carried workspace; fused=True: the layout of the *_fused entries (side arrays for the fusion fields)."""
+    L = _lib.lib()
+    n = (L.rnnt_hip_beam_stream_fused_workspace_bytes if fused else L.rnnt_hip_beam_stream_workspace_bytes)(C.byref(d))
     if n == 0:
         raise ValueError("streaming beam search: invalid sizes or caps (all caps must be >= 1)")
     return n
 
 
-def beam_stream_reset(d, rows: torch.Tensor, build_table: bool) -> None:
-    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to."""
+def beam_stream_reset(d, rows: torch.Tensor, build_table: bool, fusion=None) -> None:
+    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to.
+    fusion: the rnnt_beam_fusion struct of a stream opened with one (fusion_struct): the fused layout, automaton state 0."""
     _need_gpu(rows)
     _check_buffer("rows", rows, (rows.numel(),), torch.int32, rows.device)
+    if fusion is not None:
+        check(_lib.lib().rnnt_hip_beam_stream_reset_fused(C.byref(d), C.byref(fusion), _addr(rows), rows.numel(), int(build_table),
+                                                          _stream()), "rnnt_hip_beam_stream_reset_fused")
+        return
     check(_lib.lib().rnnt_hip_beam_stream_reset(C.byref(d), _addr(rows), rows.numel(), int(build_table), _stream()),
           "rnnt_hip_beam_stream_reset")
 
 
 def beam_stream_chunk(d, A: torch.Tensor, lens: torch.Tensor, frames: Optional[torch.Tensor] = None,
-                      commit_frames: Optional[torch.Tensor] = None) -> None:
+                      commit_frames: Optional[torch.Tensor] = None, fusion=None) -> None:
     """One chunk: A (T,B,V) from stream_rnn_chunk, lens (B) int32 on device; the outputs d points to are written.  With
     frames (B, beam, max_len) and commit_frames (B, max_nodes), int32 on device: rnnt_hip_beam_stream_chunk_timed, the same
-    kernel, which also writes the tail's and the committed tokens' absolute frames."""
+    kernel, which also writes the tail's and the committed tokens' absolute frames.  fusion: the rnnt_beam_fusion struct the
+    stream was reset with (rnnt_hip_beam_stream_chunk_fused, with or without frames)."""
     _need_gpu(A, lens)
     _check_buffer("A", A, (A.shape[0], d.B, d.V), torch.float32, A.device)
     _check_buffer("lengths", lens, (d.B,), torch.int32, A.device)
     d.T, d.A, d.lens = A.shape[0], _addr(A), _addr(lens)
     try:
+        tm = None
         if frames is not None:
             _check_buffer("frames", frames, (d.B, d.beam, d.max_len), torch.int32, A.device)
             _check_buffer("commit_frames", commit_frames, (d.B, d.max_nodes), torch.int32, A.device)
             tm = _lib.BeamTiming(_addr(frames), _addr(commit_frames))
+        if fusion is not None:
+            check(_lib.lib().rnnt_hip_beam_stream_chunk_fused(C.byref(d), C.byref(fusion), C.byref(tm) if tm is not None else None,
+                                                              _stream()), "rnnt_hip_beam_stream_chunk_fused")
+        elif frames is not None:
             check(_lib.lib().rnnt_hip_beam_stream_chunk_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_beam_stream_chunk_timed")
         else:
             check(_lib.lib().rnnt_hip_beam_stream_chunk(C.byref(d), _stream()), "rnnt_hip_beam_stream_chunk")

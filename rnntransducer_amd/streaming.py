@@ -19,6 +19,10 @@ Streaming beam search (`JointNet.init_beam_stream` / `recognize_beams_stream`, c
     for chunk, lengths in feed:
         nbest = jointnet.recognize_beams_stream(chunk, lengths, state)    # per stream: y_star lists, best first
         partial = state.stable_prefix(0)                                  # the tokens of stream 0 no later chunk can change
+
+`init_beam_stream(..., fusion=TokenFusion)` makes the streams search with token-level fusion (fusion.py): the automaton is fixed
+when the state is opened, every carried hypothesis keeps its automaton state and total on the device, and `final` is applied
+only where the n-best is ranked, so the n-best after every chunk is still the offline fused result for the frames fed so far.
 """
 from __future__ import annotations
 
@@ -149,10 +153,15 @@ class BeamStreamState:
     after every chunk), max_len = 256 uncommitted tokens of a y_star.  Bytes per stream (`bytes_per_stream`; all of them,
     `workspace_bytes`): 32 * (max_candidates + max_pops) + 4 * max_states * (slot + 1) + 20 * max_nodes + 256 with slot =
     L * Hp * (2 if LSTM else 1) + V floats; at Hp = 512, V = 72, one LSTM layer and beam 5 that is 2.15 MB (0.29 MB A entries,
-    1.69 MB state slots, 0.16 MB nodes) against about 20 MB for the offline defaults."""
+    1.69 MB state slots, 0.16 MB nodes) against about 20 MB for the offline defaults.
+
+    fusion (a TokenFusion over the model's V tokens, on the state's device; ValueError otherwise): the search of
+    recognize_beams(fusion=...).  It is fixed here; the workspace grows by 12 * (max_candidates + max_pops) bytes per stream
+    (automaton state and fp64 total beside every A and B entry) and `nbest` entries are (y_star, asr_score, fused_score).  A
+    positive bonus can make a frame's pop loop run away: max_pops ends it (RnntHipError), the stream must then be reset."""
 
     def __init__(self, jointnet, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
-                 state_beam: float = 4.6, expand_beam: float = 2.3, device=None, **caps):
+                 state_beam: float = 4.6, expand_beam: float = 2.3, device=None, fusion=None, **caps):
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         enc = jointnet.encoder.rnn
@@ -167,6 +176,9 @@ class BeamStreamState:
         unknown = set(caps) - set(ops.BEAM_STREAM_CAPS)
         if unknown:
             raise TypeError(f"init_beam_stream: unknown keyword(s) {sorted(unknown)}; the caps are {ops.BEAM_STREAM_CAPS}")
+        ops.check_fusion(fusion, jointnet.num_classes, device, "init_beam_stream")
+        self.fusion = fusion
+        self._final0 = float(fusion.final[0]) if fusion is not None else 0.0   # read once: a reset does not sync for it
         self._net = jointnet
         self.batch_size, self.blank = int(batch_size), int(blank_token_id)
         self.beam, self.improved = int(beam_widths), bool(improved)
@@ -178,7 +190,7 @@ class BeamStreamState:
         self.enc_c = z(enc.num_layers, enc.hidden_size) if enc.CELL == CELL_LSTM else None
         self.frames_seen = torch.zeros(B, device=device, dtype=torch.int64)
         d, _ = self._descriptor(bare=True)
-        self.workspace_bytes = ops.beam_stream_workspace_bytes(d)
+        self.workspace_bytes = ops.beam_stream_workspace_bytes(d, fused=fusion is not None)
         self.workspace = torch.zeros(self.workspace_bytes + 256, device=device, dtype=torch.uint8)
         self._ws_off = -self.workspace.data_ptr() % 256
         ngate = {0: 4, 1: 3}.get(jointnet.decoder.rnn.CELL, 1)
@@ -189,6 +201,7 @@ class BeamStreamState:
         self._tokens = torch.zeros(B, self.beam, self.caps["max_len"], device=device, dtype=torch.int32)
         self._lens = torch.zeros(B, self.beam, device=device, dtype=torch.int32)
         self._scores = torch.zeros(B, self.beam, device=device, dtype=torch.float64)
+        self._fused = torch.zeros(B, self.beam, device=device, dtype=torch.float64) if fusion is not None else None
         self._commit = torch.zeros(B, self.caps["max_nodes"], device=device, dtype=torch.int32)
         # the timed chunk entry's outputs, made by the first chunk that asks for frames
         self._frames: Optional[torch.Tensor] = None
@@ -197,7 +210,7 @@ class BeamStreamState:
         self.committed_frames: List[Optional[List[int]]] = [[-1] for _ in range(B)]
         self.nbest_frames: List[Optional[List[List[int]]]] = [[[-1]] for _ in range(B)]
         self.committed: List[List[int]] = [[self.blank] for _ in range(B)]
-        self.nbest = [[([self.blank], 0.0)] for _ in range(B)]
+        self.nbest = [[self._start_entry()] for _ in range(B)]
         self.failed = [False] * B
         self.last_stats = torch.zeros(B, BEAM_NSTATS, dtype=torch.int32)   # of the last chunk: ops.beam_search's stats columns
         self._reset(list(range(B)), build_table=True)
@@ -205,6 +218,15 @@ class BeamStreamState:
     @property
     def device(self) -> torch.device:
         return self.enc_h.device
+
+    def _start_entry(self):
+        """The n-best entry of a stream that has seen no frames: (y_star, asr_score[, fused_score]); final[0] belongs to it."""
+        if self.fusion is None:
+            return ([self.blank], 0.0)
+        return ([self.blank], 0.0, self._final0)
+
+    def _fusion_struct(self):
+        return None if self.fusion is None else ops.fusion_struct(self.fusion, self._fused)
 
     def _descriptor(self, bare: bool = False):
         net, dec = self._net, self._net.decoder
@@ -289,19 +311,19 @@ class BeamStreamState:
                 t.index_fill_(1, idx, 0.0)
         self.frames_seen.index_fill_(0, idx, 0)
         d, keep = self._descriptor()
-        ops.beam_stream_reset(d, idx.to(torch.int32), build_table)
+        ops.beam_stream_reset(d, idx.to(torch.int32), build_table, self._fusion_struct())
         for r in rows:
-            self.committed[r], self.nbest[r], self.failed[r] = [self.blank], [([self.blank], 0.0)], False
+            self.committed[r], self.nbest[r], self.failed[r] = [self.blank], [self._start_entry()], False
             self.committed_frames[r], self.nbest_frames[r] = [-1], [[-1]]
 
     def results(self, return_scores: bool, return_frames: bool = False):
-        if not return_frames:
-            return [[(list(y), s) for y, s in hyps] if return_scores else [list(y) for y, _ in hyps] for hyps in self.nbest]
+        if not return_frames:   # an entry is (y_star, asr_score[, fused_score])
+            return [[(list(y), *s) for y, *s in hyps] if return_scores else [list(y) for y, *_ in hyps] for hyps in self.nbest]
         unknown = [b for b, f in enumerate(self.nbest_frames) if f is None]
         if unknown:
             raise ValueError(f"stream(s) {unknown[:4]} were fed a chunk without return_frames=True since their last reset: their "
                              "frames are unknown")
-        return [[(list(y), list(f), s) if return_scores else (list(y), list(f)) for (y, s), f in zip(hyps, frs)]
+        return [[(list(y), list(f), *s) if return_scores else (list(y), list(f)) for (y, *s), f in zip(hyps, frs)]
                 for hyps, frs in zip(self.nbest, self.nbest_frames)]
 
     def run_chunk(self, A: torch.Tensor, lens_dev: torch.Tensor, timed: bool = False) -> None:
@@ -314,9 +336,9 @@ class BeamStreamState:
             if self._frames is None:
                 self._frames = torch.zeros_like(self._tokens)
                 self._commit_frames = torch.zeros_like(self._commit)
-            ops.beam_stream_chunk(d, A, lens_dev, self._frames, self._commit_frames)
+            ops.beam_stream_chunk(d, A, lens_dev, self._frames, self._commit_frames, fusion=self._fusion_struct())
         else:
-            ops.beam_stream_chunk(d, A, lens_dev)
+            ops.beam_stream_chunk(d, A, lens_dev, fusion=self._fusion_struct())
         self.frames_seen += lens_dev
         host = self._small.cpu()   # the host sync of the chunk; the result slices below are copied from an idle stream
         count, status, ncommit = host[0].tolist(), host[1].tolist(), host[2].tolist()
@@ -324,13 +346,15 @@ class BeamStreamState:
         ran = [b for b in range(B) if count[b] >= 0 and status[b] == 0]
         if ran:
             lens_h, scores_h = self._lens.cpu().tolist(), self._scores.cpu().tolist()
+            fused_h = self._fused.cpu().tolist() if self.fusion is not None else None
             tok_h = self._tokens[:, :, :max(1, max(max(lens_h[b]) for b in ran))].cpu()
             com_h = self._commit[:, :max(1, max(ncommit[b] for b in ran))].cpu()
             if timed:
                 fr_h, cfr_h = self._frames[:, :, :tok_h.shape[2]].cpu(), self._commit_frames[:, :com_h.shape[1]].cpu()
             for b in ran:
                 self.committed[b] += com_h[b, :ncommit[b]].tolist()
-                self.nbest[b] = [(self.committed[b] + tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])]
+                self.nbest[b] = [(self.committed[b] + tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) +
+                                 (() if fused_h is None else (fused_h[b][r],)) for r in range(count[b])]
                 if timed:
                     self.committed_frames[b] += cfr_h[b, :ncommit[b]].tolist()
                     self.nbest_frames[b] = [self.committed_frames[b] + fr_h[b, r, :lens_h[b][r]].tolist() for r in range(count[b])]
