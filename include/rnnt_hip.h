@@ -417,6 +417,36 @@ int rnnt_hip_loss_from_logits_fwd_bwd_ex(const void* logits, int32_t dtype, cons
                                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FastEmit regularisation (Yu et al., ICASSP 2021) of the three gradient entry points above: the same arguments plus
+ * `fastemit_lambda` after `gscale`.  Per lattice cell (t,u) with occupancy w = cb + ce, blank-transition posterior cb and
+ * label-transition posterior ce (0 at u = u_lens[b]), the gradient with respect to the LABEL log-probability is scaled by
+ * (1 + lambda), the blank's is left alone, and the result goes through the log-softmax exactly:
+ *   dz[t,u,v] = softmax_v (w + lambda ce) - [v = blank] cb - [v = y_u] (1 + lambda) ce
+ * i.e. the exact gradient of  nll_b + lambda * sum_{t,u} stopgrad(ce[t,u]) * (-emit(t,u)).  sum_v dz = 0 in every cell, as for the
+ * plain loss.  (Forms that scale only the label entry of the logit gradient lose that; this library does not reproduce them.)
+ *   - ONLY THE GRADIENT CHANGES: nll is the unregularised -log P(y|x), bit for bit what lambda = 0 returns, so loss curves stay
+ *     comparable across lambda.  The forward call (dA = dC = NULL / grad = NULL) ignores lambda apart from validating it.
+ *   - lambda multiplies nothing else: gscale, gvec, strides, the t_lens[b] = 0 rule and the workspace (size and layout) are as
+ *     above.  A row with u_lens[b] = 0 has no label transition: its gradient is bitwise that of lambda = 0.
+ *   - lambda = 0 runs the same kernels as the entries above (which forward here with 0): bitwise the same results.
+ *   - lambda < 0, NaN or infinite: RNNT_ERR_INVALID, before any device work.
+ * ---------------------------------------------------------------------------------------------- */
+int rnnt_hip_joint_loss_fwd_bwd_fastemit(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                         const float* bias, const int32_t* labels, const int32_t* t_lens,
+                                         const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                         float gscale, float fastemit_lambda, float* nll, float* dA, float* dC, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+int rnnt_hip_joint_loss_bwd_fastemit(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                     const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                     int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                     float fastemit_lambda, const float* gvec, int32_t gvec_stride, float* dA, float* dC,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int rnnt_hip_loss_from_logits_fwd_bwd_fastemit(const void* logits, int32_t dtype, const int32_t* labels, const int32_t* t_lens,
+                                               const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                               float gscale, float fastemit_lambda, float* nll, void* grad, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Forced alignment: the best (Viterbi) RNN-T path of a KNOWN transcript, per utterance, on the device.  No (B,T,U+1,V) tensor:
  * the same two numbers per lattice cell as the loss, blk(t,u) = log p(blank | t,u) and emit(t,u) = log p(y_u | t,u), then the
  * lattice sweep of the loss in the (max, +) semiring:

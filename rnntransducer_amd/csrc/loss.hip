@@ -481,8 +481,20 @@ __device__ __forceinline__ CellS cell_scalars(const float* __restrict__ blk, con
   return c;
 }
 
+// FastEmit (include/rnnt_hip.h): the gradient with respect to the LABEL log-probability of every cell is scaled by
+// (1 + lambda), the blank's is left alone, and the result goes through the log-softmax exactly:
+//   dz[v] = softmax_v (w + lambda ce) - [v = blank] cb - [v = y_u] (1 + lambda) ce          (sum over v: still 0)
+// i.e. the plain kernels' arithmetic on two changed per-cell scalars.  Every gradient kernel has a template flag FE: the FE = false
+// instance is the code without this feature (lambda is never read), FE = true applies fastemit_cell where the scalars are made.
+// A cell without a label transition (ce = 0: u = U_b) keeps its scalars bit for bit.
+__device__ __forceinline__ void fastemit_cell(CellS& c, float lambda) {
+  c.w = c.w + lambda * c.ce;
+  c.ce = (1.f + lambda) * c.ce;
+}
+
 // grid (ceil(T/32), B), 256 threads; wave w owns frames w, w+4, ... of the tile; lanes run along v.
 // dynamic LDS: cells[TT][U1] (CellS) | Cs[U1][64] | dCs[U1][64] | ys[U1]
+template <bool FE>
 __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                        const float* __restrict__ bias, const int* __restrict__ labels,
                                                        const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -491,7 +503,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
                                                        const double* __restrict__ ll, int T, int U1, int V, int blank,
                                                        long a_sb, long a_st, long c_sb, long c_su, float gscale_in,
                                                        const float* __restrict__ gvec, int gvec_stride,
-                                                       float* __restrict__ dA, float* __restrict__ dCp) {
+                                                       float* __restrict__ dA, float* __restrict__ dCp, float fe_lambda) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   CellS* cells = reinterpret_cast<CellS*>(smem);
   float* Cs = reinterpret_cast<float*>(cells + TT * U1);
@@ -515,6 +527,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
     if (t < Tb && u <= Ub) {
       const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
       c = cell_scalars(blk, emit, alpha, beta, rowbase, T, t, u, Tb, Ub, logZ, zb);
+      if (FE) fastemit_cell(c, fe_lambda);
     }
     cells[tl * U1 + u] = c;
   }
@@ -613,7 +626,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
 // in registers across the chunks and the dC rows are written per 8-row block as before, so the arithmetic (and its order) is the
 // unchunked kernel's.  Every wave stays to the end (the chunks' barriers), the ones beyond the vocabulary only help build the table.
 // ------------------------------------------------------------------------------------------------
-template <int NW, bool CHUNKED>
+template <int NW, bool CHUNKED, bool FE>
 __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                             const float* __restrict__ bias, const int* __restrict__ labels,
                                                             const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -622,7 +635,8 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
                                                             const double* __restrict__ ll, int T, int U1, int V, int blank,
                                                             long a_sb, long a_st, long c_sb, long c_su, float gscale_in,
                                                             const float* __restrict__ gvec, int gvec_stride,
-                                                            float* __restrict__ dA, float* __restrict__ dCp, int ul) {
+                                                            float* __restrict__ dA, float* __restrict__ dCp, int ul,
+                                                            float fe_lambda) {
   const int UL = CHUNKED ? ul : U1;                      // label positions per table
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2* wl = reinterpret_cast<float2*>(smem);          // [TT][UL] {occupancy w, row lse * log2 e}: what the inner loop reads (8-byte broadcasts)
@@ -668,6 +682,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
         const int tc = min(t, Tbc - 1), uc = max(min(u, Ub), 0);   // a cell of the lattice whatever (t, u) is (frame 0 of an empty row)
         const float zb = Ab[(long)tc * a_st + blank] + Cb[(long)uc * c_su + blank] + bias_blank;
         c[q] = cell_scalars(blk, emit, alpha, beta, rowbase, T, tc, uc, Tbc, Ub, logZ, zb);
+        if (FE) fastemit_cell(c[q], fe_lambda);   // both tables carry the FastEmit values: wl its w, cbe its ce
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -767,13 +782,13 @@ __global__ void __launch_bounds__(256) reduce_dc_kernel(const float* __restrict_
 }
 
 // dense d/d logits: one wavefront per cell
-template <typename TZ>
+template <typename TZ, bool FE>
 __global__ void __launch_bounds__(256) grad_dense_kernel(const TZ* __restrict__ Z, const int* __restrict__ labels,
                                                          const int* __restrict__ t_lens, const int* __restrict__ u_lens,
                                                          const float* __restrict__ blk, const float* __restrict__ emit,
                                                          const double* __restrict__ alpha, const double* __restrict__ beta,
                                                          const double* __restrict__ ll, int B, int T, int U1, int V,
-                                                         int blank, float gscale, TZ* __restrict__ G) {
+                                                         int blank, float gscale, TZ* __restrict__ G, float fe_lambda) {
   const int lane = threadIdx.x & 63;
   const long ncell = (long)B * T * U1;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((long)gridDim.x * blockDim.x) >> 6;
@@ -788,7 +803,8 @@ __global__ void __launch_bounds__(256) grad_dense_kernel(const TZ* __restrict__ 
       for (int v = lane; v < V; v += 64) stf(g, v, 0.f);
       continue;
     }
-    const CellS c = cell_scalars(blk, emit, alpha, beta, (long)b * U1 * T, T, t, u, Tb, Ub, ll[b], ldf(z, blank));
+    CellS c = cell_scalars(blk, emit, alpha, beta, (long)b * U1 * T, T, t, u, Tb, Ub, ll[b], ldf(z, blank));
+    if (FE) fastemit_cell(c, fe_lambda);
     const int y = (u < U1 - 1) ? labels[(long)b * (U1 - 1) + u] : -1;
     for (int v = lane; v < V; v += 64) {
       float x = c.w * expf(ldf(z, v) - c.lse);
@@ -966,10 +982,18 @@ static int launch_lse_sep(const float* A, int64_t a_sb, int64_t a_st, const floa
   return RNNT_OK;
 }
 
-static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+// FastEmit's lambda is an argument of the backward only: finite and >= 0 (checked before any device work, like every argument)
+static int check_fastemit(float lambda, const char* who) {
+  RNNT_CHECK_ARG(lambda >= 0.f && lambda <= 3.4028234664e38f, "%s: fastemit_lambda must be finite and >= 0 (got %g)", who, (double)lambda);
+  return RNNT_OK;
+}
+
+// fe = 0 launches the FE = false instances (the kernels as they are without FastEmit), fe > 0 the FE = true ones
+template <bool FE>
+static int launch_grad_sep_fe(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
                            const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
                            int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
-                           float* dC, hipStream_t s) {
+                           float* dC, float fe, hipStream_t s) {
   const int ntiles = (int)ceil_div(T, TT);
   const double cells = (double)B * T * U1;
   ProfScope prof(RNNT_K_LATGRAD, 4.0 * 2.0 * ((double)B * T * V + (double)B * U1 * V) + 24.0 * cells, s);
@@ -983,26 +1007,26 @@ static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_
     const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
     if (lds <= LDS_MAX) {
       if (lds > 64 * 1024)
-        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, false>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
                          w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, U1);
+                         w.dCp, U1, fe);
     } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
       const size_t per_row = (size_t)TT * sizeof(CellS);
       const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
       const int nchunks = (int)ceil_div(U1, ul_max);
       const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
       const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, true>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
                          w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, ul);
+                         w.dCp, ul, fe);
     }
   } else {
     if (lds_sep > 64 * 1024)
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
-    hipLaunchKernelGGL(grad_sep_kernel, dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
-                       w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp);
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
+    hipLaunchKernelGGL(grad_sep_kernel<FE>, dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
+                       w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp, fe);
   }
   RNNT_CHECK_LAUNCH();
   const long per_b = (long)U1 * V;
@@ -1012,17 +1036,30 @@ static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_
   return RNNT_OK;
 }
 
+static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                           const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
+                           int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
+                           float* dC, float fe, hipStream_t s) {
+  if (fe != 0.f)
+    return launch_grad_sep_fe<true>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec,
+                                    gvec_stride, dA, dC, fe, s);
+  return launch_grad_sep_fe<false>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec,
+                                   gvec_stride, dA, dC, 0.f, s);
+}
+
 extern "C" size_t rnnt_hip_joint_loss_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
   if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
   return carve(nullptr, B, T, U1, V, true).total;
 }
 
-extern "C" int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
-                                           int64_t c_su, const float* bias, const int32_t* labels,
-                                           const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
-                                           int32_t U1, int32_t V, int32_t blank, float gscale, float* nll, float* dA,
-                                           float* dC, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int rnnt_hip_joint_loss_fwd_bwd_fastemit(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
+                                                    int64_t c_su, const float* bias, const int32_t* labels,
+                                                    const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
+                                                    int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
+                                                    float* nll, float* dA, float* dC, void* workspace, size_t workspace_bytes,
+                                                    void* stream) {
   if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
+  if (int rc = check_fastemit(fastemit_lambda, "joint_loss")) return rc;
   RNNT_CHECK_ARG(A && C && bias, "joint_loss: null A/C/bias");
   RNNT_CHECK_ARG((dA == nullptr) == (dC == nullptr), "joint_loss: dA and dC must both be given or both be NULL");
   const LossWs w = carve(workspace, B, T, U1, V, true);
@@ -1032,15 +1069,26 @@ extern "C" int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t
   if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
   hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
   RNNT_CHECK_LAUNCH();
-  if (dA) return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nullptr, 0, dA, dC, s);
+  if (dA)
+    return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nullptr, 0, dA, dC,
+                           fastemit_lambda, s);
   return RNNT_OK;
 }
 
-extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
-                                       const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
-                                       int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
-                                       const float* gvec, int32_t gvec_stride, float* dA, float* dC, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
+extern "C" int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
+                                           int64_t c_su, const float* bias, const int32_t* labels,
+                                           const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
+                                           int32_t U1, int32_t V, int32_t blank, float gscale, float* nll, float* dA,
+                                           float* dC, void* workspace, size_t workspace_bytes, void* stream) {
+  return rnnt_hip_joint_loss_fwd_bwd_fastemit(A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, 0.f,
+                                              nll, dA, dC, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rnnt_hip_joint_loss_bwd_fastemit(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                                const float* bias, const int32_t* labels, const int32_t* t_lens,
+                                                const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                                float gscale, float fastemit_lambda, const float* gvec, int32_t gvec_stride,
+                                                float* dA, float* dC, void* workspace, size_t workspace_bytes, void* stream) {
   // second half of rnnt_hip_joint_loss_fwd_bwd: the workspace still holds blk / emit / alpha / beta / logZ of a forward call
   // (dA = dC = NULL) on the SAME A, C, bias, labels, lengths
   RNNT_CHECK_ARG(labels && t_lens && u_lens && B >= 1 && T >= 1 && U1 >= 1 && V >= 2 && blank >= 0 && blank < V,
@@ -1048,10 +1096,20 @@ extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_s
   RNNT_CHECK_ARG(A && C && bias && dA && dC, "joint_loss_bwd: null A/C/bias/dA/dC");
   RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "joint_loss_bwd: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
   RNNT_CHECK_ARG(U1 <= 64 * 8, "joint_loss_bwd: U+1 = %d exceeds the 512 label positions of the forward", U1);
+  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_bwd")) return rc;
   const LossWs w = carve(workspace, B, T, U1, V, true);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_loss_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, gvec_stride, dA,
-                         dC, (hipStream_t)stream);
+                         dC, fastemit_lambda, (hipStream_t)stream);
+}
+
+extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                       const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                       int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                       const float* gvec, int32_t gvec_stride, float* dA, float* dC, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return rnnt_hip_joint_loss_bwd_fastemit(A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, 0.f,
+                                          gvec, gvec_stride, dA, dC, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rnnt_hip_scaled_sum_f32(const float* x, int32_t n, float scale, float* out, void* stream) {
@@ -1091,9 +1149,10 @@ static int launch_lse_dense(const void* logits, const int32_t* labels, int32_t B
 
 template <typename TZ>
 static int loss_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
-                                 int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float* nll,
-                                 void* grad, void* workspace, size_t workspace_bytes, void* stream) {
+                                 int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fe,
+                                 float* nll, void* grad, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
+  if (int rc = check_fastemit(fe, "loss_from_logits")) return rc;
   RNNT_CHECK_ARG(logits, "loss_from_logits: null logits");
   const LossWs w = carve(workspace, B, T, U1, V, true);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "loss_from_logits: workspace too small (%zu < %zu)", workspace_bytes, w.total);
@@ -1106,28 +1165,44 @@ static int loss_from_logits_impl(const void* logits, const int32_t* labels, cons
   RNNT_CHECK_LAUNCH();
   if (grad) {
     ProfScope prof(RNNT_K_LATGRAD, 2.0 * sizeof(TZ) * (double)ncell * V + 24.0 * (double)ncell, s);
-    hipLaunchKernelGGL((grad_dense_kernel<TZ>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk, w.emit,
-                       w.alpha, w.beta, w.ll, B, T, U1, V, blank, gscale, (TZ*)grad);
+    if (fe != 0.f)
+      hipLaunchKernelGGL((grad_dense_kernel<TZ, true>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk,
+                         w.emit, w.alpha, w.beta, w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, fe);
+    else
+      hipLaunchKernelGGL((grad_dense_kernel<TZ, false>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk,
+                         w.emit, w.alpha, w.beta, w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, 0.f);
     RNNT_CHECK_LAUNCH();
   }
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_fastemit(const void* logits, int32_t dtype, const int32_t* labels,
+                                                          const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
+                                                          int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
+                                                          float* nll, void* grad, void* workspace, size_t workspace_bytes,
+                                                          void* stream) {
+  switch (dtype) {
+    case RNNT_DTYPE_F32:
+      return loss_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream);
+    case RNNT_DTYPE_F16:
+      return loss_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream);
+    case RNNT_DTYPE_BF16:
+      return loss_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream);
+    default:
+      set_error("loss_from_logits: unknown dtype code %d", dtype);
+      return RNNT_ERR_INVALID;
+  }
 }
 
 extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_ex(const void* logits, int32_t dtype, const int32_t* labels,
                                                     const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
                                                     int32_t U1, int32_t V, int32_t blank, float gscale, float* nll, void* grad,
                                                     void* workspace, size_t workspace_bytes, void* stream) {
-  switch (dtype) {
-    case RNNT_DTYPE_F32:
-      return loss_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nll, grad, workspace, workspace_bytes, stream);
-    case RNNT_DTYPE_F16:
-      return loss_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nll, grad, workspace, workspace_bytes, stream);
-    case RNNT_DTYPE_BF16:
-      return loss_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nll, grad, workspace, workspace_bytes, stream);
-    default:
-      set_error("loss_from_logits: unknown dtype code %d", dtype);
-      return RNNT_ERR_INVALID;
-  }
+  return rnnt_hip_loss_from_logits_fwd_bwd_fastemit(logits, dtype, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, 0.f, nll, grad,
+                                                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int rnnt_hip_loss_from_logits_fwd_bwd(const float* logits, const int32_t* labels, const int32_t* t_lens,

@@ -9,21 +9,27 @@ CTCLoss — the CTC loss on per-frame logits (the auxiliary loss on the encoder'
 import torch
 import torch.nn as nn
 
-from .ops import Alignment, CtcLossFn, RnntLossFromLogitsFn, align_from_logits
+from .ops import Alignment, CtcLossFn, RnntLossFromLogitsFn, align_from_logits, check_fastemit_lambda
 
 
 class RNNTLoss(nn.Module):
-    def __init__(self, blank: int = 0, reduction: str = "mean"):
+    """`fastemit_lambda` > 0 (finite, >= 0; default 0) adds FastEmit regularisation (Yu et al., ICASSP 2021): the gradient with respect
+    to the label log-probabilities of every lattice cell is scaled by 1 + lambda and taken through the log-softmax exactly
+    (include/rnnt_hip.h), which trains the model to emit sooner.  ONLY THE GRADIENT CHANGES: the returned loss is the unregularised
+    negative log-likelihood, bit for bit what lambda = 0 returns."""
+
+    def __init__(self, blank: int = 0, reduction: str = "mean", fastemit_lambda: float = 0.0):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
         self.blank, self.reduction = int(blank), reduction
+        self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
 
     def forward(self, logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor,
                 target_lengths: torch.Tensor) -> torch.Tensor:
         if logits.dim() != 4:
             raise ValueError("logits must be (B, T, U+1, V)")
-        nll = RnntLossFromLogitsFn.apply(logits, targets, logit_lengths, target_lengths, self.blank)
+        nll = RnntLossFromLogitsFn.apply(logits, targets, logit_lengths, target_lengths, self.blank, self.fastemit_lambda)
         if self.reduction == "mean":
             return nll.mean()
         if self.reduction == "sum":

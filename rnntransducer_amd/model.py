@@ -14,6 +14,8 @@ Differences, all inside the hot path:
   * `jointnet_params["aux_ctc"] = True` adds a CTC head on the encoder (JointNet.ctc_head) and `args.ctc_weight` (default 0.0) the
     auxiliary CTC loss of joint CTC + transducer training to `training_step`: loss = rnnt + ctc_weight * ctc.  Both are off by
     default; the reference has neither.
+  * `args.fastemit_lambda` (default 0.0: off) adds FastEmit regularisation to `training_step`: the lattice gradient is changed so that
+    the model learns to emit sooner, the logged loss stays the unregularised one (JointNet.loss).  The reference has no such knob.
   * `validation_step` stays on the GPU (the reference moves the module to the CPU at model.py:65-72 because its
     decode is a host loop): fused loss + on-device greedy search; it returns token ids, and texts only if a
     tokenizer object was attached as `self.tokenizer`.
@@ -24,6 +26,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
+from .ops import check_fastemit_lambda
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -55,7 +58,8 @@ class RNNTransducer(_Base):
             raise ValueError(f"args.compute_precision must be 'fp32' or 'fp16', got {cp!r}")
         self.jointnet.set_compute_precision(cp)
         # model.py:28-39 picks torchaudio (precision 16) or warp-transducer; both are this one HIP module here
-        self.rnnt_loss = RNNTLoss(blank=self.blank_token_id, reduction="mean")
+        self.fastemit_lambda = check_fastemit_lambda(getattr(args, "fastemit_lambda", 0.0) or 0.0)
+        self.rnnt_loss = RNNTLoss(blank=self.blank_token_id, reduction="mean", fastemit_lambda=self.fastemit_lambda)
         self.ctc_weight = float(getattr(args, "ctc_weight", 0.0) or 0.0)
         if self.ctc_weight > 0.0 and not self.jointnet.aux_ctc:
             raise ValueError("args.ctc_weight > 0 needs the CTC head: set jointnet_params['aux_ctc'] = True")
@@ -143,7 +147,7 @@ class RNNTransducer(_Base):
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
                                   audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None,
-                                  ctc_weight=self.ctc_weight)
+                                  ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda)
         if pl is not None and getattr(self, "_trainer", None) is not None:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}

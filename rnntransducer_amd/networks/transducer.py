@@ -98,7 +98,8 @@ class JointNet(nn.Module):
         return JointLogitsFn.apply(enc, dec, self.fc.weight, self.fc.bias)
 
     def loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int,
-             reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False):
+             reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False,
+             fastemit_lambda: float = 0.0):
         """-log P(y|x) through the fused path (no (B,T,U+1,V) tensor): per utterance, shape (B,) (reduction "none"), or the 0-d
         "mean" / "sum" over the batch (model.py:39 builds the reference's loss with reduction="mean").
         `audio_lengths`: the python list of frame counts the reference's collate hands over next to the tensor (dataloader.py:20,49).
@@ -109,7 +110,10 @@ class JointNet(nn.Module):
         `ctc_weight` != 0 (aux_ctc=True only): the result is rnnt + ctc_weight * ctc under the same reduction, the CTC term
         being the CTC loss of `targets` on ctc_head(encoder output); ONE encoder forward feeds both.  return_parts=True returns
         (total, rnnt, ctc); with ctc_weight = 0 the CTC part is then computed without a graph and total is the RNN-T loss.
-        With ctc_weight = 0 and return_parts=False the head is not touched: same bits as a model without it."""
+        With ctc_weight = 0 and return_parts=False the head is not touched: same bits as a model without it.
+        `fastemit_lambda` > 0: FastEmit regularisation of the transducer term's GRADIENT (label log-probability gradients scaled by
+        1 + lambda, through the log-softmax exactly: include/rnnt_hip.h), which trains the model to emit sooner.  The returned value
+        stays the unregularised loss, bit for bit that of lambda = 0; the CTC term is untouched.  Finite and >= 0."""
         with_ctc = ctc_weight != 0.0 or return_parts
         if with_ctc:
             self._need_ctc_head("loss(ctc_weight != 0 or return_parts=True)")
@@ -121,7 +125,8 @@ class JointNet(nn.Module):
             audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), reduction == "none")
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
-        out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction)
+        out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction,
+                                fastemit_lambda)
         out = out if inv is None else out.index_select(0, inv)
         if not with_ctc:
             return out

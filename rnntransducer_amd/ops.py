@@ -6,6 +6,7 @@ All internal activations are TIME-MAJOR (T,B,F): one LSTM step touches one conti
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -747,15 +748,26 @@ def _joint_backward(enc, dec, W, dA, dC, needs, w_tgt=None, b_tgt=None):
     return d_enc, d_dec, dW, db
 
 
+def check_fastemit_lambda(fastemit_lambda) -> float:
+    """FastEmit's weight (include/rnnt_hip.h): a finite number >= 0, as the library itself requires."""
+    lam = float(fastemit_lambda)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"fastemit_lambda must be finite and >= 0, got {fastemit_lambda!r}")
+    return lam
+
+
 class JointLossFn(torch.autograd.Function):
     """enc (T,B,Oe), dec (U1,B,Od) time-major -> per-utterance NLL (B,).  Never builds (B,T,U1,V).
     forward: A/C pre-GEMMs + log-softmax terms + alpha/beta (kept in a workspace); backward: the lattice gradient kernel with
     the upstream per-utterance gradient folded in (1/B under reduction="mean", model.py:39), then the joint's own backward.
-    Under torch.no_grad() (validation_step) no gradient kernel runs and nothing is kept."""
+    Under torch.no_grad() (validation_step) no gradient kernel runs and nothing is kept.
+    fastemit_lambda > 0: FastEmit regularisation of the GRADIENT (label log-probability gradients scaled by 1 + lambda, through the
+    log-softmax exactly; include/rnnt_hip.h).  The returned loss stays the unregularised NLL, bit for bit that of lambda = 0."""
 
     @staticmethod
-    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none"):
+    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0):
         _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
+        ctx.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
         w_param, b_param = W, bias
         enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
         for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
@@ -795,14 +807,14 @@ class JointLossFn(torch.autograd.Function):
         gvec = _f32c(g.to(torch.float32), "grad of the loss")
         scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
         dA, dC = torch.empty_like(A), torch.empty_like(Cm)
-        check(_lib.lib().rnnt_hip_joint_loss_bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
-                                                 _addr(t_lens), _addr(u_lens), B, T, U1, V, ctx.blank,
-                                                 ctx.red_scale if scalar else 1.0, _addr(gvec), 0 if scalar else 1,
-                                                 _addr(dA), _addr(dC), _addr(ws), ws.numel(), _stream()),
-              "rnnt_hip_joint_loss_bwd")
+        check(_lib.lib().rnnt_hip_joint_loss_bwd_fastemit(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
+                                                          _addr(t_lens), _addr(u_lens), B, T, U1, V, ctx.blank,
+                                                          ctx.red_scale if scalar else 1.0, ctx.fastemit_lambda, _addr(gvec),
+                                                          0 if scalar else 1, _addr(dA), _addr(dC), _addr(ws), ws.numel(), _stream()),
+              "rnnt_hip_joint_loss_bwd_fastemit")
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
                                                _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
-        return d_enc, d_dec, dW, db, None, None, None, None, None, None
+        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None
 
 
 class JointLogitsFn(torch.autograd.Function):
@@ -832,11 +844,13 @@ class JointLogitsFn(torch.autograd.Function):
 
 
 class RnntLossFromLogitsFn(torch.autograd.Function):
-    """warp-transducer-shaped loss on dense logits (model.py:39,57) -> per-utterance NLL (B,)."""
+    """warp-transducer-shaped loss on dense logits (model.py:39,57) -> per-utterance NLL (B,).
+    fastemit_lambda > 0: FastEmit regularisation of the gradient only (see JointLossFn); the NLL is that of lambda = 0."""
 
     @staticmethod
-    def forward(ctx, logits, targets, t_lens, u_lens, blank):
+    def forward(ctx, logits, targets, t_lens, u_lens, blank, fastemit_lambda=0.0):
         _need_gpu(logits, targets, t_lens, u_lens)
+        lam = check_fastemit_lambda(fastemit_lambda)
         codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
         if logits.dtype not in codes:
             raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
@@ -852,10 +866,10 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
         grad = torch.empty_like(logits) if logits.requires_grad else None
         nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
         ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
-        check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_ex(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
-                                                              _addr(u_lens), B, T, U1, V, int(blank), 1.0, _addr(nll),
-                                                              _addr(grad), _addr(ws), nws, _stream()),
-              "rnnt_hip_loss_from_logits_fwd_bwd_ex")
+        check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_fastemit(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
+                                                                    _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(nll),
+                                                                    _addr(grad), _addr(ws), nws, _stream()),
+              "rnnt_hip_loss_from_logits_fwd_bwd_fastemit")
         ctx.grad = grad
         return nll
 
@@ -863,7 +877,7 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.grad
         ctx.grad = None
-        return (grad.float() * g.to(torch.float32).view(-1, 1, 1, 1)).to(grad.dtype), None, None, None, None
+        return (grad.float() * g.to(torch.float32).view(-1, 1, 1, 1)).to(grad.dtype), None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
