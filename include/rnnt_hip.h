@@ -855,7 +855,9 @@ int rnnt_hip_beam_stream_chunk_fused(const rnnt_beam_stream_desc* d, const rnnt_
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft
- *   center=True), zeros up to Lp.  out (B, Lp).
+ *   center=True), zeros up to Lp.  out (B, Lp).  lens[b] is clamped to [0, ld]; a row of length 0 is all zeros.  A
+ *   length 0 < lens[b] <= pad is outside the contract (one reflection does not land inside the utterance; torch.stft
+ *   raises there): the positions it cannot reach are written as 0.
  * The windowed DFT is then ONE rnnt_hip_gemm_f32 over the frames in place: M = B*F rows with a_div = F, a_so = Lp,
  *   a_si = hop, K = n_fft, B = hann * [cos | -sin] basis (2*n_bins, n_fft).
  * rnnt_hip_power_mel_log1p: spec (M, 2*n_bins) = [re | im] -> out (M, n_mels) = log1p(fb^T |X|^2), rows whose frame index

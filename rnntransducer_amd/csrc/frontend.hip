@@ -29,7 +29,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 __global__ void __launch_bounds__(1024) frontend_norm_pad_kernel(const float* __restrict__ wav, long ld, const int* __restrict__ lens,
                                                                   int P, long Lp, int normalize, float* __restrict__ out) {
   __shared__ double red[16];
-  const int b = blockIdx.x, L = lens[b];
+  const int b = blockIdx.x;
+  // clamped to the row: a length beyond ld would read past it (past the allocation for the last row), a negative one is 0
+  const int L = (int)min((long)max(lens[b], 0), ld);
   const float* x = wav + (long)b * ld;
   float* y = out + (long)b * Lp;
   float mean = 0.f, rstd = 1.f;

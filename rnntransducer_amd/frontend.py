@@ -68,14 +68,31 @@ class LogMelFrontend(nn.Module):
     @torch.no_grad()
     def forward(self, wav: torch.Tensor, lengths: Union[Sequence[int], torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
         """wav (B, L_max) float32 on the GPU (anything beyond lengths[b] is ignored), lengths in samples ->
-        (features (B, T_max, n_mels) float32 with zeros after each utterance's last frame, frame counts (B,) int32)."""
-        _need_gpu(wav, self.basis)
+        (features (B, T_max, n_mels) float32 with zeros after each utterance's last frame, frame counts (B,) int32).
+
+        Lengths given as a Python sequence (the reference's form, dataloader.py:20) are checked on the host, before any
+        device work and without a device sync: a length outside [0, L_max], or one with 0 < L <= n_fft // 2 (a single
+        reflection does not land inside the utterance: the reference's reflect pad raises there too), raises ValueError
+        naming the utterance.  Lengths given as a device tensor are not read back: they are clamped to [0, L_max] on the
+        device, and 0 < L <= n_fft // 2 is outside the contract (the positions one reflection cannot reach are zeros)."""
         if wav.dim() != 2 or wav.dtype != torch.float32:
             raise ValueError("wav must be (B, L_max) float32")
-        wav = wav.contiguous()
         B, Lmax = wav.shape
-        lens = lengths_to_device(lengths, wav.device)
         P = self.n_fft // 2
+        if not isinstance(lengths, torch.Tensor):
+            lengths = [int(n) for n in lengths]
+            if len(lengths) != B:
+                raise ValueError(f"{len(lengths)} lengths for a batch of {B} utterances")
+            for b, n in enumerate(lengths):
+                if n < 0 or n > Lmax:
+                    raise ValueError(f"utterance {b}: length {n} outside [0, {Lmax}]")
+                if 0 < n <= P:
+                    raise ValueError(f"utterance {b}: length {n} is not longer than the reflect padding n_fft // 2 = {P}")
+        elif lengths.numel() != B:
+            raise ValueError(f"{lengths.numel()} lengths for a batch of {B} utterances")
+        _need_gpu(wav, self.basis)
+        wav = wav.contiguous()
+        lens = lengths_to_device(lengths, wav.device).clamp(0, Lmax)
         F = self.num_frames(Lmax)
         Lp = (Lmax + 2 * P + 3) // 4 * 4
         padded = torch.empty(B, Lp, device=wav.device, dtype=torch.float32)

@@ -1,5 +1,6 @@
 """Input side: LogMelFrontend on the GPU vs the CPU oracle (oracle/frontend_oracle.py: torch.stft in float64 +
-the documented HTK filterbank), SpecAugment properties, and the oracle's own sanity on the CPU."""
+the documented HTK filterbank), SpecAugment properties, and on the CPU: the oracle's own sanity (at the default configuration and at
+the ones tests/test_gpu_frontend_kernels.py runs) and the checks LogMelFrontend makes on the host before any device work."""
 import math
 
 import numpy as np
@@ -29,6 +30,59 @@ def test_package_filterbank_equals_oracle_constants():
     from rnntransducer_amd.frontend import melscale_fbanks_htk
     got = melscale_fbanks_htk(201, 0.0, 8000.0, 80, 16000).double().numpy()
     assert np.abs(got - melscale_fbanks_htk64(201, 0.0, 8000.0, 80, 16000)).max() < 1e-6
+
+
+# Other configurations than the default (tests/test_gpu_frontend_kernels.py runs them on the GPU): n_fft = 512 with hop 128 and
+# 40 mels, and with hop 160 and 128 mels (257 x 128 filterbank + 16 frames of power: 148032 B of LDS, just under the 160 KiB guard).
+OTHER_CONFIGS = [(0.032, 0.008, 40), (0.032, 0.01, 128)]
+OTHER_LENGTHS = [257, 258, 4000, 5003]   # one and two samples more than the reflect pad n_fft // 2 = 256, ..., L_max
+
+
+def other_config_wave(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    t = torch.arange(n) / 16000.0
+    return 0.3 * torch.randn(n, generator=g) * (0.5 + 0.5 * torch.sin(2 * math.pi * 3.0 * t)) + 0.2 * torch.sin(2 * math.pi * 440.0 * t) + 0.05
+
+
+@pytest.mark.parametrize("window,stride,n_mels", OTHER_CONFIGS)
+def test_oracle_runs_at_the_other_configurations(window, stride, n_mels):
+    n_fft, hop = int(math.ceil(16000 * window)), int(16000 * stride)
+    assert n_fft == 512 and hop in (128, 160)
+    for n in OTHER_LENGTHS:
+        feats = log_mel(other_config_wave(n, n).numpy(), window_size_sec=window, window_stride_sec=stride, n_mels=n_mels)
+        assert feats.shape == (1 + n // hop, n_mels) and np.isfinite(feats).all() and feats.max() > 0.0
+    with pytest.raises(RuntimeError):   # one reflection does not land inside the utterance: torch.stft's reflect pad raises
+        log_mel(other_config_wave(256, 1).numpy(), window_size_sec=window, window_stride_sec=stride, n_mels=n_mels)
+
+
+def test_frontend_refuses_windows_and_strides_the_kernels_cannot_take():
+    from rnntransducer_amd.frontend import LogMelFrontend
+    with pytest.raises(ValueError, match="n_fft"):
+        LogMelFrontend(window_size_sec=0.0255)    # n_fft = 408: not a multiple of 16
+    with pytest.raises(ValueError, match="hop"):
+        LogMelFrontend(window_stride_sec=0.0101)  # hop = 161: not a multiple of 4
+    fe = LogMelFrontend(window_size_sec=0.032, window_stride_sec=0.008, n_mels=40)
+    assert (fe.n_fft, fe.hop, fe.n_bins, tuple(fe.fb.shape)) == (512, 128, 257, (257, 40))
+
+
+def test_python_lengths_are_checked_on_the_host_before_any_device_work():
+    """Lengths as a Python sequence (the reference's form): a length outside [0, L_max], or one a single reflection cannot pad
+    (0 < L <= n_fft // 2, where the reference's reflect pad raises too), is a ValueError naming the utterance.  The waveform is
+    on the CPU here: the check comes before the device is asked for (a good batch on the CPU is refused as a CPU tensor)."""
+    from rnntransducer_amd._lib import RnntHipError
+    from rnntransducer_amd.frontend import LogMelFrontend
+    fe = LogMelFrontend()
+    wav = torch.zeros(3, 1000)
+    for bad, who in (([1000, 1001, 500], "utterance 1"), ([1000, 500, -1], "utterance 2"), ([200, 500, 1000], "utterance 0"),
+                     ([1000, 1, 1000], "utterance 1")):
+        with pytest.raises(ValueError, match=who):
+            fe(wav, bad)
+    with pytest.raises(ValueError):
+        fe(wav, [1000, 1000])          # two lengths for three utterances
+    with pytest.raises(ValueError):
+        fe(wav, torch.tensor([1000, 1000]))
+    with pytest.raises(RnntHipError):  # lengths 0, n_fft // 2 + 1 and L_max are all fine: only the device is missing
+        fe(wav, [0, 201, 1000])
 
 
 @pytest.mark.gpu

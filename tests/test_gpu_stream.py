@@ -1,4 +1,5 @@
-"""Streaming greedy recognition on the GPU (csrc/stream.hip): the chunked encoder against float64, bitwise chunk invariance,
+"""(The encoder kernels at their own shape edges, driven without a model: tests/test_gpu_stream_shapes.py.)
+Streaming greedy recognition on the GPU (csrc/stream.hip): the chunked encoder against float64, bitwise chunk invariance,
 tokens against the offline search (the oracle's and this library's), slot reset, many streams, determinism and the guards."""
 import pytest
 import torch
