@@ -507,6 +507,46 @@ int rnnt_hip_ctc_loss_bwd(const float* logits, int64_t z_sb, int64_t z_st, const
 int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T, int32_t V,
                         int32_t blank, int32_t* tokens, int32_t* counts, int32_t* frames, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTC prefix beam search on per-frame logits (the encoder's CTC head), optionally with token fusion.  csrc/ctc_beam.hip, DESIGN.md §19.
+ * Logits, strides and t_lens as for the CTC entries above (t_lens[b] is clamped to [0,T]; frames t >= t_lens[b] are never read).
+ * Per utterance, lp[t,v] is the fp32 log-softmax of the logits row, as the CTC loss computes it.  A hypothesis is a prefix l (a token
+ * list without blanks; equal adjacent tokens are legal) with two fp64 log-probabilities: pb, the mass of its paths ending in blank,
+ * and pnb, the mass of its paths ending in l[-1]; p(l) = logaddexp(pb, pnb).  With fusion it also carries an automaton state and an
+ * fp64 total = the sum of arc[s, k] over its tokens in append order from state 0 (it depends on the prefix only).
+ *   start     the beam is [()] with pb = 0, pnb = -inf, state 0, total 0
+ *   frame t   the beam holds at most W prefixes in rank order r = 0..; candidate tokens C_t = {k != blank : lp[t,k] >= token_min_logp}
+ *             (token_min_logp = -inf: every non-blank token).  For the prefix l at rank r with last token e (none for ()):
+ *               survivor l, id r (V+1):            pb' = p(l) + lp[t,blank]; stay term pnb(l) + lp[t,e] (-inf for ()), whether or not
+ *                                                  e is in C_t
+ *               extension l + k, k in C_t, id r (V+1) + 1 + k:   extension term pb(l) + lp[t,k] if k == e, else p(l) + lp[t,k]
+ *             An extension l + k that equals a prefix l2 of the current beam is the same candidate as l2's survivor and takes the
+ *             survivor's id; pnb' = logaddexp(stay term, extension term), a missing term being -inf (logaddexp(x, -inf) = x exactly).
+ *             A prefix that was pruned earlier and is reached again is a new candidate with only its extension term.
+ *             Candidate score = logaddexp(pb', pnb'); rank key = score + total', descending, then id ascending; candidates with
+ *             score -inf are dropped; the first W form the next beam.
+ *   output    up to W hypotheses per utterance, best first by score (with fusion: by score + total + final[state]), ties in the last
+ *             frame's order; t_lens[b] = 0 gives [()] with score 0.  No length normalisation.
+ * Outputs: counts (B) int32 = hypotheses of utterance b; for o < counts[b]: lens[b,o], tokens[b,o,:lens[b,o]] (tokens is (B, W, T)
+ * int32; a prefix has at most t_lens[b] tokens), scores[b,o] (fp64: the CTC log-probability mass the search kept for that labelling),
+ * with fusion fusion->fused_scores[b,o] = score + total + final[state] ((B, W) fp64; must not be NULL then), and frames (B, W, T)
+ * int32 or NULL: per token the frame whose extension step first created its prefix-tree node (a prefix keeps ONE node however often
+ * it is pruned and reached again; frames increase along a hypothesis).  Nothing is written for o >= counts[b] or past lens[b,o].
+ * fusion: NULL, or the tables of rnnt_beam_fusion above over the SAME V (next values outside [0,S) are clamped); the unfused
+ * instance of the kernel does not touch them, and an all-zero automaton gives the unfused lists and score bits.
+ * Limits, checked on the host before any launch (RNNT_ERR_INVALID): 1 <= W <= 128, V >= 2, 0 <= blank < V, W (V+1) <= 2^24,
+ * token_min_logp neither NaN nor +inf, n_states >= 1 and n_states * V <= 2^27, non-NULL pointers, workspace (8-byte aligned) of
+ * rnnt_hip_ctc_beam_workspace_bytes(B, T, V, W) bytes (0 for sizes outside the limits): the candidate keys, the prefix tree of at
+ * most 1 + W T nodes per utterance and the frames' log-sum-exps.  One launch, one workgroup per utterance, every sum in one fixed
+ * order: the same bits on every call, and a row alone gives the bits it gives in any batch.
+ * ---------------------------------------------------------------------------------------------- */
+struct rnnt_beam_fusion;
+size_t rnnt_hip_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t W);
+int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T, int32_t V,
+                             int32_t blank, int32_t W, float token_min_logp, const struct rnnt_beam_fusion* fusion, int32_t* tokens,
+                             int32_t* lens, double* scores, int32_t* frames, int32_t* counts, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* One fused AdamW step over FLAT fp32 buffers (all parameters / gradients / moments of the module laid out back to back):
  * replaces torch.optim.AdamW's multi-tensor kernels at model.py:111-115.  Same update as torch (decoupled weight decay,
  * bias corrections from `step` >= 1). */

@@ -1,0 +1,452 @@
+// CTC prefix beam search on per-frame logits (the encoder's CTC head), with token fusion, for gfx950.  DESIGN.md §19.
+//
+// Definition (include/rnnt_hip.h states it in full).  lp[t,v] = z[t,v] - logsumexp_v z[t,:] in fp32, as ctc_terms_kernel (ctc.hip).
+// A hypothesis is a prefix l (tokens without blanks) with pb / pnb, the fp64 log-mass of its paths ending in blank / in l[-1];
+// p = logaddexp(pb, pnb).  Frame t, member at rank r with last token e, candidate tokens C_t = {k != blank: lp[t,k] >= min_logp}:
+//   survivor   id r(V+1)      : pb' = p + lp[t,blank];  pnb' = logaddexp(pnb + lp[t,e], extension term of its parent, if the parent
+//                               is in the beam and l[-1] is in C_t)
+//   extension  id r(V+1)+1+k  : pnb' = (k == e ? pb : p) + lp[t,k], unless l + k is a member of the beam: then it is that
+//                               member's survivor
+//   key = logaddexp(pb', pnb') + total'; the first W by (key descending, id ascending) are the next beam.
+//
+// Prefix tree: nodes (parent, token, frame, first_child, next_sibling), append-only, node 0 = the empty prefix.  A node is looked up
+// among its parent's children before it is created, so a prefix has ONE node however often it is pruned and reached again, and
+// "l + k is a member" is the comparison (parent node, token) against the at most W members.
+//
+// One workgroup of 1024 threads per utterance, no communication between workgroups.  Per frame:
+//   fill     every candidate's key as an order-preserving 64-bit integer into the utterance's scratch (0 = no candidate); lanes along
+//            the flat candidate index, so along v within a member's row
+//   select   radix select of the W-th largest (key, then lowest id) over 8-bit digits: integer LDS histograms (the counts do not
+//            depend on the order of the atomic adds), at most 8 passes over the key and 3 over the id, stops at the first pass whose
+//            bin holds exactly what is still missing
+//   gather   the selected candidates into LDS, ranked there by counting (the total order is strict, so ranks are a permutation)
+//   build    the next beam in rank order: survivors copy, extensions find or create their node; new nodes are numbered in rank
+//            order by one thread and linked into their parent's child list by the first new child of that parent
+// Every sum has one fixed order (logaddexp_d is symmetric in its arguments) and every output one writer: bitwise reproducible, and
+// a row's result does not depend on the batch around it.  Loops are bounded by T, W, V or the 11 digits of the select.
+#include "common.hpp"
+#include "lattice_shared.hpp"
+
+namespace rnnt {
+namespace {
+
+constexpr int CB_THREADS = 1024;
+constexpr int CB_WMAX = 128;
+constexpr int CB_IDBITS = 24;   // candidate ids r (V+1) + j fit 24 bits: three 8-bit digits break exact ties
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ int cb_clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
+
+// order-preserving map of a double that is > -inf and not NaN onto [2^52, 2^64): 0 stays free for "no candidate"
+__device__ __forceinline__ u64 cb_sortable(double x) {
+  const u64 u = __builtin_bit_cast(u64, x + 0.0);   // (-0.0 + 0.0 = +0.0: one pattern per value)
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+struct CbBeam {
+  double pb[CB_WMAX], pnb[CB_WMAX], tot[CB_WMAX];
+  int node[CB_WMAX], st[CB_WMAX], tok[CB_WMAX], par[CB_WMAX];   // tok / par: the node's token and parent (-1 for the empty prefix)
+};
+
+struct CbShared {
+  CbBeam beam[2];
+  double p[CB_WMAX], cpb[CB_WMAX], cpnb[CB_WMAX];   // p of the members; pb' / pnb' of their survivors
+  int src[CB_WMAX];                                 // rank of the member whose extension by tok[r] is member r (-1: none)
+  u64 sel_key[CB_WMAX];
+  int sel_id[CB_WMAX], pending[CB_WMAX];
+  int hist[256];
+  int nvalid, nsel, need, bin, cnt, nnodes;
+  u64 kprefix;        // the digits of the threshold key chosen so far (all 64 bits after pass 7)
+  unsigned iprefix;   // then the digits of the threshold's complemented id
+};
+
+struct CbNodes {
+  int *parent, *token, *frame, *child, *sib;
+};
+
+// the bin d with sum_{d' > d} hist[d'] < need <= sum_{d' >= d} hist[d'] (wave 0; lane l owns bins 255-4l .. 252-4l)
+__device__ __forceinline__ void cb_pick_bin(CbShared& sh, int lane) {
+  int h[4], s = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { h[i] = sh.hist[255 - 4 * lane - i]; s += h[i]; }
+  int inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o);
+    if (lane >= o) inc += v;
+  }
+  const int need = sh.need;
+  const unsigned long long hit = __ballot(inc >= need);
+  if (hit == 0ull) {   // (fewer matches than needed: cannot happen while need <= the number of candidates; keep the state sane)
+    if (lane == 0) { sh.bin = 0; sh.cnt = need; }
+    return;
+  }
+  const int first = __ffsll((long long)hit) - 1;
+  if (lane == first) {
+    int above = inc - s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (above + h[i] >= need) {
+        sh.bin = 255 - 4 * lane - i;
+        sh.cnt = h[i];
+        sh.need = need - above;
+        break;
+      }
+      above += h[i];
+    }
+  }
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __restrict__ Z, long z_sb, long z_st,
+                                                              const int* __restrict__ t_lens, int T, int V, int blank, int W,
+                                                              float min_logp, const int* __restrict__ fnext,
+                                                              const float* __restrict__ farc, const float* __restrict__ ffinal,
+                                                              int n_states, float* __restrict__ lse_ws, u64* __restrict__ key_ws,
+                                                              int* __restrict__ node_ws, int* __restrict__ tokens,
+                                                              int* __restrict__ lens, double* __restrict__ scores,
+                                                              double* __restrict__ fused, int* __restrict__ frames,
+                                                              int* __restrict__ counts) {
+  __shared__ CbShared sh;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Tb = cb_clampi(t_lens[b], 0, T);
+  const int V1 = V + 1;
+  const long maxn = 1 + (long)W * T;
+  const float* Zb = Z + (long)b * z_sb;
+  float* lse = lse_ws + (long)b * T;
+  u64* ck = key_ws + (long)b * W * V1;
+  CbNodes nd;
+  nd.parent = node_ws + (long)b * 5 * maxn;
+  nd.token = nd.parent + maxn;
+  nd.frame = nd.token + maxn;
+  nd.child = nd.frame + maxn;
+  nd.sib = nd.child + maxn;
+
+  // row log-sum-exp of every valid frame, the arithmetic of ctc_terms_kernel: a wavefront per frame, lanes along v
+  for (int t = wave; t < Tb; t += CB_THREADS / 64) {
+    const float* z = Zb + (long)t * z_st;
+    float m = -__builtin_huge_valf();
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, z[v]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += expf(z[v] - m);
+    s = wave_sum(s);
+    if (lane == 0) lse[t] = m + logf(s);
+  }
+  if (tid < 2 * CB_WMAX) {   // every slot of both beams holds a valid (dead) member from the start
+    CbBeam& c = sh.beam[tid / CB_WMAX];
+    const int r = tid % CB_WMAX;
+    c.pb[r] = NEG_INF; c.pnb[r] = NEG_INF; c.tot[r] = 0.0;
+    c.node[r] = 0; c.st[r] = 0; c.tok[r] = -1; c.par[r] = -1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    CbBeam& c = sh.beam[0];
+    c.pb[0] = 0.0; c.pnb[0] = NEG_INF; c.tot[0] = 0.0;
+    c.node[0] = 0; c.st[0] = 0; c.tok[0] = -1; c.par[0] = -1;
+    nd.parent[0] = -1; nd.token[0] = -1; nd.frame[0] = -1; nd.child[0] = -1; nd.sib[0] = -1;
+    sh.nnodes = 1;
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  int n = 1, cur = 0;
+  for (int t = 0; t < Tb; ++t) {
+    CbBeam& c = sh.beam[cur];
+    CbBeam& nw = sh.beam[cur ^ 1];
+    const float* z = Zb + (long)t * z_st;
+    const float l = lse[t];
+    // ---- members: p, and the member (if any) whose extension by tok[r] is member r
+    if (tid < n) {
+      sh.p[tid] = logaddexp_d(c.pb[tid], c.pnb[tid]);
+      int s = -1;
+      const int par = c.par[tid];
+      if (par >= 0)
+        for (int r = 0; r < n; ++r)
+          if (c.node[r] == par) s = r;   // (nodes of members are distinct: at most one hit)
+      sh.src[tid] = s;
+    }
+    if (tid == 0) { sh.nvalid = 0; sh.nsel = 0; sh.kprefix = 0ull; sh.iprefix = 0u; }
+    __syncthreads();
+    // ---- fill: keys of all n (V+1) candidates
+    const int N = n * V1;
+    for (int idx = tid; idx < N; idx += CB_THREADS) {
+      const int r = idx / V1, j = idx - r * V1;
+      u64 key = 0ull;
+      if (j == 0) {
+        const int e = c.tok[r], s = sh.src[r];
+        const double pbn = sh.p[r] + (double)(z[blank] - l);
+        double pnbn = NEG_INF;
+        if (e >= 0) {
+          const float le = z[e] - l;
+          pnbn = c.pnb[r] + (double)le;                      // the stay term: whether or not e is a candidate token
+          if (s >= 0 && le >= min_logp) {                    // its parent's extension by e, when e is one
+            const double ext = (c.tok[s] == e ? c.pb[s] : sh.p[s]) + (double)le;
+            pnbn = logaddexp_d(pnbn, ext);
+          }
+        }
+        sh.cpb[r] = pbn;
+        sh.cpnb[r] = pnbn;
+        const double k = logaddexp_d(pbn, pnbn) + (FUSED ? c.tot[r] : 0.0);
+        if (k > NEG_INF) key = cb_sortable(k);
+      } else {
+        const int k = j - 1;
+        const float lk = z[k] - l;
+        if (k != blank && lk >= min_logp) {
+          double x = (k == c.tok[r] ? c.pb[r] : sh.p[r]) + (double)lk;
+          if (FUSED) x += c.tot[r] + (double)farc[(long)c.st[r] * V + k];
+          if (x > NEG_INF) key = cb_sortable(x);
+        }
+      }
+      ck[idx] = key;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // an extension that is a member of the beam is that member's survivor: its own slot is no candidate (one writer: member r)
+    if (tid < n && sh.src[tid] >= 0) ck[sh.src[tid] * V1 + 1 + c.tok[tid]] = 0ull;
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- select: radix select of the min(W, candidates) best in the order (key descending, id ascending)
+    int passes = 0;
+    for (int pass = 0; pass < 8 + CB_IDBITS / 8; ++pass) {   // (uniform)
+      if (tid < 256) sh.hist[tid] = 0;
+      __syncthreads();
+      const u64 kprefix = sh.kprefix;
+      const unsigned iprefix = sh.iprefix;
+      int mine = 0;
+      for (int idx = tid; idx < N; idx += CB_THREADS) {
+        const u64 key = ck[idx];
+        if (key == 0ull) continue;
+        ++mine;
+        int digit;
+        if (pass < 8) {
+          if (pass > 0 && (key >> (64 - 8 * pass)) != kprefix) continue;
+          digit = (int)((key >> (56 - 8 * pass)) & 255ull);
+        } else {   // exact ties of the key: the LOWEST id first, so the digits of the complemented id
+          const int q = pass - 8;
+          const unsigned nid = ~(unsigned)idx & ((1u << CB_IDBITS) - 1u);
+          if (key != kprefix) continue;
+          if (q > 0 && (nid >> (CB_IDBITS - 8 * q)) != iprefix) continue;
+          digit = (int)((nid >> (CB_IDBITS - 8 - 8 * q)) & 255u);
+        }
+        atomicAdd(&sh.hist[digit], 1);
+      }
+      if (pass == 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+        if (lane == 0 && mine) atomicAdd(&sh.nvalid, mine);
+      }
+      __syncthreads();
+      if (pass == 0 && tid == 0) sh.need = min(W, sh.nvalid);
+      __syncthreads();
+      if (sh.need == 0) break;   // (uniform) no candidate at all: the beam dies (only with non-finite logits)
+      if (wave == 0) cb_pick_bin(sh, lane);
+      __syncthreads();
+      const bool done = sh.cnt == sh.need;   // the whole bin is taken
+      passes = pass + 1;
+      __syncthreads();
+      if (tid == 0) {
+        if (pass < 8) sh.kprefix = (kprefix << 8) | (u64)sh.bin;
+        else sh.iprefix = (iprefix << 8) | (unsigned)sh.bin;
+      }
+      if (done) break;   // (uniform)
+    }
+    __syncthreads();
+    // ---- gather the selected candidates
+    if (min(W, sh.nvalid) > 0) {
+      const u64 kprefix = sh.kprefix;
+      const unsigned iprefix = sh.iprefix;
+      for (int idx = tid; idx < N; idx += CB_THREADS) {
+        const u64 key = ck[idx];
+        if (key == 0ull) continue;
+        bool take;
+        if (passes <= 8) {
+          take = (key >> (64 - 8 * passes)) >= kprefix;
+        } else {
+          const unsigned nid = ~(unsigned)idx & ((1u << CB_IDBITS) - 1u);
+          take = key > kprefix || (key == kprefix && (nid >> (CB_IDBITS - 8 * (passes - 8))) >= iprefix);
+        }
+        if (take) {
+          const int slot = atomicAdd(&sh.nsel, 1);
+          if (slot < CB_WMAX) { sh.sel_key[slot] = key; sh.sel_id[slot] = idx; }
+        }
+      }
+    }
+    __syncthreads();
+    const int m = min(min(W, sh.nvalid), sh.nsel);   // (the select takes exactly min(W, candidates))
+    // ---- build the next beam in rank order
+    int rank = -1, kk = -1;
+    if (tid < m) {
+      const u64 key = sh.sel_key[tid];
+      const int id = sh.sel_id[tid];
+      rank = 0;
+      for (int i = 0; i < m; ++i) {
+        const u64 ok = sh.sel_key[i];
+        rank += (ok > key || (ok == key && sh.sel_id[i] < id)) ? 1 : 0;
+      }
+      const int r = id / V1, j = id - r * V1;
+      int pend = 0;
+      if (j == 0) {
+        nw.pb[rank] = sh.cpb[r]; nw.pnb[rank] = sh.cpnb[r]; nw.tot[rank] = c.tot[r];
+        nw.node[rank] = c.node[r]; nw.st[rank] = c.st[r]; nw.tok[rank] = c.tok[r]; nw.par[rank] = c.par[r];
+      } else {
+        kk = j - 1;
+        const float lk = z[kk] - l;
+        nw.pb[rank] = NEG_INF;
+        nw.pnb[rank] = (kk == c.tok[r] ? c.pb[r] : sh.p[r]) + (double)lk;
+        if (FUSED) {
+          const long o = (long)c.st[r] * V + kk;
+          nw.tot[rank] = c.tot[r] + (double)farc[o];
+          nw.st[rank] = cb_clampi(fnext[o], 0, n_states - 1);
+        } else {
+          nw.tot[rank] = 0.0;
+          nw.st[rank] = 0;
+        }
+        const int par = c.node[r];
+        nw.tok[rank] = kk;
+        nw.par[rank] = par;
+        // the prefix's node, if it was created before (a node has at most V - 1 children)
+        int ch = nd.child[par];
+        for (int i = 0; i < V && ch >= 0; ++i) {
+          if (nd.token[ch] == kk) break;
+          ch = nd.sib[ch];
+        }
+        nw.node[rank] = ch;
+        pend = ch < 0 ? 1 : 0;
+      }
+      sh.pending[rank] = pend;
+    }
+    __syncthreads();
+    if (tid == 0) {   // new nodes are numbered in rank order
+      int nn = sh.nnodes;
+      for (int i = 0; i < m; ++i)
+        if (sh.pending[i]) nw.node[i] = nn++;
+      sh.nnodes = nn;
+    }
+    __syncthreads();
+    if (rank >= 0 && sh.pending[rank]) {
+      const int me = nw.node[rank], par = nw.par[rank];
+      if (me < maxn) {   // (at most W new nodes per frame: always true)
+        nd.parent[me] = par; nd.token[me] = kk; nd.frame[me] = t; nd.child[me] = -1;
+        bool leader = true;
+        for (int i = 0; i < rank; ++i) leader = leader && !(sh.pending[i] && nw.par[i] == par);
+        if (leader) {   // the first new child of this parent links all of them, in rank order, in front of the list
+          int head = nd.child[par];
+          for (int i = rank; i < m; ++i) {
+            if (sh.pending[i] && nw.par[i] == par) {
+              nd.sib[nw.node[i]] = head;
+              head = nw.node[i];
+            }
+          }
+          nd.child[par] = head;
+        }
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+    n = m;
+    cur ^= 1;
+  }
+
+  // ---- output: stable order by score (FUSED: score + total + final[state]), then the back-trace of every hypothesis
+  CbBeam& c = sh.beam[cur];
+  if (tid < n) {
+    const double sc = logaddexp_d(c.pb[tid], c.pnb[tid]);
+    sh.p[tid] = sc;
+    sh.cpb[tid] = FUSED ? (sc + c.tot[tid]) + (double)ffinal[c.st[tid]] : sc;
+  }
+  __syncthreads();
+  if (tid < n) {
+    const double key = sh.cpb[tid];
+    int o = 0;
+    for (int i = 0; i < n; ++i) o += (sh.cpb[i] > key || (sh.cpb[i] == key && i < tid)) ? 1 : 0;
+    o = min(o, W - 1);
+    const long base = (long)b * W + o;
+    int len = 0;
+    for (int x = c.node[tid]; x > 0 && len < T; x = nd.parent[x]) ++len;
+    int x = c.node[tid];
+    for (int i = len - 1; i >= 0; --i) {
+      tokens[base * T + i] = nd.token[x];
+      if (frames) frames[base * T + i] = nd.frame[x];
+      x = nd.parent[x];
+    }
+    lens[base] = len;
+    scores[base] = sh.p[tid];
+    if (FUSED) fused[base] = key;
+  }
+  if (tid == 0) counts[b] = n;
+}
+
+struct CbWs {
+  float* lse;
+  u64* keys;
+  int* nodes;
+  size_t total;
+};
+
+CbWs carve_cb(void* ws, int64_t B, int64_t T, int64_t V, int64_t W) {
+  CbWs w;
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
+  w.keys = reinterpret_cast<u64*>(take((size_t)B * W * (V + 1) * 8));
+  w.nodes = reinterpret_cast<int*>(take((size_t)B * 5 * (1 + W * T) * 4));
+  w.lse = reinterpret_cast<float*>(take((size_t)B * T * 4));
+  w.total = off;
+  return w;
+}
+
+bool cb_dims_ok(int64_t B, int64_t T, int64_t V, int64_t W) {
+  return B >= 1 && T >= 1 && V >= 2 && W >= 1 && W <= CB_WMAX && W * (V + 1) <= (1ll << CB_IDBITS) && 1 + W * T < (1ll << 31) / 5;
+}
+
+}  // namespace
+}  // namespace rnnt
+
+using namespace rnnt;
+
+extern "C" size_t rnnt_hip_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t W) {
+  if (!cb_dims_ok(B, T, V, W)) return 0;
+  return carve_cb(nullptr, B, T, V, W).total;
+}
+
+extern "C" int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
+                                        int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_fusion* fusion,
+                                        int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  RNNT_CHECK_ARG(B >= 1 && T >= 1, "ctc_beam_search: B and T must be positive (B=%d T=%d)", B, T);
+  RNNT_CHECK_ARG(W >= 1 && W <= CB_WMAX, "ctc_beam_search: beam width W = %d outside [1,%d]", W, CB_WMAX);
+  RNNT_CHECK_ARG(V >= 2, "ctc_beam_search: V = %d < 2 (a blank and at least one token)", V);
+  RNNT_CHECK_ARG(blank >= 0 && blank < V, "ctc_beam_search: blank %d outside [0,%d)", blank, V);
+  RNNT_CHECK_ARG(!(token_min_logp != token_min_logp) && token_min_logp < __builtin_huge_valf(),
+                 "ctc_beam_search: token_min_logp must be a number below +inf (-inf: no pruning)");
+  RNNT_CHECK_ARG(cb_dims_ok(B, T, V, W), "ctc_beam_search: W (V+1) = %lld exceeds 2^%d candidates per frame, or W T = %lld the node index",
+                 (long long)W * (V + 1), CB_IDBITS, (long long)W * T);
+  RNNT_CHECK_ARG(logits && t_lens && tokens && lens && scores && counts, "ctc_beam_search: null logits/lengths/tokens/lens/scores/counts");
+  RNNT_CHECK_ARG(z_sb >= 1 && z_st >= V, "ctc_beam_search: logits strides (z_sb = %lld, z_st = %lld) must be positive, z_st >= V",
+                 (long long)z_sb, (long long)z_st);
+  if (fusion) {
+    RNNT_CHECK_ARG(fusion->next && fusion->arc && fusion->final, "ctc_beam_search: null fusion table");
+    RNNT_CHECK_ARG(fusion->n_states >= 1 && (int64_t)fusion->n_states * V <= (1ll << 27),
+                   "ctc_beam_search: fusion n_states = %d with V = %d outside [1, 2^27 / V]: the tables must be (S, V) over the logits' V",
+                   fusion->n_states, V);
+    RNNT_CHECK_ARG(fusion->fused_scores, "ctc_beam_search: null fused_scores with a fusion automaton");
+  }
+  const CbWs w = carve_cb(workspace, B, T, V, W);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_beam_search: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  RNNT_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "ctc_beam_search: workspace must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope prof(RNNT_K_MISC, 4.0 * (double)B * T * V * (1.0 + W), s);
+  if (fusion)
+    hipLaunchKernelGGL((ctc_beam_kernel<true>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
+                       token_min_logp, fusion->next, fusion->arc, fusion->final, fusion->n_states, w.lse, w.keys, w.nodes, tokens,
+                       lens, scores, fusion->fused_scores, frames, counts);
+  else
+    hipLaunchKernelGGL((ctc_beam_kernel<false>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
+                       token_min_logp, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr, 1, w.lse, w.keys, w.nodes,
+                       tokens, lens, scores, (double*)nullptr, frames, counts);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}

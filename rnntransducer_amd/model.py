@@ -163,6 +163,11 @@ class RNNTransducer(_Base):
         """JointNet.recognize_ctc_greedy with this model's blank: the encoder-only greedy decode through the CTC head."""
         return self.jointnet.recognize_ctc_greedy(inputs, inputs_lengths, self.blank_token_id, return_frames)
 
+    def recognize_ctc_beams(self, inputs, inputs_lengths, beam_widths: int = 16, **kw):
+        """JointNet.recognize_ctc_beams with this model's blank: the encoder-only CTC prefix beam search through the CTC head
+        (token_min_logp=, fusion=, return_scores=, return_frames=)."""
+        return self.jointnet.recognize_ctc_beams(inputs, inputs_lengths, self.blank_token_id, beam_widths, **kw)
+
     def init_stream(self, batch_size: int, device=None):
         """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
         return self.jointnet.init_stream(batch_size, self.blank_token_id, device)

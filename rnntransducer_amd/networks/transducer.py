@@ -22,11 +22,13 @@ fused loss's per-cell terms: the loss's lattice sweep in the (max, +) semiring (
 training (`loss(..., ctc_weight=w)`, `ctc_loss` for CTC pre-training of the encoder) and an encoder-only greedy decode
 (`recognize_ctc_greedy`); csrc/ctc.hip.  Off by default: parameters, their initialisation and every result stay as without it.
 """
+import math
+
 import torch
 import torch.nn as nn
 
-from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, check_fusion, ctc_greedy, greedy_decode,
-                   stream_greedy)
+from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, check_ctc_beam_args, check_fusion,
+                   ctc_beam_search, ctc_greedy, greedy_decode, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -164,6 +166,35 @@ class JointNet(nn.Module):
         t_lens = lengths_to_device(inputs_lengths, inputs.device)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         return ctc_greedy(self.ctc_head(enc), t_lens, blank_token_id, time_major=True, return_frames=return_frames)
+
+    @torch.no_grad()
+    def recognize_ctc_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16, *,
+                            token_min_logp: float = -math.inf, fusion=None, return_scores: bool = False,
+                            return_frames: bool = False):
+        """Encoder-only CTC prefix beam search through the CTC head (csrc/ctc_beam.hip): up to `beam_widths`
+        (<= 128) token lists per utterance (no blanks, no leading blank), best first by the CTC log-probability mass the search
+        kept for each labelling; no length normalisation.  The prediction net is not run, so this works before it is trained
+        and with bidirectional encoders.  For a single utterance the list itself, otherwise one list per utterance (as
+        recognize_beams).  token_min_logp: per frame only tokens whose log-softmax reaches it extend a prefix (-inf: all).
+        return_scores: (tokens, score) pairs, score fp64.  return_frames: frames is appended last, per token the encoder frame
+        at which its prefix first entered the beam.
+        fusion (a TokenFusion on the model's device, used as it is): the search ranks by score + the automaton's total, the
+        output by score + total + final; with return_scores the entries are (tokens, score, fused_score).  A CTC hypothesis has
+        no leading blank: its totals are fusion.score([blank] + tokens).  Limitation: TokenFusion.from_hotwords refuses a phrase
+        that repeats a token back to back (the transducer's y_star never holds one), although a CTC hypothesis can.
+        eval() mode only; ValueError for a missing head, training mode or bad arguments, before anything is launched."""
+        self._need_ctc_head("recognize_ctc_beams")
+        if self.training:
+            raise ValueError("recognize_ctc_beams expects eval() mode (dropout inactive), like recognize_ctc_greedy")
+        check_ctc_beam_args(beam_widths, token_min_logp, "recognize_ctc_beams")
+        check_fusion(fusion, self.num_classes, self.ctc_head.weight.device, "recognize_ctc_beams")
+        t_lens = lengths_to_device(inputs_lengths, inputs.device)
+        enc = self.encoder.forward_time_major(inputs, t_lens)
+        res = ctc_beam_search(self.ctc_head(enc), t_lens, blank_token_id, beam_widths, token_min_logp=token_min_logp,
+                              time_major=True, fusion=fusion, return_frames=return_frames)
+        if not return_scores:   # an entry is (tokens, score[, fused_score][, frames])
+            res = [[(e[0], e[-1]) if return_frames else e[0] for e in hyps] for hyps in res]
+        return res[0] if len(res) == 1 else res
 
     @torch.no_grad()
     def align(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, audio_lengths=None):

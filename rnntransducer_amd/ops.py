@@ -970,6 +970,71 @@ def ctc_greedy(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, *, time_m
     return [tokens[b, :n[b]].long() for b in range(B)]
 
 
+CTC_BEAM_MAX_WIDTH = 128
+
+
+def check_ctc_beam_args(beam_width, token_min_logp, what: str) -> None:
+    """ValueError unless 1 <= beam_width <= 128 and token_min_logp is a number below +inf: before anything is launched."""
+    if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
+        raise ValueError(f"{what}: beam width must be an integer in [1, {CTC_BEAM_MAX_WIDTH}], got {beam_width!r}")
+    if isinstance(token_min_logp, bool) or not isinstance(token_min_logp, (int, float)) or math.isnan(token_min_logp) \
+            or token_min_logp == math.inf:
+        raise ValueError(f"{what}: token_min_logp must be a number below +inf (-inf: no pruning), got {token_min_logp!r}")
+
+
+@torch.no_grad()
+def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam_width: int, *, token_min_logp: float = -math.inf,
+                    time_major: bool = False, fusion=None, return_frames: bool = False):
+    """CTC prefix beam search (include/rnnt_hip.h: rnnt_hip_ctc_beam_search, csrc/ctc_beam.hip) on logits (B,T,V) (time_major:
+    (T,B,V)) fp32, t_lens (B,) int32: per utterance up to `beam_width` (<= 128) hypotheses, best first, as a list of
+    (tokens, score) — tokens a list without blanks, score the fp64 CTC log-probability mass the search kept for that labelling, no
+    length normalisation.  token_min_logp: per frame only tokens with log-softmax >= it extend a prefix (-inf: all).
+    fusion (a fusion.TokenFusion over the same V on the logits' device): the search ranks by score + the automaton's total of
+    the prefix, the output by score + total + final; every entry is then (tokens, score, fused_score).  return_frames appends
+    `frames`: per token the frame at which its prefix first entered the beam.  One launch, then one host copy of the counts and
+    lengths (and one per returned array).  Argument errors raise ValueError before anything is launched."""
+    check_ctc_beam_args(beam_width, token_min_logp, "ctc_beam_search")
+    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    if V < 2 or not 0 <= int(blank) < V:
+        raise ValueError(f"ctc_beam_search: V = {V} < 2 or blank {blank} outside [0, {V})")
+    if beam_width * (V + 1) > 1 << 24:
+        raise ValueError(f"ctc_beam_search: beam_width * (V + 1) = {beam_width * (V + 1)} exceeds 2^24 candidates per frame")
+    check_fusion(fusion, V, logits.device, "ctc_beam_search")
+    _need_gpu(logits, t_lens)
+    logits = _f32c(logits, "logits")
+    if t_lens.dtype != torch.int32:
+        raise ValueError(f"logit lengths must be int32, got {t_lens.dtype}")
+    if t_lens.shape != (B,):
+        raise ValueError(f"logit lengths must be (B,) = ({B},), got {tuple(t_lens.shape)}")
+    t_lens = t_lens.contiguous()
+    dev, W, L = logits.device, beam_width, _lib.lib()
+    tokens = torch.empty(B, W, T, device=dev, dtype=torch.int32)
+    small = torch.empty(B + B * W, device=dev, dtype=torch.int32)   # counts | lens: one transfer
+    scores = torch.empty(B, W, device=dev, dtype=torch.float64)
+    frames = torch.empty(B, W, T, device=dev, dtype=torch.int32) if return_frames else None
+    fused = torch.empty(B, W, device=dev, dtype=torch.float64) if fusion is not None else None
+    fs = fusion_struct(fusion, fused) if fusion is not None else None
+    nws = L.rnnt_hip_ctc_beam_workspace_bytes(B, T, V, W)
+    if nws == 0:
+        raise ValueError(f"ctc_beam_search: sizes outside the kernel's limits (B={B} T={T} V={V} W={W})")
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    check(L.rnnt_hip_ctc_beam_search(_addr(logits), z_sb, z_st, _addr(t_lens), B, T, V, int(blank), W, float(token_min_logp),
+                                     C.byref(fs) if fs is not None else None, _addr(tokens), _addr(small, B), _addr(scores),
+                                     _addr(frames), _addr(small), _addr(ws), nws, _stream()), "rnnt_hip_ctc_beam_search")
+    host = small.cpu()   # the only host sync of the search
+    count, lens_h = host[:B].tolist(), host[B:].reshape(B, W).tolist()
+    longest = max([1] + [lens_h[b][r] for b in range(B) for r in range(count[b])])
+    tok_h, scores_h = tokens[:, :, :longest].cpu(), scores.cpu().tolist()
+    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if fusion is not None:
+        fused_h = fused.cpu().tolist()
+        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
+    if return_frames:
+        fr_h = frames[:, :, :longest].cpu()
+        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # forced alignment (include/rnnt_hip.h: rnnt_hip_joint_align / rnnt_hip_align_from_logits_ex): best path of a known transcript
 # --------------------------------------------------------------------------------------------------
