@@ -892,6 +892,81 @@ int rnnt_hip_beam_stream_chunk_fused(const rnnt_beam_stream_desc* d, const rnnt_
                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Frame-synchronous transducer beam search with batched hypothesis steps.  csrc/beam_sync.hip, DESIGN.md §20.
+ * The search every other transducer toolkit decodes with (time-synchronous / "modified" beam search): every frame expands the
+ * whole beam at once, emits at most max_symbols tokens, merges hypotheses with the same token sequence by logaddexp (a score is
+ * probability mass, not one path), and advances the prediction net once for all new hypotheses together.  Its cost per frame is
+ * bounded by W, V and S alone, with or without fusion.  rnnt_hip_beam_search stays the reference-faithful best-first search.
+ *
+ * Inputs: A (time-major: frame t of utterance b at A + t*a_st + b*a_sb, V floats) = gelu(enc_t) W_e^T + bias as for
+ * rnnt_hip_beam_search; the prediction net and its half of the joint; blank; W = beam in [1,64]; S = max_symbols in [1,4];
+ * token_min_logp (-inf: no pruning; neither NaN nor +inf); optionally the automaton of rnnt_beam_fusion over the same V.
+ * Hypothesis: a prefix-tree node (its token sequence y; the root is [blank]; ONE node per prefix), an fp64 score, a
+ * prediction-net state with its joint half Cv, and with fusion an automaton state and an fp64 total.
+ * lp_h[v] = the fp32 log-softmax over v of A_t[v] + Cv_h[v].
+ *   start    one hypothesis: the root, score 0; its state is one step on blank from the zero state
+ *   frame    for each t < t_lens[b] (clamped to [0,T]; NULL: T), with C = the beam A and D = empty, rounds r = 0..S-1; an empty C
+ *            stops the rounds:
+ *     1. candidates of the member h at rank i of C: blank with value score_h + lp_h[blank], and every v != blank with
+ *        lp_h[v] >= token_min_logp with value score_h + lp_h[v]; candidate id i V + v.  With fusion the rank key is
+ *        value + total', total' = total_h for blank and total_h + arc[s_h, v] otherwise; the pruning test stays on lp.
+ *     2. the min(W, #candidates) best by (key descending, id ascending) are selected; a value or key of -inf is dropped.
+ *     3. in rank order: a selected blank closes h: it is added to D under h's node, and if that node is in D already the scores
+ *        merge, score = logaddexp(old, new) (state and total are the same by construction).  A selected token v makes the
+ *        child: its node is found among the parent node's children or created; it carries the new score, the automaton advanced
+ *        (next values outside [0,S) are clamped) and the prediction-net state one step further.  If r < S-1 the child joins the
+ *        next round's C in rank order; if r = S-1 it is added to D like a closed one: the frame advances without a blank, as
+ *        greedy search does after max_iters tokens.
+ *     4. the next A = the min(W, |D|) best of D by (score [+ total] descending, order of first insertion into D ascending).
+ *   output   A after the last valid frame, best first by score (fused: score + total + final[state]), ties in A's order, no length
+ *            normalisation; t_lens[b] = 0 gives [[blank]] with score 0.
+ * Outputs: count (B) = hypotheses of utterance b; for o < count[b]: lens[b,o], tokens[b,o,:lens] (tokens is (B, W, 1 + S T) int32;
+ * y with the leading blank, as rnnt_hip_beam_search returns y_star), scores[b,o] fp64, with fusion fusion->fused_scores[b,o], and
+ * with timing timing->frames (B, W, 1 + S T): per token the frame at which its prefix's node was created (-1 for the leading
+ * blank).  Nothing is written for o >= count[b] or past lens[b,o].
+ * Bounds: at most W new nodes per round, 1 + W S T nodes per utterance, |D| <= (S+1) W, len(y) <= 1 + S T: everything is bounded in
+ * advance, the search has no cap that can overflow and no error path at run time; the workspace query sizes all of it (the layer-0
+ * input table, the candidate keys, the prefix tree and (S+2) W state slots per utterance).
+ * step_group: 0, or a smaller number of hypotheses per step group than the LDS budget allows (rnnt_hip_beam_sync_step_group tells
+ * the number in use, at most 8); a hypothesis's state is the same bits in any group, so results do not depend on it.
+ * Every limit is checked on the host before any launch (RNNT_ERR_INVALID): W, S, V >= 2, blank, W V <= 2^24, 1 + W S T < 2^31 / 5,
+ * the threshold, pointers, strides, the fusion tables (n_states >= 1, n_states * V <= 2^27, non-NULL tables and fused_scores), the
+ * workspace (256-byte aligned, rnnt_hip_beam_sync_workspace_bytes(d) bytes; 0 for sizes outside the limits).
+ * One table launch and one search launch, a workgroup per utterance, every sum in one fixed order: the same bits on every call,
+ * and a row alone gives the bits it gives in any batch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_sync_desc {
+  int32_t T, B, V;       /* frames, utterances, vocabulary (V >= 2) */
+  int32_t Hp, O, L;      /* as rnnt_decode_desc */
+  int32_t cell, blank;
+  int32_t beam, max_symbols; /* W in [1,64], S in [1,4] */
+  int32_t step_group;    /* 0, or hypotheses per step group (smaller than the LDS would hold) */
+  float token_min_logp;
+  const float* A;        /* gelu(enc) W_e^T + bias, time-major */
+  int64_t a_st, a_sb;    /* strides of A in floats: frame, utterance ((T,B,V) contiguous: B*V, V) */
+  const int32_t* t_lens; /* (B) device, or NULL */
+  const float* emb;
+  const float* w_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* w_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* b_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* b_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* w_o;
+  const float* b_o;
+  const float* w_d;      /* fc.weight[:, O_enc:], row stride ld_d floats */
+  int64_t ld_d;
+  void* workspace;       /* rnnt_hip_beam_sync_workspace_bytes(d) bytes, 256-byte aligned */
+  size_t workspace_bytes;
+  int32_t* tokens;       /* (B, beam, 1 + max_symbols*T) */
+  int32_t* lens;         /* (B, beam) */
+  double* scores;        /* (B, beam) */
+  int32_t* count;        /* (B) */
+} rnnt_beam_sync_desc;
+size_t rnnt_hip_beam_sync_workspace_bytes(const rnnt_beam_sync_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_sync_step_group(const rnnt_beam_sync_desc* d);          /* hypotheses per step group; 0 if invalid */
+int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion /* or NULL */,
+                              const rnnt_beam_timing* timing /* or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

@@ -168,6 +168,11 @@ class RNNTransducer(_Base):
         (token_min_logp=, fusion=, return_scores=, return_frames=)."""
         return self.jointnet.recognize_ctc_beams(inputs, inputs_lengths, self.blank_token_id, beam_widths, **kw)
 
+    def recognize_beams_sync(self, inputs, inputs_lengths, **kw):
+        """JointNet.recognize_beams_sync with this model's blank: the frame-synchronous transducer beam search with batched
+        hypothesis steps (beam_widths=, max_symbols=, token_min_logp=, fusion=, return_scores=, return_frames=)."""
+        return self.jointnet.recognize_beams_sync(inputs, inputs_lengths, self.blank_token_id, **kw)
+
     def init_stream(self, batch_size: int, device=None):
         """JointNet.init_stream with this model's blank: per-stream state for recognize_greedy_stream."""
         return self.jointnet.init_stream(batch_size, self.blank_token_id, device)

@@ -27,8 +27,8 @@ import math
 import torch
 import torch.nn as nn
 
-from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, check_ctc_beam_args, check_fusion,
-                   ctc_beam_search, ctc_greedy, greedy_decode, stream_greedy)
+from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, beam_search_sync, check_beam_sync_args,
+                   check_ctc_beam_args, check_fusion, ctc_beam_search, ctc_greedy, greedy_decode, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -304,6 +304,42 @@ class JointNet(nn.Module):
                           dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
                           expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, fusion=fusion, **caps)
         if return_frames:   # an entry is (y_star, asr_score[, fused_score], frames)
+            outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
+        else:
+            outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
+        return outs[0] if len(outs) == 1 else outs
+
+    @torch.no_grad()
+    def recognize_beams_sync(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16,
+                             max_symbols: int = 1, *, token_min_logp: float = -math.inf, fusion=None,
+                             return_scores: bool = False, return_frames: bool = False):
+        """Frame-synchronous beam search (csrc/beam_sync.hip), the search other transducer toolkits decode with:
+        per frame the whole beam (beam_widths <= 64) expands at once, at most max_symbols (<= 4) tokens are emitted,
+        hypotheses with the same token sequence are merged by logaddexp (a score is probability mass, not one path), and the
+        prediction net advances once for all new hypotheses together.  Its cost per frame is bounded by beam_widths, V and
+        max_symbols alone, so it cannot run away, with or without fusion, and no cap can overflow; recognize_beams stays the
+        reference-faithful best-first search.  Returns up to beam_widths token lists y (leading blank included, as
+        recognize_beams returns y_star), best first by score, no length normalisation; the list itself for a single utterance,
+        otherwise one list per utterance.  return_scores: (y, score) pairs, fp64.  return_frames: (y, frames) pairs, (y, frames,
+        score) with return_scores: per token the encoder frame at which its prefix first appeared (-1 for the leading blank);
+        frames do not decrease along a hypothesis and at most max_symbols are equal.  token_min_logp: per frame only tokens
+        whose log-softmax reaches it extend a hypothesis (-inf: all).
+        fusion (a TokenFusion on the model's device): the search ranks by score + the automaton's total, the output by score +
+        total + final; with return_scores the entries carry score and then fused_score.
+        Any encoder direction.  eval() mode only; ValueError for training mode or bad arguments, before anything is launched."""
+        if self.training:
+            raise ValueError("recognize_beams_sync expects eval() mode (dropout inactive), like recognize_beams")
+        check_beam_sync_args(beam_widths, max_symbols, token_min_logp, "recognize_beams_sync")
+        check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams_sync")
+        if not 0 <= int(blank_token_id) < self.num_classes:
+            raise ValueError(f"recognize_beams_sync: blank {blank_token_id} outside [0,{self.num_classes})")
+        t_lens = lengths_to_device(inputs_lengths, inputs.device)
+        enc = self.encoder.forward_time_major(inputs, t_lens)
+        dec = self.decoder
+        res = beam_search_sync(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                               dec.out_proj.weight, dec.out_proj.bias, int(blank_token_id), beam_widths, max_symbols, t_lens,
+                               token_min_logp=token_min_logp, frames=return_frames, fusion=fusion)
+        if return_frames:   # an entry is (y, score[, fused_score], frames)
             outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
         else:
             outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]

@@ -1356,6 +1356,98 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
 
 
 # --------------------------------------------------------------------------------------------------
+# frame-synchronous beam search with batched hypothesis steps (include/rnnt_hip.h: rnnt_hip_beam_sync_search, csrc/beam_sync.hip)
+# --------------------------------------------------------------------------------------------------
+def check_beam_sync_args(beam_width, max_symbols, token_min_logp, what: str) -> None:
+    """ValueError unless 1 <= beam_width <= 64, 1 <= max_symbols <= 4 and token_min_logp is a number below +inf."""
+    if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 1 <= beam_width <= _lib.BEAM_SYNC_MAX_WIDTH:
+        raise ValueError(f"{what}: beam width must be an integer in [1, {_lib.BEAM_SYNC_MAX_WIDTH}], got {beam_width!r}")
+    if isinstance(max_symbols, bool) or not isinstance(max_symbols, int) or not 1 <= max_symbols <= _lib.BEAM_SYNC_MAX_SYMBOLS:
+        raise ValueError(f"{what}: max_symbols must be an integer in [1, {_lib.BEAM_SYNC_MAX_SYMBOLS}], got {max_symbols!r}")
+    if isinstance(token_min_logp, bool) or not isinstance(token_min_logp, (int, float)) or math.isnan(token_min_logp) \
+            or token_min_logp == math.inf:
+        raise ValueError(f"{what}: token_min_logp must be a number below +inf (-inf: no pruning), got {token_min_logp!r}")
+
+
+@torch.no_grad()
+def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
+                     cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam_width: int, max_symbols: int = 1,
+                     t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf, frames: bool = False,
+                     fusion=None, step_group: int = 0):
+    """Frame-synchronous transducer beam search (include/rnnt_hip.h: rnnt_hip_beam_sync_search, csrc/beam_sync.hip, DESIGN.md
+    §20) on enc_tm (T,B,Oe) encoder outputs (time-major): per frame the whole beam (beam_width <= 64) expands at once, at most
+    max_symbols (<= 4) tokens are emitted, hypotheses with the same token sequence merge by logaddexp, and the prediction net
+    advances once for all new hypotheses together.  -> per utterance up to beam_width entries (y, score), best first by score
+    (fp64: the log-probability mass the search kept for y; no length normalisation), y with the leading blank as beam_search
+    returns y_star.  t_lens (B) int32 on device = frames visited per utterance (None: all T).  token_min_logp: per frame only
+    tokens whose log-softmax reaches it extend a hypothesis (-inf: all; the blank is never pruned).
+    fusion (a fusion.TokenFusion on enc_tm's device): ranked by score + the automaton's total, the output by score + total +
+    final; every entry is then (y, score, fused_score).  frames=True appends `frames`: per token the frame at which its prefix's
+    node was created (-1 for the leading blank).  step_group: 0, or a smaller number of hypotheses per step group than the
+    kernel would take (results do not depend on it).
+    The cost per frame is bounded by beam_width, V and max_symbols: no cap can overflow.  One search launch, then one host copy
+    of the counts and lengths (and one per returned array).  Argument errors raise ValueError before anything runs."""
+    check_beam_sync_args(beam_width, max_symbols, token_min_logp, "beam_search_sync")
+    if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
+        raise ValueError(f"beam_search_sync: step_group must be an integer >= 0, got {step_group!r}")
+    if enc_tm.dim() != 3 or fc_w.dim() != 2:
+        raise ValueError(f"beam_search_sync: encoder outputs must be (T,B,Oe) and fc (V,Oe+Od), got {tuple(enc_tm.shape)} / "
+                         f"{tuple(fc_w.shape)}")
+    T, B, Oe = enc_tm.shape
+    V, Ocat = fc_w.shape
+    if V < 2:
+        raise ValueError(f"beam_search_sync: V = {V} < 2 (a blank and at least one token)")
+    if beam_width * V > 1 << 24:
+        raise ValueError(f"beam_search_sync: beam_width * V = {beam_width * V} exceeds 2^24 candidates per round")
+    if T < 1 or B < 1:
+        raise ValueError(f"beam_search_sync: T and B must be positive, got T={T} B={B}")
+    d = _lib.BeamSyncDesc()
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, int(blank), "beam_search_sync")
+    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
+        raise ValueError(f"beam_search_sync: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
+                         f"encoder width {Oe}")
+    check_fusion(fusion, V, enc_tm.device, "beam_search_sync")
+    if t_lens is not None and (t_lens.dtype != torch.int32 or tuple(t_lens.shape) != (B,)):
+        raise ValueError(f"beam_search_sync: t_lens must be (B,) = ({B},) int32, got {tuple(t_lens.shape)} {t_lens.dtype}")
+    _need_gpu(enc_tm, fc_w, emb_w)
+    enc_tm = _f32c(enc_tm, "encoder outputs")
+    dev, W, S, L = enc_tm.device, beam_width, max_symbols, _lib.lib()
+    A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
+    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    max_len = 1 + S * T
+    tokens = torch.empty(B, W, max_len, device=dev, dtype=torch.int32)
+    small = torch.empty(B + B * W, device=dev, dtype=torch.int32)   # counts | lens: one transfer
+    scores = torch.empty(B, W, device=dev, dtype=torch.float64)
+    d.T, d.B, d.beam, d.max_symbols, d.step_group, d.token_min_logp = T, B, W, S, step_group, float(token_min_logp)
+    d.A, d.a_st, d.a_sb = _addr(A), B * V, V
+    d.t_lens = _addr(t_lens.contiguous()) if t_lens is not None else None
+    nws = L.rnnt_hip_beam_sync_workspace_bytes(C.byref(d))
+    if nws == 0:
+        raise ValueError("beam_search_sync: " + L.rnnt_hip_last_error().decode("utf-8", "replace"))
+    ws = torch.empty(nws + 256, device=dev, dtype=torch.uint8)
+    d.workspace, d.workspace_bytes = (_addr(ws) + 255) // 256 * 256, nws
+    d.tokens, d.lens, d.scores, d.count = _addr(tokens), _addr(small, B), _addr(scores), _addr(small)
+    fr = torch.empty(B, W, max_len, device=dev, dtype=torch.int32) if frames else None
+    tm = _lib.BeamTiming(_addr(fr), None) if frames else None
+    fused = torch.empty(B, W, device=dev, dtype=torch.float64) if fusion is not None else None
+    fs = fusion_struct(fusion, fused) if fusion is not None else None
+    check(L.rnnt_hip_beam_sync_search(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None,
+                                      _stream()), "rnnt_hip_beam_sync_search")
+    host = small.cpu()   # the only host sync of the search
+    count, lens_h = host[:B].tolist(), host[B:].reshape(B, W).tolist()
+    longest = max([1] + [lens_h[b][r] for b in range(B) for r in range(count[b])])
+    tok_h, scores_h = tokens[:, :, :longest].cpu(), scores.cpu().tolist()
+    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if fusion is not None:
+        fused_h = fused.cpu().tolist()
+        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
+    if frames:
+        fr_h = fr[:, :, :longest].cpu()
+        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # streaming greedy recognition (include/rnnt_hip.h: rnnt_hip_stream_rnn_chunk / rnnt_hip_stream_greedy[_reset]); the state
 # tensors belong to streaming.GreedyStreamState
 # --------------------------------------------------------------------------------------------------
