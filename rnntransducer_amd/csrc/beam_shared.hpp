@@ -12,6 +12,7 @@
 // FUSED = false every fused statement is compiled out and the kernel is statement for statement the unfused one.
 #pragma once
 #include "decode_shared.hpp"
+#include "search_shared.hpp"   // check_fusion_struct: one check of the fusion struct for every fused search
 
 namespace rnnt {
 namespace {
@@ -72,9 +73,8 @@ struct BeamLayout {
 static BeamLayout beam_layout(int V, int Hp, int L, int cell, int max_candidates, int max_pops, int max_states, int max_nodes,
                               bool stream, bool fused = false) {
   BeamLayout l;
-  const int NG = cell == RNNT_CELL_LSTM ? 4 : (cell == RNNT_CELL_GRU ? 3 : 1);
-  l.table_bytes = align256((size_t)V * NG * Hp * sizeof(float));
-  l.slot_floats = (int)((L * Hp * (cell == RNNT_CELL_LSTM ? 2 : 1) + V + 3) & ~3);
+  l.table_bytes = align256((size_t)V * cell_gates(cell) * Hp * sizeof(float));
+  l.slot_floats = slot_floats(L, Hp, cell, V);
   l.off_a = stream ? (size_t)BS_HEADER_BYTES : 0;
   l.off_b = l.off_a + align256((size_t)max_candidates * sizeof(Hyp));
   l.off_slots = l.off_b + align256((size_t)max_pops * sizeof(Hyp));
@@ -561,11 +561,8 @@ static inline void beam_set_layout(BeamK& k, void* workspace, const BeamLayout& 
 // the fused entries' extra struct, checked on the host before any device work; copies it into the kernel's descriptor
 static int beam_fill_fusion(const rnnt_beam_fusion* f, int V, BeamK& k, const char* who) {
   RNNT_CHECK_ARG(f != nullptr, "%s: null fusion struct", who);
-  RNNT_CHECK_ARG(f->n_states >= 1, "%s: fusion needs n_states >= 1", who);
-  RNNT_CHECK_ARG((int64_t)f->n_states * V <= ((int64_t)1 << 27), "%s: fusion tables hold n_states * V <= 2^27 entries", who);
-  RNNT_CHECK_ARG(f->next && f->arc && f->final, "%s: null fusion table (next, arc, final) with n_states %d", who,
-                 f->n_states);
-  RNNT_CHECK_ARG(f->fused_scores, "%s: null fused_scores output", who);
+  const int rc = check_fusion_struct(f, V, who);
+  if (rc != RNNT_OK) return rc;
   k.fnext = f->next; k.farc = f->arc; k.ffinal = f->final; k.n_states = f->n_states; k.fused_scores = f->fused_scores;
   return RNNT_OK;
 }

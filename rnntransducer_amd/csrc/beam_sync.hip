@@ -27,9 +27,8 @@
 //            (batched step, below)
 //   softmax  a wavefront per member row, lanes along v; the same wavefront then fills the row's candidate keys as
 //            order-preserving 64-bit integers (0 = no candidate)
-//   select   the radix select of ctc_beam.hip (key, then lowest id; integer LDS histograms; at most 8 + 3 passes), copied
-//   build    ranked by counting, one writer per element; new nodes are numbered in rank order by one thread; a parent's new
-//            children are linked by its first new child
+//   select   the W best by (key descending, lowest id): select_top of search_shared.hpp, the function ctc_beam.hip calls
+//   build    ranked by counting, one writer per element; nodes are found or created in the prefix tree of search_shared.hpp
 // A child's step is deferred to the round that reads its state: the children of a frame's last round get theirs at the next
 // frame's start, so only if they survive the frame's top-W of D, and nothing steps after the last frame.
 //
@@ -44,7 +43,7 @@
 // children, W for the next beam's pending steps; the free list is rebuilt at every frame's start from the slots the beam holds.
 // All score sums are fp64 with logaddexp_d in the fixed order above: bitwise reproducible.
 #include "beam_shared.hpp"
-#include "lattice_shared.hpp"
+#include "search_shared.hpp"
 
 namespace rnnt {
 namespace {
@@ -56,16 +55,6 @@ constexpr int BS_SLOTMAX = (BS_SMAX + 2) * BS_WMAX;
 constexpr int BS_IDBITS = 24;   // candidate ids i V + v fit 24 bits: three 8-bit digits break exact ties
 constexpr int BS_GT = 8;        // hypotheses per step group at most: 8 RU x 8 accumulators per lane
 constexpr int BS_NW = DEC_THREADS / 64;
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int bs_clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
-// order-preserving map of a double that is > -inf and not NaN onto [2^52, 2^64): 0 stays free for "no candidate"
-__device__ __forceinline__ u64 bs_sortable(double x) {
-  const u64 u = __builtin_bit_cast(u64, x + 0.0);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 struct BsList {   // C of one round, in rank order
   double score[BS_WMAX], tot[BS_WMAX];
@@ -80,9 +69,8 @@ struct BsShared {
   // D, in order of first insertion
   double dscore[BS_DMAX], dtot[BS_DMAX];
   int dnode[BS_DMAX], dst[BS_DMAX], dslot[BS_DMAX], dtok[BS_DMAX];
-  // the selected candidates, then by rank
-  u64 sel_key[BS_WMAX];
-  int sel_id[BS_WMAX];
+  SelectState<BS_WMAX> sel;
+  // the selected candidates by rank
   double rval[BS_WMAX], rtot[BS_WMAX];
   int rnode[BS_WMAX], rpar[BS_WMAX], rst[BS_WMAX], rslot[BS_WMAX], rtok[BS_WMAX];
   int pending[BS_WMAX];   // its node is still to be created
@@ -94,10 +82,7 @@ struct BsShared {
   int gidx[BS_WMAX];      // step: the members that advance, in member order
   int gnew[BS_WMAX];      //       and the slots they get
   int wcount[BS_NW];
-  int hist[256];
-  int nvalid, nsel, need, bin, cnt, nnodes, nD, nnext, npend, fpos;
-  u64 kprefix;
-  unsigned iprefix;
+  int nnodes, nD, nnext, npend, fpos;
 };
 
 struct BsK : PredNet {
@@ -124,43 +109,6 @@ struct BsK : PredNet {
   int n_states;
   double* fused;
 };
-
-struct BsNodes {
-  int *parent, *token, *frame, *child, *sib;
-};
-
-// the bin d with sum_{d' > d} hist[d'] < need <= sum_{d' >= d} hist[d'] (wave 0; lane l owns bins 255-4l .. 252-4l)
-__device__ __forceinline__ void bs_pick_bin(BsShared& sh, int lane) {
-  int h[4], s = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { h[i] = sh.hist[255 - 4 * lane - i]; s += h[i]; }
-  int inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o);
-    if (lane >= o) inc += v;
-  }
-  const int need = sh.need;
-  const unsigned long long hit = __ballot(inc >= need);
-  if (hit == 0ull) {   // (cannot happen while need <= the number of candidates; keep the state sane)
-    if (lane == 0) { sh.bin = 0; sh.cnt = need; }
-    return;
-  }
-  const int first = __ffsll((long long)hit) - 1;
-  if (lane == first) {
-    int above = inc - s;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (above + h[i] >= need) {
-        sh.bin = 255 - 4 * lane - i;
-        sh.cnt = h[i];
-        sh.need = need - above;
-        break;
-      }
-      above += h[i];
-    }
-  }
-}
 
 // y_j[r] = dot(W[r, :cols], x_j) (+ bias[r]) for r in [0, rows) and the g <= BS_GT hypotheses j of a group: matvec
 // (decode_shared.hpp) with the RU weight rows of a wave loaded once and used for every j.  x_j = x + j * xs (LDS, 16-byte
@@ -227,8 +175,7 @@ struct BsStepLds {
   int LH, NG;
 };
 inline size_t bs_step_floats(int L, int Hp, int O, int cell) {
-  const int NG = cell == RNNT_CELL_LSTM ? 4 : (cell == RNNT_CELL_GRU ? 3 : 1);
-  return (size_t)L * Hp * (cell == RNNT_CELL_LSTM ? 2 : 1) + (size_t)NG * Hp * (L > 1 ? 2 : 1) + O;
+  return (size_t)L * Hp * (cell == RNNT_CELL_LSTM ? 2 : 1) + (size_t)cell_gates(cell) * Hp * (L > 1 ? 2 : 1) + O;
 }
 
 // The members of `ls` (n of them) whose step is pending advance together: each gets a free slot, reads its parent's state and
@@ -323,16 +270,11 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int V = p.V, W = p.W, S = p.S, SF = p.SF, NS = p.NS, blank = p.blank;
-  const int Tb = p.t_lens ? bs_clampi(p.t_lens[b], 0, p.T) : p.T;
+  const int Tb = p.t_lens ? clampi(p.t_lens[b], 0, p.T) : p.T;
   const long maxn = p.maxn;
   u64* ck = p.keys + (long)b * W * V;
   float* slots = p.slots + (long)b * NS * SF;
-  BsNodes nd;
-  nd.parent = p.nodes + (long)b * 5 * maxn;
-  nd.token = nd.parent + maxn;
-  nd.frame = nd.token + maxn;
-  nd.child = nd.frame + maxn;
-  nd.sib = nd.child + maxn;
+  const PrefixTree nd = tree_view(p.nodes + (long)b * 5 * maxn, maxn);
   BsStepLds sl;
   sl.NG = cell_gates(p.cell);
   sl.LH = p.L * p.Hp;
@@ -356,7 +298,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
     BsList& c = sh.c[0];
     c.score[0] = 0.0; c.tot[0] = 0.0; c.node[0] = 0; c.st[0] = 0;
     c.slot[0] = -1; c.tok[0] = blank;   // one step on blank from the zero state, as every search here primes an utterance
-    nd.parent[0] = -1; nd.token[0] = blank; nd.frame[0] = -1; nd.child[0] = -1; nd.sib[0] = -1;
+    tree_root(nd, blank);   // the leading blank
     sh.nnodes = 1; sh.fpos = 0; sh.nD = 0; sh.nnext = 0;
   }
   __threadfence_block();
@@ -377,7 +319,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
       if (r == 0) {   // the free list of this frame: every slot the beam does not hold, in slot order
         for (int i = tid; i < NS; i += DEC_THREADS) sh.used[i] = 0;
         __syncthreads();
-        if (tid < n) sh.used[bs_clampi(c.slot[tid], 0, NS - 1)] = 1;   // (slots of members are distinct)
+        if (tid < n) sh.used[clampi(c.slot[tid], 0, NS - 1)] = 1;   // (slots of members are distinct)
         __syncthreads();
         const bool fr = tid < NS && !sh.used[tid < NS ? tid : 0];
         const unsigned long long bal = __ballot(fr);
@@ -389,10 +331,10 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
         if (tid == 0) sh.fpos = 0;
         __syncthreads();
       }
-      if (tid == 0) { sh.nvalid = 0; sh.nsel = 0; sh.kprefix = 0ull; sh.iprefix = 0u; sh.nnext = 0; }
+      if (tid == 0) { select_reset(sh.sel); sh.nnext = 0; }
       // ---- log-softmax of every member row and its candidate keys: a wavefront per row, lanes along v
       for (int i = wave; i < n; i += BS_NW) {
-        const float* Cv = slots + (long)bs_clampi(c.slot[i], 0, NS - 1) * SF + (SF - V);   // (clamp: always in range)
+        const float* Cv = slots + (long)clampi(c.slot[i], 0, NS - 1) * SF + (SF - V);   // (clamp: always in range)
         float m = -__builtin_huge_valf();
         for (int v = lane; v < V; v += 64) m = fmaxf(m, At[v] + Cv[v]);
         m = wave_max(m);
@@ -410,7 +352,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
             const double val = sc + (double)lp;
             double k = val;
             if (FUSED) k = val + (v == blank ? tt : tt + (double)p.farc[(long)st * V + v]);
-            if (val > NEG_INF && k > NEG_INF) key = bs_sortable(k);   // (NaN compares false: dropped)
+            if (val > NEG_INF && k > NEG_INF) key = sortable_key(k);   // (NaN compares false: dropped)
           }
           ck[(long)i * V + v] = key;
         }
@@ -418,89 +360,17 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
       __threadfence_block();
       __syncthreads();
 
-      // ---- select: radix select of the min(W, candidates) best in the order (key descending, id ascending)
-      const int N = n * V;
-      int passes = 0;
-      for (int pass = 0; pass < 8 + BS_IDBITS / 8; ++pass) {   // (uniform)
-        if (tid < 256) sh.hist[tid] = 0;
-        __syncthreads();
-        const u64 kprefix = sh.kprefix;
-        const unsigned iprefix = sh.iprefix;
-        int mine = 0;
-        for (int idx = tid; idx < N; idx += DEC_THREADS) {
-          const u64 key = ck[idx];
-          if (key == 0ull) continue;
-          ++mine;
-          int digit;
-          if (pass < 8) {
-            if (pass > 0 && (key >> (64 - 8 * pass)) != kprefix) continue;
-            digit = (int)((key >> (56 - 8 * pass)) & 255ull);
-          } else {   // exact ties of the key: the LOWEST id first, so the digits of the complemented id
-            const int q = pass - 8;
-            const unsigned nid = ~(unsigned)idx & ((1u << BS_IDBITS) - 1u);
-            if (key != kprefix) continue;
-            if (q > 0 && (nid >> (BS_IDBITS - 8 * q)) != iprefix) continue;
-            digit = (int)((nid >> (BS_IDBITS - 8 - 8 * q)) & 255u);
-          }
-          atomicAdd(&sh.hist[digit], 1);
-        }
-        if (pass == 0) {
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-          if (lane == 0 && mine) atomicAdd(&sh.nvalid, mine);
-        }
-        __syncthreads();
-        if (pass == 0 && tid == 0) sh.need = min(W, sh.nvalid);
-        __syncthreads();
-        if (sh.need == 0) break;   // (uniform) no candidate at all: the round selects nothing
-        if (wave == 0) bs_pick_bin(sh, lane);
-        __syncthreads();
-        const bool done = sh.cnt == sh.need;   // the whole bin is taken
-        passes = pass + 1;
-        __syncthreads();
-        if (tid == 0) {
-          if (pass < 8) sh.kprefix = (kprefix << 8) | (u64)sh.bin;
-          else sh.iprefix = (iprefix << 8) | (unsigned)sh.bin;
-        }
-        if (done) break;   // (uniform)
-      }
-      __syncthreads();
-      // ---- gather the selected candidates
-      if (min(W, sh.nvalid) > 0) {
-        const u64 kprefix = sh.kprefix;
-        const unsigned iprefix = sh.iprefix;
-        for (int idx = tid; idx < N; idx += DEC_THREADS) {
-          const u64 key = ck[idx];
-          if (key == 0ull) continue;
-          bool take;
-          if (passes <= 8) {
-            take = (key >> (64 - 8 * passes)) >= kprefix;
-          } else {
-            const unsigned nid = ~(unsigned)idx & ((1u << BS_IDBITS) - 1u);
-            take = key > kprefix || (key == kprefix && (nid >> (BS_IDBITS - 8 * (passes - 8))) >= iprefix);
-          }
-          if (take) {
-            const int slot = atomicAdd(&sh.nsel, 1);
-            if (slot < BS_WMAX) { sh.sel_key[slot] = key; sh.sel_id[slot] = idx; }
-          }
-        }
-      }
-      __syncthreads();
-      const int m = min(min(W, sh.nvalid), sh.nsel);   // (the select takes exactly min(W, candidates))
+      // ---- select the min(W, candidates) best in the order (key descending, id ascending)
+      const int m = select_top<BS_WMAX, BS_IDBITS, DEC_THREADS>(sh.sel, ck, n * V, W);
       const int nD0 = sh.nD;
 
       // ---- build, by rank: the closed hypothesis or the child, its node, and where it goes
       int rank = -1;
       if (tid < m) {
-        const u64 key = sh.sel_key[tid];
-        const int id = sh.sel_id[tid];
-        rank = 0;
-        for (int i = 0; i < m; ++i) {
-          const u64 ok = sh.sel_key[i];
-          rank += (ok > key || (ok == key && sh.sel_id[i] < id)) ? 1 : 0;
-        }
+        const int id = sh.sel.sel_id[tid];
+        rank = select_rank(sh.sel, tid, m);
         const int i = id / V, v = id - i * V;
-        const float* Cv = slots + (long)bs_clampi(c.slot[i], 0, NS - 1) * SF + (SF - V);   // (clamp: always in range)
+        const float* Cv = slots + (long)clampi(c.slot[i], 0, NS - 1) * SF + (SF - V);   // (clamp: always in range)
         const float lp = ((At[v] + Cv[v]) - c.mx[i]) - c.ls[i];   // the fill's expression: the same bits
         sh.rval[rank] = c.score[i] + (double)lp;
         int node, pend = 0;
@@ -515,7 +385,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
           if (FUSED) {
             const long o = (long)c.st[i] * V + v;
             sh.rtot[rank] = c.tot[i] + (double)p.farc[o];
-            sh.rst[rank] = bs_clampi(p.fnext[o], 0, p.n_states - 1);
+            sh.rst[rank] = clampi(p.fnext[o], 0, p.n_states - 1);
           } else {
             sh.rtot[rank] = 0.0;
             sh.rst[rank] = 0;
@@ -523,14 +393,8 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
           const int par = c.node[i];
           sh.rtok[rank] = v;
           sh.rpar[rank] = par;
-          // the prefix's node, if it was created before (a node has at most V - 1 children)
-          int ch = nd.child[par];
-          for (int q = 0; q < V && ch >= 0; ++q) {
-            if (nd.token[ch] == v) break;
-            ch = nd.sib[ch];
-          }
-          node = ch;
-          pend = ch < 0 ? 1 : 0;
+          node = tree_find_child(nd, par, v, V);   // the prefix's node, if it was created before
+          pend = node < 0 ? 1 : 0;
           sh.tod[rank] = last_round ? 1 : 0;
         }
         sh.rslot[rank] = c.slot[i];   // a closed hypothesis keeps its state; a child's step starts from its parent's
@@ -552,32 +416,18 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
       }
       __syncthreads();
       if (tid == 0) {   // in rank order: new nodes are numbered, D grows, the next C fills
-        int nn = sh.nnodes, nDn = nD0, nxt = 0;
+        tree_number(sh.pending, sh.rnode, m, sh.nnodes);
+        int nDn = nD0, nxt = 0;
         for (int i = 0; i < m; ++i) {
-          if (sh.pending[i]) sh.rnode[i] = nn++;
           if (sh.tod[i]) sh.target[i] = sh.dpos[i] >= 0 ? sh.dpos[i] : (sh.dup[i] >= 0 ? sh.target[sh.dup[i]] : nDn++);
           else sh.target[i] = nxt++;
         }
-        sh.nnodes = nn; sh.nD = nDn; sh.nnext = nxt;
+        sh.nD = nDn; sh.nnext = nxt;
       }
       __syncthreads();
       if (rank >= 0) {
-        const int me = sh.rnode[rank], par = sh.rpar[rank], tg = sh.target[rank];
-        if (sh.pending[rank] && me < maxn) {   // (at most W new nodes per round: always true)
-          nd.parent[me] = par; nd.token[me] = sh.rtok[rank]; nd.frame[me] = t; nd.child[me] = -1;
-          bool leader = true;
-          for (int i = 0; i < rank; ++i) leader = leader && !(sh.pending[i] && sh.rpar[i] == par);
-          if (leader) {   // the first new child of this parent links all of them, in rank order, in front of the list
-            int head = nd.child[par];
-            for (int i = rank; i < m; ++i) {
-              if (sh.pending[i] && sh.rpar[i] == par) {
-                nd.sib[sh.rnode[i]] = head;
-                head = sh.rnode[i];
-              }
-            }
-            nd.child[par] = head;
-          }
-        }
+        const int me = sh.rnode[rank], tg = sh.target[rank];
+        if (sh.pending[rank]) tree_link(nd, maxn, sh.pending, sh.rpar, sh.rnode, rank, m, sh.rtok[rank], t);
         if (!sh.tod[rank]) {   // the child joins the next round's C; its step runs at that round's start
           nx.score[tg] = sh.rval[rank]; nx.tot[tg] = sh.rtot[rank]; nx.node[tg] = me; nx.st[tg] = sh.rst[rank];
           nx.slot[tg] = sh.rslot[rank]; nx.tok[tg] = sh.rtok[rank];
@@ -623,20 +473,9 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
   __syncthreads();
   if (tid < nA) {
     const double key = sh.rval[tid];
-    int o = 0;
-    for (int i = 0; i < nA; ++i) o += (sh.rval[i] > key || (sh.rval[i] == key && i < tid)) ? 1 : 0;
-    o = min(o, W - 1);
-    const long base = (long)b * W + o;
-    const int ML = p.max_len;
-    int len = 1;
-    for (int x = a.node[tid]; x > 0 && len < ML; x = nd.parent[x]) ++len;
-    int x = a.node[tid];
-    for (int i = len - 1; i >= 0; --i) {   // the root carries the leading blank and frame -1
-      p.tokens[base * ML + i] = nd.token[x];
-      if (p.frames) p.frames[base * ML + i] = nd.frame[x];
-      x = i > 0 ? nd.parent[x] : x;
-    }
-    p.lens[base] = len;
+    const long base = (long)b * W + output_slot(sh.rval, tid, nA, W);
+    const int ML = p.max_len;   // the root carries the leading blank and frame -1
+    p.lens[base] = tree_backtrace(nd, a.node[tid], true, ML, p.tokens + base * ML, p.frames ? p.frames + base * ML : nullptr);
     p.scores[base] = a.score[tid];
     if (FUSED) p.fused[base] = key;
   }
@@ -657,16 +496,14 @@ BsWs carve_bs(void* ws, const rnnt_beam_sync_desc* d) {
   BsWs w;
   char* p = reinterpret_cast<char*>(ws);
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  const int NG = d->cell == RNNT_CELL_LSTM ? 4 : (d->cell == RNNT_CELL_GRU ? 3 : 1);
   const int64_t B = d->B, W = d->beam, S = d->max_symbols, V = d->V, T = d->T;
-  w.SF = (int)((d->L * d->Hp * (d->cell == RNNT_CELL_LSTM ? 2 : 1) + d->V + 3) & ~3);
+  w.SF = slot_floats(d->L, d->Hp, d->cell, d->V);
   w.NS = (int)((S + 2) * W);
   w.maxn = 1 + W * S * T;
-  w.table = reinterpret_cast<float*>(take((size_t)V * NG * d->Hp * 4));
-  w.keys = reinterpret_cast<u64*>(take((size_t)B * W * V * 8));
-  w.nodes = reinterpret_cast<int*>(take((size_t)B * 5 * w.maxn * 4));
-  w.slots = reinterpret_cast<float*>(take((size_t)B * w.NS * w.SF * 4));
+  w.table = reinterpret_cast<float*>(ws_take(p, off, (size_t)V * cell_gates(d->cell) * d->Hp * 4));
+  w.keys = reinterpret_cast<u64*>(ws_take(p, off, (size_t)B * W * V * 8));
+  w.nodes = reinterpret_cast<int*>(ws_take(p, off, (size_t)B * 5 * w.maxn * 4));
+  w.slots = reinterpret_cast<float*>(ws_take(p, off, (size_t)B * w.NS * w.SF * 4));
   w.total = off;
   return w;
 }
@@ -693,11 +530,10 @@ int bs_check_dims(const rnnt_beam_sync_desc* d, const char* who) {
                  (long long)d->beam * d->V, BS_IDBITS);
   RNNT_CHECK_ARG(1 + (int64_t)d->beam * d->max_symbols * d->T < (1ll << 31) / 5, "%s: 1 + W S T = %lld nodes exceed the node index",
                  who, 1 + (long long)d->beam * d->max_symbols * d->T);
-  RNNT_CHECK_ARG(!(d->token_min_logp != d->token_min_logp) && d->token_min_logp < __builtin_huge_valf(),
-                 "%s: token_min_logp must be a number below +inf (-inf: no pruning)", who);
-  RNNT_CHECK_ARG(d->step_group >= 0, "%s: step_group %d < 0 (0: as many as the LDS holds)", who, d->step_group);
-  const int rc = prednet_check_dims<true>(d, who, RNNT_ERR_INVALID);
+  int rc = check_token_min_logp(d->token_min_logp, who);
   if (rc != RNNT_OK) return rc;
+  RNNT_CHECK_ARG(d->step_group >= 0, "%s: step_group %d < 0 (0: as many as the LDS holds)", who, d->step_group);
+  if ((rc = prednet_check_dims<true>(d, who, RNNT_ERR_INVALID)) != RNNT_OK) return rc;
   RNNT_CHECK_ARG(bs_group(d) >= 1, "%s: one hypothesis's step needs %zu B of LDS beside %zu B of search state (> 160 KiB)", who,
                  bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float), sizeof(BsShared));
   return RNNT_OK;
@@ -729,13 +565,7 @@ extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnn
   RNNT_CHECK_ARG(timing == nullptr || timing->frames, "%s: timing given without its output (frames)", who);
   BsK k;
   if ((rc = fill_prednet<true>(d, k, who)) != RNNT_OK) return rc;
-  if (fusion) {
-    RNNT_CHECK_ARG(fusion->next && fusion->arc && fusion->final, "%s: null fusion table (next, arc, final)", who);
-    RNNT_CHECK_ARG(fusion->n_states >= 1 && (int64_t)fusion->n_states * d->V <= (1ll << 27),
-                   "%s: fusion n_states = %d with V = %d outside [1, 2^27 / V]: the tables must be (S, V) over the joint's V", who,
-                   fusion->n_states, d->V);
-    RNNT_CHECK_ARG(fusion->fused_scores, "%s: null fused_scores with a fusion automaton", who);
-  }
+  if (fusion && (rc = check_fusion_struct(fusion, d->V, who)) != RNNT_OK) return rc;
   const BsWs w = carve_bs(d->workspace, d);
   RNNT_CHECK_ARG(d->workspace && d->workspace_bytes >= w.total, "%s: workspace too small (%zu < %zu)", who, d->workspace_bytes, w.total);
   RNNT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);

@@ -16,16 +16,13 @@
 // One workgroup of 1024 threads per utterance, no communication between workgroups.  Per frame:
 //   fill     every candidate's key as an order-preserving 64-bit integer into the utterance's scratch (0 = no candidate); lanes along
 //            the flat candidate index, so along v within a member's row
-//   select   radix select of the W-th largest (key, then lowest id) over 8-bit digits: integer LDS histograms (the counts do not
-//            depend on the order of the atomic adds), at most 8 passes over the key and 3 over the id, stops at the first pass whose
-//            bin holds exactly what is still missing
-//   gather   the selected candidates into LDS, ranked there by counting (the total order is strict, so ranks are a permutation)
-//   build    the next beam in rank order: survivors copy, extensions find or create their node; new nodes are numbered in rank
-//            order by one thread and linked into their parent's child list by the first new child of that parent
+//   select   the W best by (key descending, lowest id), gathered into LDS and ranked there: select_top, select_rank
+//            (search_shared.hpp)
+//   build    the next beam in rank order: survivors copy, extensions find or create their node (the prefix tree of
+//            search_shared.hpp)
 // Every sum has one fixed order (logaddexp_d is symmetric in its arguments) and every output one writer: bitwise reproducible, and
 // a row's result does not depend on the batch around it.  Loops are bounded by T, W, V or the 11 digits of the select.
-#include "common.hpp"
-#include "lattice_shared.hpp"
+#include "search_shared.hpp"
 
 namespace rnnt {
 namespace {
@@ -33,16 +30,6 @@ namespace {
 constexpr int CB_THREADS = 1024;
 constexpr int CB_WMAX = 128;
 constexpr int CB_IDBITS = 24;   // candidate ids r (V+1) + j fit 24 bits: three 8-bit digits break exact ties
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ int cb_clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
-// order-preserving map of a double that is > -inf and not NaN onto [2^52, 2^64): 0 stays free for "no candidate"
-__device__ __forceinline__ u64 cb_sortable(double x) {
-  const u64 u = __builtin_bit_cast(u64, x + 0.0);   // (-0.0 + 0.0 = +0.0: one pattern per value)
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 struct CbBeam {
   double pb[CB_WMAX], pnb[CB_WMAX], tot[CB_WMAX];
@@ -53,50 +40,10 @@ struct CbShared {
   CbBeam beam[2];
   double p[CB_WMAX], cpb[CB_WMAX], cpnb[CB_WMAX];   // p of the members; pb' / pnb' of their survivors
   int src[CB_WMAX];                                 // rank of the member whose extension by tok[r] is member r (-1: none)
-  u64 sel_key[CB_WMAX];
-  int sel_id[CB_WMAX], pending[CB_WMAX];
-  int hist[256];
-  int nvalid, nsel, need, bin, cnt, nnodes;
-  u64 kprefix;        // the digits of the threshold key chosen so far (all 64 bits after pass 7)
-  unsigned iprefix;   // then the digits of the threshold's complemented id
+  SelectState<CB_WMAX> sel;
+  int pending[CB_WMAX];                             // by rank: its node is still to be created
+  int nnodes;
 };
-
-struct CbNodes {
-  int *parent, *token, *frame, *child, *sib;
-};
-
-// the bin d with sum_{d' > d} hist[d'] < need <= sum_{d' >= d} hist[d'] (wave 0; lane l owns bins 255-4l .. 252-4l)
-__device__ __forceinline__ void cb_pick_bin(CbShared& sh, int lane) {
-  int h[4], s = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { h[i] = sh.hist[255 - 4 * lane - i]; s += h[i]; }
-  int inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o);
-    if (lane >= o) inc += v;
-  }
-  const int need = sh.need;
-  const unsigned long long hit = __ballot(inc >= need);
-  if (hit == 0ull) {   // (fewer matches than needed: cannot happen while need <= the number of candidates; keep the state sane)
-    if (lane == 0) { sh.bin = 0; sh.cnt = need; }
-    return;
-  }
-  const int first = __ffsll((long long)hit) - 1;
-  if (lane == first) {
-    int above = inc - s;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (above + h[i] >= need) {
-        sh.bin = 255 - 4 * lane - i;
-        sh.cnt = h[i];
-        sh.need = need - above;
-        break;
-      }
-      above += h[i];
-    }
-  }
-}
 
 template <bool FUSED>
 __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __restrict__ Z, long z_sb, long z_st,
@@ -110,18 +57,13 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
                                                               int* __restrict__ counts) {
   __shared__ CbShared sh;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Tb = cb_clampi(t_lens[b], 0, T);
+  const int Tb = clampi(t_lens[b], 0, T);
   const int V1 = V + 1;
   const long maxn = 1 + (long)W * T;
   const float* Zb = Z + (long)b * z_sb;
   float* lse = lse_ws + (long)b * T;
   u64* ck = key_ws + (long)b * W * V1;
-  CbNodes nd;
-  nd.parent = node_ws + (long)b * 5 * maxn;
-  nd.token = nd.parent + maxn;
-  nd.frame = nd.token + maxn;
-  nd.child = nd.frame + maxn;
-  nd.sib = nd.child + maxn;
+  const PrefixTree nd = tree_view(node_ws + (long)b * 5 * maxn, maxn);
 
   // row log-sum-exp of every valid frame, the arithmetic of ctc_terms_kernel: a wavefront per frame, lanes along v
   for (int t = wave; t < Tb; t += CB_THREADS / 64) {
@@ -145,7 +87,7 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
     CbBeam& c = sh.beam[0];
     c.pb[0] = 0.0; c.pnb[0] = NEG_INF; c.tot[0] = 0.0;
     c.node[0] = 0; c.st[0] = 0; c.tok[0] = -1; c.par[0] = -1;
-    nd.parent[0] = -1; nd.token[0] = -1; nd.frame[0] = -1; nd.child[0] = -1; nd.sib[0] = -1;
+    tree_root(nd, -1);   // the empty prefix
     sh.nnodes = 1;
   }
   __threadfence_block();
@@ -167,7 +109,7 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
           if (c.node[r] == par) s = r;   // (nodes of members are distinct: at most one hit)
       sh.src[tid] = s;
     }
-    if (tid == 0) { sh.nvalid = 0; sh.nsel = 0; sh.kprefix = 0ull; sh.iprefix = 0u; }
+    if (tid == 0) select_reset(sh.sel);
     __syncthreads();
     // ---- fill: keys of all n (V+1) candidates
     const int N = n * V1;
@@ -189,14 +131,14 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
         sh.cpb[r] = pbn;
         sh.cpnb[r] = pnbn;
         const double k = logaddexp_d(pbn, pnbn) + (FUSED ? c.tot[r] : 0.0);
-        if (k > NEG_INF) key = cb_sortable(k);
+        if (k > NEG_INF) key = sortable_key(k);
       } else {
         const int k = j - 1;
         const float lk = z[k] - l;
         if (k != blank && lk >= min_logp) {
           double x = (k == c.tok[r] ? c.pb[r] : sh.p[r]) + (double)lk;
           if (FUSED) x += c.tot[r] + (double)farc[(long)c.st[r] * V + k];
-          if (x > NEG_INF) key = cb_sortable(x);
+          if (x > NEG_INF) key = sortable_key(x);
         }
       }
       ck[idx] = key;
@@ -208,84 +150,13 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
     __threadfence_block();
     __syncthreads();
 
-    // ---- select: radix select of the min(W, candidates) best in the order (key descending, id ascending)
-    int passes = 0;
-    for (int pass = 0; pass < 8 + CB_IDBITS / 8; ++pass) {   // (uniform)
-      if (tid < 256) sh.hist[tid] = 0;
-      __syncthreads();
-      const u64 kprefix = sh.kprefix;
-      const unsigned iprefix = sh.iprefix;
-      int mine = 0;
-      for (int idx = tid; idx < N; idx += CB_THREADS) {
-        const u64 key = ck[idx];
-        if (key == 0ull) continue;
-        ++mine;
-        int digit;
-        if (pass < 8) {
-          if (pass > 0 && (key >> (64 - 8 * pass)) != kprefix) continue;
-          digit = (int)((key >> (56 - 8 * pass)) & 255ull);
-        } else {   // exact ties of the key: the LOWEST id first, so the digits of the complemented id
-          const int q = pass - 8;
-          const unsigned nid = ~(unsigned)idx & ((1u << CB_IDBITS) - 1u);
-          if (key != kprefix) continue;
-          if (q > 0 && (nid >> (CB_IDBITS - 8 * q)) != iprefix) continue;
-          digit = (int)((nid >> (CB_IDBITS - 8 - 8 * q)) & 255u);
-        }
-        atomicAdd(&sh.hist[digit], 1);
-      }
-      if (pass == 0) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-        if (lane == 0 && mine) atomicAdd(&sh.nvalid, mine);
-      }
-      __syncthreads();
-      if (pass == 0 && tid == 0) sh.need = min(W, sh.nvalid);
-      __syncthreads();
-      if (sh.need == 0) break;   // (uniform) no candidate at all: the beam dies (only with non-finite logits)
-      if (wave == 0) cb_pick_bin(sh, lane);
-      __syncthreads();
-      const bool done = sh.cnt == sh.need;   // the whole bin is taken
-      passes = pass + 1;
-      __syncthreads();
-      if (tid == 0) {
-        if (pass < 8) sh.kprefix = (kprefix << 8) | (u64)sh.bin;
-        else sh.iprefix = (iprefix << 8) | (unsigned)sh.bin;
-      }
-      if (done) break;   // (uniform)
-    }
-    __syncthreads();
-    // ---- gather the selected candidates
-    if (min(W, sh.nvalid) > 0) {
-      const u64 kprefix = sh.kprefix;
-      const unsigned iprefix = sh.iprefix;
-      for (int idx = tid; idx < N; idx += CB_THREADS) {
-        const u64 key = ck[idx];
-        if (key == 0ull) continue;
-        bool take;
-        if (passes <= 8) {
-          take = (key >> (64 - 8 * passes)) >= kprefix;
-        } else {
-          const unsigned nid = ~(unsigned)idx & ((1u << CB_IDBITS) - 1u);
-          take = key > kprefix || (key == kprefix && (nid >> (CB_IDBITS - 8 * (passes - 8))) >= iprefix);
-        }
-        if (take) {
-          const int slot = atomicAdd(&sh.nsel, 1);
-          if (slot < CB_WMAX) { sh.sel_key[slot] = key; sh.sel_id[slot] = idx; }
-        }
-      }
-    }
-    __syncthreads();
-    const int m = min(min(W, sh.nvalid), sh.nsel);   // (the select takes exactly min(W, candidates))
+    // ---- select the min(W, candidates) best in the order (key descending, id ascending)
+    const int m = select_top<CB_WMAX, CB_IDBITS, CB_THREADS>(sh.sel, ck, N, W);
     // ---- build the next beam in rank order
     int rank = -1, kk = -1;
     if (tid < m) {
-      const u64 key = sh.sel_key[tid];
-      const int id = sh.sel_id[tid];
-      rank = 0;
-      for (int i = 0; i < m; ++i) {
-        const u64 ok = sh.sel_key[i];
-        rank += (ok > key || (ok == key && sh.sel_id[i] < id)) ? 1 : 0;
-      }
+      const int id = sh.sel.sel_id[tid];
+      rank = select_rank(sh.sel, tid, m);
       const int r = id / V1, j = id - r * V1;
       int pend = 0;
       if (j == 0) {
@@ -299,7 +170,7 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
         if (FUSED) {
           const long o = (long)c.st[r] * V + kk;
           nw.tot[rank] = c.tot[r] + (double)farc[o];
-          nw.st[rank] = cb_clampi(fnext[o], 0, n_states - 1);
+          nw.st[rank] = clampi(fnext[o], 0, n_states - 1);
         } else {
           nw.tot[rank] = 0.0;
           nw.st[rank] = 0;
@@ -307,43 +178,16 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
         const int par = c.node[r];
         nw.tok[rank] = kk;
         nw.par[rank] = par;
-        // the prefix's node, if it was created before (a node has at most V - 1 children)
-        int ch = nd.child[par];
-        for (int i = 0; i < V && ch >= 0; ++i) {
-          if (nd.token[ch] == kk) break;
-          ch = nd.sib[ch];
-        }
+        const int ch = tree_find_child(nd, par, kk, V);   // the prefix's node, if it was created before
         nw.node[rank] = ch;
         pend = ch < 0 ? 1 : 0;
       }
       sh.pending[rank] = pend;
     }
     __syncthreads();
-    if (tid == 0) {   // new nodes are numbered in rank order
-      int nn = sh.nnodes;
-      for (int i = 0; i < m; ++i)
-        if (sh.pending[i]) nw.node[i] = nn++;
-      sh.nnodes = nn;
-    }
+    if (tid == 0) tree_number(sh.pending, nw.node, m, sh.nnodes);
     __syncthreads();
-    if (rank >= 0 && sh.pending[rank]) {
-      const int me = nw.node[rank], par = nw.par[rank];
-      if (me < maxn) {   // (at most W new nodes per frame: always true)
-        nd.parent[me] = par; nd.token[me] = kk; nd.frame[me] = t; nd.child[me] = -1;
-        bool leader = true;
-        for (int i = 0; i < rank; ++i) leader = leader && !(sh.pending[i] && nw.par[i] == par);
-        if (leader) {   // the first new child of this parent links all of them, in rank order, in front of the list
-          int head = nd.child[par];
-          for (int i = rank; i < m; ++i) {
-            if (sh.pending[i] && nw.par[i] == par) {
-              nd.sib[nw.node[i]] = head;
-              head = nw.node[i];
-            }
-          }
-          nd.child[par] = head;
-        }
-      }
-    }
+    if (rank >= 0 && sh.pending[rank]) tree_link(nd, maxn, sh.pending, nw.par, nw.node, rank, m, kk, t);
     __threadfence_block();
     __syncthreads();
     n = m;
@@ -360,19 +204,8 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
   __syncthreads();
   if (tid < n) {
     const double key = sh.cpb[tid];
-    int o = 0;
-    for (int i = 0; i < n; ++i) o += (sh.cpb[i] > key || (sh.cpb[i] == key && i < tid)) ? 1 : 0;
-    o = min(o, W - 1);
-    const long base = (long)b * W + o;
-    int len = 0;
-    for (int x = c.node[tid]; x > 0 && len < T; x = nd.parent[x]) ++len;
-    int x = c.node[tid];
-    for (int i = len - 1; i >= 0; --i) {
-      tokens[base * T + i] = nd.token[x];
-      if (frames) frames[base * T + i] = nd.frame[x];
-      x = nd.parent[x];
-    }
-    lens[base] = len;
+    const long base = (long)b * W + output_slot(sh.cpb, tid, n, W);
+    lens[base] = tree_backtrace(nd, c.node[tid], false, T, tokens + base * T, frames ? frames + base * T : nullptr);
     scores[base] = sh.p[tid];
     if (FUSED) fused[base] = key;
   }
@@ -390,10 +223,9 @@ CbWs carve_cb(void* ws, int64_t B, int64_t T, int64_t V, int64_t W) {
   CbWs w;
   char* p = reinterpret_cast<char*>(ws);
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  w.keys = reinterpret_cast<u64*>(take((size_t)B * W * (V + 1) * 8));
-  w.nodes = reinterpret_cast<int*>(take((size_t)B * 5 * (1 + W * T) * 4));
-  w.lse = reinterpret_cast<float*>(take((size_t)B * T * 4));
+  w.keys = reinterpret_cast<u64*>(ws_take(p, off, (size_t)B * W * (V + 1) * 8));
+  w.nodes = reinterpret_cast<int*>(ws_take(p, off, (size_t)B * 5 * (1 + W * T) * 4));
+  w.lse = reinterpret_cast<float*>(ws_take(p, off, (size_t)B * T * 4));
   w.total = off;
   return w;
 }
@@ -420,20 +252,14 @@ extern "C" int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64
   RNNT_CHECK_ARG(W >= 1 && W <= CB_WMAX, "ctc_beam_search: beam width W = %d outside [1,%d]", W, CB_WMAX);
   RNNT_CHECK_ARG(V >= 2, "ctc_beam_search: V = %d < 2 (a blank and at least one token)", V);
   RNNT_CHECK_ARG(blank >= 0 && blank < V, "ctc_beam_search: blank %d outside [0,%d)", blank, V);
-  RNNT_CHECK_ARG(!(token_min_logp != token_min_logp) && token_min_logp < __builtin_huge_valf(),
-                 "ctc_beam_search: token_min_logp must be a number below +inf (-inf: no pruning)");
+  int rc = check_token_min_logp(token_min_logp, "ctc_beam_search");
+  if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(cb_dims_ok(B, T, V, W), "ctc_beam_search: W (V+1) = %lld exceeds 2^%d candidates per frame, or W T = %lld the node index",
                  (long long)W * (V + 1), CB_IDBITS, (long long)W * T);
   RNNT_CHECK_ARG(logits && t_lens && tokens && lens && scores && counts, "ctc_beam_search: null logits/lengths/tokens/lens/scores/counts");
   RNNT_CHECK_ARG(z_sb >= 1 && z_st >= V, "ctc_beam_search: logits strides (z_sb = %lld, z_st = %lld) must be positive, z_st >= V",
                  (long long)z_sb, (long long)z_st);
-  if (fusion) {
-    RNNT_CHECK_ARG(fusion->next && fusion->arc && fusion->final, "ctc_beam_search: null fusion table");
-    RNNT_CHECK_ARG(fusion->n_states >= 1 && (int64_t)fusion->n_states * V <= (1ll << 27),
-                   "ctc_beam_search: fusion n_states = %d with V = %d outside [1, 2^27 / V]: the tables must be (S, V) over the logits' V",
-                   fusion->n_states, V);
-    RNNT_CHECK_ARG(fusion->fused_scores, "ctc_beam_search: null fused_scores with a fusion automaton");
-  }
+  if (fusion && (rc = check_fusion_struct(fusion, V, "ctc_beam_search")) != RNNT_OK) return rc;
   const CbWs w = carve_cb(workspace, B, T, V, W);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_beam_search: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   RNNT_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "ctc_beam_search: workspace must be 8-byte aligned");

@@ -101,7 +101,10 @@ __device__ __forceinline__ void matvec(const float* __restrict__ W, long ld, int
   }
 }
 
-__device__ __forceinline__ int cell_gates(int cell) { return cell == RNNT_CELL_LSTM ? 4 : (cell == RNNT_CELL_GRU ? 3 : 1); }
+__host__ __device__ __forceinline__ int cell_gates(int cell) { return cell == RNNT_CELL_LSTM ? 4 : (cell == RNNT_CELL_GRU ? 3 : 1); }
+
+// floats of a stored prediction-net state: h[L*Hp] | c[L*Hp] (LSTM) | C[V], padded to 4
+inline int slot_floats(int L, int Hp, int cell, int V) { return (L * Hp * (cell == RNNT_CELL_LSTM ? 2 : 1) + V + 3) & ~3; }
 
 // The L stacked cells of one step (torch.nn.LSTM / GRU / RNN equations), in place on LDS state h[L][Hp], c[L][Hp].  On entry
 // x[0:Hp] holds the layer-0 input (the token's embedding row); gi / gh are 4*Hp scratch each.  gi0, if not null, is the

@@ -973,13 +973,37 @@ def ctc_greedy(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, *, time_m
 CTC_BEAM_MAX_WIDTH = 128
 
 
-def check_ctc_beam_args(beam_width, token_min_logp, what: str) -> None:
-    """ValueError unless 1 <= beam_width <= 128 and token_min_logp is a number below +inf: before anything is launched."""
-    if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 1 <= beam_width <= CTC_BEAM_MAX_WIDTH:
-        raise ValueError(f"{what}: beam width must be an integer in [1, {CTC_BEAM_MAX_WIDTH}], got {beam_width!r}")
+def _check_search_args(what: str, token_min_logp, **ranges) -> None:
+    """ValueError unless every name=(value, max) of `ranges` is an integer in [1, max] and token_min_logp is a number below
+    +inf: the argument checks of the frame-synchronous searches."""
+    for name, (value, top) in ranges.items():
+        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= top:
+            raise ValueError(f"{what}: {name} must be an integer in [1, {top}], got {value!r}")
     if isinstance(token_min_logp, bool) or not isinstance(token_min_logp, (int, float)) or math.isnan(token_min_logp) \
             or token_min_logp == math.inf:
         raise ValueError(f"{what}: token_min_logp must be a number below +inf (-inf: no pruning), got {token_min_logp!r}")
+
+
+def check_ctc_beam_args(beam_width, token_min_logp, what: str) -> None:
+    """ValueError unless 1 <= beam_width <= 128 and token_min_logp is a number below +inf: before anything is launched."""
+    _check_search_args(what, token_min_logp, **{"beam width": (beam_width, CTC_BEAM_MAX_WIDTH)})
+
+
+def _hyps_to_host(count, lens_h, tokens, scores, fused=None, frames=None):
+    """The searches' result lists from their device outputs: count (B) and lens_h (B, W) are already on the host (the one
+    copy of counts and lengths), tokens / frames (B, W, max_len), scores / fused (B, W).  One host copy per array, tokens and
+    frames cut to the longest returned hypothesis first.  -> per utterance [(tokens, score[, fused][, frames]), ...]."""
+    B = len(count)
+    longest = max([1] + [lens_h[b][r] for b in range(B) for r in range(count[b])])
+    tok_h, scores_h = tokens[:, :, :longest].cpu(), scores.cpu().tolist()
+    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
+    if fused is not None:
+        fused_h = fused.cpu().tolist()
+        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
+    if frames is not None:
+        fr_h = frames[:, :, :longest].cpu()
+        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
+    return out
 
 
 @torch.no_grad()
@@ -1022,17 +1046,7 @@ def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam
                                      C.byref(fs) if fs is not None else None, _addr(tokens), _addr(small, B), _addr(scores),
                                      _addr(frames), _addr(small), _addr(ws), nws, _stream()), "rnnt_hip_ctc_beam_search")
     host = small.cpu()   # the only host sync of the search
-    count, lens_h = host[:B].tolist(), host[B:].reshape(B, W).tolist()
-    longest = max([1] + [lens_h[b][r] for b in range(B) for r in range(count[b])])
-    tok_h, scores_h = tokens[:, :, :longest].cpu(), scores.cpu().tolist()
-    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
-    if fusion is not None:
-        fused_h = fused.cpu().tolist()
-        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
-    if return_frames:
-        fr_h = frames[:, :, :longest].cpu()
-        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
-    return out
+    return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, frames)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1319,7 +1333,7 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
     d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
-    tm = None
+    tm = fr = fused = None
     if frames:
         fr = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
         tm = _lib.BeamTiming(_addr(fr), None)
@@ -1341,15 +1355,7 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
                    "max_len": max_len}.get(kw)
             raise RnntHipError(f"beam search: utterance {b} exceeded the cap on {what} ({kw}={cap}); raise it with the {kw}= "
                                "keyword (the reference's search is unbounded here)")
-    lens_h, scores_h = lens.cpu().tolist(), scores.cpu().tolist()
-    tok_h = tokens[:, :, :max(1, max(max(r) for r in lens_h))].cpu()
-    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
-    if fusion is not None:
-        fused_h = fused.cpu().tolist()
-        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
-    if frames:
-        fr_h = fr[:, :, :tok_h.shape[2]].cpu()
-        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
+    out = _hyps_to_host(count, lens.cpu().tolist(), tokens, scores, fused, fr)
     if stats:
         return out, host.reshape(-1)[2 * B:].reshape(B, _lib.BEAM_NSTATS)
     return out
@@ -1360,13 +1366,8 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
 # --------------------------------------------------------------------------------------------------
 def check_beam_sync_args(beam_width, max_symbols, token_min_logp, what: str) -> None:
     """ValueError unless 1 <= beam_width <= 64, 1 <= max_symbols <= 4 and token_min_logp is a number below +inf."""
-    if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 1 <= beam_width <= _lib.BEAM_SYNC_MAX_WIDTH:
-        raise ValueError(f"{what}: beam width must be an integer in [1, {_lib.BEAM_SYNC_MAX_WIDTH}], got {beam_width!r}")
-    if isinstance(max_symbols, bool) or not isinstance(max_symbols, int) or not 1 <= max_symbols <= _lib.BEAM_SYNC_MAX_SYMBOLS:
-        raise ValueError(f"{what}: max_symbols must be an integer in [1, {_lib.BEAM_SYNC_MAX_SYMBOLS}], got {max_symbols!r}")
-    if isinstance(token_min_logp, bool) or not isinstance(token_min_logp, (int, float)) or math.isnan(token_min_logp) \
-            or token_min_logp == math.inf:
-        raise ValueError(f"{what}: token_min_logp must be a number below +inf (-inf: no pruning), got {token_min_logp!r}")
+    _check_search_args(what, token_min_logp, **{"beam width": (beam_width, _lib.BEAM_SYNC_MAX_WIDTH),
+                                                "max_symbols": (max_symbols, _lib.BEAM_SYNC_MAX_SYMBOLS)})
 
 
 @torch.no_grad()
@@ -1434,17 +1435,7 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
     check(L.rnnt_hip_beam_sync_search(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None,
                                       _stream()), "rnnt_hip_beam_sync_search")
     host = small.cpu()   # the only host sync of the search
-    count, lens_h = host[:B].tolist(), host[B:].reshape(B, W).tolist()
-    longest = max([1] + [lens_h[b][r] for b in range(B) for r in range(count[b])])
-    tok_h, scores_h = tokens[:, :, :longest].cpu(), scores.cpu().tolist()
-    out = [[(tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) for r in range(count[b])] for b in range(B)]
-    if fusion is not None:
-        fused_h = fused.cpu().tolist()
-        out = [[(y, s, fused_h[b][r]) for r, (y, s) in enumerate(hyps)] for b, hyps in enumerate(out)]
-    if frames:
-        fr_h = fr[:, :, :longest].cpu()
-        out = [[(*e, fr_h[b, r, :len(e[0])].tolist()) for r, e in enumerate(hyps)] for b, hyps in enumerate(out)]
-    return out
+    return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, fr)
 
 
 # --------------------------------------------------------------------------------------------------

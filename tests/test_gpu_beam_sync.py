@@ -221,16 +221,20 @@ def test_fewer_candidates_than_the_beam_is_wide():
 
 
 def test_uniform_logits_tie_in_id_order():
-    ora, tn, pn = K.model(5, 4, 1, "lstm", 8, 3)
-    with torch.no_grad():
-        ora.fc.weight.zero_()
-        ora.fc.bias.zero_()
-    x = K.audio(2, 3)
-    net = _jointnet(tn, pn, 5, ora)
-    got = _decode(net, x, [2], 0, 3, 1)
-    want = R.search(ora, x, [2], 0, 3, 1)[0].hyps
-    assert [(y, f) for y, _, f in got] == [(y, f) for y, _, f in want] == [([0], [-1]), ([0, 1], [-1, 0]), ([0, 2], [-1, 0])]
-    assert all(K.close(s, w) for (_, s, _), (_, w, _) in zip(got, want))
+    """All keys of a round are equal: the select chooses by its id passes alone.  V = 5: one populated bin in all but the last
+    8-bit digit of the id; V = 300: the middle digit decides too (the first: test_gpu_ctc_beam.py, the same function)."""
+    for V in (5, 300):
+        ora, tn, pn = K.model(V, 4, 1, "lstm", 8, 3)
+        with torch.no_grad():
+            ora.fc.weight.zero_()
+            ora.fc.bias.zero_()
+        x = K.audio(2, 3)
+        net = _jointnet(tn, pn, V, ora)
+        got = _decode(net, x, [2], 0, 3, 1)
+        want = R.search(ora, x, [2], 0, 3, 1)[0].hyps
+        assert [(y, f) for y, _, f in got] == [(y, f) for y, _, f in want] == [([0], [-1]), ([0, 1], [-1, 0]), ([0, 2], [-1, 0])]
+        assert all(K.close(s, w) for (_, s, _), (_, w, _) in zip(got, want))
+        assert all(K.close(s, -2.0 * math.log(V)) for _, s, _ in got)
 
 
 # 6. fusion --------------------------------------------------------------------------------------------------------------------------

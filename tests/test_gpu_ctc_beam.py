@@ -90,11 +90,19 @@ def test_exhaustive_beam_matches_the_ctc_loss_kernels():
     assert all(a[1] >= b[1] for a, b in zip(got, got[1:]))
 
 
-@pytest.mark.parametrize("T,blank", [(1, 0), (2, 0), (1, 1), (2, 2)])
-def test_uniform_logits_tie_in_id_order(T, blank):
-    want, _, _ = R.search(np.zeros((T, 3), np.float32), blank, 3)
-    got = search(torch.zeros(1, T, 3), torch.tensor([T], dtype=torch.int32), blank, 3)[0]
-    assert [y for y, _ in got] == [h["tokens"] for h in want]
+TIE_EXPECTED = {(1, 0): [[], [1], [2]], (2, 0): [[1], [2], []], (1, 1): [[], [0], [2]], (2, 2): [[0], [1], []]}
+
+
+# (the V = 3 cases keep the ids they always had)
+@pytest.mark.parametrize("V,T,blank", [pytest.param(V, T, blank, id=f"{T}-{blank}" if V == 3 else f"{V}-{T}-{blank}")
+                                       for V in (3, 300, 70000) for T, blank in TIE_EXPECTED])
+def test_uniform_logits_tie_in_id_order(V, T, blank):
+    """Every candidate of frame 0 has the same key bit for bit: the select picks the three lowest ids by its id passes alone.
+    V = 3: only the last 8-bit digit of the id has more than one bin populated; V = 300: the middle digit too; V = 70000: the
+    first as well (ids cross 65536)."""
+    want, _, _ = R.search(np.zeros((T, V), np.float32), blank, 3)
+    got = search(torch.zeros(1, T, V), torch.tensor([T], dtype=torch.int32), blank, 3)[0]
+    assert [y for y, _ in got] == [h["tokens"] for h in want] == TIE_EXPECTED[T, blank]
     for (y, s), h in zip(got, want):
         assert abs(s - h["score"]) <= 1e-5 * abs(h["score"])
 
