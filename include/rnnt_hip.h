@@ -967,6 +967,99 @@ int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusi
                               const rnnt_beam_timing* timing /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming frame-synchronous beam search: the search of rnnt_hip_beam_sync_search fed in chunks, the hypotheses carried on the
+ * device.  csrc/beam_sync_stream.hip, DESIGN.md §21.  The kernel is the STREAM instance of the offline entry's template
+ * (csrc/beam_sync_shared.hpp): the same frame loop, so the definition above holds word for word.
+ *
+ * After any sequence of chunks that together fed frames 0..n-1 of stream b since its last reset, its n-best is exactly what
+ * rnnt_hip_beam_sync_search returns for an utterance of those n frames: the same token lists, the same fp64 score bits (and
+ * fused_scores bits), the same per-token frames, whatever the chunking, 1-frame chunks and chunks in which the stream has no
+ * frames included.  The cost per frame is the offline one, fixed by W, V and S; there is no pop loop and nothing a score can
+ * overflow.  The only run-time error paths are the two caps max_nodes and max_len below.
+ *
+ * The workspace IS the carried state.  It starts with the layer-0 input table (V, G*Hp) (built by the reset entry when
+ * build_table != 0: the weights must not change while a state is open), followed per stream by
+ *   a 256-byte header of int32 { nA = members of the beam, prefix nodes in use, tokens committed since the reset (the leading
+ *     blank counts), frames consumed since the reset, RNNT_BEAM_ST_* status, collections run, of those the ones run at a
+ *     frame's start, largest node count seen };
+ *   the beam A in rank order, W entries each of: fp64 score[W], fp64 fusion total[W], int32 node[W], automaton state[W], state
+ *     slot[W], pending token[W].  pending token >= 0: a child of the last frame's last round whose prediction-net step has not
+ *     run; its slot is its PARENT's (-1: the zero state) and the step runs at the next frame's first round, exactly as offline.
+ *     Nothing steps after the last fed frame;
+ *   (S+2) W prediction-net state slots (h | c | Cv);
+ *   W V candidate keys (scratch of a round, not carried);
+ *   the prefix tree, 5 int32 per node (parent, token, frame, first child, next sibling), max_nodes nodes;
+ *   2 int32 per node of scratch for the collection.
+ * Reset entry: rows[0..n_rows) (device int32) start a new utterance: the beam is the offline seed (the root, score 0, automaton
+ * state 0, total 0, a pending step on blank from the zero state), the tree is the root, one token (the blank) is committed, no
+ * frames are consumed.  Other rows are not touched.  A, lens and the outputs are unused there.
+ * Chunk call, one launch, one workgroup per stream: load the beam; run frames t < lens[b] (clamped to [0,T]) of A; collect the
+ * prefix tree; write the n-best; store the beam and the header.  lens[b] == 0: the stream's workspace is not touched,
+ * count[b] = -1 ("the previous list again"), ncommit[b] = 0 and status[b] = the header's status.
+ * Frames are absolute: a node created at frame t of this chunk is stamped (frames consumed before the chunk) + t.  Nodes always
+ * carry their frame; timing only selects whether frames are written out.
+ * Collection.  Every later hypothesis extends a member of the carried beam, so R = the lowest common ancestor of the members'
+ * nodes is final.  The tokens (and frames) on the chain from below the old root down to R, R included, are appended to
+ * commit[b] (commit_frames[b]); ncommit[b] counts them for the chunk.  R becomes node 0.  Kept are exactly: the nodes on a path
+ * from R to a member, and every descendant of a member's node: those are the only nodes a later frame can look up again, and
+ * keeping them keeps the offline rule "one node per prefix, stamped at its first creation" (keeping only the paths to the
+ * members would re-create a prefix that is pruned and reached again, with a later frame).  Everything else is dropped; the
+ * compaction preserves index order.  Node numbers and sibling order enter no decision of the search.
+ * The kernel collects at the chunk's end and at the start of any frame that finds fewer than W S node slots free.  The
+ * collected tree is a function of the frames fed alone.
+ * Caps.  max_nodes (>= 1 + 4 W S) bounds the tree at any moment: if fewer than W S slots are free at a frame's start even
+ * after collecting, status RNNT_BEAM_ST_NODES; the stream stops before that frame, and which frame that is depends only on the
+ * frames fed, not on the chunking.  max_len (>= 1) bounds the tail of a RETURNED token sequence, the tokens below the root
+ * after the chunk's last collection: a longer tail gives RNNT_BEAM_ST_LEN where it would be returned, at a chunk's end.
+ * Either status is stored in the header (with the frames consumed until then): the stream's beam is no longer valid, count[b]
+ * = 0, and every later chunk returns count[b] = -1 with that status until the stream is reset.  Other streams are unaffected.
+ * Results: count / out_lens / tokens / scores (and fused_scores, frames) as rnnt_hip_beam_sync_search writes them, with rows of
+ * max_len entries that hold the TAIL of each y below the root; the full y is every token committed since the reset, leading
+ * blank first, followed by the tail.  Nothing is written for o >= count[b] or past out_lens[b,o].
+ * fusion (or NULL): the automaton must be the same for every chunk of a stream; its state and total are carried with every
+ * member, `final` is applied only where the n-best is ranked.  timing (or NULL): frames (B, beam, max_len) beside tokens and
+ * commit_frames (B, max_nodes + S T) beside commit; both or neither.
+ * Every check happens on the host before any launch (RNNT_ERR_INVALID): those of rnnt_hip_beam_sync_search, the two caps, the
+ * workspace (256-byte aligned, rnnt_hip_beam_sync_stream_workspace_bytes(d) bytes; 0 for sizes outside the limits), T >= 1, the
+ * pointers and strides of the chunk call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_sync_stream_desc {
+  int32_t T, B, V;       /* chunk frames (0 allowed for the size query and the reset), streams, vocabulary (V >= 2) */
+  int32_t Hp, O, L;      /* as rnnt_decode_desc */
+  int32_t cell, blank;
+  int32_t beam, max_symbols; /* W in [1,64], S in [1,4] */
+  int32_t step_group;    /* as rnnt_beam_sync_desc */
+  float token_min_logp;
+  int32_t max_nodes, max_len; /* caps: live prefix nodes (>= 1 + 4 W S), tokens of a returned tail (>= 1) */
+  const float* A;        /* gelu(enc) W_e^T + bias of the chunk, time-major (rnnt_hip_stream_rnn_chunk) */
+  int64_t a_st, a_sb;    /* strides of A in floats: frame, stream ((T,B,V) contiguous: B*V, V) */
+  const int32_t* lens;   /* (B) device, frames of this chunk per stream, in [0, T] */
+  const float* emb;
+  const float* w_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* w_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* b_ih[RNNT_DECODE_MAX_LAYERS];
+  const float* b_hh[RNNT_DECODE_MAX_LAYERS];
+  const float* w_o;
+  const float* b_o;
+  const float* w_d;      /* fc.weight[:, O_enc:], row stride ld_d floats */
+  int64_t ld_d;
+  void* workspace;       /* rnnt_hip_beam_sync_stream_workspace_bytes(d) bytes, 256-byte aligned: the carried state */
+  size_t workspace_bytes;
+  int32_t* tokens;       /* (B, beam, max_len) tail of y of rank o */
+  int32_t* out_lens;     /* (B, beam) tail lengths */
+  double* scores;        /* (B, beam) */
+  int32_t* count;        /* (B) hypotheses returned; -1 for a stream without frames in this chunk or failed earlier */
+  int32_t* status;       /* (B) RNNT_BEAM_ST_OK, RNNT_BEAM_ST_NODES or RNNT_BEAM_ST_LEN */
+  int32_t* commit;       /* (B, max_nodes + max_symbols*T) tokens committed by this chunk, oldest first */
+  int32_t* ncommit;      /* (B) */
+} rnnt_beam_sync_stream_desc;
+size_t rnnt_hip_beam_sync_stream_workspace_bytes(const rnnt_beam_sync_stream_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_sync_stream_reset(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows, int32_t build_table,
+                                    void* stream);
+int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion /* or NULL */,
+                                    const rnnt_beam_timing* timing /* or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

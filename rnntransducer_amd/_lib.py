@@ -120,6 +120,22 @@ class BeamSyncDesc(C.Structure):
                 ("scores", C.c_void_p), ("count", C.c_void_p)]
 
 
+BEAM_SYNC_STREAM_HEADER = ("n_beam", "nodes", "committed", "frames", "status", "collections", "collections_in_chunk", "peak_nodes")
+
+
+class BeamSyncStreamDesc(C.Structure):
+    _fields_ = [("T", c_i32), ("B", c_i32), ("V", c_i32), ("Hp", c_i32), ("O", c_i32), ("L", c_i32), ("cell", c_i32),
+                ("blank", c_i32), ("beam", c_i32), ("max_symbols", c_i32), ("step_group", c_i32), ("token_min_logp", C.c_float),
+                ("max_nodes", c_i32), ("max_len", c_i32),
+                ("A", C.c_void_p), ("a_st", c_i64), ("a_sb", c_i64), ("lens", C.c_void_p), ("emb", C.c_void_p),
+                ("w_ih", C.c_void_p * DECODE_MAX_LAYERS), ("w_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("b_ih", C.c_void_p * DECODE_MAX_LAYERS), ("b_hh", C.c_void_p * DECODE_MAX_LAYERS),
+                ("w_o", C.c_void_p), ("b_o", C.c_void_p), ("w_d", C.c_void_p), ("ld_d", c_i64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("tokens", C.c_void_p), ("out_lens", C.c_void_p),
+                ("scores", C.c_void_p), ("count", C.c_void_p), ("status", C.c_void_p), ("commit", C.c_void_p),
+                ("ncommit", C.c_void_p)]
+
+
 STREAM_MAX_LAYERS = 8
 
 
@@ -285,6 +301,10 @@ SYMBOLS = {
     "rnnt_hip_beam_sync_workspace_bytes": (C.c_size_t, [C.POINTER(BeamSyncDesc)]),
     "rnnt_hip_beam_sync_step_group": (C.c_int, [C.POINTER(BeamSyncDesc)]),
     "rnnt_hip_beam_sync_search": (C.c_int, [C.POINTER(BeamSyncDesc), C.POINTER(BeamFusion), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_sync_stream_workspace_bytes": (C.c_size_t, [C.POINTER(BeamSyncStreamDesc)]),
+    "rnnt_hip_beam_sync_stream_reset": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.c_void_p, c_i32, c_i32, C.c_void_p]),
+    "rnnt_hip_beam_sync_stream_chunk": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.POINTER(BeamFusion), C.POINTER(BeamTiming),
+                                                  C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
 }

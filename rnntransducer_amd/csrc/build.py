@@ -12,9 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = ["api.hip", "gemm.hip", "gemm_hp.hip", "loss.hip", "lstm.hip", "lstm5.hip", "lstm_layer.hip", "colsum_embedding.hip",
-           "decode.hip", "beam.hip", "frontend.hip", "stream.hip", "beam_stream.hip", "ctc.hip", "ctc_beam.hip", "beam_sync.hip"]
+           "decode.hip", "beam.hip", "frontend.hip", "stream.hip", "beam_stream.hip", "ctc.hip", "ctc_beam.hip", "beam_sync.hip",
+           "beam_sync_stream.hip"]
 HEADERS = ["common.hpp", "lstm_shared.hpp", "decode_shared.hpp", "beam_shared.hpp", "lattice_shared.hpp",
-           "search_shared.hpp"]
+           "search_shared.hpp", "beam_sync_shared.hpp"]
 LIB = os.path.join(HERE, "librnnt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + HERE, "-Wno-unused-result"]

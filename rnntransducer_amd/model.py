@@ -195,6 +195,17 @@ class RNNTransducer(_Base):
         return self.jointnet.recognize_beams_stream(chunk, chunk_lengths, state, return_scores=return_scores,
                                                     return_frames=return_frames)
 
+    def init_beam_sync_stream(self, batch_size: int, beam_widths: int = 16, max_symbols: int = 1, **kw):
+        """JointNet.init_beam_sync_stream with this model's blank: per-stream state for recognize_beams_sync_stream
+        (token_min_logp=, fusion=, device=, max_nodes=, max_len=; all fixed for the life of the state)."""
+        return self.jointnet.init_beam_sync_stream(batch_size, self.blank_token_id, beam_widths, max_symbols, **kw)
+
+    def recognize_beams_sync_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False, return_frames: bool = False):
+        """JointNet.recognize_beams_sync_stream: per stream the frame-synchronous search's n-best list for the frames fed so
+        far, bitwise the offline search's (with return_frames, the frame of every token too)."""
+        return self.jointnet.recognize_beams_sync_stream(chunk, chunk_lengths, state, return_scores=return_scores,
+                                                         return_frames=return_frames)
+
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
         """model.py:62-79: loss + greedy search (max 3 symbols per frame).  `pred_tokens` is a list of B 1-D LongTensors

@@ -446,3 +446,57 @@ class JointNet(nn.Module):
                                           (self.fc.weight, self.fc.bias))
             state.run_chunk(A, lens_dev, return_frames)
         return state.results(return_scores, return_frames)
+
+    def init_beam_sync_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 16, max_symbols: int = 1, *,
+                              token_min_logp: float = -math.inf, fusion=None, device=None, max_nodes: int = 8192,
+                              max_len: int = 256):
+        """A streaming.BeamSyncStreamState for `batch_size` streams, each starting as recognize_beams_sync starts an utterance:
+        the root [blank] with score 0 and one prediction-net step on blank pending.  The search options (beam_widths <= 64,
+        max_symbols <= 4, token_min_logp, fusion: a TokenFusion on the model's device) and the two caps are fixed here: max_nodes
+        bounds the LIVE prefix tree (>= 1 + 4 * beam_widths * max_symbols), max_len the uncommitted tail of a returned sequence;
+        `state.workspace_bytes` / `state.bytes_per_stream` tell what they cost.  `device`, if given, must be the model's.  The
+        weights must not change while the state is open.  Unidirectional encoders only.  ValueError for bad arguments, before
+        anything is allocated or launched."""
+        from ..streaming import BeamSyncStreamState
+        if self.training:
+            raise ValueError("init_beam_sync_stream expects eval() mode (dropout inactive), like recognize_beams_sync")
+        self.encoder.check_streamable("init_beam_sync_stream")
+        return BeamSyncStreamState(self, batch_size, blank_token_id, beam_widths, max_symbols, token_min_logp=token_min_logp,
+                                   fusion=fusion, device=device, max_nodes=max_nodes, max_len=max_len)
+
+    @torch.no_grad()
+    def recognize_beams_sync_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False,
+                                    return_frames: bool = False):
+        """Frame-synchronous beam search over the next chunk of every stream (csrc/beam_sync_stream.hip): chunk
+        (B,T_c,F) fp32 on the GPU, chunk_lengths B values in [0,T_c], `state` from this model's init_beam_sync_stream, updated in
+        place.  Returns a list of B n-best lists, each exactly what the offline search (recognize_beams_sync on this
+        encoder's outputs) gives for the frames that stream has been fed since its last reset, whatever the chunking: the same
+        token lists (leading blank included), bitwise the same fp64 scores and the same frames.  return_scores: (y, score)
+        pairs ((y, score, fused_score) with fusion); return_frames: (y, frames[, score[, fused_score]]), frames absolute, counted
+        from the reset, -1 for the leading blank.  A stream that has seen no frames returns [[blank]] with score 0 (fused_score
+        final[0]); a stream with 0 frames in this chunk is left bitwise unchanged and returns its previous list.
+        `state.stable_prefix(b)` is the part of stream b's answer that no later chunk can change.
+        The cost of a frame is fixed by beam_widths, V and max_symbols.  One launch for the search and one host sync per call.
+        The only run-time errors are the two caps: a stream that outgrows max_nodes or max_len raises RnntHipError naming it
+        after the other streams have been updated, and must be reset before it is fed again.
+        Unidirectional encoders only; eval() mode only; fp32 whatever compute_precision says.  Every guard runs before any launch
+        (ValueError; RnntHipError for a failed stream that is fed again): a refused call leaves the state bitwise untouched."""
+        from ..streaming import BeamSyncStreamState, host_lengths
+        if self.training:
+            raise ValueError("recognize_beams_sync_stream expects eval() mode (dropout inactive), like recognize_beams_sync")
+        self.encoder.check_streamable("recognize_beams_sync_stream")
+        if not isinstance(state, BeamSyncStreamState):
+            raise ValueError(f"recognize_beams_sync_stream takes the state of init_beam_sync_stream, got {type(state).__name__}")
+        self.encoder.check_stream_chunk(chunk, "recognize_beams_sync_stream")
+        B, T, _ = chunk.shape
+        state.check_fits(self, B, chunk.device)
+        lens = host_lengths(chunk_lengths, B, T)
+        state.check_feedable(lens)
+        T_run = max(lens)
+        if T_run > 0:
+            lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
+            enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
+            A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
+                                          (self.fc.weight, self.fc.bias))
+            state.run_chunk(A, lens_dev, lens)
+        return state.results(return_scores, return_frames)

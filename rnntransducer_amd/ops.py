@@ -1647,3 +1647,95 @@ def beam_stream_chunk(d, A: torch.Tensor, lens: torch.Tensor, frames: Optional[t
             check(_lib.lib().rnnt_hip_beam_stream_chunk(C.byref(d), _stream()), "rnnt_hip_beam_stream_chunk")
     finally:
         d.T, d.A, d.lens = 0, None, None
+
+
+# --------------------------------------------------------------------------------------------------
+# streaming frame-synchronous beam search (include/rnnt_hip.h: rnnt_hip_beam_sync_stream_*, csrc/beam_sync_stream.hip); the
+# workspace and the output buffers belong to streaming.BeamSyncStreamState
+# --------------------------------------------------------------------------------------------------
+BEAM_SYNC_STREAM_CAPS = ("max_nodes", "max_len")
+
+
+def beam_sync_stream_caps(beam: int, max_symbols: int, *, max_nodes: int = 8192, max_len: int = 256) -> dict:
+    """The two caps of the streaming frame-synchronous search, checked: max_nodes = live prefix-tree nodes (the tree is
+    collected at every chunk's end and inside a chunk whenever a frame would not find beam * max_symbols free slots; at least
+    1 + 4 * beam * max_symbols), max_len = tokens of a returned sequence that are not yet committed."""
+    caps = dict(max_nodes=max_nodes, max_len=max_len)
+    for k, v in caps.items():
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"streaming frame-synchronous beam search: {k} must be an integer >= 1, got {v!r}")
+    need = 1 + 4 * beam * max_symbols
+    if max_nodes < need or max_nodes >= (1 << 31) // 5:
+        raise ValueError(f"streaming frame-synchronous beam search: max_nodes = {max_nodes} outside [1 + 4 * beam_widths * "
+                         f"max_symbols = {need}, 2^31 / 5)")
+    return caps
+
+
+def beam_sync_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, beam: int, max_symbols: int,
+                          token_min_logp: float, caps: dict, step_group: int = 0):
+    """Descriptor of the streaming frame-synchronous beam search with every weight shape checked against the others (raw
+    pointers) and the search options checked as beam_search_sync checks them; the workspace, A, lens and the outputs are the
+    caller's to fill.  -> (descriptor, tensors to keep alive)."""
+    what = "streaming frame-synchronous beam search"
+    check_beam_sync_args(beam, max_symbols, token_min_logp, what)
+    if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
+        raise ValueError(f"{what}: step_group must be an integer >= 0, got {step_group!r}")
+    if B < 1:
+        raise ValueError(f"{what}: {B} streams")
+    _need_gpu(fc_w, emb_w)
+    d = _lib.BeamSyncStreamDesc()
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, int(blank), what)
+    if d.V < 2 or beam * d.V > 1 << 24:
+        raise ValueError(f"{what}: V = {d.V} < 2, or beam_widths * V = {beam * d.V} exceeds 2^24 candidates per round")
+    d.T, d.B = 0, B
+    d.beam, d.max_symbols, d.step_group, d.token_min_logp = beam, max_symbols, step_group, float(token_min_logp)
+    d.max_nodes, d.max_len = caps["max_nodes"], caps["max_len"]
+    return d, keep
+
+
+def beam_sync_stream_workspace_bytes(d) -> int:
+    """Bytes of the carried workspace (ValueError with the library's message for sizes outside its limits)."""
+    L = _lib.lib()
+    n = L.rnnt_hip_beam_sync_stream_workspace_bytes(C.byref(d))
+    if n == 0:
+        raise ValueError("streaming frame-synchronous beam search: " + L.rnnt_hip_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def beam_sync_stream_reset(d, rows: torch.Tensor, build_table: bool) -> None:
+    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to."""
+    _need_gpu(rows)
+    _check_buffer("rows", rows, (rows.numel(),), torch.int32, rows.device)
+    check(_lib.lib().rnnt_hip_beam_sync_stream_reset(C.byref(d), _addr(rows), rows.numel(), int(build_table), _stream()),
+          "rnnt_hip_beam_sync_stream_reset")
+
+
+def beam_sync_stream_chunk(d, A: torch.Tensor, lens_dev: torch.Tensor, commit: torch.Tensor, frames: Optional[torch.Tensor] = None,
+                           commit_frames: Optional[torch.Tensor] = None, fusion=None) -> None:
+    """One chunk: A (T,B,V) float32 (from stream_rnn_chunk; any positive frame and stream strides with contiguous rows), lens_dev
+    (B) int32 on device, commit (B, max_nodes + max_symbols * T) int32; the outputs d points to are written.  frames
+    (B, beam, max_len) and commit_frames (shaped as commit), int32 on device: the tails' and the committed tokens' absolute
+    frames are written too.  fusion: the rnnt_beam_fusion struct of the stream's automaton (fusion_struct), the same for
+    every chunk."""
+    _need_gpu(A, lens_dev, commit)
+    dev = A.device
+    if A.dim() != 3 or tuple(A.shape[1:]) != (d.B, d.V) or A.dtype != torch.float32 or A.shape[0] < 1 or A.stride(2) != 1 \
+            or A.stride(0) < 1 or A.stride(1) < 1:
+        raise ValueError(f"A: expected float32 (T >= 1, {d.B}, {d.V}) with contiguous rows, got {tuple(A.shape)} {A.dtype} "
+                         f"strides {A.stride()}")
+    T = A.shape[0]
+    _check_buffer("lengths", lens_dev, (d.B,), torch.int32, dev)
+    ncom = d.max_nodes + d.max_symbols * T
+    _check_buffer("commit", commit, (d.B, ncom), torch.int32, dev)
+    tm = None
+    if frames is not None or commit_frames is not None:
+        _check_buffer("frames", frames, (d.B, d.beam, d.max_len), torch.int32, dev)
+        _check_buffer("commit_frames", commit_frames, (d.B, ncom), torch.int32, dev)
+        tm = _lib.BeamTiming(_addr(frames), _addr(commit_frames))
+    d.T, d.A, d.a_st, d.a_sb, d.lens, d.commit = T, _addr(A), A.stride(0), A.stride(1), _addr(lens_dev), _addr(commit)
+    try:
+        check(_lib.lib().rnnt_hip_beam_sync_stream_chunk(C.byref(d), C.byref(fusion) if fusion is not None else None,
+                                                         C.byref(tm) if tm is not None else None, _stream()),
+              "rnnt_hip_beam_sync_stream_chunk")
+    finally:
+        d.T, d.A, d.lens, d.commit = 0, None, None, None

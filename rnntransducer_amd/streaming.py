@@ -23,6 +23,16 @@ Streaming beam search (`JointNet.init_beam_stream` / `recognize_beams_stream`, c
 `init_beam_stream(..., fusion=TokenFusion)` makes the streams search with token-level fusion (fusion.py): the automaton is fixed
 when the state is opened, every carried hypothesis keeps its automaton state and total on the device, and `final` is applied
 only where the n-best is ranked, so the n-best after every chunk is still the offline fused result for the frames fed so far.
+
+Streaming frame-synchronous beam search (`JointNet.init_beam_sync_stream` / `recognize_beams_sync_stream`,
+csrc/beam_sync_stream.hip) carries the search of `recognize_beams_sync`: a fixed cost per frame, at most
+beam_widths hypotheses and (max_symbols + 2) * beam_widths state slots per stream, and after every chunk bitwise the offline
+search's n-best for the frames fed so far.
+
+    state = jointnet.init_beam_sync_stream(batch_size, blank, beam_widths=16, max_symbols=1)
+    for chunk, lengths in feed:
+        nbest = jointnet.recognize_beams_sync_stream(chunk, lengths, state, return_scores=True)
+        partial = state.stable_prefix(0)
 """
 from __future__ import annotations
 
@@ -31,7 +41,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import ops
-from ._lib import BEAM_NSTATS, BEAM_STATUS, CELL_LSTM, RnntHipError
+from ._lib import BEAM_NSTATS, BEAM_STATUS, BEAM_SYNC_STREAM_HEADER, CELL_LSTM, RnntHipError
 
 
 def host_lengths(chunk_lengths: Union[Sequence[int], torch.Tensor], B: int, T: int) -> List[int]:
@@ -369,3 +379,211 @@ class BeamStreamState:
             raise RnntHipError(f"streaming beam search: stream {b} exceeded the cap on {what} ({kw}={self.caps.get(kw)}); open the "
                                f"state with a larger {kw}= keyword.  The other streams are unaffected; stream(s) {bad[:4]} must be "
                                "reset (state.reset(rows)) before they are fed again")
+
+
+class BeamSyncStreamState:
+    """Per-stream state of `JointNet.recognize_beams_sync_stream`.  On the device:
+      enc_h / enc_c   (L_enc, B, H)   encoder state (enc_c None unless the encoder is an LSTM)
+      workspace       uint8           the carried search (include/rnnt_hip.h): the layer-0 input table of the prediction net,
+                                      then per stream a header (`header(b)`), the beam in rank order (fp64 score, fusion total,
+                                      automaton state, prefix node, state slot, pending token per member), the
+                                      (max_symbols + 2) * beam_widths state slots, a round's candidate keys and the prefix tree
+      frames_seen     (B,) int64      frames consumed since the stream's last reset
+    On the host: the committed tokens and their frames per stream (`stable_prefix`) and the n-best list of the last chunk that
+    fed it.  The search options, the fusion automaton and the caps are fixed here; the table is built from the prediction
+    net's weights when the state is opened, so the weights must not change while it is open.
+
+    Caps (`ops.beam_sync_stream_caps`): max_nodes = 8192 live prefix nodes (at least 1 + 4 * beam_widths * max_symbols; the
+    tree is collected at every chunk's end and inside a chunk when a frame needs the room), max_len = 256 uncommitted tokens of
+    a returned sequence.  These two are the ONLY run-time error paths (RnntHipError naming the cap; the stream must be reset):
+    the cost of a frame is fixed by beam_widths, V and max_symbols, there is no pop loop, and a hotword weight cannot reach
+    either cap through the scores.  Bytes per stream (`bytes_per_stream`; all of them, `workspace_bytes`): 256 + 32 W +
+    4 (S + 2) W slot + 8 W V + 28 max_nodes, each part rounded up to 256, with slot = L * Hp * (2 if LSTM else 1) + V floats."""
+
+    def __init__(self, jointnet, batch_size: int, blank_token_id: int, beam_widths: int = 16, max_symbols: int = 1, *,
+                 token_min_logp: float = float("-inf"), fusion=None, device=None, max_nodes: int = 8192, max_len: int = 256,
+                 step_group: int = 0):
+        what = "init_beam_sync_stream"
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"{what}: batch_size must be an integer >= 1, got {batch_size!r}")
+        ops.check_beam_sync_args(beam_widths, max_symbols, token_min_logp, what)
+        self.caps = ops.beam_sync_stream_caps(beam_widths, max_symbols, max_nodes=max_nodes, max_len=max_len)
+        enc = jointnet.encoder.rnn
+        home = jointnet.fc.weight.device
+        device = torch.device(device) if device is not None else home
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device != home:
+            raise ValueError(f"{what}: device {device} is not the model's ({home}); the state lives beside the weights")
+        if not 0 <= int(blank_token_id) < jointnet.num_classes:
+            raise ValueError(f"{what}: blank_token_id {blank_token_id} outside [0, {jointnet.num_classes})")
+        ops.check_fusion(fusion, jointnet.num_classes, device, what)
+        self.fusion = fusion
+        self._net = jointnet
+        self.batch_size, self.blank = int(batch_size), int(blank_token_id)
+        self.beam, self.max_symbols, self.token_min_logp = int(beam_widths), int(max_symbols), float(token_min_logp)
+        self.step_group = step_group
+        d, _ = self._descriptor(bare=True)   # (needs the GPU from here on)
+        self._final0 = float(fusion.final[0]) if fusion is not None else 0.0   # read once: a reset does not sync for it
+        B, W = self.batch_size, self.beam
+        z = lambda L, H: torch.zeros(L, B, H, device=device, dtype=torch.float32)
+        self.enc_h = z(enc.num_layers, enc.hidden_size)
+        self.enc_c = z(enc.num_layers, enc.hidden_size) if enc.CELL == CELL_LSTM else None
+        self.frames_seen = torch.zeros(B, device=device, dtype=torch.int64)
+        self.workspace_bytes = ops.beam_sync_stream_workspace_bytes(d)
+        self.workspace = torch.zeros(self.workspace_bytes + 256, device=device, dtype=torch.uint8)
+        self._ws_off = -self.workspace.data_ptr() % 256
+        ngate = {0: 4, 1: 3}.get(jointnet.decoder.rnn.CELL, 1)
+        self._table_bytes = (jointnet.num_classes * ngate * jointnet.decoder.rnn.hidden_size * 4 + 255) // 256 * 256
+        self.bytes_per_stream = (self.workspace_bytes - self._table_bytes) // B
+        self._small = torch.zeros(3, B, device=device, dtype=torch.int32)   # count | status | ncommit: one transfer
+        self._tokens = torch.zeros(B, W, self.caps["max_len"], device=device, dtype=torch.int32)
+        self._frames = torch.zeros_like(self._tokens)
+        self._lens = torch.zeros(B, W, device=device, dtype=torch.int32)
+        self._scores = torch.zeros(B, W, device=device, dtype=torch.float64)
+        self._fused = torch.zeros(B, W, device=device, dtype=torch.float64) if fusion is not None else None
+        self._commit = self._commit_frames = None   # (B, max_nodes + S T): sized by the longest chunk so far
+        self.committed: List[List[int]] = [[self.blank] for _ in range(B)]
+        self.committed_frames: List[List[int]] = [[-1] for _ in range(B)]
+        self.nbest = [[self._start_entry()] for _ in range(B)]
+        self.nbest_frames: List[List[List[int]]] = [[[-1]] for _ in range(B)]
+        self.failed = [False] * B
+        self._reset(list(range(B)), build_table=True)
+
+    @property
+    def device(self) -> torch.device:
+        return self.enc_h.device
+
+    def _start_entry(self):
+        """The n-best entry of a stream that has seen no frames: (y, score[, fused_score]); final[0] belongs to it."""
+        return ([self.blank], 0.0) if self.fusion is None else ([self.blank], 0.0, self._final0)
+
+    def _descriptor(self, bare: bool = False):
+        net, dec = self._net, self._net.decoder
+        d, keep = ops.beam_sync_stream_desc(self.batch_size, net.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(),
+                                            dec.rnn.CELL, dec.out_proj.weight, dec.out_proj.bias, self.blank, self.beam,
+                                            self.max_symbols, self.token_min_logp, self.caps, self.step_group)
+        if not bare:
+            B = self.batch_size
+            d.workspace, d.workspace_bytes = self.workspace.data_ptr() + self._ws_off, self.workspace_bytes
+            d.tokens, d.out_lens, d.scores = self._tokens.data_ptr(), self._lens.data_ptr(), self._scores.data_ptr()
+            base = self._small.data_ptr()
+            d.count, d.status, d.ncommit = base, base + 4 * B, base + 8 * B
+        return d, keep
+
+    def workspace_row(self, b: int) -> torch.Tensor:
+        """The bytes of stream b's part of the workspace (a view)."""
+        lo = self._ws_off + self._table_bytes + b * self.bytes_per_stream
+        return self.workspace[lo:lo + self.bytes_per_stream]
+
+    def header(self, b: int) -> dict:
+        """The header words of stream b's workspace part (one small copy from the device): n_beam, nodes, committed, frames,
+        status, collections, collections_in_chunk (those run at a frame's start, for room), peak_nodes."""
+        words = self.workspace_row(b)[:4 * len(BEAM_SYNC_STREAM_HEADER)].view(torch.int32).tolist()
+        return dict(zip(BEAM_SYNC_STREAM_HEADER, words))
+
+    def stable_prefix(self, b: int, return_frames: bool = False):
+        """The committed tokens of stream b, leading blank included: the longest common prefix of the token sequences of ALL
+        carried hypotheses.  Every hypothesis of any later frame extends one of those, so no later chunk can change it.
+        return_frames=True: (tokens, frames), frames aligned with the tokens (absolute; -1 for the leading blank)."""
+        if not return_frames:
+            return list(self.committed[b])
+        return list(self.committed[b]), list(self.committed_frames[b])
+
+    def check_fits(self, jointnet, B: int, device) -> None:
+        """ValueError unless this state was opened by `jointnet` for B streams on `device` and still has that layout."""
+        if self._net is not jointnet:
+            raise ValueError("this BeamSyncStreamState was opened by another model: open one with this model's "
+                             "init_beam_sync_stream")
+        if B != self.batch_size:
+            raise ValueError(f"a chunk of {B} streams for a state of {self.batch_size}")
+        if device != self.device:
+            raise ValueError(f"chunk on {device}, state on {self.device}")
+        enc = jointnet.encoder.rnn
+        want = [("enc_h", self.enc_h, (enc.num_layers, B, enc.hidden_size), torch.float32),
+                ("frames_seen", self.frames_seen, (B,), torch.int64),
+                ("workspace", self.workspace, (self.workspace_bytes + 256,), torch.uint8)]
+        if enc.CELL == CELL_LSTM:
+            want.append(("enc_c", self.enc_c, (enc.num_layers, B, enc.hidden_size), torch.float32))
+        for name, t, shape, dtype in want:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device \
+                    or not t.is_contiguous():
+                raise ValueError(f"state.{name} is not a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        if -self.workspace.data_ptr() % 256 != self._ws_off:
+            raise ValueError("state.workspace was replaced: its alignment offset no longer holds")
+
+    def check_feedable(self, lens: Sequence[int]) -> None:
+        bad = [b for b, n in enumerate(lens) if n > 0 and self.failed[b]]
+        if bad:
+            raise RnntHipError(f"streaming frame-synchronous beam search: stream(s) {bad[:4]} exceeded a cap in an earlier chunk "
+                               "and must be reset (state.reset(rows)) before they are fed again")
+
+    @torch.no_grad()
+    def reset(self, rows) -> "BeamSyncStreamState":
+        """Start a new utterance in the listed rows (zero encoder state; the beam = the root [blank] with score 0 and a pending
+        prediction-net step on blank from the zero state; committed = [blank]; frames_seen = 0).  Every other row is left
+        bitwise as it is."""
+        rows = sorted({int(r) for r in (rows.tolist() if isinstance(rows, torch.Tensor) else rows)})
+        if any(not 0 <= r < self.batch_size for r in rows):
+            raise ValueError(f"reset: rows must lie in [0, {self.batch_size})")
+        if rows:
+            self._reset(rows, build_table=False)
+        return self
+
+    def _reset(self, rows: List[int], build_table: bool) -> None:
+        idx = torch.tensor(rows, device=self.device, dtype=torch.int64)
+        for t in (self.enc_h, self.enc_c):
+            if t is not None:
+                t.index_fill_(1, idx, 0.0)
+        self.frames_seen.index_fill_(0, idx, 0)
+        d, keep = self._descriptor()
+        ops.beam_sync_stream_reset(d, idx.to(torch.int32), build_table)
+        for r in rows:
+            self.committed[r], self.committed_frames[r] = [self.blank], [-1]
+            self.nbest[r], self.nbest_frames[r], self.failed[r] = [self._start_entry()], [[-1]], False
+
+    def results(self, return_scores: bool, return_frames: bool = False):
+        if not return_frames:   # an entry is (y, score[, fused_score])
+            return [[(list(y), *s) for y, *s in hyps] if return_scores else [list(y) for y, *_ in hyps] for hyps in self.nbest]
+        return [[(list(y), list(f), *s) if return_scores else (list(y), list(f)) for (y, *s), f in zip(hyps, frs)]
+                for hyps, frs in zip(self.nbest, self.nbest_frames)]
+
+    def run_chunk(self, A: torch.Tensor, lens_dev: torch.Tensor, fed: Sequence[int]) -> None:
+        """The search over one chunk (A (T,B,V), lens_dev (B) int32, `fed` the same on the host): one launch and one host sync.
+        Updates the workspace, `committed`, `nbest`, their frames and `frames_seen`; raises RnntHipError for a stream that
+        outgrew a cap, after every other stream has been updated."""
+        B, T = self.batch_size, A.shape[0]
+        ncom = self.caps["max_nodes"] + self.max_symbols * T
+        if self._commit is None or self._commit.shape[1] != ncom:
+            self._commit = torch.empty(B, ncom, device=self.device, dtype=torch.int32)
+            self._commit_frames = torch.empty_like(self._commit)
+        d, keep = self._descriptor()
+        fs = ops.fusion_struct(self.fusion, self._fused) if self.fusion is not None else None
+        ops.beam_sync_stream_chunk(d, A, lens_dev, self._commit, self._frames, self._commit_frames, fusion=fs)
+        self.frames_seen += lens_dev   # (a stream that fails here is reset before it is fed again)
+        host = self._small.cpu()   # the host sync of the chunk; the result slices below are copied from an idle stream
+        count, status, ncommit = host[0].tolist(), host[1].tolist(), host[2].tolist()
+        bad = [b for b in range(B) if fed[b] > 0 and status[b] != 0]
+        ran = [b for b in range(B) if fed[b] > 0 and status[b] == 0 and count[b] >= 0]
+        if ran:
+            lens_h, scores_h = self._lens.cpu().tolist(), self._scores.cpu().tolist()
+            fused_h = self._fused.cpu().tolist() if self.fusion is not None else None
+            nt = max(1, max(max(lens_h[b][:count[b]], default=0) for b in ran))
+            nc = max(1, max(ncommit[b] for b in ran))
+            tok_h, fr_h = self._tokens[:, :, :nt].cpu(), self._frames[:, :, :nt].cpu()
+            com_h, cfr_h = self._commit[:, :nc].cpu(), self._commit_frames[:, :nc].cpu()
+            for b in ran:
+                self.committed[b] += com_h[b, :ncommit[b]].tolist()
+                self.committed_frames[b] += cfr_h[b, :ncommit[b]].tolist()
+                self.nbest[b] = [(self.committed[b] + tok_h[b, r, :lens_h[b][r]].tolist(), scores_h[b][r]) +
+                                 (() if fused_h is None else (fused_h[b][r],)) for r in range(count[b])]
+                self.nbest_frames[b] = [self.committed_frames[b] + fr_h[b, r, :lens_h[b][r]].tolist() for r in range(count[b])]
+        for b in bad:
+            self.failed[b] = True
+        if bad:
+            b = bad[0]
+            what, kw = BEAM_STATUS.get(status[b], ("unknown", "?"))
+            raise RnntHipError(f"streaming frame-synchronous beam search: stream {b} exceeded the cap on {what} "
+                               f"({kw}={self.caps.get(kw)}) after {self.header(b)['frames']} frames; open the state with a larger "
+                               f"{kw}= keyword.  The other streams are unaffected; stream(s) {bad[:4]} must be reset "
+                               "(state.reset(rows)) before they are fed again")
