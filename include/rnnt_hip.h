@@ -1076,6 +1076,36 @@ int rnnt_hip_frontend_norm_pad(const float* wav, int64_t ld, const int32_t* lens
 int rnnt_hip_power_mel_log1p(const float* spec, int64_t M, int32_t n_bins, const float* fb, int32_t n_mels,
                              const int32_t* nframes, int32_t frames_per_utt, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MWER (minimum word error rate) training: the pieces between rnnt_hip_beam_sync_search and the fused loss (csrc/mwer.hip).
+ * Errors are counted on token ids.
+ * rnnt_hip_edit_distance: dist[p] = Levenshtein distance (substitution, insertion, deletion cost 1 each) between the first
+ *   hyp_lens[p] tokens of row p of hyp (row stride hyp_ld) and the first ref_lens[p / ref_div] tokens of row p / ref_div of ref
+ *   (row stride ref_ld): ref_div hypotheses share one reference without a copy.  Integer arithmetic, exact.  Either length may
+ *   be 0; a length is clamped to [0, ld], and both ld must lie in [0, 511] (the loss's U + 1 <= 512) — longer rows are refused.
+ *   One wavefront per pair.
+ * rnnt_hip_nbest_pack: the search's outputs tokens (B, N, max_len) (leading blank included), counts (B), lens (B, N) -> the
+ *   loss's inputs for rows r = b*N + n:  texts (B*N, Umax+1) int64 = blank, the hypothesis, blank padding;  labels (B*N, Umax)
+ *   = the hypothesis, blank padding;  u_lens (B*N);  t_lens (B*N) = frame_lens[b], or 0 for an invalid row (the loss then gives
+ *   +inf and exact-zero gradients for it);  valid (B*N) 0 / 1.  Row (b, n) is valid when n < counts[b] and its lens - 1 tokens
+ *   are at most max_hyp_len and at most Umax; an invalid row is packed as the empty hypothesis.  lens of a rank >= counts[b]
+ *   is not read.  N <= 64, Umax and max_hyp_len in [1, 511].
+ * rnnt_hip_mwer_risk: per utterance b over its valid rows i (valid[b*N + i] != 0 and nll not NaN), in fp64:
+ *     P^_i = softmax_i(-nll_i) (the minimum nll subtracted first),  Wbar = mean_i dist_i,
+ *     risk[b] = sum_i P^_i (dist_i - Wbar),   weights[b*N + j] = gscale * d risk[b] / d nll_j = -gscale P^_j (dist_j - sum_i P^_i dist_i)
+ *   both stored as fp32.  An invalid row has weight exactly 0 and its nll (+inf) never enters the arithmetic; fewer than two
+ *   valid rows (or no valid row with a finite nll) give risk 0 and weights 0.  Sums run in index order, one wavefront per
+ *   utterance: a row's result does not depend on the batch around it.  N <= 64.
+ * All three check their arguments on the host before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+int rnnt_hip_edit_distance(const int32_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens, const int32_t* ref, int64_t ref_ld,
+                           const int32_t* ref_lens, int32_t ref_div, int32_t P, int32_t* dist, void* stream);
+int rnnt_hip_nbest_pack(const int32_t* tokens, int64_t max_len, const int32_t* counts, const int32_t* lens, const int32_t* frame_lens,
+                        int32_t B, int32_t N, int32_t Umax, int32_t max_hyp_len, int32_t blank, int64_t* texts, int32_t* labels,
+                        int32_t* u_lens, int32_t* t_lens, int32_t* valid, void* stream);
+int rnnt_hip_mwer_risk(const float* nll, const int32_t* dist, const int32_t* valid, int32_t B, int32_t N, double gscale, float* risk,
+                       float* weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ Differences, all inside the hot path:
     default; the reference has neither.
   * `args.fastemit_lambda` (default 0.0: off) adds FastEmit regularisation to `training_step`: the lattice gradient is changed so that
     the model learns to emit sooner, the logged loss stays the unregularised one (JointNet.loss).  The reference has no such knob.
+  * `args.mwer_weight` (default 0.0: off), `args.mwer_nbest` (4) and `args.mwer_max_symbols` (1) add minimum word error rate
+    fine-tuning to `training_step`: loss = rnnt + ctc_weight * ctc + mwer_weight * risk, the risk being the expected number of token
+    errors over the model's own n-best list (JointNet.mwer_loss).  With the weight at 0 the step is today's, bit for bit.
   * `validation_step` stays on the GPU (the reference moves the module to the CPU at model.py:65-72 because its
     decode is a host loop): fused loss + on-device greedy search; it returns token ids, and texts only if a
     tokenizer object was attached as `self.tokenizer`.
@@ -63,6 +66,12 @@ class RNNTransducer(_Base):
         self.ctc_weight = float(getattr(args, "ctc_weight", 0.0) or 0.0)
         if self.ctc_weight > 0.0 and not self.jointnet.aux_ctc:
             raise ValueError("args.ctc_weight > 0 needs the CTC head: set jointnet_params['aux_ctc'] = True")
+        # MWER fine-tuning (JointNet.mwer_loss): off at weight 0, and training_step then takes the plain path
+        mwer_weight = getattr(args, "mwer_weight", 0.0)
+        nbest, max_symbols = getattr(args, "mwer_nbest", 4), getattr(args, "mwer_max_symbols", 1)
+        self.mwer_nbest, self.mwer_max_symbols = (4 if nbest is None else nbest), (1 if max_symbols is None else max_symbols)
+        self.mwer_weight = JointNet.check_mwer_args(self.mwer_nbest, self.mwer_max_symbols, 0.0, 511,
+                                                    0.0 if mwer_weight is None else mwer_weight, "args.mwer_*")
 
     def forward(self, input_audios, audio_lengths, input_texts, text_lengths):
         # the reference hands these two as python lists (dataloader.py:20,37): validating them costs no device sync
@@ -144,11 +153,21 @@ class RNNTransducer(_Base):
     def training_step(self, batch, batch_idx):
         assert not getattr(self.args, "move_metrics_to_cpu", False), "DDP only (model.py:53)"
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
+        lengths = audio_lengths if isinstance(audio_lengths, (list, tuple)) else None
+        logging = pl is not None and getattr(self, "_trainer", None) is not None
+        if self.mwer_weight > 0.0:   # rnnt + ctc_weight * ctc + mwer_weight * risk over the model's own n-best list
+            out = self.jointnet.mwer_loss(
+                input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
+                nbest=self.mwer_nbest, max_symbols=self.mwer_max_symbols, mwer_weight=self.mwer_weight, reduction="mean",
+                audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda, return_parts=logging)
+            if logging:   # the parts are (total, rnnt[, ctc], risk, err1)
+                self.log("train_loss", out[0], sync_dist=True)
+                self.log("train_mwer_risk", out[-2].detach(), sync_dist=True)
+            return {"loss": out[0] if logging else out}
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
-                                  audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None,
-                                  ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda)
-        if pl is not None and getattr(self, "_trainer", None) is not None:
+                                  audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda)
+        if logging:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}
 

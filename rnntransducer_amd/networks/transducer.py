@@ -21,14 +21,18 @@ fused loss's per-cell terms: the loss's lattice sweep in the (max, +) semiring (
 `aux_ctc=True` adds `ctc_head`, a Linear(O_e -> V) on the encoder's output, for the auxiliary CTC loss of joint CTC + transducer
 training (`loss(..., ctc_weight=w)`, `ctc_loss` for CTC pre-training of the encoder) and an encoder-only greedy decode
 (`recognize_ctc_greedy`); csrc/ctc.hip.  Off by default: parameters, their initialisation and every result stay as without it.
+`mwer_loss` is minimum word error rate fine-tuning: the reference term of `loss` plus the expected number of token errors over
+the n-best list of the frame-synchronous search, with the hypotheses' losses from the fused loss over the shared encoder row
+(csrc/mwer.hip, ops.JointLossGroupedFn).
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from ..ops import (CtcLossFn, JointLogitsFn, JointLossFn, TimedTokens, beam_search, beam_search_sync, check_beam_sync_args,
-                   check_ctc_beam_args, check_fusion, ctc_beam_search, ctc_greedy, greedy_decode, stream_greedy)
+from ..ops import (MWER_MAX_LEN, CtcLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens, beam_search,
+                   beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args, check_fastemit_lambda,
+                   check_fusion, ctc_beam_search, ctc_greedy, edit_distance, greedy_decode, nbest_pack, nbest_umax, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
 from .rnn import HipLSTM
@@ -116,6 +120,14 @@ class JointNet(nn.Module):
         `fastemit_lambda` > 0: FastEmit regularisation of the transducer term's GRADIENT (label log-probability gradients scaled by
         1 + lambda, through the log-softmax exactly: include/rnnt_hip.h), which trains the model to emit sooner.  The returned value
         stays the unregularised loss, bit for bit that of lambda = 0; the CTC term is untouched.  Finite and >= 0."""
+        return self._reference_terms(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
+                                     audio_lengths, ctc_weight, return_parts, fastemit_lambda)[0]
+
+    def _reference_terms(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
+                         audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False):
+        """The body of loss(): -> (what loss() returns, (enc, targets, t_lens, u_lens, inv)) with the encoder output and the
+        per-row tensors in the row order the encoder ran in (length-sorted for a ragged batch; `inv` restores the caller's order,
+        None when nothing moved or nobody needs it).  mwer_loss builds its hypothesis term on the same encoder output."""
         with_ctc = ctc_weight != 0.0 or return_parts
         if with_ctc:
             self._need_ctc_head("loss(ctc_weight != 0 or return_parts=True)")
@@ -124,20 +136,22 @@ class JointNet(nn.Module):
         u_lens = lengths_to_device(target_lengths, dev)
         T, B = input_audios.size(1), input_audios.size(0)
         (input_audios, input_texts, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
-            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), reduction == "none")
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), reduction == "none" or want_inv)
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
         out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction,
                                 fastemit_lambda)
-        out = out if inv is None else out.index_select(0, inv)
+        unsort = inv is not None and reduction == "none"
+        shared = (enc, targets, t_lens, u_lens, inv)
+        out = out.index_select(0, inv) if unsort else out
         if not with_ctc:
-            return out
+            return out, shared
         track = ctc_weight != 0.0 and torch.is_grad_enabled()
         with torch.set_grad_enabled(track):
             ctc = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, track, reduction, True)
-        ctc = ctc if inv is None else ctc.index_select(0, inv)
+        ctc = ctc.index_select(0, inv) if unsort else ctc
         total = out + ctc_weight * ctc if ctc_weight != 0.0 else out
-        return (total, out, ctc) if return_parts else total
+        return ((total, out, ctc) if return_parts else total), shared
 
     def ctc_loss(self, input_audios, tensor_audio_lengths, targets, target_lengths, blank: int, reduction: str = "none",
                  audio_lengths=None) -> torch.Tensor:
@@ -153,6 +167,70 @@ class JointNet(nn.Module):
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         out = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction, True)
         return out if inv is None else out.index_select(0, inv)
+
+    @staticmethod
+    def check_mwer_args(nbest, max_symbols, token_min_logp, max_hyp_len, mwer_weight, what: str) -> float:
+        """ValueError unless 1 <= nbest <= 64, 1 <= max_symbols <= 4, 1 <= max_hyp_len <= 511, token_min_logp is a number below
+        +inf and mwer_weight is finite and >= 0; -> mwer_weight as a float."""
+        check_beam_sync_args(nbest, max_symbols, token_min_logp, what)
+        if isinstance(max_hyp_len, bool) or not isinstance(max_hyp_len, int) or not 1 <= max_hyp_len <= MWER_MAX_LEN:
+            raise ValueError(f"{what}: max_hyp_len must be an integer in [1, {MWER_MAX_LEN}], got {max_hyp_len!r}")
+        if isinstance(mwer_weight, bool) or not isinstance(mwer_weight, (int, float)) or not math.isfinite(mwer_weight) \
+                or mwer_weight < 0:
+            raise ValueError(f"{what}: mwer_weight must be finite and >= 0, got {mwer_weight!r}")
+        return float(mwer_weight)
+
+    def mwer_loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, *, nbest: int = 4,
+                  max_symbols: int = 1, token_min_logp: float = -math.inf, max_hyp_len: int = MWER_MAX_LEN,
+                  mwer_weight: float = 1.0, reduction: str = "mean", audio_lengths=None, ctc_weight: float = 0.0,
+                  fastemit_lambda: float = 0.0, return_parts: bool = False):
+        """Minimum word error rate fine-tuning: rnnt + ctc_weight * ctc + mwer_weight * risk, where risk is the
+        expected number of TOKEN errors over the model's own n-best list, relative to the list's mean:
+            risk_b = sum_i P^_i (W_i - mean W),   P^_i = softmax_i(-nll_i)   over the valid hypotheses i of utterance b,
+        nll_i = -log P(y_i | x) from the fused loss (the full lattice sum, not the search's score) and W_i the Levenshtein
+        distance between y_i and the transcript, on token ids.  Per step:
+          1. ONE encoder forward in the module's current mode (it feeds every term);
+          2. the frame-synchronous search (recognize_beams_sync's kernel: nbest <= 64 hypotheses, max_symbols <= 4, token_min_logp)
+             on the detached encoder output, without a graph.  The hypotheses therefore come from the TRAIN-mode encoder output
+             (dropout active if the module is in train()); the search itself never applies dropout to the prediction net;
+          3. the reference term exactly as loss() computes it (same code: ragged handling, ctc_weight, fastemit_lambda);
+          4. the prediction net on the packed hypotheses, the fused loss for the nbest rows of each utterance over its one encoder
+             row (ops.JointLossGroupedFn; FastEmit does not apply to them), the edit distances and the risk, all on the device.
+        A hypothesis longer than max_hyp_len (<= 511) tokens is left out, as are the ranks the search did not fill; an utterance
+        with fewer than two valid hypotheses has risk 0.  No host sync beyond the search's one copy of counts and lengths.
+        reduction: "none" (B,), "mean" or "sum" over B, for every term.  return_parts=True -> (total, rnnt[, ctc], risk,
+        err1) with ctc present when the module has the CTC head, err1 the mean edit distance of the 1-best hypotheses (fp32, 0-d).
+        ValueError for bad arguments before anything runs."""
+        what = "mwer_loss"
+        mwer_weight = self.check_mwer_args(nbest, max_symbols, token_min_logp, max_hyp_len, mwer_weight, what)
+        check_fastemit_lambda(fastemit_lambda)
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"{what}: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if not 0 <= int(blank) < self.num_classes:
+            raise ValueError(f"{what}: blank {blank} outside [0,{self.num_classes})")
+        parts = return_parts and self.aux_ctc
+        ref, (enc, targets, t_lens, u_lens, inv) = self._reference_terms(
+            input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction, audio_lengths, ctc_weight,
+            parts, fastemit_lambda, want_inv=True)
+        dec, B, N = self.decoder, enc.shape[1], nbest
+        tokens, lens, counts, _, host = beam_search_sync_device(
+            enc.detach(), self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+            dec.out_proj.weight, dec.out_proj.bias, int(blank), N, max_symbols, t_lens, token_min_logp=token_min_logp)
+        texts, labels, hu_lens, ht_lens, valid = nbest_pack(tokens, lens, counts, t_lens, nbest_umax(host, B, N, max_hyp_len),
+                                                            int(blank), max_hyp_len)
+        hdec = dec.forward_time_major(texts, hu_lens + 1)
+        nll = JointLossGroupedFn.apply(enc, hdec, self.fc.weight, self.fc.bias, labels, ht_lens, hu_lens, int(blank), N,
+                                       torch.is_grad_enabled())
+        dist = edit_distance(labels, hu_lens, targets, u_lens, N)
+        if inv is not None and reduction == "none":   # the caller's row order, as the reference terms come back
+            rows = (inv.unsqueeze(1) * N + torch.arange(N, device=inv.device)).reshape(-1)
+            nll, dist, valid = nll.index_select(0, rows), dist.index_select(0, rows), valid.index_select(0, rows)
+        risk = MwerRiskFn.apply(nll, dist, valid, N, reduction)
+        total = (ref[0] if parts else ref) + mwer_weight * risk
+        if not return_parts:
+            return total
+        err1 = dist.view(B, N)[:, 0].to(torch.float32).mean()
+        return (total, *ref[1:], risk, err1) if parts else (total, ref, risk, err1)
 
     @torch.no_grad()
     def recognize_ctc_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, return_frames: bool = False):

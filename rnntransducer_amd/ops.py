@@ -712,21 +712,22 @@ class lstm_launch_record:
 # fused joint + RNN-T loss  (replaces transducer.py:54-69 + model.py:39,57)
 # --------------------------------------------------------------------------------------------------
 def _joint_ac(enc, dec, W, Oe, Od, V):
-    """A (T,B,V) = gelu(enc) W[:, :Oe]^T ; C (U1,B,V) = gelu(dec) W[:, Oe:]^T  (two small GEMMs, GELU on load)."""
+    """A (T,B,V) = gelu(enc) W[:, :Oe]^T ; C (U1,Bd,V) = gelu(dec) W[:, Oe:]^T  (two small GEMMs, GELU on load)."""
     T, B = enc.shape[:2]
-    U1 = dec.shape[0]
+    U1, Bd = dec.shape[:2]   # Bd = B, or B * group label rows (JointLossGroupedFn)
     A = torch.empty(T, B, V, device=enc.device, dtype=torch.float32)
-    Cm = torch.empty(U1, B, V, device=enc.device, dtype=torch.float32)
+    Cm = torch.empty(U1, Bd, V, device=enc.device, dtype=torch.float32)
     gemm(T * B, V, Oe, enc, W, A, b_sn=Oe + Od, b_sk=1, flags=GEMM_GELU_A)
-    gemm(U1 * B, V, Od, dec, W, Cm, b_off=Oe, b_sn=Oe + Od, b_sk=1, flags=GEMM_GELU_A)
+    gemm(U1 * Bd, V, Od, dec, W, Cm, b_off=Oe, b_sn=Oe + Od, b_sk=1, flags=GEMM_GELU_A)
     return A, Cm
 
 
 def _joint_backward(enc, dec, W, dA, dC, needs, w_tgt=None, b_tgt=None):
     """d_enc, d_dec, dW, db from dA (T,B,V), dC (U1,B,V).  w_tgt / b_tgt: flat-gradient views to add into (then None is
-    returned for that gradient)."""
+    returned for that gradient).  dec and dC may hold more rows than enc (JointLossGroupedFn: a group of label rows per
+    encoder row, dA already summed over the group)."""
     T, B, Oe = enc.shape
-    U1, _, Od = dec.shape
+    U1, Bd, Od = dec.shape
     V = W.shape[0]
     O = Oe + Od
     d_enc = d_dec = dW = db = None
@@ -735,13 +736,13 @@ def _joint_backward(enc, dec, W, dA, dC, needs, w_tgt=None, b_tgt=None):
         gemm(T * B, Oe, V, dA, W, d_enc, b_sn=1, b_sk=O, aux=enc, flags=GEMM_MUL_DGELU)
     if needs[1]:
         d_dec = torch.empty_like(dec)
-        gemm(U1 * B, Od, V, dC, W, d_dec, b_off=Oe, b_sn=1, b_sk=O, aux=dec, flags=GEMM_MUL_DGELU)
+        gemm(U1 * Bd, Od, V, dC, W, d_dec, b_off=Oe, b_sn=1, b_sk=O, aux=dec, flags=GEMM_MUL_DGELU)
     if needs[2]:
         dW = torch.empty_like(W) if w_tgt is None else None
         out = dW if w_tgt is None else w_tgt
         fl = GEMM_GELU_B | (0 if w_tgt is None else GEMM_ACCUM)
         gemm(V, Oe, T * B, dA, enc, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Oe, c_div=1, c_so=O, c_si=0, flags=fl, split_k=True)
-        gemm(V, Od, U1 * B, dC, dec, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Od, c_off=Oe, c_div=1, c_so=O, c_si=0, flags=fl,
+        gemm(V, Od, U1 * Bd, dC, dec, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Od, c_off=Oe, c_div=1, c_so=O, c_si=0, flags=fl,
              split_k=True)
     if needs[3]:
         db = colsum(dA, T * B, V, into=b_tgt)
@@ -815,6 +816,68 @@ class JointLossFn(torch.autograd.Function):
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
                                                _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
         return d_enc, d_dec, dW, db, None, None, None, None, None, None, None
+
+
+class JointLossGroupedFn(torch.autograd.Function):
+    """JointLossFn for B*group label rows over B encoder rows (MWER training: the `group` hypotheses of utterance b, rows
+    b*group .. b*group + group - 1 of dec / labels / t_lens / u_lens, share encoder row b): enc (T,B,Oe), dec (U1,B*group,Od) ->
+    per-row NLL (B*group,), the bits JointLossFn gives on enc.repeat_interleave(group, dim=1).
+    A = gelu(enc) W_e^T is computed ONCE as (T,B,V) and expanded to (T,B*group,V) by a gather for the unchanged loss kernels; the
+    backward adds dA over the group in rank order (a fixed order: bitwise reproducible) before the joint's own backward, so the
+    encoder-side GEMMs run once per step, not `group` times.  reduction "none" only, and no FastEmit: the rows are hypotheses."""
+
+    @staticmethod
+    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, group, want_grad=True):
+        if isinstance(group, bool) or not isinstance(group, int) or group < 1:
+            raise ValueError(f"group must be a positive integer, got {group!r}")
+        _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
+        w_param, b_param = W, bias
+        enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
+        for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
+            if t.dtype != torch.int32:
+                raise ValueError(f"{name} must be int32 (dataloader.py:21-24), got {t.dtype}")
+        labels = labels.contiguous()
+        T, B, Oe = enc.shape
+        U1, R, Od = dec.shape
+        V = W.shape[0]
+        if R != B * group or W.shape[1] != Oe + Od or labels.shape != (R, U1 - 1) or t_lens.shape != (R,) or u_lens.shape != (R,):
+            raise ValueError(f"shape mismatch: enc {tuple(enc.shape)} dec {tuple(dec.shape)} fc {tuple(W.shape)} targets "
+                             f"{tuple(labels.shape)} lengths {tuple(t_lens.shape)} / {tuple(u_lens.shape)} for group = {group}")
+        A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
+        rows = torch.arange(R, device=enc.device, dtype=torch.int64) // group
+        Ax = A.index_select(1, rows)   # (T, B*group, V): the gather
+        del A
+        nll = torch.empty(R, device=enc.device, dtype=torch.float32)
+        nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(R, T, U1, V)
+        ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
+        check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd(_addr(Ax), V, R * V, _addr(Cm), V, R * V, _addr(bias), _addr(labels),
+                                                     _addr(t_lens), _addr(u_lens), R, T, U1, V, int(blank), 1.0,
+                                                     _addr(nll), None, None, _addr(ws), nws, _stream()),
+              "rnnt_hip_joint_loss_fwd_bwd")
+        if want_grad and any(ctx.needs_input_grad[:4]):
+            ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, Ax, Cm, ws)
+            ctx.blank, ctx.group = int(blank), group
+            ctx.w_param, ctx.b_param = w_param, b_param
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        enc, dec, W, bias, labels, t_lens, u_lens, Ax, Cm, ws = ctx.saved_tensors
+        T, B, _ = enc.shape
+        U1, R, V, G = dec.shape[0], dec.shape[1], W.shape[0], ctx.group
+        gvec = _f32c(g.to(torch.float32), "grad of the loss")
+        dAx, dC = torch.empty_like(Ax), torch.empty_like(Cm)
+        check(_lib.lib().rnnt_hip_joint_loss_bwd_fastemit(_addr(Ax), V, R * V, _addr(Cm), V, R * V, _addr(bias), _addr(labels),
+                                                          _addr(t_lens), _addr(u_lens), R, T, U1, V, ctx.blank, 1.0, 0.0,
+                                                          _addr(gvec), 1, _addr(dAx), _addr(dC), _addr(ws), ws.numel(), _stream()),
+              "rnnt_hip_joint_loss_bwd_fastemit")
+        dAg = dAx.view(T, B, G, V)
+        dA = dAg[:, :, 0].contiguous()
+        for n in range(1, G):   # rank order, one addition per rank: the same bits on every run
+            dA.add_(dAg[:, :, n])
+        d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
+                                               _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
+        return d_enc, d_dec, dW, db, None, None, None, None, None, None
 
 
 class JointLogitsFn(torch.autograd.Function):
@@ -1388,6 +1451,27 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
     kernel would take (results do not depend on it).
     The cost per frame is bounded by beam_width, V and max_symbols: no cap can overflow.  One search launch, then one host copy
     of the counts and lengths (and one per returned array).  Argument errors raise ValueError before anything runs."""
+    tokens, lens, counts, scores, host, fused, fr = _beam_search_sync_run(
+        enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens, token_min_logp, frames,
+        fusion, step_group)
+    B, W = lens.shape
+    return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, fr)
+
+
+@torch.no_grad()
+def beam_search_sync_device(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
+                            cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam_width: int, max_symbols: int = 1,
+                            t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf):
+    """beam_search_sync with its results left on the device (MWER training packs them into loss inputs there):
+    -> (tokens (B, W, 1 + max_symbols*T) int32 with the leading blank, lens (B, W) int32, counts (B,) int32, scores (B, W) fp64,
+    host): `host` is the search's one host copy, a CPU int32 tensor counts | lens.  Entries of rank >= counts[b] are unwritten."""
+    return _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
+                                 token_min_logp, False, None, 0)[:5]
+
+
+def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
+                          token_min_logp, frames, fusion, step_group):
+    """The launch behind beam_search_sync and beam_search_sync_device -> (tokens, lens, counts, scores, host, fused, frames)."""
     check_beam_sync_args(beam_width, max_symbols, token_min_logp, "beam_search_sync")
     if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
         raise ValueError(f"beam_search_sync: step_group must be an integer >= 0, got {step_group!r}")
@@ -1435,7 +1519,129 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
     check(L.rnnt_hip_beam_sync_search(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None,
                                       _stream()), "rnnt_hip_beam_sync_search")
     host = small.cpu()   # the only host sync of the search
-    return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, fr)
+    return tokens, small[B:].view(B, W), small[:B], scores, host, fused, fr
+
+
+# --------------------------------------------------------------------------------------------------
+# MWER training (include/rnnt_hip.h: rnnt_hip_edit_distance / rnnt_hip_nbest_pack / rnnt_hip_mwer_risk, csrc/mwer.hip)
+# --------------------------------------------------------------------------------------------------
+MWER_MAX_LEN = 511     # tokens per sequence of the edit distance and per packed hypothesis: the loss's U + 1 <= 512
+MWER_MAX_NBEST = 64    # = the search's beam width limit
+
+
+def _i32c(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        got = (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{name} must be int32{'' if shape is None else ' of shape ' + str(tuple(shape))}, got {got}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+@torch.no_grad()
+def edit_distance(hyp: torch.Tensor, hyp_lens: torch.Tensor, ref: torch.Tensor, ref_lens: torch.Tensor,
+                  ref_div: int = 1) -> torch.Tensor:
+    """Levenshtein distances on the device (rnnt_hip_edit_distance): hyp (P, Lh) and ref (Q, Lr) int32 token rows with int32
+    lengths (P,) / (Q,); pair p compares hyp[p, :hyp_lens[p]] with ref[p // ref_div, :ref_lens[p // ref_div]], so ref_div
+    hypotheses share one reference (P = Q * ref_div).  -> (P,) int32, exact; what metrics.edit_distance gives on the host.
+    Rows of up to 511 tokens; what lies behind a row's length is not read."""
+    if isinstance(ref_div, bool) or not isinstance(ref_div, int) or ref_div < 1:
+        raise ValueError(f"edit_distance: ref_div must be a positive integer, got {ref_div!r}")
+    if not isinstance(hyp, torch.Tensor) or not isinstance(ref, torch.Tensor) or hyp.dim() != 2 or ref.dim() != 2:
+        raise ValueError("edit_distance: hyp and ref must be 2-D int32 tensors")
+    P, Q = hyp.shape[0], ref.shape[0]
+    if P < 1 or P != Q * ref_div:
+        raise ValueError(f"edit_distance: {P} hypothesis rows do not match {Q} reference rows x ref_div = {ref_div}")
+    if hyp.shape[1] > MWER_MAX_LEN or ref.shape[1] > MWER_MAX_LEN:
+        raise ValueError(f"edit_distance: rows of up to {MWER_MAX_LEN} tokens, got {hyp.shape[1]} / {ref.shape[1]}")
+    hyp, ref = _i32c(hyp, "edit_distance: hyp"), _i32c(ref, "edit_distance: ref")
+    hyp_lens, ref_lens = _i32c(hyp_lens, "edit_distance: hyp_lens", (P,)), _i32c(ref_lens, "edit_distance: ref_lens", (Q,))
+    _need_gpu(hyp, hyp_lens, ref, ref_lens)
+    Lh, Lr = hyp.shape[1], ref.shape[1]
+    if Lh == 0:   # an empty row still needs an address
+        hyp = torch.zeros(P, 1, device=hyp.device, dtype=torch.int32)
+    if Lr == 0:
+        ref = torch.zeros(Q, 1, device=ref.device, dtype=torch.int32)
+    dist = torch.empty(P, device=hyp.device, dtype=torch.int32)
+    check(_lib.lib().rnnt_hip_edit_distance(_addr(hyp), Lh, _addr(hyp_lens), _addr(ref), Lr, _addr(ref_lens), ref_div, P, _addr(dist),
+                                            _stream()), "rnnt_hip_edit_distance")
+    return dist
+
+
+def nbest_umax(host: torch.Tensor, B: int, N: int, max_hyp_len: int = MWER_MAX_LEN) -> int:
+    """The longest valid hypothesis (tokens behind the leading blank, at most max_hyp_len) in the search's host copy counts | lens;
+    at least 1.  Host arithmetic on what the search has already copied: no device sync."""
+    counts, lens = host[:B].tolist(), host[B:].reshape(B, N).tolist()
+    return max([1] + [lens[b][n] - 1 for b in range(B) for n in range(min(counts[b], N)) if lens[b][n] - 1 <= max_hyp_len])
+
+
+@torch.no_grad()
+def nbest_pack(tokens: torch.Tensor, lens: torch.Tensor, counts: torch.Tensor, frame_lens: torch.Tensor, Umax: int, blank: int,
+               max_hyp_len: int = MWER_MAX_LEN):
+    """The device results of beam_search_sync_device -> the loss's inputs for rows r = b*N + n (rnnt_hip_nbest_pack): tokens
+    (B, N, max_len) int32 with the leading blank, lens (B, N), counts (B,), frame_lens (B,) int32, Umax from nbest_umax.
+    -> texts (B*N, Umax+1) int64 (blank, hypothesis, blank padding), labels (B*N, Umax) int32, u_lens (B*N,), t_lens (B*N,)
+    (the utterance's frame count; 0 for an invalid row, which the loss answers with +inf and exact-zero gradients), valid (B*N,)
+    int32.  A row is invalid when its rank is >= counts[b] or its hypothesis is longer than max_hyp_len tokens."""
+    if not isinstance(tokens, torch.Tensor) or tokens.dim() != 3:
+        raise ValueError("nbest_pack: tokens must be (B, N, max_len) int32")
+    B, N, max_len = tokens.shape
+    for name, v, top in (("N", N, MWER_MAX_NBEST), ("Umax", Umax, MWER_MAX_LEN), ("max_hyp_len", max_hyp_len, MWER_MAX_LEN)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top:
+            raise ValueError(f"nbest_pack: {name} must be an integer in [1, {top}], got {v!r}")
+    if B < 1 or max_len < 1:
+        raise ValueError(f"nbest_pack: tokens {tuple(tokens.shape)} has an empty dimension")
+    tokens = _i32c(tokens, "nbest_pack: tokens")
+    lens, counts = _i32c(lens, "nbest_pack: lens", (B, N)), _i32c(counts, "nbest_pack: counts", (B,))
+    frame_lens = _i32c(frame_lens, "nbest_pack: frame_lens", (B,))
+    _need_gpu(tokens, lens, counts, frame_lens)
+    dev, R = tokens.device, B * N
+    texts = torch.empty(R, Umax + 1, device=dev, dtype=torch.int64)
+    labels = torch.empty(R, Umax, device=dev, dtype=torch.int32)
+    u_lens, t_lens, valid = (torch.empty(R, device=dev, dtype=torch.int32) for _ in range(3))
+    check(_lib.lib().rnnt_hip_nbest_pack(_addr(tokens), max_len, _addr(counts), _addr(lens), _addr(frame_lens), B, N, Umax, max_hyp_len,
+                                         int(blank), _addr(texts), _addr(labels), _addr(u_lens), _addr(t_lens), _addr(valid),
+                                         _stream()), "rnnt_hip_nbest_pack")
+    return texts, labels, u_lens, t_lens, valid
+
+
+class MwerRiskFn(torch.autograd.Function):
+    """Expected number of token errors over an n-best list, relative to the list's mean (rnnt_hip_mwer_risk, fp64 inside): nll
+    (B*N,) fp32 per-hypothesis losses, dist (B*N,) int32 edit distances, valid (B*N,) int32 -> risk (B,) fp32 (reduction "none"),
+    or its 0-d "mean" / "sum" over B.  The forward also stores d risk_b / d nll_j (B*N, exactly 0 for invalid rows); the backward
+    is those weights times the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, nll, dist, valid, N, reduction="none"):
+        if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= MWER_MAX_NBEST:
+            raise ValueError(f"mwer risk: N must be an integer in [1, {MWER_MAX_NBEST}], got {N!r}")
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"mwer risk: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if nll.dim() != 1 or nll.numel() < N or nll.numel() % N:
+            raise ValueError(f"mwer risk: nll must be (B*N,) with N = {N}, got {tuple(nll.shape)}")
+        R = nll.numel()
+        B = R // N
+        nll = _f32c(nll.detach(), "mwer risk: nll")
+        dist, valid = _i32c(dist, "mwer risk: dist", (R,)), _i32c(valid, "mwer risk: valid", (R,))
+        _need_gpu(nll, dist, valid)
+        risk = torch.empty(B, device=nll.device, dtype=torch.float32)
+        weights = torch.empty(R, device=nll.device, dtype=torch.float32)
+        check(_lib.lib().rnnt_hip_mwer_risk(_addr(nll), _addr(dist), _addr(valid), B, N, 1.0, _addr(risk), _addr(weights), _stream()),
+              "rnnt_hip_mwer_risk")
+        ctx.save_for_backward(weights)
+        ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
+        ctx.N = N
+        if ctx.red_scale is None:
+            return risk
+        out = torch.empty((), device=nll.device, dtype=torch.float32)
+        check(_lib.lib().rnnt_hip_scaled_sum_f32(_addr(risk), B, ctx.red_scale, _addr(out), _stream()), "rnnt_hip_scaled_sum_f32")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (weights,) = ctx.saved_tensors
+        g = g.to(torch.float32)
+        if ctx.red_scale is not None:
+            return weights * (g * ctx.red_scale), None, None, None, None
+        return (weights.view(-1, ctx.N) * g.unsqueeze(1)).reshape(-1), None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
