@@ -263,7 +263,9 @@ __device__ __forceinline__ int hp_xcd_remap(int bid, int n) {
 // one 256 x 256 output tile (`bid` = column-major tile index) over K-tiles [z * kt_per_split, ...) of problem p.
 // F16 (RNNT_GEMM_HP_F16): the one-product form — only hi.hi is multiplied and the lo fragments are never read from LDS (the planes
 // keep their hi | lo lines: the LDS-DMA still moves both halves)
-template <bool F16>
+// PLAIN: the caller guarantees no index table, no bias and the plain C map (c_div == 1) — what hp_gemm_grouped launches; the epilogue
+// then carries no code for them.
+template <bool F16, bool PLAIN>
 __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, const int z, char* lds) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -283,7 +285,7 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
       const int row = (8 * j + wave) * 8 + (lane >> 3);
       int ma = min(m0 + row, p.M - 1);
       const int nb = min(n0 + row, p.N - 1);  // rows past the edge re-read the last row (never stored)
-      if (p.a_rowidx) ma = p.a_rowidx[ma];
+      if (!PLAIN && p.a_rowidx) ma = p.a_rowidx[ma];
       va[j] = (unsigned)ma * p.a_pitch + 16u * src_slot;
       vb[j] = (unsigned)nb * p.b_pitch + 16u * src_slot;
     }
@@ -374,38 +376,137 @@ __device__ __forceinline__ void hp_tile256(const HpGemmK& p, const int bid, cons
     __syncthreads();   // drains the LDS-DMA of the next stage (vmcnt(0)) and fences this stage's reads
 #endif
   }
-  // epilogue: D block (i, j): lane -> rows 4*(lane>>4) + reg, column lane&15
+  // epilogue: D block (i, j): lane -> rows 4*(lane>>4) + reg, column lane&15.  A lane owns 32 rows x 4 columns.  Everything a store
+  // needs that is not an accumulator — the descale factor and the output offset of each row, the column factors, the bias — is loaded
+  // and computed BEFORE the first store of a half tile: vmcnt counts stores like loads, so a load between two stores makes the wave wait
+  // until the earlier store has reached L2 (one memory round trip per row, 32 in a row, with nothing else to run on the CU: 20 us of
+  // every round of tiles, 13 since).
   const int mode = p.splits > 1 ? 0 : ((p.flags & RNNT_GEMM_ACCUM) ? 2 : 1);  // uniform: slab | store | accumulate
-  float* slab = p.splits > 1 ? p.slab + (long)z * p.M * p.N : nullptr;
+  // the output map of this launch: the slab of split z is a dense (M x N) matrix
+  float* const cbase = mode == 0 ? p.slab + (long)z * p.M * p.N : p.C;
+  const long c_so = mode == 0 ? (long)p.N : p.c_so, c_si = mode == 0 ? 0l : p.c_si;
+  const int c_div = (PLAIN || mode == 0) ? 1 : p.c_div;
+  const int* const a_rowidx = PLAIN ? nullptr : p.a_rowidx;
+  const int* const c_rowidx = (PLAIN || mode == 0) ? nullptr : p.c_rowidx;
+  const float* const bias = (PLAIN || mode == 0) ? nullptr : p.bias;
+  const int ncol = n0 + wc * 64 + (lane & 15);   // column of block j: ncol + 16 j
   float bias_v[4], sb[4];
+  bool nok[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-    bias_v[j] = (mode != 0 && p.bias && n < p.N) ? p.bias[n] : 0.f;
+    const int n = ncol + j * 16;
+    nok[j] = n < p.N;
+    bias_v[j] = 0.f;
     sb[j] = hp_inv_scale_from_amax(p.b_amax[min(n, p.N - 1)]);
   }
+  if (bias) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+    for (int j = 0; j < 4; ++j) {
+      const float bv = bias[min(ncol + j * 16, p.N - 1)];
+      bias_v[j] = nok[j] ? bv : 0.f;
+    }
+  }
+  const int mrow = m0 + wr * 128 + 4 * (lane >> 4);   // row of (block i, register reg): mrow + 16 i + reg
+  // 32-bit byte offsets from one base through a buffer resource of HP_C_SPAN bytes: a masked row or column takes the offset HP_C_OOB,
+  // which the range check drops (a store) or answers with 0 (a load) — no branch around a memory instruction, so the compiler counts
+  // what is in flight instead of draining it.  The 64 j bytes of column block j ride in the instruction's scalar offset, which the range
+  // check leaves out (HP_C_LIMIT keeps them inside the span).
+  constexpr unsigned HP_C_SPAN = 0x80000000u, HP_C_OOB = 0x80000000u, HP_C_LIMIT = HP_C_SPAN - 256u;
+  // (the base is the same in every lane; said so, or the queue-driven kernel wraps every buffer instruction in a waterfall loop)
+  const unsigned long cb = reinterpret_cast<unsigned long>(cbase);
+  float* const cbase_u = reinterpret_cast<float*>(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(cb >> 32)) << 32) |
+                                                  (unsigned)__builtin_amdgcn_readfirstlane((int)cb));
+  auto c_row = [&](int mo) -> long { return (long)(mo / c_div) * c_so + (long)(mo % c_div) * c_si; };   // element offset of output row mo
+  // Two halves of 64 rows per wave (16 per lane): with the tables of all 32 rows and their index loads in flight the compiler spills
+  // beside the 128 accumulators (the second half's loads wait for the first half's stores: one drain per tile).
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int m = m0 + wr * 128 + i * 16 + 4 * (lane >> 4) + reg;
-      const bool mok = m < p.M;
-      const int mc = mok ? m : 0;
-      const float sa = hp_inv_scale_from_amax(p.a_amax[p.a_rowidx ? p.a_rowidx[mc] : mc]);
-      const int mo = p.c_rowidx ? p.c_rowidx[mc] : mc;
-      float* crow = mode == 0 ? slab + (long)mc * p.N : p.C + (long)(mo / p.c_div) * p.c_so + (long)(mo % p.c_div) * p.c_si;
-      float old[4] = {0.f, 0.f, 0.f, 0.f};
-      if (mode == 2) {
+  for (int h = 0; h < 2; ++h) {
+    float sa[16];
+    unsigned roff[16];
+    bool fits = true;
+    {
+      int ar[16], mo[16];   // plane row of A and output row, per row of this half (rows past M: row 0, never stored)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-          if (mok && n < p.N) old[j] = crow[n];
-        }
+      for (int r = 0; r < 16; ++r) {
+        const int m = mrow + 16 * (4 * h + (r >> 2)) + (r & 3);
+        ar[r] = mo[r] = m < p.M ? m : 0;
+      }
+      if (a_rowidx) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ar[r] = a_rowidx[ar[r]];
+      }
+      if (c_rowidx) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mo[r] = c_rowidx[mo[r]];
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wc * 64 + j * 16 + (lane & 15);
-        if (mok && n < p.N) crow[n] = acc[i][j][reg] * sa * sb[j] + bias_v[j] + old[j];
+      for (int r = 0; r < 16; ++r) sa[r] = hp_inv_scale_from_amax(p.a_amax[ar[r]]);
+      auto set_row = [&](int r, long elem) {
+        const bool mok = mrow + 16 * (4 * h + (r >> 2)) + (r & 3) < p.M;
+        const long b = (elem + ncol) * 4;
+        fits = fits && (!mok || (unsigned long)b < (unsigned long)HP_C_LIMIT);
+        roff[r] = mok ? (unsigned)b : HP_C_OOB;
+      };
+      if (c_div == 1) {   // the common map costs no division
+#pragma unroll
+        for (int r = 0; r < 16; ++r) set_row(r, (long)mo[r] * c_so);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) set_row(r, c_row(mo[r]));
+      }
+    }
+    if (__builtin_amdgcn_ballot_w64(!fits) == 0) {   // (uniform per wave) every row this wave stores lies within 2 GB of the base
+      const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(cbase_u, 0, (int)HP_C_SPAN, HP_RSRC);
+      if (mode == 2) {
+        // accumulate: the old values of a 16-row block are loaded before that block's stores: 8 load -> store turnarounds per tile
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+          float old[4][4];
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              old[reg][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(nok[j] ? roff[4 * ii + reg] : HP_C_OOB), 64 * j, 0));
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float v = acc[4 * h + ii][j][reg] * sa[4 * ii + reg] * sb[j] + bias_v[j] + old[reg][j];
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rc, (int)(nok[j] ? roff[4 * ii + reg] : HP_C_OOB), 64 * j, 0);
+            }
+        }
+      } else {
+        const float old = 0.f;   // (the sum keeps its shape: x + 0 turns a -0 into +0)
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float v = acc[4 * h + ii][j][reg] * sa[4 * ii + reg] * sb[j] + bias_v[j] + old;
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rc, (int)(nok[j] ? roff[4 * ii + reg] : HP_C_OOB), 64 * j, 0);
+            }
+      }
+      continue;
+    }
+    // the addressed span of C does not fit 32-bit offsets (or a stride is negative): 64-bit addresses per row
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int m = mrow + 16 * (4 * h + ii) + reg;
+        const bool mok = m < p.M;
+        const int mc = mok ? m : 0;
+        float* crow = cbase + c_row(c_rowidx ? c_rowidx[mc] : mc);
+        float old[4] = {0.f, 0.f, 0.f, 0.f};
+        if (mode == 2) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (mok && nok[j]) old[j] = crow[ncol + 16 * j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (mok && nok[j]) crow[ncol + 16 * j] = acc[4 * h + ii][j][reg] * sa[4 * ii + reg] * sb[j] + bias_v[j] + old[j];
       }
     }
   }
@@ -429,7 +530,7 @@ __global__ void __launch_bounds__(512, 1) gemm_hp_kernel(const HpGemmK p) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int bid = hp_xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   if (p.group_m > 0) bid = hp_grouped_tile(bid, p.tiles_m, p.tiles_n, p.group_m);
-  hp_tile256<F16>(p, bid, blockIdx.y, lds);
+  hp_tile256<F16, false>(p, bid, blockIdx.y, lds);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -487,7 +588,7 @@ __global__ void __launch_bounds__(512, 1) gemm_hpq_kernel(const HpGemmQ q) {
       const HpGemmK& p = q.prob[pi];
       const int local = u - (pi ? q.unit_end[pi - 1] : 0);
       const int tn = local % p.tiles_n, z = (local / p.tiles_n) % p.splits, tm = local / (p.tiles_n * p.splits);
-      hp_tile256<F16>(p, tn * p.tiles_m + tm, z, lds);
+      hp_tile256<F16, true>(p, tn * p.tiles_m + tm, z, lds);
     }
   }
 }
