@@ -1060,6 +1060,56 @@ int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc* d, const r
                                     const rnnt_beam_timing* timing /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Backoff n-gram fusion for the searches whose cost per frame is bounded: the frame-synchronous transducer search, its
+ * streaming form and the CTC prefix beam search.  csrc/search_shared.hpp (ngram_lookup), DESIGN.md §23.
+ * The automaton of rnnt_beam_fusion in sparse (CSR) form: one state per context of a backoff n-gram model, whose row lists only
+ * the tokens the model lists after that context; every other token backs off.  Device tables:
+ *   row_ptr (S+1) int32    arcs of state s are [row_ptr[s], row_ptr[s+1])
+ *   tok     (E)   int32    token ids, strictly ascending inside a state
+ *   arc     (E)   float32  the score of that append (weight * ln p)
+ *   next    (E)   int32    state after the append
+ *   bow     (S)   float32  the score of backing off from s (weight * ln backoff)
+ *   backoff (S)   int32    where s backs off to; the root backs off to itself
+ *   final   (S)   float32  added once, only when a hypothesis is ranked for output
+ * State 0 is the start state.  The root's row lists every token 0..V-1 (so n_arcs >= V), which ends every lookup.
+ * Lookup of token k in state s:
+ *     acc = 0.0 (fp64); h = s
+ *     repeat at most `order` times:
+ *         if k is listed in h at e:  return arc' = (float)(acc + (double)arc[e]),  next[e]
+ *         if h == root: break
+ *         acc += (double)bow[h];  h = backoff[h]
+ *     return (float)acc, root            (unreachable with tables as described)
+ * arc' enters the search exactly where the dense arc[s*V + k] does, as (double)arc' added to the fp64 total in append order, and
+ * next where the dense next does: a dense rnnt_beam_fusion filled with arc' and next for every (s, k) gives the same bits.
+ * On the device every index read from a table is clamped into its range and the walk is bounded by order <= 8: tables that
+ * break the description cost a wrong score, never an out-of-range read or an unbounded loop.
+ * The *_ngram entries take the descriptor, the workspace and every other argument of the entry they extend, unchanged; they run
+ * the backoff instance of the same kernel template.  Checked on the host before any launch (RNNT_ERR_INVALID), beside the
+ * extended entry's own checks: a NULL struct or table, n_states >= 1, 0 <= root < n_states, 1 <= order <= 8, n_arcs >= V, a
+ * non-NULL fused_scores.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_ngram {
+  const int32_t* row_ptr; /* (S+1) device */
+  const int32_t* tok;     /* (E) device */
+  const float* arc;       /* (E) device */
+  const int32_t* next;    /* (E) device */
+  const float* bow;       /* (S) device */
+  const int32_t* backoff; /* (S) device */
+  const float* final;     /* (S) device */
+  int32_t root, order;    /* the empty context's state; the longest walk, in [1,8] */
+  int32_t n_states, n_arcs; /* S >= 1, E >= V */
+  double* fused_scores;   /* (B, beam) device, beside scores: score + total + final[state] */
+} rnnt_beam_ngram;
+int rnnt_hip_beam_sync_search_ngram(const rnnt_beam_sync_desc* d, const rnnt_beam_ngram* lm, const rnnt_beam_timing* timing /* or NULL */,
+                                    void* stream);
+int rnnt_hip_beam_sync_stream_chunk_ngram(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_ngram* lm,
+                                          const rnnt_beam_timing* timing /* or NULL */, void* stream);
+int rnnt_hip_ctc_beam_search_ngram(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
+                                   int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_ngram* lm,
+                                   int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

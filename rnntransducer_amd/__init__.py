@@ -2,10 +2,10 @@
 a C ABI, see include/rnnt_hip.h), exposed through the reference's own module surface."""
 from .data import AudioDataLoader, collate_batch
 from .frontend import LogMelFrontend, spec_augment
-from .fusion import TokenFusion
+from .fusion import NgramFusion, TokenFusion
 from .loss import CTCLoss, RNNTLoss
 from .model import RNNTransducer
 from .networks import AudioTransNet, JointNet, TextPredNet
 
 __all__ = ["RNNTransducer", "JointNet", "AudioTransNet", "TextPredNet", "RNNTLoss", "CTCLoss", "LogMelFrontend", "spec_augment",
-           "AudioDataLoader", "collate_batch", "TokenFusion"]
+           "AudioDataLoader", "collate_batch", "TokenFusion", "NgramFusion"]

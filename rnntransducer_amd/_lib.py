@@ -185,6 +185,12 @@ class BeamFusion(C.Structure):
                 ("fused_scores", C.c_void_p)]
 
 
+class BeamNgram(C.Structure):
+    _fields_ = [("row_ptr", C.c_void_p), ("tok", C.c_void_p), ("arc", C.c_void_p), ("next", C.c_void_p), ("bow", C.c_void_p),
+                ("backoff", C.c_void_p), ("final", C.c_void_p), ("root", c_i32), ("order", c_i32), ("n_states", c_i32),
+                ("n_arcs", c_i32), ("fused_scores", C.c_void_p)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -305,6 +311,12 @@ SYMBOLS = {
     "rnnt_hip_beam_sync_stream_reset": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.c_void_p, c_i32, c_i32, C.c_void_p]),
     "rnnt_hip_beam_sync_stream_chunk": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.POINTER(BeamFusion), C.POINTER(BeamTiming),
                                                   C.c_void_p]),
+    "rnnt_hip_beam_sync_search_ngram": (C.c_int, [C.POINTER(BeamSyncDesc), C.POINTER(BeamNgram), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_sync_stream_chunk_ngram": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.POINTER(BeamNgram), C.POINTER(BeamTiming),
+                                                        C.c_void_p]),
+    "rnnt_hip_ctc_beam_search_ngram": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float,
+                                                 C.POINTER(BeamNgram), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_edit_distance": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, C.c_void_p,

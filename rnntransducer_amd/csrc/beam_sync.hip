@@ -42,7 +42,7 @@
 // State slots (h | c | Cv) live in the caller's workspace, (S+2) W per utterance: W for the beam, (S-1) W for the rounds'
 // children, W for the next beam's pending steps; the free list is rebuilt at every frame's start from the slots the beam holds.
 // All score sums are fp64 with logaddexp_d in the fixed order above: bitwise reproducible.
-// The kernel (beam_sync_kernel<FUSED, STREAM>) lives in beam_sync_shared.hpp: this file launches its STREAM = false instances,
+// The kernel (beam_sync_kernel<FUSE, STREAM>) lives in beam_sync_shared.hpp: this file launches its STREAM = false instances,
 // beam_sync_stream.hip the streaming ones.
 #include "beam_sync_shared.hpp"
 
@@ -100,9 +100,9 @@ extern "C" int rnnt_hip_beam_sync_step_group(const rnnt_beam_sync_desc* d) {
   return bs_group(d);
 }
 
-extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_timing* timing,
-                                         void* stream) {
-  const char* who = "beam_sync_search";
+// the search behind both entries: fusion (dense tables), lm (backoff tables), or neither
+static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm, bool ngram,
+                     const rnnt_beam_timing* timing, void* stream, const char* who) {
   int rc = bs_check_dims(d, who);
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->A && d->tokens && d->lens && d->scores && d->count, "%s: null A/tokens/lens/scores/count", who);
@@ -112,6 +112,8 @@ extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnn
   BsK k;
   if ((rc = fill_prednet<true>(d, k, who)) != RNNT_OK) return rc;
   if (fusion && (rc = check_fusion_struct(fusion, d->V, who)) != RNNT_OK) return rc;
+  k.ng = NgramLm{};
+  if (ngram && (rc = check_ngram_struct(lm, d->V, k.ng, who)) != RNNT_OK) return rc;
   const BsWs w = carve_bs(d->workspace, d);
   RNNT_CHECK_ARG(d->workspace && d->workspace_bytes >= w.total, "%s: workspace too small (%zu < %zu)", who, d->workspace_bytes, w.total);
   RNNT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
@@ -124,9 +126,12 @@ extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnn
   k.frames = timing ? timing->frames : nullptr;
   k.fnext = fusion ? fusion->next : nullptr; k.farc = fusion ? fusion->arc : nullptr; k.ffinal = fusion ? fusion->final : nullptr;
   k.n_states = fusion ? fusion->n_states : 1; k.fused = fusion ? fusion->fused_scores : nullptr;
+  if (ngram) { k.ffinal = lm->final; k.n_states = lm->n_states; k.fused = lm->fused_scores; }
   const size_t lds = (size_t)k.G * bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  const void* fn = fusion ? (const void*)beam_sync_kernel<true, false> : (const void*)beam_sync_kernel<false, false>;
+  const void* fn = ngram    ? (const void*)beam_sync_kernel<FUSE_NGRAM, false>
+                   : fusion ? (const void*)beam_sync_kernel<FUSE_DENSE, false>
+                            : (const void*)beam_sync_kernel<FUSE_NONE, false>;
   if (lds + sizeof(BsShared) > 64 * 1024) RNNT_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V * d->beam, s);
   BeamK tk{};   // the layer-0 input table: the beam search's kernel, the same matvec and so the same bits
@@ -134,8 +139,19 @@ extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnn
   tk.table = w.table;
   hipLaunchKernelGGL(beam_table_kernel, dim3(d->V), dim3(DEC_THREADS), (size_t)d->Hp * sizeof(float), s, tk);
   RNNT_CHECK_LAUNCH();
-  if (fusion) hipLaunchKernelGGL((beam_sync_kernel<true, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
-  else hipLaunchKernelGGL((beam_sync_kernel<false, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (fusion) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else hipLaunchKernelGGL((beam_sync_kernel<FUSE_NONE, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_timing* timing,
+                                         void* stream) {
+  return bs_search(d, fusion, nullptr, false, timing, stream, "beam_sync_search");
+}
+
+extern "C" int rnnt_hip_beam_sync_search_ngram(const rnnt_beam_sync_desc* d, const rnnt_beam_ngram* lm, const rnnt_beam_timing* timing,
+                                               void* stream) {
+  return bs_search(d, nullptr, lm, true, timing, stream, "beam_sync_search_ngram");
 }

@@ -1,4 +1,4 @@
-// The kernel of the frame-synchronous transducer beam search, beam_sync_kernel<FUSED, STREAM>, and what its two launchers share:
+// The kernel of the frame-synchronous transducer beam search, beam_sync_kernel<FUSE, STREAM>, and what its two launchers share:
 // beam_sync.hip (the offline entry, STREAM = false; the definition and the kernel's plan stand at its top) and
 // beam_sync_stream.hip (the search fed in chunks, STREAM = true).  STREAM adds only what lies around the frame
 // loop: the load of the carried beam in place of the seed, the prefix-tree collection (bs_collect, at the chunk's end and at the
@@ -72,6 +72,7 @@ struct BsK : PredNet {
   const float* farc;
   const float* ffinal;
   int n_states;
+  NgramLm ng;           // FUSE_NGRAM: the backoff tables in place of fnext / farc (ffinal, n_states and fused serve both)
   double* fused;
   // STREAM (beam_sync_stream.hip): stream b's carried state is the workspace part at ws + b * ws_stride, laid out by the off_*
   char* ws;
@@ -376,8 +377,11 @@ __device__ __forceinline__ void bs_collect(BsShared& sh, const PrefixTree& nd, i
   __syncthreads();
 }
 
-template <bool FUSED, bool STREAM>
+// FUSE: the fusion policy (search_shared.hpp).  FUSE_DENSE reads farc / fnext at (state, token); FUSE_NGRAM asks ngram_lookup
+// for the same two values at the same two places, the candidate-key fill and the build of the selected children.
+template <int FUSE, bool STREAM>
 __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
+  constexpr bool FUSED = FUSE != FUSE_NONE;
   __shared__ BsShared sh;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -493,7 +497,10 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
           if (v == blank || lp >= p.min_logp) {
             const double val = sc + (double)lp;
             double k = val;
-            if (FUSED) k = val + (v == blank ? tt : tt + (double)p.farc[(long)st * V + v]);
+            if constexpr (FUSE == FUSE_NGRAM) {   // only a candidate that passed the prune walks the tables
+              int unused;
+              k = val + (v == blank ? tt : tt + (double)ngram_lookup(p.ng, st, v, unused));
+            } else if (FUSED) k = val + (v == blank ? tt : tt + (double)p.farc[(long)st * V + v]);
             if (val > NEG_INF && k > NEG_INF) key = sortable_key(k);   // (NaN compares false: dropped)
           }
           ck[(long)i * V + v] = key;
@@ -524,7 +531,12 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
           sh.rpar[rank] = -1;
           sh.tod[rank] = 1;
         } else {
-          if (FUSED) {
+          if constexpr (FUSE == FUSE_NGRAM) {
+            int ns;
+            const float arc = ngram_lookup(p.ng, c.st[i], v, ns);   // the fill's value: the same walk, the same bits
+            sh.rtot[rank] = c.tot[i] + (double)arc;
+            sh.rst[rank] = ns;
+          } else if (FUSED) {
             const long o = (long)c.st[i] * V + v;
             sh.rtot[rank] = c.tot[i] + (double)p.farc[o];
             sh.rst[rank] = clampi(p.fnext[o], 0, p.n_states - 1);
@@ -633,7 +645,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
   }
 
   // ---- output: stable order by score (FUSED: score + total + final[state]), then the back-trace of every hypothesis
-  if (tid < nA) sh.rval[tid] = FUSED ? (a.score[tid] + a.tot[tid]) + (double)p.ffinal[a.st[tid]] : a.score[tid];
+  if (tid < nA) sh.rval[tid] = FUSED ? (a.score[tid] + a.tot[tid]) + (double)p.ffinal[FUSE == FUSE_NGRAM ? clampi(a.st[tid], 0, p.n_states - 1) : a.st[tid]] : a.score[tid];
   __syncthreads();
   if (tid < nA) {
     const double key = sh.rval[tid];

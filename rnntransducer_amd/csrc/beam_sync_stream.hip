@@ -1,5 +1,5 @@
 // Streaming frame-synchronous beam search: rnnt_hip_beam_sync_search's search fed in chunks (semantics in include/rnnt_hip.h,
-// DESIGN.md §21).  The kernel is beam_sync_kernel<FUSED, true> of beam_sync_shared.hpp: the offline frame loop, started from the
+// DESIGN.md §21).  The kernel is beam_sync_kernel<FUSE, true> of beam_sync_shared.hpp: the offline frame loop, started from the
 // carried beam of the stream's workspace instead of the seed, with the prefix-tree collection (bs_collect) at the chunk's end
 // and wherever a frame would not find W S free node slots.  One launch per chunk, one workgroup per stream; a stream's part of
 // the workspace is touched only by its workgroup, so a stream's result cannot depend on the others.  Chunk invariance: A is
@@ -79,7 +79,7 @@ int bss_fill(const rnnt_beam_sync_stream_desc* d, BsK& k, const char* who) {
   k.slots = nullptr; k.keys = nullptr; k.nodes = nullptr;
   k.SF = l.SF; k.NS = l.NS; k.maxn = d->max_nodes; k.max_len = d->max_len;
   k.tokens = nullptr; k.lens = nullptr; k.scores = nullptr; k.counts = nullptr; k.frames = nullptr;
-  k.fnext = nullptr; k.farc = nullptr; k.ffinal = nullptr; k.n_states = 1; k.fused = nullptr;
+  k.fnext = nullptr; k.farc = nullptr; k.ffinal = nullptr; k.n_states = 1; k.fused = nullptr; k.ng = NgramLm{};
   k.ws = reinterpret_cast<char*>(d->workspace) + l.table_bytes;
   k.ws_stride = l.stride;
   k.off_beam = l.off_beam; k.off_slots = l.off_slots; k.off_keys = l.off_keys; k.off_nodes = l.off_nodes;
@@ -123,9 +123,9 @@ extern "C" int rnnt_hip_beam_sync_stream_reset(const rnnt_beam_sync_stream_desc*
   return RNNT_OK;
 }
 
-extern "C" int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion,
-                                               const rnnt_beam_timing* timing, void* stream) {
-  const char* who = "beam_sync_stream_chunk";
+// the chunk call behind both entries: fusion (dense tables), lm (backoff tables), or neither
+static int bss_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm, bool ngram,
+                     const rnnt_beam_timing* timing, void* stream, const char* who) {
   BsK k;
   int rc = bss_fill(d, k, who);
   if (rc != RNNT_OK) return rc;
@@ -137,6 +137,7 @@ extern "C" int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc*
   RNNT_CHECK_ARG(timing == nullptr || (timing->frames && timing->commit_frames),
                  "%s: timing given without its outputs (frames, commit_frames)", who);
   if (fusion && (rc = check_fusion_struct(fusion, d->V, who)) != RNNT_OK) return rc;
+  if (ngram && (rc = check_ngram_struct(lm, d->V, k.ng, who)) != RNNT_OK) return rc;
   k.A = d->A; k.a_st = (long)d->a_st; k.a_sb = (long)d->a_sb; k.t_lens = d->lens;
   k.tokens = d->tokens; k.lens = d->out_lens; k.scores = d->scores; k.counts = d->count;
   k.status = d->status; k.commit = d->commit; k.ncommit = d->ncommit;
@@ -144,13 +145,27 @@ extern "C" int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc*
   k.frames = timing ? timing->frames : nullptr; k.commit_frames = timing ? timing->commit_frames : nullptr;
   k.fnext = fusion ? fusion->next : nullptr; k.farc = fusion ? fusion->arc : nullptr; k.ffinal = fusion ? fusion->final : nullptr;
   k.n_states = fusion ? fusion->n_states : 1; k.fused = fusion ? fusion->fused_scores : nullptr;
+  if (ngram) { k.ffinal = lm->final; k.n_states = lm->n_states; k.fused = lm->fused_scores; }
   const size_t lds = (size_t)k.G * bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  const void* fn = fusion ? (const void*)beam_sync_kernel<true, true> : (const void*)beam_sync_kernel<false, true>;
+  const void* fn = ngram    ? (const void*)beam_sync_kernel<FUSE_NGRAM, true>
+                   : fusion ? (const void*)beam_sync_kernel<FUSE_DENSE, true>
+                            : (const void*)beam_sync_kernel<FUSE_NONE, true>;
   if (lds + sizeof(BsShared) > 64 * 1024) RNNT_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V * d->beam, s);
-  if (fusion) hipLaunchKernelGGL((beam_sync_kernel<true, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
-  else hipLaunchKernelGGL((beam_sync_kernel<false, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (fusion) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else hipLaunchKernelGGL((beam_sync_kernel<FUSE_NONE, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion,
+                                               const rnnt_beam_timing* timing, void* stream) {
+  return bss_chunk(d, fusion, nullptr, false, timing, stream, "beam_sync_stream_chunk");
+}
+
+extern "C" int rnnt_hip_beam_sync_stream_chunk_ngram(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_ngram* lm,
+                                                     const rnnt_beam_timing* timing, void* stream) {
+  return bss_chunk(d, nullptr, lm, true, timing, stream, "beam_sync_stream_chunk_ngram");
 }

@@ -45,7 +45,9 @@ struct CbShared {
   int nnodes;
 };
 
-template <bool FUSED>
+// FUSE: the fusion policy (search_shared.hpp).  FUSE_DENSE reads farc / fnext at (state, token); FUSE_NGRAM asks ngram_lookup (ng)
+// for the same two values at the same two places, the candidate-key fill and the build of the selected extensions.
+template <int FUSE>
 __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __restrict__ Z, long z_sb, long z_st,
                                                               const int* __restrict__ t_lens, int T, int V, int blank, int W,
                                                               float min_logp, const int* __restrict__ fnext,
@@ -54,7 +56,8 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
                                                               int* __restrict__ node_ws, int* __restrict__ tokens,
                                                               int* __restrict__ lens, double* __restrict__ scores,
                                                               double* __restrict__ fused, int* __restrict__ frames,
-                                                              int* __restrict__ counts) {
+                                                              int* __restrict__ counts, const NgramLm ng) {
+  constexpr bool FUSED = FUSE != FUSE_NONE;
   __shared__ CbShared sh;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Tb = clampi(t_lens[b], 0, T);
@@ -137,7 +140,10 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
         const float lk = z[k] - l;
         if (k != blank && lk >= min_logp) {
           double x = (k == c.tok[r] ? c.pb[r] : sh.p[r]) + (double)lk;
-          if (FUSED) x += c.tot[r] + (double)farc[(long)c.st[r] * V + k];
+          if constexpr (FUSE == FUSE_NGRAM) {   // only a candidate that passed the prune walks the tables
+            int unused;
+            x += c.tot[r] + (double)ngram_lookup(ng, c.st[r], k, unused);
+          } else if (FUSED) x += c.tot[r] + (double)farc[(long)c.st[r] * V + k];
           if (x > NEG_INF) key = sortable_key(x);
         }
       }
@@ -167,7 +173,12 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
         const float lk = z[kk] - l;
         nw.pb[rank] = NEG_INF;
         nw.pnb[rank] = (kk == c.tok[r] ? c.pb[r] : sh.p[r]) + (double)lk;
-        if (FUSED) {
+        if constexpr (FUSE == FUSE_NGRAM) {
+          int ns;
+          const float arc = ngram_lookup(ng, c.st[r], kk, ns);   // the fill's value: the same walk, the same bits
+          nw.tot[rank] = c.tot[r] + (double)arc;
+          nw.st[rank] = ns;
+        } else if (FUSED) {
           const long o = (long)c.st[r] * V + kk;
           nw.tot[rank] = c.tot[r] + (double)farc[o];
           nw.st[rank] = clampi(fnext[o], 0, n_states - 1);
@@ -199,7 +210,7 @@ __global__ void __launch_bounds__(CB_THREADS) ctc_beam_kernel(const float* __res
   if (tid < n) {
     const double sc = logaddexp_d(c.pb[tid], c.pnb[tid]);
     sh.p[tid] = sc;
-    sh.cpb[tid] = FUSED ? (sc + c.tot[tid]) + (double)ffinal[c.st[tid]] : sc;
+    sh.cpb[tid] = FUSED ? (sc + c.tot[tid]) + (double)ffinal[FUSE == FUSE_NGRAM ? clampi(c.st[tid], 0, n_states - 1) : c.st[tid]] : sc;
   }
   __syncthreads();
   if (tid < n) {
@@ -244,10 +255,11 @@ extern "C" size_t rnnt_hip_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_
   return carve_cb(nullptr, B, T, V, W).total;
 }
 
-extern "C" int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
-                                        int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_fusion* fusion,
-                                        int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts,
-                                        void* workspace, size_t workspace_bytes, void* stream) {
+// the search behind both entries: fusion (dense tables), lm (backoff tables), or neither
+static int cb_search(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T, int32_t V,
+                     int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm,
+                     bool ngram, int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   RNNT_CHECK_ARG(B >= 1 && T >= 1, "ctc_beam_search: B and T must be positive (B=%d T=%d)", B, T);
   RNNT_CHECK_ARG(W >= 1 && W <= CB_WMAX, "ctc_beam_search: beam width W = %d outside [1,%d]", W, CB_WMAX);
   RNNT_CHECK_ARG(V >= 2, "ctc_beam_search: V = %d < 2 (a blank and at least one token)", V);
@@ -260,19 +272,41 @@ extern "C" int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64
   RNNT_CHECK_ARG(z_sb >= 1 && z_st >= V, "ctc_beam_search: logits strides (z_sb = %lld, z_st = %lld) must be positive, z_st >= V",
                  (long long)z_sb, (long long)z_st);
   if (fusion && (rc = check_fusion_struct(fusion, V, "ctc_beam_search")) != RNNT_OK) return rc;
+  NgramLm ng{};
+  if (ngram && (rc = check_ngram_struct(lm, V, ng, "ctc_beam_search_ngram")) != RNNT_OK) return rc;
   const CbWs w = carve_cb(workspace, B, T, V, W);
   RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_beam_search: workspace too small (%zu < %zu)", workspace_bytes, w.total);
   RNNT_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "ctc_beam_search: workspace must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)B * T * V * (1.0 + W), s);
-  if (fusion)
-    hipLaunchKernelGGL((ctc_beam_kernel<true>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
+  if (ngram)
+    hipLaunchKernelGGL((ctc_beam_kernel<FUSE_NGRAM>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank,
+                       W, token_min_logp, (const int*)nullptr, (const float*)nullptr, lm->final, lm->n_states, w.lse, w.keys, w.nodes,
+                       tokens, lens, scores, lm->fused_scores, frames, counts, ng);
+  else if (fusion)
+    hipLaunchKernelGGL((ctc_beam_kernel<FUSE_DENSE>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
                        token_min_logp, fusion->next, fusion->arc, fusion->final, fusion->n_states, w.lse, w.keys, w.nodes, tokens,
-                       lens, scores, fusion->fused_scores, frames, counts);
+                       lens, scores, fusion->fused_scores, frames, counts, ng);
   else
-    hipLaunchKernelGGL((ctc_beam_kernel<false>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
+    hipLaunchKernelGGL((ctc_beam_kernel<FUSE_NONE>), dim3(B), dim3(CB_THREADS), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, W,
                        token_min_logp, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr, 1, w.lse, w.keys, w.nodes,
-                       tokens, lens, scores, (double*)nullptr, frames, counts);
+                       tokens, lens, scores, (double*)nullptr, frames, counts, ng);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_ctc_beam_search(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
+                                        int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_fusion* fusion,
+                                        int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  return cb_search(logits, z_sb, z_st, t_lens, B, T, V, blank, W, token_min_logp, fusion, nullptr, false, tokens, lens, scores, frames,
+                   counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rnnt_hip_ctc_beam_search_ngram(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
+                                              int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_ngram* lm,
+                                              int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  return cb_search(logits, z_sb, z_st, t_lens, B, T, V, blank, W, token_min_logp, nullptr, lm, true, tokens, lens, scores, frames, counts,
+                   workspace, workspace_bytes, stream);
 }

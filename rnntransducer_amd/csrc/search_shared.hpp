@@ -19,6 +19,50 @@ __device__ __forceinline__ u64 sortable_key(double x) {
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
+// ---- fusion policies ----------------------------------------------------------------------------------------------------
+// How a search kernel reads its automaton: not at all, the dense (S, V) tables of rnnt_beam_fusion, or the backoff n-gram
+// tables of rnnt_beam_ngram through ngram_lookup.
+enum { FUSE_NONE = 0, FUSE_DENSE = 1, FUSE_NGRAM = 2 };
+constexpr int NGRAM_MAX_ORDER = 8;
+
+struct NgramLm {   // rnnt_beam_ngram's tables (include/rnnt_hip.h), checked by check_ngram_struct
+  const int *row_ptr, *tok, *next, *backoff;
+  const float *arc, *bow;
+  int root, order, n_states, n_arcs;
+};
+
+// The lookup of include/rnnt_hip.h (rnnt_beam_ngram): the float32 the append of token k in state s adds, and the state after
+// it.  Per level a binary search of the state's row (the root lists every token, so entry k of its row is tried first).  Every
+// index read from a table is clamped into the table it indexes, the search of a row is bounded by 32 halvings and the walk by
+// order <= NGRAM_MAX_ORDER levels: tables that break the contract give a wrong score, nothing else.  k in [0, V), V <= n_arcs.
+__device__ __forceinline__ float ngram_lookup(const NgramLm& g, int s, int k, int& nxt) {
+  double acc = 0.0;
+  int h = clampi(s, 0, g.n_states - 1);
+  for (int lvl = 0; lvl < NGRAM_MAX_ORDER && lvl < g.order; ++lvl) {
+    const int lo = clampi(g.row_ptr[h], 0, g.n_arcs), hi = clampi(g.row_ptr[h + 1], lo, g.n_arcs);
+    int e = -1;
+    if (h == g.root && k < hi - lo && g.tok[lo + k] == k) e = lo + k;
+    if (e < 0) {
+      int a = lo, b = hi;
+      for (int it = 0; it < 32 && a < b; ++it) {
+        const int m = a + ((b - a) >> 1);
+        if (g.tok[m] < k) a = m + 1;
+        else b = m;
+      }
+      if (a < hi && g.tok[a] == k) e = a;
+    }
+    if (e >= 0) {
+      nxt = clampi(g.next[e], 0, g.n_states - 1);
+      return (float)(acc + (double)g.arc[e]);
+    }
+    if (h == g.root) break;
+    acc += (double)g.bow[h];
+    h = clampi(g.backoff[h], 0, g.n_states - 1);
+  }
+  nxt = g.root;
+  return (float)acc;
+}
+
 // ---- select -----------------------------------------------------------------------------------------------------------
 // The W best of N candidates in the order (key descending, id ascending); the id of a candidate is its index in the key
 // array, a key of 0 is no candidate.  Radix select of the W-th best over 8-bit digits: integer LDS histograms (the counts do
@@ -264,6 +308,21 @@ inline int check_fusion_struct(const rnnt_beam_fusion* f, int V, const char* who
                  "%s: fusion n_states = %d with V = %d: the tables are (n_states, V) and hold at most 2^27 entries", who, f->n_states, V);
   RNNT_CHECK_ARG(f->next && f->arc && f->final, "%s: null fusion table (next, arc, final) with n_states %d", who, f->n_states);
   RNNT_CHECK_ARG(f->fused_scores, "%s: null fused_scores output with a fusion automaton", who);
+  return RNNT_OK;
+}
+
+// an *_ngram entry's rnnt_beam_ngram, before any device work; fills the kernel's view of it
+inline int check_ngram_struct(const rnnt_beam_ngram* g, int V, NgramLm& lm, const char* who) {
+  RNNT_CHECK_ARG(g != nullptr, "%s: null ngram struct", who);
+  RNNT_CHECK_ARG(g->row_ptr && g->tok && g->arc && g->next && g->bow && g->backoff && g->final,
+                 "%s: null ngram table (row_ptr, tok, arc, next, bow, backoff, final)", who);
+  RNNT_CHECK_ARG(g->n_states >= 1, "%s: ngram needs n_states >= 1, got %d", who, g->n_states);
+  RNNT_CHECK_ARG(g->root >= 0 && g->root < g->n_states, "%s: ngram root %d outside [0, n_states = %d)", who, g->root, g->n_states);
+  RNNT_CHECK_ARG(g->order >= 1 && g->order <= NGRAM_MAX_ORDER, "%s: ngram order %d outside [1,%d]", who, g->order, NGRAM_MAX_ORDER);
+  RNNT_CHECK_ARG(g->n_arcs >= V, "%s: ngram n_arcs = %d < V = %d (the root lists every token)", who, g->n_arcs, V);
+  RNNT_CHECK_ARG(g->fused_scores, "%s: null fused_scores output with an ngram automaton", who);
+  lm.row_ptr = g->row_ptr; lm.tok = g->tok; lm.next = g->next; lm.backoff = g->backoff; lm.arc = g->arc; lm.bow = g->bow;
+  lm.root = g->root; lm.order = g->order; lm.n_states = g->n_states; lm.n_arcs = g->n_arcs;
   return RNNT_OK;
 }
 

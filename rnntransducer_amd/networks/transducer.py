@@ -256,8 +256,8 @@ class JointNet(nn.Module):
         recognize_beams).  token_min_logp: per frame only tokens whose log-softmax reaches it extend a prefix (-inf: all).
         return_scores: (tokens, score) pairs, score fp64.  return_frames: frames is appended last, per token the encoder frame
         at which its prefix first entered the beam.
-        fusion (a TokenFusion on the model's device, used as it is): the search ranks by score + the automaton's total, the
-        output by score + total + final; with return_scores the entries are (tokens, score, fused_score).  A CTC hypothesis has
+        fusion (a TokenFusion or an NgramFusion on the model's device, used as it is): the search ranks by score + the automaton's
+        total, the output by score + total + final; with return_scores the entries are (tokens, score, fused_score).  A CTC hypothesis has
         no leading blank: its totals are fusion.score([blank] + tokens).  Limitation: TokenFusion.from_hotwords refuses a phrase
         that repeats a token back to back (the transducer's y_star never holds one), although a CTC hypothesis can.
         eval() mode only; ValueError for a missing head, training mode or bad arguments, before anything is launched."""
@@ -265,7 +265,7 @@ class JointNet(nn.Module):
         if self.training:
             raise ValueError("recognize_ctc_beams expects eval() mode (dropout inactive), like recognize_ctc_greedy")
         check_ctc_beam_args(beam_widths, token_min_logp, "recognize_ctc_beams")
-        check_fusion(fusion, self.num_classes, self.ctc_head.weight.device, "recognize_ctc_beams")
+        check_fusion(fusion, self.num_classes, self.ctc_head.weight.device, "recognize_ctc_beams", ngram=True)
         t_lens = lengths_to_device(inputs_lengths, inputs.device)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         res = ctc_beam_search(self.ctc_head(enc), t_lens, blank_token_id, beam_widths, token_min_logp=token_min_logp,
@@ -366,7 +366,8 @@ class JointNet(nn.Module):
         final) / len(y_star), the prune test stays on the ASR log-probabilities.  With return_scores each hypothesis carries
         asr_score (what it is without fusion: the sum of the ASR log-probabilities) and then fused_score = asr_score + total +
         final, both fp64.  A positive bonus can make a frame's pop loop run away (so can the reference's hotwords): the
-        max_pops cap ends it in RnntHipError naming max_pops, and the next call succeeds."""
+        max_pops cap ends it in RnntHipError naming max_pops, and the next call succeeds.  A backoff n-gram model (NgramFusion)
+        is refused here with a ValueError that names the searches that take one: those whose cost per frame is bounded."""
         if lm is not None or hotwords is not None:
             raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
                                       "lm=None and hotwords=None, and give token-level hotwords or an LM table as fusion= "
@@ -402,13 +403,14 @@ class JointNet(nn.Module):
         score) with return_scores: per token the encoder frame at which its prefix first appeared (-1 for the leading blank);
         frames do not decrease along a hypothesis and at most max_symbols are equal.  token_min_logp: per frame only tokens
         whose log-softmax reaches it extend a hypothesis (-inf: all).
-        fusion (a TokenFusion on the model's device): the search ranks by score + the automaton's total, the output by score +
-        total + final; with return_scores the entries carry score and then fused_score.
+        fusion (a TokenFusion, or an NgramFusion: a backoff n-gram model built from an ARPA file or from token-id n-grams, on
+        the model's device): the search ranks by score + the automaton's total, the output by score + total + final; with
+        return_scores the entries carry score and then fused_score.
         Any encoder direction.  eval() mode only; ValueError for training mode or bad arguments, before anything is launched."""
         if self.training:
             raise ValueError("recognize_beams_sync expects eval() mode (dropout inactive), like recognize_beams")
         check_beam_sync_args(beam_widths, max_symbols, token_min_logp, "recognize_beams_sync")
-        check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams_sync")
+        check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams_sync", ngram=True)
         if not 0 <= int(blank_token_id) < self.num_classes:
             raise ValueError(f"recognize_beams_sync: blank {blank_token_id} outside [0,{self.num_classes})")
         t_lens = lengths_to_device(inputs_lengths, inputs.device)
@@ -530,7 +532,7 @@ class JointNet(nn.Module):
                               max_len: int = 256):
         """A streaming.BeamSyncStreamState for `batch_size` streams, each starting as recognize_beams_sync starts an utterance:
         the root [blank] with score 0 and one prediction-net step on blank pending.  The search options (beam_widths <= 64,
-        max_symbols <= 4, token_min_logp, fusion: a TokenFusion on the model's device) and the two caps are fixed here: max_nodes
+        max_symbols <= 4, token_min_logp, fusion: a TokenFusion or NgramFusion on the model's device) and the two caps are fixed here: max_nodes
         bounds the LIVE prefix tree (>= 1 + 4 * beam_widths * max_symbols), max_len the uncommitted tail of a returned sequence;
         `state.workspace_bytes` / `state.bytes_per_stream` tell what they cost.  `device`, if given, must be the model's.  The
         weights must not change while the state is open.  Unidirectional encoders only.  ValueError for bad arguments, before

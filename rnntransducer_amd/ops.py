@@ -1076,7 +1076,7 @@ def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam
     (T,B,V)) fp32, t_lens (B,) int32: per utterance up to `beam_width` (<= 128) hypotheses, best first, as a list of
     (tokens, score) — tokens a list without blanks, score the fp64 CTC log-probability mass the search kept for that labelling, no
     length normalisation.  token_min_logp: per frame only tokens with log-softmax >= it extend a prefix (-inf: all).
-    fusion (a fusion.TokenFusion over the same V on the logits' device): the search ranks by score + the automaton's total of
+    fusion (a fusion.TokenFusion or fusion.NgramFusion over the same V on the logits' device): the search ranks by score + the automaton's total of
     the prefix, the output by score + total + final; every entry is then (tokens, score, fused_score).  return_frames appends
     `frames`: per token the frame at which its prefix first entered the beam.  One launch, then one host copy of the counts and
     lengths (and one per returned array).  Argument errors raise ValueError before anything is launched."""
@@ -1086,7 +1086,7 @@ def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam
         raise ValueError(f"ctc_beam_search: V = {V} < 2 or blank {blank} outside [0, {V})")
     if beam_width * (V + 1) > 1 << 24:
         raise ValueError(f"ctc_beam_search: beam_width * (V + 1) = {beam_width * (V + 1)} exceeds 2^24 candidates per frame")
-    check_fusion(fusion, V, logits.device, "ctc_beam_search")
+    check_fusion(fusion, V, logits.device, "ctc_beam_search", ngram=True)
     _need_gpu(logits, t_lens)
     logits = _f32c(logits, "logits")
     if t_lens.dtype != torch.int32:
@@ -1105,9 +1105,10 @@ def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam
     if nws == 0:
         raise ValueError(f"ctc_beam_search: sizes outside the kernel's limits (B={B} T={T} V={V} W={W})")
     ws = torch.empty(nws, device=dev, dtype=torch.uint8)
-    check(L.rnnt_hip_ctc_beam_search(_addr(logits), z_sb, z_st, _addr(t_lens), B, T, V, int(blank), W, float(token_min_logp),
-                                     C.byref(fs) if fs is not None else None, _addr(tokens), _addr(small, B), _addr(scores),
-                                     _addr(frames), _addr(small), _addr(ws), nws, _stream()), "rnnt_hip_ctc_beam_search")
+    entry = "rnnt_hip_ctc_beam_search_ngram" if isinstance(fs, _lib.BeamNgram) else "rnnt_hip_ctc_beam_search"
+    check(getattr(L, entry)(_addr(logits), z_sb, z_st, _addr(t_lens), B, T, V, int(blank), W, float(token_min_logp),
+                            C.byref(fs) if fs is not None else None, _addr(tokens), _addr(small, B), _addr(scores),
+                            _addr(frames), _addr(small), _addr(ws), nws, _stream()), entry)
     host = small.cpu()   # the only host sync of the search
     return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, frames)
 
@@ -1326,13 +1327,22 @@ def prednet_step(tokens: torch.Tensor, emb_w: torch.Tensor, rnn_weights, cell: i
 # beam search (replaces the host loop of transducer.py:215-361 with lm=None, hotwords=None; with fusion=, the lm_score branch
 # over a token automaton: fusion.py)
 # --------------------------------------------------------------------------------------------------
-def check_fusion(fusion, V: int, device, what: str) -> None:
-    """ValueError unless `fusion` is None or a TokenFusion over V tokens on `device`: before anything is launched."""
+NGRAM_SEARCHES = "recognize_beams_sync, init_beam_sync_stream / recognize_beams_sync_stream and recognize_ctc_beams"
+
+
+def check_fusion(fusion, V: int, device, what: str, ngram: bool = False) -> None:
+    """ValueError unless `fusion` is None or a TokenFusion over V tokens on `device`, or, where the search walks backoff tables
+    (ngram=True), an NgramFusion: before anything is launched."""
     if fusion is None:
         return
-    from .fusion import TokenFusion
-    if not isinstance(fusion, TokenFusion):
-        raise ValueError(f"{what}: fusion must be a rnntransducer_amd.TokenFusion, got {type(fusion).__name__}")
+    from .fusion import NgramFusion, TokenFusion
+    if isinstance(fusion, NgramFusion):
+        if not ngram:
+            raise ValueError(f"{what}: an NgramFusion is taken by the searches whose cost per frame is bounded ({NGRAM_SEARCHES}); "
+                             "this search takes a TokenFusion (NgramFusion.to_dense() where it fits)")
+    elif not isinstance(fusion, TokenFusion):
+        raise ValueError(f"{what}: fusion must be a rnntransducer_amd.TokenFusion{' or NgramFusion' if ngram else ''}, got "
+                         f"{type(fusion).__name__}")
     if fusion.vocab_size != V:
         raise ValueError(f"{what}: the fusion automaton is over {fusion.vocab_size} tokens, the model's joint over {V}")
     if fusion.device != device:
@@ -1340,7 +1350,13 @@ def check_fusion(fusion, V: int, device, what: str) -> None:
 
 
 def fusion_struct(fusion, fused_scores: torch.Tensor):
-    """rnnt_beam_fusion of a checked TokenFusion (raw pointers: the caller keeps `fusion` and `fused_scores` alive)."""
+    """rnnt_beam_fusion of a checked TokenFusion, or rnnt_beam_ngram of a checked NgramFusion (raw pointers: the caller keeps
+    `fusion` and `fused_scores` alive)."""
+    from .fusion import NgramFusion
+    if isinstance(fusion, NgramFusion):
+        return _lib.BeamNgram(_addr(fusion.row_ptr), _addr(fusion.tok), _addr(fusion.arc), _addr(fusion.next), _addr(fusion.bow),
+                              _addr(fusion.backoff), _addr(fusion.final), fusion.root, fusion.order, fusion.n_states, fusion.n_arcs,
+                              _addr(fused_scores))
     return _lib.BeamFusion(_addr(fusion.next), _addr(fusion.arc), _addr(fusion.final), fusion.n_states, _addr(fused_scores))
 
 
@@ -1445,8 +1461,8 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
     (fp64: the log-probability mass the search kept for y; no length normalisation), y with the leading blank as beam_search
     returns y_star.  t_lens (B) int32 on device = frames visited per utterance (None: all T).  token_min_logp: per frame only
     tokens whose log-softmax reaches it extend a hypothesis (-inf: all; the blank is never pruned).
-    fusion (a fusion.TokenFusion on enc_tm's device): ranked by score + the automaton's total, the output by score + total +
-    final; every entry is then (y, score, fused_score).  frames=True appends `frames`: per token the frame at which its prefix's
+    fusion (a fusion.TokenFusion or fusion.NgramFusion on enc_tm's device): ranked by score + the automaton's total, the output by
+    score + total + final; every entry is then (y, score, fused_score).  frames=True appends `frames`: per token the frame at which its prefix's
     node was created (-1 for the leading blank).  step_group: 0, or a smaller number of hypotheses per step group than the
     kernel would take (results do not depend on it).
     The cost per frame is bounded by beam_width, V and max_symbols: no cap can overflow.  One search launch, then one host copy
@@ -1461,12 +1477,15 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
 @torch.no_grad()
 def beam_search_sync_device(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                             cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam_width: int, max_symbols: int = 1,
-                            t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf):
+                            t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf, fusion=None):
     """beam_search_sync with its results left on the device (MWER training packs them into loss inputs there):
     -> (tokens (B, W, 1 + max_symbols*T) int32 with the leading blank, lens (B, W) int32, counts (B,) int32, scores (B, W) fp64,
-    host): `host` is the search's one host copy, a CPU int32 tensor counts | lens.  Entries of rank >= counts[b] are unwritten."""
-    return _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
-                                 token_min_logp, False, None, 0)[:5]
+    host): `host` is the search's one host copy, a CPU int32 tensor counts | lens.  Entries of rank >= counts[b] are unwritten.
+    fusion (a TokenFusion or NgramFusion): the search ranks with it as beam_search_sync does, and the tuple gains a sixth entry,
+    fused (B, W) fp64."""
+    out = _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
+                                token_min_logp, False, fusion, 0)
+    return out[:5] if fusion is None else out[:6]
 
 
 def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
@@ -1491,7 +1510,7 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
         raise ValueError(f"beam_search_sync: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
                          f"encoder width {Oe}")
-    check_fusion(fusion, V, enc_tm.device, "beam_search_sync")
+    check_fusion(fusion, V, enc_tm.device, "beam_search_sync", ngram=True)
     if t_lens is not None and (t_lens.dtype != torch.int32 or tuple(t_lens.shape) != (B,)):
         raise ValueError(f"beam_search_sync: t_lens must be (B,) = ({B},) int32, got {tuple(t_lens.shape)} {t_lens.dtype}")
     _need_gpu(enc_tm, fc_w, emb_w)
@@ -1516,8 +1535,9 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     tm = _lib.BeamTiming(_addr(fr), None) if frames else None
     fused = torch.empty(B, W, device=dev, dtype=torch.float64) if fusion is not None else None
     fs = fusion_struct(fusion, fused) if fusion is not None else None
-    check(L.rnnt_hip_beam_sync_search(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None,
-                                      _stream()), "rnnt_hip_beam_sync_search")
+    entry = "rnnt_hip_beam_sync_search_ngram" if isinstance(fs, _lib.BeamNgram) else "rnnt_hip_beam_sync_search"
+    check(getattr(L, entry)(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None, _stream()),
+          entry)
     host = small.cpu()   # the only host sync of the search
     return tokens, small[B:].view(B, W), small[:B], scores, host, fused, fr
 
@@ -1921,8 +1941,8 @@ def beam_sync_stream_chunk(d, A: torch.Tensor, lens_dev: torch.Tensor, commit: t
     """One chunk: A (T,B,V) float32 (from stream_rnn_chunk; any positive frame and stream strides with contiguous rows), lens_dev
     (B) int32 on device, commit (B, max_nodes + max_symbols * T) int32; the outputs d points to are written.  frames
     (B, beam, max_len) and commit_frames (shaped as commit), int32 on device: the tails' and the committed tokens' absolute
-    frames are written too.  fusion: the rnnt_beam_fusion struct of the stream's automaton (fusion_struct), the same for
-    every chunk."""
+    frames are written too.  fusion: the rnnt_beam_fusion or rnnt_beam_ngram struct of the stream's automaton (fusion_struct), the
+    same for every chunk."""
     _need_gpu(A, lens_dev, commit)
     dev = A.device
     if A.dim() != 3 or tuple(A.shape[1:]) != (d.B, d.V) or A.dtype != torch.float32 or A.shape[0] < 1 or A.stride(2) != 1 \
@@ -1940,8 +1960,8 @@ def beam_sync_stream_chunk(d, A: torch.Tensor, lens_dev: torch.Tensor, commit: t
         tm = _lib.BeamTiming(_addr(frames), _addr(commit_frames))
     d.T, d.A, d.a_st, d.a_sb, d.lens, d.commit = T, _addr(A), A.stride(0), A.stride(1), _addr(lens_dev), _addr(commit)
     try:
-        check(_lib.lib().rnnt_hip_beam_sync_stream_chunk(C.byref(d), C.byref(fusion) if fusion is not None else None,
-                                                         C.byref(tm) if tm is not None else None, _stream()),
-              "rnnt_hip_beam_sync_stream_chunk")
+        entry = "rnnt_hip_beam_sync_stream_chunk_ngram" if isinstance(fusion, _lib.BeamNgram) else "rnnt_hip_beam_sync_stream_chunk"
+        check(getattr(_lib.lib(), entry)(C.byref(d), C.byref(fusion) if fusion is not None else None,
+                                         C.byref(tm) if tm is not None else None, _stream()), entry)
     finally:
         d.T, d.A, d.lens, d.commit = 0, None, None, None

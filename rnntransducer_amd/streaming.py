@@ -417,7 +417,7 @@ class BeamSyncStreamState:
             raise ValueError(f"{what}: device {device} is not the model's ({home}); the state lives beside the weights")
         if not 0 <= int(blank_token_id) < jointnet.num_classes:
             raise ValueError(f"{what}: blank_token_id {blank_token_id} outside [0, {jointnet.num_classes})")
-        ops.check_fusion(fusion, jointnet.num_classes, device, what)
+        ops.check_fusion(fusion, jointnet.num_classes, device, what, ngram=True)
         self.fusion = fusion
         self._net = jointnet
         self.batch_size, self.blank = int(batch_size), int(blank_token_id)
