@@ -447,6 +447,41 @@ int rnnt_hip_loss_from_logits_fwd_bwd_fastemit(const void* logits, int32_t dtype
                                                size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Alignment-restricted loss (Ar-RNN-T, Mahadeokar et al. 2021): per-label emission windows.  The _fastemit entries above plus two
+ * device tables `emit_lo`, `emit_hi` of B rows of U = U1 - 1 int32 entries, row stride `win_stride` elements (positive, >= U: a
+ * (B,U) view of a wider table passes).  Label u of row b (u < u_lens[b]) may be emitted at frame t only if
+ *   max(emit_lo[b][u], 0) <= t <= min(emit_hi[b][u], t_lens[b] - 1);
+ * entries at u >= u_lens[b] are never read; blank transitions are unrestricted.  The lattice is the usual one with emit(t,u) = -inf
+ * outside the window: nll is -log of the sum over the paths that emit every label inside its window, the gradient is that value's
+ * gradient (the same per-cell formula; a cell no allowed path visits contributes exactly 0).  Windows need not be monotone.
+ *   - Work: with L[u] = max(0, lo[0..u-1]) and R[u] = min(hi[u..Ub-1], Tb-1), only cells with L[u] <= t <= R[u] can lie on an allowed
+ *     path.  The V-wide terms of every other cell are not computed (log-sum-exp and gradient kernels); the sweep is unchanged.
+ *   - An infeasible row (an empty window, windows that leave no monotone path, t_lens[b] = 0) returns nll = +inf and exact-zero
+ *     dA / dC (grad) rows, without NaN: CTCLoss's convention for a transcript that does not fit its frames.
+ *   - Full windows (lo <= 0, hi >= t_lens[b] - 1 for every label) give nll, dA, dC bit for bit those of the _fastemit entries
+ *     with the same lambda; a row gives the same bits alone as in a batch; fastemit_lambda acts on the live cells as above.
+ *   - Workspace: rnnt_hip_joint_loss_window_workspace_bytes (the plain layout followed by the band tables).  The backward-only entry
+ *     takes the workspace of a forward call of rnnt_hip_joint_loss_fwd_bwd_window (dA = dC = NULL) on the same operands and windows.
+ *   - Null window tables or a bad stride: RNNT_ERR_INVALID, before any device work.  The entries without windows are untouched.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_joint_loss_window_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V);
+int rnnt_hip_joint_loss_fwd_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                       const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                       int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                       float fastemit_lambda, const int32_t* emit_lo, const int32_t* emit_hi, int64_t win_stride,
+                                       float* nll, float* dA, float* dC, void* workspace, size_t workspace_bytes, void* stream);
+int rnnt_hip_joint_loss_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                   const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                   int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
+                                   const float* gvec, int32_t gvec_stride, float* dA, float* dC, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int rnnt_hip_loss_from_logits_fwd_bwd_window(const void* logits, int32_t dtype, const int32_t* labels, const int32_t* t_lens,
+                                             const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                             float gscale, float fastemit_lambda, const int32_t* emit_lo, const int32_t* emit_hi,
+                                             int64_t win_stride, float* nll, void* grad, void* workspace, size_t workspace_bytes,
+                                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Forced alignment: the best (Viterbi) RNN-T path of a KNOWN transcript, per utterance, on the device.  No (B,T,U+1,V) tensor:
  * the same two numbers per lattice cell as the loss, blk(t,u) = log p(blank | t,u) and emit(t,u) = log p(y_u | t,u), then the
  * lattice sweep of the loss in the (max, +) semiring:

@@ -37,15 +37,87 @@ __device__ __forceinline__ void stf(float* p, long i, float v) { p[i] = v; }
 __device__ __forceinline__ void stf(__half* p, long i, float v) { p[i] = __float2half(v); }
 __device__ __forceinline__ void stf(__hip_bfloat16* p, long i, float v) { p[i] = __float2bfloat16(v); }
 // ------------------------------------------------------------------------------------------------
+// Emission windows (alignment-restricted loss; include/rnnt_hip.h).  Label u of row b may be emitted at frame t only
+// if lo[b][u] <= t <= hi[b][u]: emit(t,u) = -inf elsewhere, everything else is the usual lattice.  The BAND is a work-skipping
+// device on top of that: with L[u] = max(0, lo[0..u-1]) and R[u] = min(hi[u..Ub-1], Tb-1), a cell can lie on an allowed path only
+// if L[u] <= t <= R[u]; both tables are non-decreasing in u, so the live cells of a frame (and of a 32-frame tile) are one interval
+// of u.  Cells outside the band get blk = emit = -inf without their V-wide terms being computed (no allowed path passes through
+// them, so the sums over allowed paths do not change) and the gradient kernels leave them out.  Every kernel below has a template
+// flag W: the W = false instance is the code without this feature (the tables are never read).
+// band_kernel: one workgroup per row.  An infeasible row (an empty window, windows that force labels out of order, no frame) gets
+// an EMPTY band (L > R everywhere) and feas = 0: nothing of it is computed, its NLL is +inf and its gradient rows are exact zeros.
+// Rows of the tables beyond u_len are empty too.  Entries lo / hi at u >= u_len are never read.
+// ------------------------------------------------------------------------------------------------
+constexpr int BAND_NONE_L = 0x3fffffff, BAND_NONE_R = -1;
+
+struct Win {   // what the lse kernels read
+  const int *L, *R;      // [B][U1] band
+  const int *lo, *hi;    // the caller's windows, row stride `stride`
+  const int* u_lens;
+  long stride;
+};
+
+struct Band {   // what the gradient kernels read
+  const int *L, *R;
+};
+// A kernel with the flag W takes its tables as a trailing parameter PACK: empty for W = false, so that instance has the parameter
+// list (and the kernel-argument block) of the kernel without this feature; one Win / Band for W = true.
+template <typename T>
+__device__ __forceinline__ T pick_tables(T t) { return t; }
+template <typename T>
+__device__ __forceinline__ T pick_tables() { return T{}; }
+
+__global__ void __launch_bounds__(256) band_kernel(const int* __restrict__ lo, const int* __restrict__ hi, long stride,
+                                                   const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T, int U1,
+                                                   int* __restrict__ L, int* __restrict__ R, int* __restrict__ feas) {
+  __shared__ int sl[512], sr[512];   // U+1 <= 512
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Tb = min(t_lens[b], T), Ub = max(min(u_lens[b], U1 - 1), 0);
+  const int* lob = lo + (long)b * stride;
+  const int* hib = hi + (long)b * stride;
+  bool ok = Tb >= 1;
+  for (int u = tid; u < Ub; u += 256) {
+    const int l = max(lob[u], 0), h = min(hib[u], Tb - 1);
+    sl[u] = l;
+    sr[u] = h;
+    ok = ok && l <= h;
+  }
+  __syncthreads();
+  if (tid == 0) {         // L[u] = max(0, lo[0 .. u-1]): running maximum, in place (sl[u] <- L[u+1])
+    int m = 0;
+    for (int u = 0; u < Ub; ++u) { m = max(m, sl[u]); sl[u] = m; }
+  } else if (tid == 64) {   // R[u] = min(hi[u .. Ub-1], Tb-1): running minimum from the end, in place
+    int m = Tb - 1;
+    for (int u = Ub - 1; u >= 0; --u) { m = min(m, sr[u]); sr[u] = m; }
+  }
+  __syncthreads();
+  for (int u = tid; u <= Ub; u += 256) {
+    const int l = u == 0 ? 0 : sl[u - 1], r = u == Ub ? Tb - 1 : sr[u];
+    ok = ok && l <= r;
+  }
+  const int feasible = __syncthreads_and(ok);
+  for (int u = tid; u < U1; u += 256) {
+    const bool in = feasible && u <= Ub;
+    L[(long)b * U1 + u] = in ? (u == 0 ? 0 : sl[u - 1]) : BAND_NONE_L;
+    R[(long)b * U1 + u] = in ? (u == Ub ? Tb - 1 : sr[u]) : BAND_NONE_R;
+  }
+  if (tid == 0) feas[b] = feasible;
+}
+
+// ------------------------------------------------------------------------------------------------
 // per-cell log-sum-exp, separable logits.  grid (ceil(T/32), ceil(U1/8), B), 256 threads = 32 t x 8 u
+// W: a tile without a live cell only writes its -inf entries; in a live tile the threads of dead cells stage but do not sum
 // ------------------------------------------------------------------------------------------------
 constexpr int LSE_UT = 8, LSE_VC = 128;
 
+template <bool W, typename... WT>
 __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                       const float* __restrict__ bias, const int* __restrict__ labels,
                                                       int T, int U1, int V, int blank, long a_sb, long a_st,
                                                       long c_sb, long c_su, float* __restrict__ blk,
-                                                      float* __restrict__ emit) {
+                                                      float* __restrict__ emit, WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Win");
+  const Win win = pick_tables<Win>(wt...);
   __shared__ float As[TT][LSE_VC + 1];
   __shared__ float Cs[LSE_UT][LSE_VC + 1];
   const int b = blockIdx.z, t0 = blockIdx.x * TT, u0 = blockIdx.y * LSE_UT;
@@ -53,6 +125,19 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
   const int t = t0 + tl, u = u0 + ul;
   const float* Ab = A + (long)b * a_sb;
   const float* Cb = C + (long)b * c_sb;
+  bool live = true;
+  if (W) {
+    live = t < T && u < U1;
+    if (live) live = t >= win.L[(long)b * U1 + u] && t <= win.R[(long)b * U1 + u];
+    if (!__syncthreads_or(live)) {   // (uniform) no live cell in this tile
+      if (t < T && u < U1) {
+        const long o = ((long)b * U1 + u) * T + t;
+        blk[o] = -__builtin_huge_valf();
+        emit[o] = -__builtin_huge_valf();
+      }
+      return;
+    }
+  }
 
   float m = -__builtin_huge_valf(), s = 0.f;
   for (int v0 = 0; v0 < V; v0 += LSE_VC) {
@@ -67,6 +152,7 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
       Cs[r][c] = (u0 + r < U1 && c < vc) ? Cb[(long)(u0 + r) * c_su + v0 + c] + bias[v0 + c] : 0.f;
     }
     __syncthreads();
+    if (W && !live) continue;   // (no barrier is skipped: both are above)
     float cm = -__builtin_huge_valf();
     for (int c = 0; c < vc; ++c) cm = fmaxf(cm, As[tl][c] + Cs[ul][c]);
     const float nm = fmaxf(m, cm);
@@ -76,8 +162,13 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
     m = nm;
   }
   if (t < T && u < U1) {
-    const float lse = m + logf(s);
     const long o = ((long)b * U1 + u) * T + t;
+    if (W && !live) {
+      blk[o] = -__builtin_huge_valf();
+      emit[o] = -__builtin_huge_valf();
+      return;
+    }
+    const float lse = m + logf(s);
     const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
     blk[o] = zb - lse;
     float e = 0.f;
@@ -85,6 +176,8 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
       const int y = labels[(long)b * (U1 - 1) + u];
       e = Ab[(long)t * a_st + y] + Cb[(long)u * c_su + y] + bias[y] - lse;
     }
+    if (W && u < U1 - 1 && u < win.u_lens[b] && (t < win.lo[(long)b * win.stride + u] || t > win.hi[(long)b * win.stride + u]))
+      e = -__builtin_huge_valf();   // outside label u's window
     emit[o] = e;
   }
 }
@@ -100,11 +193,14 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
 constexpr int LSV_UR = 4, LSV_UT = 8 * LSV_UR, LSV_VC = 128;
 constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
 
+template <bool W, typename... WT>
 __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                        const float* __restrict__ bias, const int* __restrict__ labels,
                                                        int T, int U1, int V, int blank, long a_sb, long a_st,
                                                        long c_sb, long c_su, float* __restrict__ blk,
-                                                       float* __restrict__ emit) {
+                                                       float* __restrict__ emit, WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Win");
+  const Win win = pick_tables<Win>(wt...);
   __shared__ float As[TT][LSV_VC + 1];
   __shared__ float Cs[LSV_UT][LSV_VC + 1];
   const int b = blockIdx.z, t0 = blockIdx.x * TT, u0 = blockIdx.y * LSV_UT;
@@ -112,6 +208,29 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
   const int t = t0 + tl;
   const float* Ab = A + (long)b * a_sb;
   const float* Cb = C + (long)b * c_sb;
+  bool live[LSV_UR], any = true;   // W: a thread sums when one of its four cells is live; a tile without a live cell only writes -inf
+  if (W) {
+    any = false;
+#pragma unroll
+    for (int r = 0; r < LSV_UR; ++r) {
+      const int u = u0 + ug * LSV_UR + r;
+      live[r] = t < T && u < U1;
+      if (live[r]) live[r] = t >= win.L[(long)b * U1 + u] && t <= win.R[(long)b * U1 + u];
+      any = any || live[r];
+    }
+    if (!__syncthreads_or(any)) {   // (uniform)
+#pragma unroll
+      for (int r = 0; r < LSV_UR; ++r) {
+        const int u = u0 + ug * LSV_UR + r;
+        if (t < T && u < U1) {
+          const long o = ((long)b * U1 + u) * T + t;
+          blk[o] = -__builtin_huge_valf();
+          emit[o] = -__builtin_huge_valf();
+        }
+      }
+      return;
+    }
+  }
 
   float m[LSV_UR], s[LSV_UR];   // running maximum (log2 domain) and sum of 2^(x - m)
 #pragma unroll
@@ -128,6 +247,7 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
       Cs[r][c] = (u0 + r < U1 && c < vc) ? (Cb[(long)(u0 + r) * c_su + v0 + c] + bias[v0 + c]) * LOG2E_F : 0.f;
     }
     __syncthreads();
+    if (W && !any) continue;   // (no barrier is skipped: both are above)
     float cm[LSV_UR];
 #pragma unroll
     for (int r = 0; r < LSV_UR; ++r) cm[r] = -__builtin_huge_valf();
@@ -154,8 +274,13 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
   for (int r = 0; r < LSV_UR; ++r) {
     const int u = u0 + ug * LSV_UR + r;
     if (t < T && u < U1) {
-      const float lse = (m[r] + __builtin_amdgcn_logf(s[r])) * LN2_F;   // v_log_f32 = log2
       const long o = ((long)b * U1 + u) * T + t;
+      if (W && !live[r]) {
+        blk[o] = -__builtin_huge_valf();
+        emit[o] = -__builtin_huge_valf();
+        continue;
+      }
+      const float lse = (m[r] + __builtin_amdgcn_logf(s[r])) * LN2_F;   // v_log_f32 = log2
       const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
       blk[o] = zb - lse;
       float e = 0.f;
@@ -163,20 +288,37 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
         const int y = labels[(long)b * (U1 - 1) + u];
         e = Ab[(long)t * a_st + y] + Cb[(long)u * c_su + y] + bias[y] - lse;
       }
+      if (W && u < U1 - 1 && u < win.u_lens[b] && (t < win.lo[(long)b * win.stride + u] || t > win.hi[(long)b * win.stride + u]))
+        e = -__builtin_huge_valf();   // outside label u's window
       emit[o] = e;
     }
   }
 }
 
 // dense logits (B,T,U1,V): one wavefront per cell, lanes along v, grid-stride over cells
-template <typename TZ>
+template <typename TZ, bool W, typename... WT>
 __global__ void __launch_bounds__(256) lse_dense_kernel(const TZ* __restrict__ Z, const int* __restrict__ labels,
                                                         int B, int T, int U1, int V, int blank,
-                                                        float* __restrict__ blk, float* __restrict__ emit) {
+                                                        float* __restrict__ blk, float* __restrict__ emit, WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Win");
+  const Win win = pick_tables<Win>(wt...);
   const int lane = threadIdx.x & 63;
   const long ncell = (long)B * T * U1;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((long)gridDim.x * blockDim.x) >> 6;
   for (long cell = wave0; cell < ncell; cell += nw) {
+    if (W) {   // a cell outside the band: -inf entries, its logits are not read
+      const int u = (int)(cell % U1);
+      const long bt = cell / U1;
+      const int t = (int)(bt % T), b = (int)(bt / T);
+      if (t < win.L[(long)b * U1 + u] || t > win.R[(long)b * U1 + u]) {
+        if (lane == 0) {
+          const long o = ((long)b * U1 + u) * T + t;
+          blk[o] = -__builtin_huge_valf();
+          emit[o] = -__builtin_huge_valf();
+        }
+        continue;
+      }
+    }
     const TZ* z = Z + cell * V;
     float m = -__builtin_huge_valf();
     for (int v = lane; v < V; v += 64) m = fmaxf(m, ldf(z, v));
@@ -191,7 +333,10 @@ __global__ void __launch_bounds__(256) lse_dense_kernel(const TZ* __restrict__ Z
       const float lse = m + logf(s);
       const long o = ((long)b * U1 + u) * T + t;
       blk[o] = ldf(z, blank) - lse;
-      emit[o] = (u < U1 - 1) ? ldf(z, labels[(long)b * (U1 - 1) + u]) - lse : 0.f;
+      float e = (u < U1 - 1) ? ldf(z, labels[(long)b * (U1 - 1) + u]) - lse : 0.f;
+      if (W && u < U1 - 1 && u < win.u_lens[b] && (t < win.lo[(long)b * win.stride + u] || t > win.hi[(long)b * win.stride + u]))
+        e = -__builtin_huge_valf();   // outside label u's window
+      emit[o] = e;
     }
   }
 }
@@ -492,9 +637,30 @@ __device__ __forceinline__ void fastemit_cell(CellS& c, float lambda) {
   c.ce = (1.f + lambda) * c.ce;
 }
 
+// Emission windows in the gradient kernels (W = true): [ua, ub] = the label positions u <= Ub whose band [L[u], R[u]] meets the
+// frames [t0, t0 + TT) of this tile.  L and R are non-decreasing in u, so these positions are one interval; empty: ua > ub.
+// Called by every thread of the workgroup (two barriers).
+__device__ __forceinline__ void tile_band(const int* __restrict__ wL, const int* __restrict__ wR, int t0, int Ub, int tid,
+                                          int nthreads, int* band, int& ua, int& ub) {
+  if (tid == 0) { band[0] = BAND_NONE_L; band[1] = -1; }
+  __syncthreads();
+  for (int u = tid; u <= Ub; u += nthreads)
+    if (wL[u] <= t0 + TT - 1 && wR[u] >= t0) {
+      atomicMin(&band[0], u);
+      atomicMax(&band[1], u);
+    }
+  __syncthreads();
+  ua = band[0];
+  ub = band[1];
+}
+constexpr float DEAD_LSE = 1e30f;   // the lse of a cell outside the band: exp(x - lse) = 0
+
 // grid (ceil(T/32), B), 256 threads; wave w owns frames w, w+4, ... of the tile; lanes run along v.
 // dynamic LDS: cells[TT][U1] (CellS) | Cs[U1][64] | dCs[U1][64] | ys[U1]
-template <bool FE>
+// W: the u loop runs over the chunks of 8 (aligned as without windows, so that full windows keep every sum's order) that meet the
+// tile's interval; a dead cell inside them adds exact zeros, with no branch in the inner loop (a per-cell skip measured 1.9x slower
+// with full windows: it serialises the table reads)
+template <bool FE, bool W, typename... WT>
 __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                        const float* __restrict__ bias, const int* __restrict__ labels,
                                                        const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -503,7 +669,11 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
                                                        const double* __restrict__ ll, int T, int U1, int V, int blank,
                                                        long a_sb, long a_st, long c_sb, long c_su, float gscale_in,
                                                        const float* __restrict__ gvec, int gvec_stride,
-                                                       float* __restrict__ dA, float* __restrict__ dCp, float fe_lambda) {
+                                                       float* __restrict__ dA, float* __restrict__ dCp, float fe_lambda,
+                                                       WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Band");
+  const Band bt = pick_tables<Band>(wt...);
+  const int *wL = bt.L, *wR = bt.R;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   CellS* cells = reinterpret_cast<CellS*>(smem);
   float* Cs = reinterpret_cast<float*>(cells + TT * U1);
@@ -520,11 +690,19 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
   const float* Cb = C + (long)b * c_sb;
   float* dCtile = dCp + ((long)b * ntiles + tile) * U1 * V;
 
+  int ua = 0, ub = Ub;
+  if (W) {
+    __shared__ int band[2];
+    wL += (long)b * U1;
+    wR += (long)b * U1;
+    tile_band(wL, wR, t0, Ub, tid, 256, band, ua, ub);
+  }
+
   for (int i = tid; i < U1; i += 256) ys[i] = (i < U1 - 1) ? labels[(long)b * (U1 - 1) + i] : -1;
   for (int i = tid; i < TT * U1; i += 256) {
     const int u = i / TT, tl = i % TT, t = t0 + tl;   // consecutive threads -> consecutive frames: alpha / beta / blk / emit rows are read coalesced
-    CellS c = {0.f, 0.f, 0.f, 0.f};
-    if (t < Tb && u <= Ub) {
+    CellS c = {0.f, W ? DEAD_LSE : 0.f, 0.f, 0.f};
+    if (t < Tb && u <= Ub && (!W || (t >= wL[u] && t <= wR[u]))) {
       const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
       c = cell_scalars(blk, emit, alpha, beta, rowbase, T, t, u, Tb, Ub, logZ, zb);
       if (FE) fastemit_cell(c, fe_lambda);
@@ -556,7 +734,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
       a[i] = fok[i] ? Ab[(long)t * a_st + v] : 0.f;
       accA[i] = 0.f;
     }
-    for (int u0 = 0; u0 <= Ub; u0 += UC) {
+    for (int u0 = W ? (ua & ~(UC - 1)) : 0; u0 <= (W ? ub : Ub); u0 += UC) {
       float accC[UC], cs[UC];
       int yv[UC];
 #pragma unroll
@@ -574,7 +752,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
         for (int j = 0; j < UC; ++j) {
           const int u = u0 + j;
           if (u > Ub) break;
-          const CellS c = crow[u];
+          const CellS c = crow[u];   // (W: a dead cell has w = cb = ce = 0 and an lse that sends the exponential to 0: g = 0 exactly)
           // v_exp_f32 form: |rel err| <~ 3e-7 on a value in [0, 1] (the softmax probability times a path weight <= 1), i.e. an
           // absolute gradient error ~1e-7 against the 2e-5 the tests allow; ocml expf was 2/3 of this loop's instructions
           float g = c.w * __expf(a[i] + cs[j] - c.lse);
@@ -625,8 +803,10 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
 // CHUNKED = true : the table holds UL (a multiple of UC) label positions at a time and is rebuilt per chunk; accA keeps accumulating
 // in registers across the chunks and the dC rows are written per 8-row block as before, so the arithmetic (and its order) is the
 // unchunked kernel's.  Every wave stays to the end (the chunks' barriers), the ones beyond the vocabulary only help build the table.
+// W (emission windows): cells outside the band enter the table as cells outside the lattice do (exact zeros), and an 8-row block
+// that does not meet the tile's interval [ua, ub] skips its 32 x 8 x 64 exponentials and stores its zero dC rows.
 // ------------------------------------------------------------------------------------------------
-template <int NW, bool CHUNKED, bool FE>
+template <int NW, bool CHUNKED, bool FE, bool W, typename... WT>
 __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                             const float* __restrict__ bias, const int* __restrict__ labels,
                                                             const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -636,7 +816,10 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
                                                             long a_sb, long a_st, long c_sb, long c_su, float gscale_in,
                                                             const float* __restrict__ gvec, int gvec_stride,
                                                             float* __restrict__ dA, float* __restrict__ dCp, int ul,
-                                                            float fe_lambda) {
+                                                            float fe_lambda, WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Band");
+  const Band bt = pick_tables<Band>(wt...);
+  const int *wL = bt.L, *wR = bt.R;
   const int UL = CHUNKED ? ul : U1;                      // label positions per table
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2* wl = reinterpret_cast<float2*>(smem);          // [TT][UL] {occupancy w, row lse * log2 e}: what the inner loop reads (8-byte broadcasts)
@@ -658,6 +841,13 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
   const float* Cb = C + (long)b * c_sb;
   float* dCtile = dCp + ((long)b * ntiles + tile) * U1 * V;
   const int nf = max(0, min(TT, Tb - t0));            // valid frames of this tile (uniform)
+  int ua = 0, ub = Ub;
+  if (W) {
+    __shared__ int band[2];
+    wL += (long)b * U1;
+    wR += (long)b * U1;
+    tile_band(wL, wR, t0, Ub, tid, 64 * NW, band, ua, ub);
+  }
 
   for (int i = tid; i < U1; i += 64 * NW) ys[i] = (i < U1 - 1) ? labels[(long)b * (U1 - 1) + i] : -1;
   const float bias_blank = bias[blank];
@@ -678,6 +868,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
         const int i = i0 + q * 64 * NW;
         const int u = min(uc0 + i / TT, U1 - 1), tl = i % TT, t = t0 + tl;
         in[q] = i < TT * nrow && t < Tb && u <= Ub;
+        if (W) in[q] = in[q] && t >= wL[u] && t <= wR[u];   // (u <= U1 - 1: inside the tables)
         dst[q] = i < TT * nrow ? tl * UL + (u - uc0) : -1;
         const int tc = min(t, Tbc - 1), uc = max(min(u, Ub), 0);   // a cell of the lattice whatever (t, u) is (frame 0 of an empty row)
         const float zb = Ab[(long)tc * a_st + blank] + Cb[(long)uc * c_su + blank] + bias_blank;
@@ -715,7 +906,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
         accC[j] = 0.f;
         cs2[j] = vok ? (Cb[(long)u * c_su + v] + bias_v) * LOG2E_F : 0.f;
       }
-      if (u0 <= Ub) {
+      if (W ? (u0 <= ub && u0 + UC > ua) : (u0 <= Ub)) {
         // branch-free over the whole 32 x 8 block (cells outside the lattice contribute exact zeros; label positions beyond U1 - 1
         // re-read the last row's table entries, whose sums are not stored): the 256 table reads and v_exp_f32 pipeline freely
 #pragma unroll
@@ -782,13 +973,16 @@ __global__ void __launch_bounds__(256) reduce_dc_kernel(const float* __restrict_
 }
 
 // dense d/d logits: one wavefront per cell
-template <typename TZ, bool FE>
+template <typename TZ, bool FE, bool W, typename... WT>
 __global__ void __launch_bounds__(256) grad_dense_kernel(const TZ* __restrict__ Z, const int* __restrict__ labels,
                                                          const int* __restrict__ t_lens, const int* __restrict__ u_lens,
                                                          const float* __restrict__ blk, const float* __restrict__ emit,
                                                          const double* __restrict__ alpha, const double* __restrict__ beta,
                                                          const double* __restrict__ ll, int B, int T, int U1, int V,
-                                                         int blank, float gscale, TZ* __restrict__ G, float fe_lambda) {
+                                                         int blank, float gscale, TZ* __restrict__ G, float fe_lambda, WT... wt) {
+  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Band");
+  const Band bt = pick_tables<Band>(wt...);
+  const int *wL = bt.L, *wR = bt.R;
   const int lane = threadIdx.x & 63;
   const long ncell = (long)B * T * U1;
   const long wave0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((long)gridDim.x * blockDim.x) >> 6;
@@ -799,7 +993,9 @@ __global__ void __launch_bounds__(256) grad_dense_kernel(const TZ* __restrict__ 
     const int Tb = t_lens[b], Ub = u_lens[b];
     const TZ* z = Z + cell * V;
     TZ* g = G + cell * V;
-    if (t >= Tb || u > Ub) {
+    bool dead = t >= Tb || u > Ub;
+    if (W) dead = dead || t < wL[(long)b * U1 + u] || t > wR[(long)b * U1 + u];   // outside the band: a zero gradient
+    if (dead) {
       for (int v = lane; v < V; v += 64) stf(g, v, 0.f);
       continue;
     }
@@ -834,6 +1030,12 @@ __global__ void nll_kernel(const double* __restrict__ ll, int B, float* __restri
   if (b < B) nll[b] = (float)(-ll[b]);
 }
 
+// emission windows: an infeasible row's NLL is +inf by its flag (its sweeps ran on an all -inf lattice: ll = -inf as well)
+__global__ void nll_window_kernel(const double* __restrict__ ll, const int* __restrict__ feas, int B, float* __restrict__ nll) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) nll[b] = feas[b] ? (float)(-ll[b]) : __builtin_huge_valf();
+}
+
 // out[0] = scale * sum_i x[i]: one wavefront, fixed order (lane partial sums over i = lane, lane + 64, ... then a butterfly)
 __global__ void __launch_bounds__(64) scaled_sum_kernel(const float* __restrict__ x, int n, float scale, float* __restrict__ out) {
   float s = 0.f;
@@ -864,6 +1066,41 @@ LossWs carve(void* ws, int B, int T, int U1, int V, bool with_slabs) {
   w.dCp = reinterpret_cast<float*>(take(with_slabs ? (size_t)B * ntiles * U1 * V * 4 : 0));
   w.total = off;
   return w;
+}
+
+// the windowed loss: the plain workspace, then the band tables L, R ([B][U1] int32) and the feasibility flags ([B])
+struct WinWs {
+  LossWs w;
+  int *L, *R, *feas;
+  size_t total;
+};
+
+WinWs carve_window(void* ws, int B, int T, int U1, int V) {
+  WinWs x;
+  x.w = carve(ws, B, T, U1, V, true);
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = x.w.total;
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
+  x.L = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
+  x.R = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
+  x.feas = reinterpret_cast<int*>(take((size_t)B * 4));
+  x.total = off;
+  return x;
+}
+
+int check_window(const void* emit_lo, const void* emit_hi, int64_t win_stride, int U1, const char* who) {
+  RNNT_CHECK_ARG(emit_lo && emit_hi, "%s: null emit_lo / emit_hi", who);
+  RNNT_CHECK_ARG(win_stride >= 1 && win_stride >= U1 - 1, "%s: the window tables' row stride %lld must be positive and at least U = %d",
+                 who, (long long)win_stride, U1 - 1);
+  return RNNT_OK;
+}
+
+int launch_band(const WinWs& x, const int32_t* emit_lo, const int32_t* emit_hi, int64_t win_stride, const int* t_lens,
+                const int* u_lens, int B, int T, int U1, hipStream_t s) {
+  hipLaunchKernelGGL(band_kernel, dim3(B), dim3(256), 0, s, emit_lo, emit_hi, (long)win_stride, t_lens, u_lens, T, U1, x.L, x.R,
+                     x.feas);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
 }
 
 int check_common(const void* labels, const void* t_lens, const void* u_lens, int B, int T, int U1, int V, int blank,
@@ -966,17 +1203,28 @@ static bool large_vocab(int V) {
 // blk / emit of every lattice cell from the separable operands (the loss and the alignment share it)
 static int launch_lse_sep(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su, const float* bias,
                           const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float* blk, float* emit,
-                          hipStream_t s) {
+                          hipStream_t s, const Win* win = nullptr) {
   const int ntiles = (int)ceil_div(T, TT);
   const double cells = (double)B * T * U1;
   {
   ProfScope prof(RNNT_K_LSE, 4.0 * ((double)B * T * V + (double)B * U1 * V) + 8.0 * cells, s);
-  if (large_vocab(V))
-    hipLaunchKernelGGL(lse_sepv_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSV_UT), B), dim3(256), 0, s, A, C, bias, labels,
-                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, blk, emit);
-  else
-    hipLaunchKernelGGL(lse_sep_kernel, dim3(ntiles, (unsigned)ceil_div(U1, LSE_UT), B), dim3(256), 0, s, A, C, bias, labels,
-                       T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, blk, emit);
+  const dim3 gv(ntiles, (unsigned)ceil_div(U1, LSV_UT), B), gs(ntiles, (unsigned)ceil_div(U1, LSE_UT), B);
+  // win: emission windows, the W = true instances; without, the kernels as they are without that feature
+  if (large_vocab(V)) {
+    if (win)
+      hipLaunchKernelGGL((lse_sepv_kernel<true, Win>), gv, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
+                         (long)c_sb, (long)c_su, blk, emit, *win);
+    else
+      hipLaunchKernelGGL(lse_sepv_kernel<false>, gv, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
+                         (long)c_sb, (long)c_su, blk, emit);
+  } else {
+    if (win)
+      hipLaunchKernelGGL((lse_sep_kernel<true, Win>), gs, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
+                         (long)c_sb, (long)c_su, blk, emit, *win);
+    else
+      hipLaunchKernelGGL(lse_sep_kernel<false>, gs, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
+                         (long)c_sb, (long)c_su, blk, emit);
+  }
   }
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
@@ -988,12 +1236,13 @@ static int check_fastemit(float lambda, const char* who) {
   return RNNT_OK;
 }
 
-// fe = 0 launches the FE = false instances (the kernels as they are without FastEmit), fe > 0 the FE = true ones
-template <bool FE>
+// fe = 0 launches the FE = false instances (the kernels as they are without FastEmit), fe > 0 the FE = true ones; W with the band
+// tables of the windowed entries (wt: one Band for W = true, nothing for W = false)
+template <bool FE, bool W, typename... WT>
 static int launch_grad_sep_fe(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
                            const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
                            int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
-                           float* dC, float fe, hipStream_t s) {
+                           float* dC, float fe, hipStream_t s, WT... wt) {
   const int ntiles = (int)ceil_div(T, TT);
   const double cells = (double)B * T * U1;
   ProfScope prof(RNNT_K_LATGRAD, 4.0 * 2.0 * ((double)B * T * V + (double)B * U1 * V) + 24.0 * cells, s);
@@ -1007,26 +1256,26 @@ static int launch_grad_sep_fe(const LossWs& w, const float* A, int64_t a_sb, int
     const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
     if (lds <= LDS_MAX) {
       if (lds > 64 * 1024)
-        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE, W, WT...>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
                          w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, U1, fe);
+                         w.dCp, U1, fe, wt...);
     } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
       const size_t per_row = (size_t)TT * sizeof(CellS);
       const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
       const int nchunks = (int)ceil_div(U1, ul_max);
       const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
       const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+      hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE, W, WT...>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
                          w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, ul, fe);
+                         w.dCp, ul, fe, wt...);
     }
   } else {
     if (lds_sep > 64 * 1024)
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
-    hipLaunchKernelGGL(grad_sep_kernel<FE>, dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
-                       w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp, fe);
+      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
+    hipLaunchKernelGGL((grad_sep_kernel<FE, W, WT...>), dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
+                       w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp, fe, wt...);
   }
   RNNT_CHECK_LAUNCH();
   const long per_b = (long)U1 * V;
@@ -1039,12 +1288,13 @@ static int launch_grad_sep_fe(const LossWs& w, const float* A, int64_t a_sb, int
 static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
                            const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
                            int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
-                           float* dC, float fe, hipStream_t s) {
-  if (fe != 0.f)
-    return launch_grad_sep_fe<true>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec,
-                                    gvec_stride, dA, dC, fe, s);
-  return launch_grad_sep_fe<false>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec,
-                                   gvec_stride, dA, dC, 0.f, s);
+                           float* dC, float fe, hipStream_t s, const int* wL = nullptr, const int* wR = nullptr) {
+#define GS(FE, W, LAM, ...)                                                                                                  \
+  launch_grad_sep_fe<FE, W>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, \
+                            gvec_stride, dA, dC, LAM, s, ##__VA_ARGS__)
+  if (wL) return fe != 0.f ? GS(true, true, fe, Band{wL, wR}) : GS(false, true, 0.f, Band{wL, wR});
+  return fe != 0.f ? GS(true, false, fe) : GS(false, false, 0.f);
+#undef GS
 }
 
 extern "C" size_t rnnt_hip_joint_loss_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
@@ -1112,6 +1362,57 @@ extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_s
                                           gvec, gvec_stride, dA, dC, workspace, workspace_bytes, stream);
 }
 
+/* ---- emission windows (include/rnnt_hip.h): the entries above with the band tables and the W = true kernel instances ---- */
+extern "C" size_t rnnt_hip_joint_loss_window_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
+  if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
+  return carve_window(nullptr, B, T, U1, V).total;
+}
+
+extern "C" int rnnt_hip_joint_loss_fwd_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
+                                                  int64_t c_su, const float* bias, const int32_t* labels, const int32_t* t_lens,
+                                                  const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
+                                                  float gscale, float fastemit_lambda, const int32_t* emit_lo,
+                                                  const int32_t* emit_hi, int64_t win_stride, float* nll, float* dA, float* dC,
+                                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
+  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_window")) return rc;
+  if (int rc = check_window(emit_lo, emit_hi, win_stride, U1, "joint_loss_window")) return rc;
+  RNNT_CHECK_ARG(A && C && bias, "joint_loss_window: null A/C/bias");
+  RNNT_CHECK_ARG((dA == nullptr) == (dC == nullptr), "joint_loss_window: dA and dC must both be given or both be NULL");
+  const WinWs x = carve_window(workspace, B, T, U1, V);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= x.total, "joint_loss_window: workspace too small (%zu < %zu)", workspace_bytes, x.total);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_band(x, emit_lo, emit_hi, win_stride, t_lens, u_lens, B, T, U1, s)) return rc;
+  const Win win = {x.L, x.R, emit_lo, emit_hi, u_lens, (long)win_stride};
+  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, x.w.blk, x.w.emit, s, &win)) return rc;
+  if (int rc = launch_alphabeta(x.w, t_lens, u_lens, B, T, U1, s)) return rc;   // the sweep as it is: it reads the masked tables
+  hipLaunchKernelGGL(nll_window_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, x.w.ll, x.feas, B, nll);
+  RNNT_CHECK_LAUNCH();
+  if (dA)
+    return launch_grad_sep(x.w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nullptr, 0, dA,
+                           dC, fastemit_lambda, s, x.L, x.R);
+  return RNNT_OK;
+}
+
+extern "C" int rnnt_hip_joint_loss_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                              const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                              int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                              float fastemit_lambda, const float* gvec, int32_t gvec_stride, float* dA, float* dC,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  // second half of rnnt_hip_joint_loss_fwd_bwd_window: the workspace still holds the band tables and blk / emit / alpha / beta / logZ
+  // of a forward call (dA = dC = NULL) on the SAME operands and windows
+  RNNT_CHECK_ARG(labels && t_lens && u_lens && B >= 1 && T >= 1 && U1 >= 1 && V >= 2 && blank >= 0 && blank < V,
+                 "joint_loss_bwd_window: bad dims / null pointer");
+  RNNT_CHECK_ARG(A && C && bias && dA && dC, "joint_loss_bwd_window: null A/C/bias/dA/dC");
+  RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "joint_loss_bwd_window: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
+  RNNT_CHECK_ARG(U1 <= 64 * 8, "joint_loss_bwd_window: U+1 = %d exceeds the 512 label positions of the forward", U1);
+  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_bwd_window")) return rc;
+  const WinWs x = carve_window(workspace, B, T, U1, V);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= x.total, "joint_loss_bwd_window: workspace too small (%zu < %zu)", workspace_bytes, x.total);
+  return launch_grad_sep(x.w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, gvec_stride,
+                         dA, dC, fastemit_lambda, (hipStream_t)stream, x.L, x.R);
+}
+
 extern "C" int rnnt_hip_scaled_sum_f32(const float* x, int32_t n, float scale, float* out, void* stream) {
   RNNT_CHECK_ARG(x && out && n >= 0, "scaled_sum: bad arguments");
   hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, x, n, scale, out);
@@ -1137,11 +1438,16 @@ static unsigned dense_grid(long ncell) { return (unsigned)(ceil_div(ncell, 4) < 
 
 template <typename TZ>
 static int launch_lse_dense(const void* logits, const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
-                            float* blk, float* emit, hipStream_t s) {
+                            float* blk, float* emit, hipStream_t s, const Win* win = nullptr) {
   const long ncell = (long)B * T * U1;
   {
   ProfScope prof(RNNT_K_LSE, (double)sizeof(TZ) * (double)ncell * V + 8.0 * (double)ncell, s);
-  hipLaunchKernelGGL((lse_dense_kernel<TZ>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V, blank, blk, emit);
+  if (win)
+    hipLaunchKernelGGL((lse_dense_kernel<TZ, true, Win>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V,
+                       blank, blk, emit, *win);
+  else
+    hipLaunchKernelGGL((lse_dense_kernel<TZ, false>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V,
+                       blank, blk, emit);
   }
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
@@ -1150,27 +1456,44 @@ static int launch_lse_dense(const void* logits, const int32_t* labels, int32_t B
 template <typename TZ>
 static int loss_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
                                  int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fe,
-                                 float* nll, void* grad, void* workspace, size_t workspace_bytes, void* stream) {
+                                 float* nll, void* grad, void* workspace, size_t workspace_bytes, void* stream,
+                                 bool windowed = false, const int32_t* emit_lo = nullptr, const int32_t* emit_hi = nullptr,
+                                 int64_t win_stride = 0) {
   if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
   if (int rc = check_fastemit(fe, "loss_from_logits")) return rc;
+  if (windowed)
+    if (int rc = check_window(emit_lo, emit_hi, win_stride, U1, "loss_from_logits_window")) return rc;
   RNNT_CHECK_ARG(logits, "loss_from_logits: null logits");
-  const LossWs w = carve(workspace, B, T, U1, V, true);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "loss_from_logits: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  // windowed: the plain workspace plus the band tables, and the W = true kernel instances (the sweep is the same)
+  const WinWs x = windowed ? carve_window(workspace, B, T, U1, V) : WinWs{carve(workspace, B, T, U1, V, true), nullptr, nullptr, nullptr, 0};
+  const LossWs& w = x.w;
+  const size_t need = windowed ? x.total : w.total;
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= need, "loss_from_logits: workspace too small (%zu < %zu)", workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const long ncell = (long)B * T * U1;
   const unsigned grid = dense_grid(ncell);
-  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
+  const Win win = {x.L, x.R, emit_lo, emit_hi, u_lens, (long)win_stride};
+  if (windowed)
+    if (int rc = launch_band(x, emit_lo, emit_hi, win_stride, t_lens, u_lens, B, T, U1, s)) return rc;
+  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s, windowed ? &win : nullptr)) return rc;
   if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
-  hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
+  if (windowed)
+    hipLaunchKernelGGL(nll_window_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, x.feas, B, nll);
+  else
+    hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
   RNNT_CHECK_LAUNCH();
   if (grad) {
     ProfScope prof(RNNT_K_LATGRAD, 2.0 * sizeof(TZ) * (double)ncell * V + 24.0 * (double)ncell, s);
-    if (fe != 0.f)
-      hipLaunchKernelGGL((grad_dense_kernel<TZ, true>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk,
-                         w.emit, w.alpha, w.beta, w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, fe);
-    else
-      hipLaunchKernelGGL((grad_dense_kernel<TZ, false>), dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk,
-                         w.emit, w.alpha, w.beta, w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, 0.f);
+#define GD(KERNEL, LAM, ...)                                                                                                       \
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk, w.emit, w.alpha, w.beta, \
+                     w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, LAM, ##__VA_ARGS__)
+    const Band band = {x.L, x.R};
+    if (windowed) {
+      if (fe != 0.f) GD((grad_dense_kernel<TZ, true, true, Band>), fe, band); else GD((grad_dense_kernel<TZ, false, true, Band>), 0.f, band);
+    } else {
+      if (fe != 0.f) GD((grad_dense_kernel<TZ, true, false>), fe); else GD((grad_dense_kernel<TZ, false, false>), 0.f);
+    }
+#undef GD
     RNNT_CHECK_LAUNCH();
   }
   return RNNT_OK;
@@ -1193,6 +1516,28 @@ extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_fastemit(const void* logits, in
                                           workspace_bytes, stream);
     default:
       set_error("loss_from_logits: unknown dtype code %d", dtype);
+      return RNNT_ERR_INVALID;
+  }
+}
+
+extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_window(const void* logits, int32_t dtype, const int32_t* labels,
+                                                        const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
+                                                        int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
+                                                        const int32_t* emit_lo, const int32_t* emit_hi, int64_t win_stride,
+                                                        float* nll, void* grad, void* workspace, size_t workspace_bytes,
+                                                        void* stream) {
+  switch (dtype) {
+    case RNNT_DTYPE_F32:
+      return loss_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
+    case RNNT_DTYPE_F16:
+      return loss_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
+    case RNNT_DTYPE_BF16:
+      return loss_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
+                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
+    default:
+      set_error("loss_from_logits_window: unknown dtype code %d", dtype);
       return RNNT_ERR_INVALID;
   }
 }

@@ -16,7 +16,10 @@ class RNNTLoss(nn.Module):
     """`fastemit_lambda` > 0 (finite, >= 0; default 0) adds FastEmit regularisation (Yu et al., ICASSP 2021): the gradient with respect
     to the label log-probabilities of every lattice cell is scaled by 1 + lambda and taken through the log-softmax exactly
     (include/rnnt_hip.h), which trains the model to emit sooner.  ONLY THE GRADIENT CHANGES: the returned loss is the unregularised
-    negative log-likelihood, bit for bit what lambda = 0 returns."""
+    negative log-likelihood, bit for bit what lambda = 0 returns.
+    `forward(..., emit_windows=(lo, hi))`, two (B, U) int32 tensors, gives the alignment-restricted loss (Ar-RNN-T): label u of row b
+    may be emitted only at frames lo[b,u] .. hi[b,u] (ops.emit_windows builds them around a reference alignment); a row whose windows
+    leave no path has loss +inf and a zero gradient.  None (the default): the unrestricted loss."""
 
     def __init__(self, blank: int = 0, reduction: str = "mean", fastemit_lambda: float = 0.0):
         super().__init__()
@@ -26,10 +29,11 @@ class RNNTLoss(nn.Module):
         self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
 
     def forward(self, logits: torch.Tensor, targets: torch.Tensor, logit_lengths: torch.Tensor,
-                target_lengths: torch.Tensor) -> torch.Tensor:
+                target_lengths: torch.Tensor, emit_windows=None) -> torch.Tensor:
         if logits.dim() != 4:
             raise ValueError("logits must be (B, T, U+1, V)")
-        nll = RnntLossFromLogitsFn.apply(logits, targets, logit_lengths, target_lengths, self.blank, self.fastemit_lambda)
+        nll = RnntLossFromLogitsFn.apply(logits, targets, logit_lengths, target_lengths, self.blank, self.fastemit_lambda,
+                                         emit_windows)
         if self.reduction == "mean":
             return nll.mean()
         if self.reduction == "sum":

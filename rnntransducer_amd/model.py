@@ -16,6 +16,9 @@ Differences, all inside the hot path:
     default; the reference has neither.
   * `args.fastemit_lambda` (default 0.0: off) adds FastEmit regularisation to `training_step`: the lattice gradient is changed so that
     the model learns to emit sooner, the logged loss stays the unregularised one (JointNet.loss).  The reference has no such knob.
+  * `args.ar_left` / `args.ar_right` (default None: off) make `training_step` train the alignment-restricted loss (Ar-RNN-T): the batch
+    then carries an 8th element, a (B, U) int32 table of reference frames (a teacher's `align`, `recognize_ctc_greedy(...,
+    return_frames=True)`, an external aligner), and label u may be emitted only at frames [frame - ar_left, frame + ar_right].
   * `args.mwer_weight` (default 0.0: off), `args.mwer_nbest` (4) and `args.mwer_max_symbols` (1) add minimum word error rate
     fine-tuning to `training_step`: loss = rnnt + ctc_weight * ctc + mwer_weight * risk, the risk being the expected number of token
     errors over the model's own n-best list (JointNet.mwer_loss).  With the weight at 0 the step is today's, bit for bit.
@@ -29,7 +32,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
-from .ops import check_fastemit_lambda
+from .ops import check_fastemit_lambda, emit_windows
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -63,6 +66,13 @@ class RNNTransducer(_Base):
         # model.py:28-39 picks torchaudio (precision 16) or warp-transducer; both are this one HIP module here
         self.fastemit_lambda = check_fastemit_lambda(getattr(args, "fastemit_lambda", 0.0) or 0.0)
         self.rnnt_loss = RNNTLoss(blank=self.blank_token_id, reduction="mean", fastemit_lambda=self.fastemit_lambda)
+        # alignment-restricted loss (JointNet.loss's emit_windows): both knobs or neither; None leaves training_step as it is
+        self.ar_left, self.ar_right = getattr(args, "ar_left", None), getattr(args, "ar_right", None)
+        if (self.ar_left is None) != (self.ar_right is None):
+            raise ValueError("args.ar_left and args.ar_right must be set together")
+        for name, v in (("args.ar_left", self.ar_left), ("args.ar_right", self.ar_right)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+                raise ValueError(f"{name} must be an integer >= 0 or None, got {v!r}")
         self.ctc_weight = float(getattr(args, "ctc_weight", 0.0) or 0.0)
         if self.ctc_weight > 0.0 and not self.jointnet.aux_ctc:
             raise ValueError("args.ctc_weight > 0 needs the CTC head: set jointnet_params['aux_ctc'] = True")
@@ -152,9 +162,18 @@ class RNNTransducer(_Base):
 
     def training_step(self, batch, batch_idx):
         assert not getattr(self.args, "move_metrics_to_cpu", False), "DDP only (model.py:53)"
+        windows = None
+        if self.ar_left is not None:   # alignment-restricted loss: the batch's 8th element is the (B, U) reference frame table
+            if len(batch) != 8:
+                raise ValueError(f"args.ar_left / args.ar_right are set: training_step takes an 8-element batch whose last element is "
+                                 f"the (B, U) int32 reference frame table, got {len(batch)} elements")
+            windows = emit_windows(batch[7], batch[2], batch[6], self.ar_left, self.ar_right)
+            batch = batch[:7]
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         lengths = audio_lengths if isinstance(audio_lengths, (list, tuple)) else None
         logging = pl is not None and getattr(self, "_trainer", None) is not None
+        if windows is not None and self.mwer_weight > 0.0:
+            raise ValueError("args.ar_left / args.ar_right do not combine with args.mwer_weight > 0: mwer_loss takes no emission windows")
         if self.mwer_weight > 0.0:   # rnnt + ctc_weight * ctc + mwer_weight * risk over the model's own n-best list
             out = self.jointnet.mwer_loss(
                 input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
@@ -166,7 +185,8 @@ class RNNTransducer(_Base):
             return {"loss": out[0] if logging else out}
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
-                                  audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda)
+                                  audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda,
+                                  emit_windows=windows)
         if logging:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}

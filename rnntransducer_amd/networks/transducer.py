@@ -31,7 +31,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import (MWER_MAX_LEN, CtcLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens, beam_search,
-                   beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args, check_fastemit_lambda,
+                   beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args, check_emit_windows,
+                   check_fastemit_lambda,
                    check_fusion, ctc_beam_search, ctc_greedy, edit_distance, greedy_decode, nbest_pack, nbest_umax, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
@@ -105,7 +106,7 @@ class JointNet(nn.Module):
 
     def loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int,
              reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False,
-             fastemit_lambda: float = 0.0):
+             fastemit_lambda: float = 0.0, emit_windows=None):
         """-log P(y|x) through the fused path (no (B,T,U+1,V) tensor): per utterance, shape (B,) (reduction "none"), or the 0-d
         "mean" / "sum" over the batch (model.py:39 builds the reference's loss with reduction="mean").
         `audio_lengths`: the python list of frame counts the reference's collate hands over next to the tensor (dataloader.py:20,49).
@@ -119,12 +120,16 @@ class JointNet(nn.Module):
         With ctc_weight = 0 and return_parts=False the head is not touched: same bits as a model without it.
         `fastemit_lambda` > 0: FastEmit regularisation of the transducer term's GRADIENT (label log-probability gradients scaled by
         1 + lambda, through the log-softmax exactly: include/rnnt_hip.h), which trains the model to emit sooner.  The returned value
-        stays the unregularised loss, bit for bit that of lambda = 0; the CTC term is untouched.  Finite and >= 0."""
+        stays the unregularised loss, bit for bit that of lambda = 0; the CTC term is untouched.  Finite and >= 0.
+        `emit_windows` = (lo, hi), two (B, U) int32 tensors in the CALLER's row order (they follow their rows through the ragged
+        sort): the alignment-restricted transducer term, label u of row b only at frames lo[b,u] .. hi[b,u] (ops.emit_windows builds
+        them around a reference alignment; include/rnnt_hip.h).  A row whose windows leave no path has loss +inf and a zero gradient.
+        The CTC term is untouched.  None: the unrestricted loss."""
         return self._reference_terms(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
-                                     audio_lengths, ctc_weight, return_parts, fastemit_lambda)[0]
+                                     audio_lengths, ctc_weight, return_parts, fastemit_lambda, emit_windows=emit_windows)[0]
 
     def _reference_terms(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
-                         audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False):
+                         audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False, emit_windows=None):
         """The body of loss(): -> (what loss() returns, (enc, targets, t_lens, u_lens, inv)) with the encoder output and the
         per-row tensors in the row order the encoder ran in (length-sorted for a ragged batch; `inv` restores the caller's order,
         None when nothing moved or nobody needs it).  mwer_loss builds its hypothesis term on the same encoder output."""
@@ -135,12 +140,19 @@ class JointNet(nn.Module):
         t_lens = lengths_to_device(tensor_audio_lengths, dev)
         u_lens = lengths_to_device(target_lengths, dev)
         T, B = input_audios.size(1), input_audios.size(0)
-        (input_audios, input_texts, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
-            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), reduction == "none" or want_inv)
+        win = check_emit_windows(emit_windows, B, targets.size(1), dev)
+        rows = (input_audios, input_texts, targets) + (() if win is None else (win[0], win[1]))   # the windows are sorted with their rows
+        rows, t_lens, u_lens, enc_lens, inv = self._ragged_rows(audio_lengths, T, B, dev, t_lens, u_lens, rows,
+                                                                reduction == "none" or want_inv)
+        input_audios, input_texts, targets = rows[:3]
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
-        out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction,
-                                fastemit_lambda)
+        if win is None:
+            out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
+                                    reduction, fastemit_lambda)
+        else:
+            out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
+                                    reduction, fastemit_lambda, (rows[3], rows[4]))
         unsort = inv is not None and reduction == "none"
         shared = (enc, targets, t_lens, u_lens, inv)
         out = out.index_select(0, inv) if unsort else out
@@ -196,6 +208,7 @@ class JointNet(nn.Module):
           3. the reference term exactly as loss() computes it (same code: ragged handling, ctc_weight, fastemit_lambda);
           4. the prediction net on the packed hypotheses, the fused loss for the nbest rows of each utterance over its one encoder
              row (ops.JointLossGroupedFn; FastEmit does not apply to them), the edit distances and the risk, all on the device.
+        No emission windows (loss()'s emit_windows): the rows of the risk term are hypotheses and have no reference alignment.
         A hypothesis longer than max_hyp_len (<= 511) tokens is left out, as are the ranks the search did not fill; an utterance
         with fewer than two valid hypotheses has risk 0.  No host sync beyond the search's one copy of counts and lengths.
         reduction: "none" (B,), "mean" or "sum" over B, for every term.  return_parts=True -> (total, rnnt[, ctc], risk,

@@ -757,18 +757,62 @@ def check_fastemit_lambda(fastemit_lambda) -> float:
     return lam
 
 
+def check_emit_windows(emit_windows, B: int, U: int, device):
+    """Emission windows of the alignment-restricted loss (include/rnnt_hip.h): None, or a pair (lo, hi) of (B, U) int32 tensors on
+    `device`.  -> None, or (lo, hi, row stride) as the library takes them (contiguous; one column of padding when U = 0, so that the
+    pointers are not null).  ValueError for anything else, before anything runs."""
+    if emit_windows is None:
+        return None
+    if not isinstance(emit_windows, (tuple, list)) or len(emit_windows) != 2:
+        raise ValueError(f"emit_windows must be None or a pair (lo, hi) of (B, U) int32 tensors, got {type(emit_windows).__name__}")
+    out = []
+    for name, t in zip(("emit_windows lo", "emit_windows hi"), emit_windows):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32, got {t.dtype}")
+        if tuple(t.shape) != (B, U):
+            raise ValueError(f"{name} must be (B, U) = ({B}, {U}), got {tuple(t.shape)}")
+        if t.device != torch.device(device):
+            raise ValueError(f"{name} must be on {device}, got {t.device}")
+        out.append(t.contiguous() if U > 0 else torch.zeros(B, 1, dtype=torch.int32, device=t.device))
+    return out[0], out[1], max(U, 1)
+
+
+def emit_windows(frames, t_lens, u_lens, left: int, right: int):
+    """(lo, hi) = (frames - left, frames + right), int32, for the `emit_windows` argument of the losses: label u of row b may be
+    emitted at most `left` frames before and `right` frames after its reference frame frames[b, u].  `frames`: a (B, U) integer table
+    such as align().frames (entries past u_lens[b] are not read by the loss; -1 there is fine).  The loss itself clamps the windows to
+    [0, t_lens[b] - 1]; t_lens / u_lens are only checked against the table's batch size here.  Plain torch ops: not a hot path."""
+    for name, v in (("left", left), ("right", right)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"emit_windows: {name} must be an integer >= 0, got {v!r}")
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 2 or frames.is_floating_point() or frames.dtype == torch.bool:
+        raise ValueError("emit_windows: frames must be a (B, U) integer tensor")
+    for name, t in (("t_lens", t_lens), ("u_lens", u_lens)):
+        n = len(t) if isinstance(t, (list, tuple)) else (t.numel() if isinstance(t, torch.Tensor) else None)
+        if n != frames.shape[0]:
+            raise ValueError(f"emit_windows: {name} must hold one length per row of frames ({frames.shape[0]})")
+    fr = frames.to(torch.int32)
+    return fr - left, fr + right
+
+
 class JointLossFn(torch.autograd.Function):
     """enc (T,B,Oe), dec (U1,B,Od) time-major -> per-utterance NLL (B,).  Never builds (B,T,U1,V).
     forward: A/C pre-GEMMs + log-softmax terms + alpha/beta (kept in a workspace); backward: the lattice gradient kernel with
     the upstream per-utterance gradient folded in (1/B under reduction="mean", model.py:39), then the joint's own backward.
     Under torch.no_grad() (validation_step) no gradient kernel runs and nothing is kept.
     fastemit_lambda > 0: FastEmit regularisation of the GRADIENT (label log-probability gradients scaled by 1 + lambda, through the
-    log-softmax exactly; include/rnnt_hip.h).  The returned loss stays the unregularised NLL, bit for bit that of lambda = 0."""
+    log-softmax exactly; include/rnnt_hip.h).  The returned loss stays the unregularised NLL, bit for bit that of lambda = 0.
+    emit_windows = (lo, hi), two (B,U) int32 tensors: the alignment-restricted loss (label u only at frames lo[b,u] .. hi[b,u]; an
+    infeasible row has NLL +inf and a zero gradient; include/rnnt_hip.h).  None: the unrestricted loss, the entries without windows."""
 
     @staticmethod
-    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0):
+    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0,
+                emit_windows=None):
         _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
         ctx.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
+        win = check_emit_windows(emit_windows, enc.shape[1], dec.shape[0] - 1, enc.device)
         w_param, b_param = W, bias
         enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
         for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
@@ -783,12 +827,22 @@ class JointLossFn(torch.autograd.Function):
                              f"targets {tuple(labels.shape)}")
         A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
         nll = torch.empty(B, device=enc.device, dtype=torch.float32)
-        nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
-        ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
-        check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
-                                                     _addr(t_lens), _addr(u_lens), B, T, U1, V, int(blank), 1.0,
-                                                     _addr(nll), None, None, _addr(ws), nws, _stream()),
-              "rnnt_hip_joint_loss_fwd_bwd")
+        if win is None:
+            nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
+            ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
+            check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
+                                                         _addr(t_lens), _addr(u_lens), B, T, U1, V, int(blank), 1.0,
+                                                         _addr(nll), None, None, _addr(ws), nws, _stream()),
+                  "rnnt_hip_joint_loss_fwd_bwd")
+        else:
+            nws = _lib.lib().rnnt_hip_joint_loss_window_workspace_bytes(B, T, U1, V)
+            ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
+            check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd_window(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
+                                                                _addr(t_lens), _addr(u_lens), B, T, U1, V, int(blank), 1.0,
+                                                                ctx.fastemit_lambda, _addr(win[0]), _addr(win[1]), win[2],
+                                                                _addr(nll), None, None, _addr(ws), nws, _stream()),
+                  "rnnt_hip_joint_loss_fwd_bwd_window")
+        ctx.windowed = win is not None   # the backward reads the band tables the forward left in the workspace
         if want_grad and any(ctx.needs_input_grad[:4]):  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
             ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws)
             ctx.blank = int(blank)
@@ -808,14 +862,15 @@ class JointLossFn(torch.autograd.Function):
         gvec = _f32c(g.to(torch.float32), "grad of the loss")
         scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
         dA, dC = torch.empty_like(A), torch.empty_like(Cm)
-        check(_lib.lib().rnnt_hip_joint_loss_bwd_fastemit(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
-                                                          _addr(t_lens), _addr(u_lens), B, T, U1, V, ctx.blank,
-                                                          ctx.red_scale if scalar else 1.0, ctx.fastemit_lambda, _addr(gvec),
-                                                          0 if scalar else 1, _addr(dA), _addr(dC), _addr(ws), ws.numel(), _stream()),
-              "rnnt_hip_joint_loss_bwd_fastemit")
+        L = _lib.lib()
+        bwd, what = ((L.rnnt_hip_joint_loss_bwd_window, "rnnt_hip_joint_loss_bwd_window") if ctx.windowed else
+                     (L.rnnt_hip_joint_loss_bwd_fastemit, "rnnt_hip_joint_loss_bwd_fastemit"))
+        check(bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(t_lens), _addr(u_lens), B, T, U1, V,
+                  ctx.blank, ctx.red_scale if scalar else 1.0, ctx.fastemit_lambda, _addr(gvec), 0 if scalar else 1, _addr(dA),
+                  _addr(dC), _addr(ws), ws.numel(), _stream()), what)
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
                                                _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
-        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None
+        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None, None
 
 
 class JointLossGroupedFn(torch.autograd.Function):
@@ -824,7 +879,8 @@ class JointLossGroupedFn(torch.autograd.Function):
     per-row NLL (B*group,), the bits JointLossFn gives on enc.repeat_interleave(group, dim=1).
     A = gelu(enc) W_e^T is computed ONCE as (T,B,V) and expanded to (T,B*group,V) by a gather for the unchanged loss kernels; the
     backward adds dA over the group in rank order (a fixed order: bitwise reproducible) before the joint's own backward, so the
-    encoder-side GEMMs run once per step, not `group` times.  reduction "none" only, and no FastEmit: the rows are hypotheses."""
+    encoder-side GEMMs run once per step, not `group` times.  reduction "none" only, and no FastEmit: the rows are hypotheses.
+    No emission windows either (JointLossFn's emit_windows): a hypothesis has no reference alignment to build them from."""
 
     @staticmethod
     def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, group, want_grad=True):
@@ -908,12 +964,16 @@ class JointLogitsFn(torch.autograd.Function):
 
 class RnntLossFromLogitsFn(torch.autograd.Function):
     """warp-transducer-shaped loss on dense logits (model.py:39,57) -> per-utterance NLL (B,).
-    fastemit_lambda > 0: FastEmit regularisation of the gradient only (see JointLossFn); the NLL is that of lambda = 0."""
+    fastemit_lambda > 0: FastEmit regularisation of the gradient only (see JointLossFn); the NLL is that of lambda = 0.
+    emit_windows = (lo, hi), (B,U) int32: the alignment-restricted loss (see JointLossFn); None: the unrestricted one."""
 
     @staticmethod
-    def forward(ctx, logits, targets, t_lens, u_lens, blank, fastemit_lambda=0.0):
+    def forward(ctx, logits, targets, t_lens, u_lens, blank, fastemit_lambda=0.0, emit_windows=None):
         _need_gpu(logits, targets, t_lens, u_lens)
         lam = check_fastemit_lambda(fastemit_lambda)
+        if logits.dim() != 4:
+            raise ValueError("logits must be (B, T, U+1, V)")
+        win = check_emit_windows(emit_windows, logits.shape[0], logits.shape[2] - 1, logits.device)
         codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
         if logits.dtype not in codes:
             raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
@@ -927,12 +987,21 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
         targets = targets.contiguous()
         nll = torch.empty(B, device=logits.device, dtype=torch.float32)
         grad = torch.empty_like(logits) if logits.requires_grad else None
-        nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
-        ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
-        check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_fastemit(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
-                                                                    _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(nll),
-                                                                    _addr(grad), _addr(ws), nws, _stream()),
-              "rnnt_hip_loss_from_logits_fwd_bwd_fastemit")
+        if win is None:
+            nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
+            ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
+            check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_fastemit(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
+                                                                        _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(nll),
+                                                                        _addr(grad), _addr(ws), nws, _stream()),
+                  "rnnt_hip_loss_from_logits_fwd_bwd_fastemit")
+        else:
+            nws = _lib.lib().rnnt_hip_joint_loss_window_workspace_bytes(B, T, U1, V)
+            ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
+            check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_window(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
+                                                                      _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(win[0]),
+                                                                      _addr(win[1]), win[2], _addr(nll), _addr(grad), _addr(ws), nws,
+                                                                      _stream()),
+                  "rnnt_hip_loss_from_logits_fwd_bwd_window")
         ctx.grad = grad
         return nll
 
@@ -940,7 +1009,7 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.grad
         ctx.grad = None
-        return (grad.float() * g.to(torch.float32).view(-1, 1, 1, 1)).to(grad.dtype), None, None, None, None, None
+        return (grad.float() * g.to(torch.float32).view(-1, 1, 1, 1)).to(grad.dtype), None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
