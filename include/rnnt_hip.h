@@ -945,6 +945,7 @@ int rnnt_hip_beam_stream_chunk_fused(const rnnt_beam_stream_desc* d, const rnnt_
  *     1. candidates of the member h at rank i of C: blank with value score_h + lp_h[blank], and every v != blank with
  *        lp_h[v] >= token_min_logp with value score_h + lp_h[v]; candidate id i V + v.  With fusion the rank key is
  *        value + total', total' = total_h for blank and total_h + arc[s_h, v] otherwise; the pruning test stays on lp.
+ *        (Internal-LM subtraction, rnnt_hip_beam_sync_search_ilm below: total' = (total_h + arc[s_h, v]) - mu * ilm_h[v].)
  *     2. the min(W, #candidates) best by (key descending, id ascending) are selected; a value or key of -inf is dropped.
  *     3. in rank order: a selected blank closes h: it is added to D under h's node, and if that node is in D already the scores
  *        merge, score = logaddexp(old, new) (state and total are the same by construction).  A selected token v makes the
@@ -1143,6 +1144,54 @@ int rnnt_hip_ctc_beam_search_ngram(const float* logits, int64_t z_sb, int64_t z_
                                    int32_t V, int32_t blank, int32_t W, float token_min_logp, const rnnt_beam_ngram* lm,
                                    int32_t* tokens, int32_t* lens, double* scores, int32_t* frames, int32_t* counts, void* workspace,
                                    size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Internal-LM subtraction (ILME; Meng et al. 2021, "Internal Language Model Estimation for Domain-Adaptive End-to-End Speech
+ * Recognition") for the frame-synchronous search and its streaming form.  csrc/beam_sync_shared.hpp, DESIGN.md §25.
+ * A transducer's prediction net is a language model of the training transcripts; shallow fusion with an external LM counts a
+ * language prior twice.  The internal LM is the joint with the encoder's contribution zeroed: the joint is
+ * fc(gelu(cat(enc, dec))) and gelu(0) = 0, so the internal-LM logits of hypothesis h are exactly Cv_h[v] + bias[v], with Cv_h the
+ * joint half the search already keeps per prediction-net state and bias = fc.bias.
+ * Definition.  For v != blank:
+ *     ilm_h[v] = ((Cv_h[v] + bias[v]) - m_h) - lse_h                                   (fp32)
+ * the log-softmax over the NON-BLANK vocabulary: m_h = max over v != blank of Cv_h[v] + bias[v], lse_h = log of the sum over
+ * v != blank of exp((Cv_h[v] + bias[v]) - m_h).  The blank is excluded from the maximum and from the sum.
+ * With weight mu > 0, step 1 of rnnt_hip_beam_sync_search's definition changes in one place: for a candidate v != blank
+ *     total' = (total_h + (double)arc[s_h, v]) - (double)mu * (double)ilm_h[v]         (fp64, no fused multiply-add)
+ * This one expression is evaluated where the candidate keys are filled and again where the selected candidates are built: the
+ * same bits at both.  The blank is unchanged (total' = total_h).  Everything else reads as before: ranking by score + total,
+ * the top-W of D, the output order by score + total + final[state], fused_scores, frames; the pruning test stays on lp, the ASR
+ * log-probability.  fused_scores = score + total + final with total = the automaton's arcs along y minus mu times the sum of
+ * ilm over y's tokens.
+ * ilm_h is a function of y alone, because the prediction-net state is; so are the automaton's state and total.  The merge
+ * rule's "state and total are the same by construction" therefore still holds with the term in the total.
+ * -mu * ilm_h[v] is a per-token bonus >= 0.  The search is bounded by W, V, S and T in advance and has no pop loop: no bonus,
+ * however large, can make a cap overflow (rnnt_hip_beam_search's best-first search has no such bound and takes no ilm).
+ * V = 2 has one non-blank token: m = the logit, exp(0) = 1, log 1 = 0, ilm = 0 and total' = (total + arc) - 0: the *_ilm entry
+ * returns the bits of the entry it extends.
+ * (m_h, lse_h) is computed once per prediction-net step (a wavefront per new state, lanes along v, in an order that depends on
+ * neither the step group nor the hypothesis's place in it) and kept per state slot: 2 floats per slot behind the other
+ * workspace parts ((B, NS, 2) offline; one more carried part per stream, which chunk boundaries and collections leave alone:
+ * a collection moves prefix nodes, never state slots).  So the *_ilm entries have their own workspace queries, and a stream
+ * opened for them its own reset.  The descriptor and every other argument are those of the entry they extend.
+ * Entries: exactly one of fusion / lm is given (ILM subtraction alone: a one-state all-zero rnnt_beam_fusion); ilm is required.
+ * Checked on the host before any launch (RNNT_ERR_INVALID), beside the extended entry's own checks: ilm NULL, bias NULL, weight
+ * not finite or <= 0, both or neither of fusion / lm, the workspace smaller than the *_ilm query's size or misaligned.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rnnt_beam_ilm {
+  const float* bias;      /* (V) fc.bias, device */
+  float weight;           /* mu: finite, > 0 */
+} rnnt_beam_ilm;
+size_t rnnt_hip_beam_sync_ilm_workspace_bytes(const rnnt_beam_sync_desc* d);  /* 0 if the descriptor's sizes are invalid */
+int rnnt_hip_beam_sync_search_ilm(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion /* or NULL */,
+                                  const rnnt_beam_ngram* lm /* or NULL */, const rnnt_beam_ilm* ilm,
+                                  const rnnt_beam_timing* timing /* or NULL */, void* stream);
+size_t rnnt_hip_beam_sync_stream_ilm_workspace_bytes(const rnnt_beam_sync_stream_desc* d);  /* 0 if the sizes are invalid */
+int rnnt_hip_beam_sync_stream_reset_ilm(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows, int32_t build_table,
+                                        void* stream);
+int rnnt_hip_beam_sync_stream_chunk_ilm(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion /* or NULL */,
+                                        const rnnt_beam_ngram* lm /* or NULL */, const rnnt_beam_ilm* ilm,
+                                        const rnnt_beam_timing* timing /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).

@@ -191,6 +191,10 @@ class BeamNgram(C.Structure):
                 ("n_arcs", c_i32), ("fused_scores", C.c_void_p)]
 
 
+class BeamIlm(C.Structure):
+    _fields_ = [("bias", C.c_void_p), ("weight", C.c_float)]
+
+
 # every symbol include/rnnt_hip.h declares: (name, restype, argtypes)
 SYMBOLS = {
     "rnnt_hip_version": (C.c_int, []),
@@ -328,6 +332,13 @@ SYMBOLS = {
     "rnnt_hip_ctc_beam_search_ngram": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float,
                                                  C.POINTER(BeamNgram), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_beam_sync_ilm_workspace_bytes": (C.c_size_t, [C.POINTER(BeamSyncDesc)]),
+    "rnnt_hip_beam_sync_search_ilm": (C.c_int, [C.POINTER(BeamSyncDesc), C.POINTER(BeamFusion), C.POINTER(BeamNgram),
+                                                C.POINTER(BeamIlm), C.POINTER(BeamTiming), C.c_void_p]),
+    "rnnt_hip_beam_sync_stream_ilm_workspace_bytes": (C.c_size_t, [C.POINTER(BeamSyncStreamDesc)]),
+    "rnnt_hip_beam_sync_stream_reset_ilm": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.c_void_p, c_i32, c_i32, C.c_void_p]),
+    "rnnt_hip_beam_sync_stream_chunk_ilm": (C.c_int, [C.POINTER(BeamSyncStreamDesc), C.POINTER(BeamFusion), C.POINTER(BeamNgram),
+                                                      C.POINTER(BeamIlm), C.POINTER(BeamTiming), C.c_void_p]),
     "rnnt_hip_frontend_norm_pad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, c_i64, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_power_mel_log1p": (C.c_int, [C.c_void_p, c_i64, c_i32, C.c_void_p, c_i32, C.c_void_p, c_i32, C.c_void_p, C.c_void_p]),
     "rnnt_hip_edit_distance": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i32, c_i32, C.c_void_p,

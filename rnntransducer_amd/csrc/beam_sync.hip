@@ -42,8 +42,9 @@
 // State slots (h | c | Cv) live in the caller's workspace, (S+2) W per utterance: W for the beam, (S-1) W for the rounds'
 // children, W for the next beam's pending steps; the free list is rebuilt at every frame's start from the slots the beam holds.
 // All score sums are fp64 with logaddexp_d in the fixed order above: bitwise reproducible.
-// The kernel (beam_sync_kernel<FUSE, STREAM>) lives in beam_sync_shared.hpp: this file launches its STREAM = false instances,
-// beam_sync_stream.hip the streaming ones.
+// The kernel (beam_sync_kernel<FUSE, STREAM, ILM>) lives in beam_sync_shared.hpp: this file launches its STREAM = false
+// instances, beam_sync_stream.hip the streaming ones.  ILM (the *_ilm entries): internal-LM subtraction, for a
+// non-blank candidate total' = (total_h + arc[s_h, v]) - mu * ilm_h[v] with ilm_h the log-softmax over v != blank of Cv_h + fc.bias.
 #include "beam_sync_shared.hpp"
 
 namespace rnnt {
@@ -54,12 +55,13 @@ struct BsWs {
   u64* keys;
   int* nodes;
   float* slots;
+  float* ilm;   // the *_ilm entries only: (B, NS, 2) pairs, behind every other part
   size_t total;
   int SF, NS;
   long maxn;
 };
 
-BsWs carve_bs(void* ws, const rnnt_beam_sync_desc* d) {
+BsWs carve_bs(void* ws, const rnnt_beam_sync_desc* d, bool ilm = false) {
   BsWs w;
   char* p = reinterpret_cast<char*>(ws);
   size_t off = 0;
@@ -71,6 +73,7 @@ BsWs carve_bs(void* ws, const rnnt_beam_sync_desc* d) {
   w.keys = reinterpret_cast<u64*>(ws_take(p, off, (size_t)B * W * V * 8));
   w.nodes = reinterpret_cast<int*>(ws_take(p, off, (size_t)B * 5 * w.maxn * 4));
   w.slots = reinterpret_cast<float*>(ws_take(p, off, (size_t)B * w.NS * w.SF * 4));
+  w.ilm = ilm ? reinterpret_cast<float*>(ws_take(p, off, (size_t)B * w.NS * 2 * 4)) : nullptr;
   w.total = off;
   return w;
 }
@@ -100,9 +103,9 @@ extern "C" int rnnt_hip_beam_sync_step_group(const rnnt_beam_sync_desc* d) {
   return bs_group(d);
 }
 
-// the search behind both entries: fusion (dense tables), lm (backoff tables), or neither
+// the search behind every entry: fusion (dense tables), lm (backoff tables), or neither; ilm on top of either of the two
 static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm, bool ngram,
-                     const rnnt_beam_timing* timing, void* stream, const char* who) {
+                     const rnnt_beam_ilm* ilm, const rnnt_beam_timing* timing, void* stream, const char* who) {
   int rc = bs_check_dims(d, who);
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->A && d->tokens && d->lens && d->scores && d->count, "%s: null A/tokens/lens/scores/count", who);
@@ -114,7 +117,7 @@ static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusio
   if (fusion && (rc = check_fusion_struct(fusion, d->V, who)) != RNNT_OK) return rc;
   k.ng = NgramLm{};
   if (ngram && (rc = check_ngram_struct(lm, d->V, k.ng, who)) != RNNT_OK) return rc;
-  const BsWs w = carve_bs(d->workspace, d);
+  const BsWs w = carve_bs(d->workspace, d, ilm != nullptr);
   RNNT_CHECK_ARG(d->workspace && d->workspace_bytes >= w.total, "%s: workspace too small (%zu < %zu)", who, d->workspace_bytes, w.total);
   RNNT_CHECK_ARG((reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
   k.T = d->T; k.B = d->B; k.W = d->beam; k.S = d->max_symbols; k.G = bs_group(d);
@@ -127,9 +130,12 @@ static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusio
   k.fnext = fusion ? fusion->next : nullptr; k.farc = fusion ? fusion->arc : nullptr; k.ffinal = fusion ? fusion->final : nullptr;
   k.n_states = fusion ? fusion->n_states : 1; k.fused = fusion ? fusion->fused_scores : nullptr;
   if (ngram) { k.ffinal = lm->final; k.n_states = lm->n_states; k.fused = lm->fused_scores; }
+  k.ilm_bias = ilm ? ilm->bias : nullptr; k.ilm_w = ilm ? ilm->weight : 0.f; k.ilm = w.ilm; k.off_ilm = 0;
   const size_t lds = (size_t)k.G * bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  const void* fn = ngram    ? (const void*)beam_sync_kernel<FUSE_NGRAM, false>
+  const void* fn = ilm      ? (ngram ? (const void*)beam_sync_kernel<FUSE_NGRAM, false, true>
+                                     : (const void*)beam_sync_kernel<FUSE_DENSE, false, true>)
+                   : ngram  ? (const void*)beam_sync_kernel<FUSE_NGRAM, false>
                    : fusion ? (const void*)beam_sync_kernel<FUSE_DENSE, false>
                             : (const void*)beam_sync_kernel<FUSE_NONE, false>;
   if (lds + sizeof(BsShared) > 64 * 1024) RNNT_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -139,7 +145,9 @@ static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusio
   tk.table = w.table;
   hipLaunchKernelGGL(beam_table_kernel, dim3(d->V), dim3(DEC_THREADS), (size_t)d->Hp * sizeof(float), s, tk);
   RNNT_CHECK_LAUNCH();
-  if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  if (ilm && ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, false, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (ilm) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, false, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   else if (fusion) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   else hipLaunchKernelGGL((beam_sync_kernel<FUSE_NONE, false>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   RNNT_CHECK_LAUNCH();
@@ -148,10 +156,24 @@ static int bs_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusio
 
 extern "C" int rnnt_hip_beam_sync_search(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_timing* timing,
                                          void* stream) {
-  return bs_search(d, fusion, nullptr, false, timing, stream, "beam_sync_search");
+  return bs_search(d, fusion, nullptr, false, nullptr, timing, stream, "beam_sync_search");
 }
 
 extern "C" int rnnt_hip_beam_sync_search_ngram(const rnnt_beam_sync_desc* d, const rnnt_beam_ngram* lm, const rnnt_beam_timing* timing,
                                                void* stream) {
-  return bs_search(d, nullptr, lm, true, timing, stream, "beam_sync_search_ngram");
+  return bs_search(d, nullptr, lm, true, nullptr, timing, stream, "beam_sync_search_ngram");
+}
+
+// internal-LM subtraction: the workspace of the entry it extends plus the (B, NS, 2) pairs
+extern "C" size_t rnnt_hip_beam_sync_ilm_workspace_bytes(const rnnt_beam_sync_desc* d) {
+  if (bs_check_dims(d, "beam_sync_search_ilm") != RNNT_OK) return 0;
+  return carve_bs(nullptr, d, true).total;
+}
+
+extern "C" int rnnt_hip_beam_sync_search_ilm(const rnnt_beam_sync_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm,
+                                             const rnnt_beam_ilm* ilm, const rnnt_beam_timing* timing, void* stream) {
+  const char* who = "beam_sync_search_ilm";
+  const int rc = bs_check_ilm(ilm, fusion, lm, who);
+  if (rc != RNNT_OK) return rc;
+  return bs_search(d, fusion, lm, lm != nullptr, ilm, timing, stream, who);
 }

@@ -1,8 +1,10 @@
-// The kernel of the frame-synchronous transducer beam search, beam_sync_kernel<FUSE, STREAM>, and what its two launchers share:
+// The kernel of the frame-synchronous transducer beam search, beam_sync_kernel<FUSE, STREAM, ILM>, and what its two launchers share:
 // beam_sync.hip (the offline entry, STREAM = false; the definition and the kernel's plan stand at its top) and
 // beam_sync_stream.hip (the search fed in chunks, STREAM = true).  STREAM adds only what lies around the frame
 // loop: the load of the carried beam in place of the seed, the prefix-tree collection (bs_collect, at the chunk's end and at the
-// start of a frame that finds fewer than W S node slots free), the store, and the `commit` output.
+// start of a frame that finds fewer than W S node slots free), the store, and the `commit` output.  ILM (only with a fusion
+// policy) subtracts the internal language model: a (max, lse) pair per state slot, written by the step that fills
+// the slot, and one more term where the fusion arc is added.  Nothing of it lives in BsShared: the other instances keep their LDS.
 #pragma once
 #include "beam_shared.hpp"
 #include "search_shared.hpp"
@@ -83,7 +85,27 @@ struct BsK : PredNet {
   int* ncommit;         // (B)
   long commit_ld;
   const int* rows;      // the reset kernel's row list
+  // ILM: fc.bias (V), the weight mu, and the (NS, 2) float pairs (m, lse) per state slot: offline at ilm + b NS 2, STREAM in
+  // stream b's workspace part at off_ilm
+  const float* ilm_bias;
+  float ilm_w;
+  float* ilm;
+  size_t off_ilm;
 };
+
+// Internal-LM subtraction (include/rnnt_hip.h).  The log-probability of token v != blank under the pair (m, lse) of a slot:
+__device__ __forceinline__ float ilm_logp(const float* Cv, const float* bias, float m, float lse, int v) {
+  return ((Cv[v] + bias[v]) - m) - lse;
+}
+// total' of a non-blank candidate: the header's ONE fp64 expression, called where the keys are filled and where the selected
+// candidates are built.  Contraction is off: a fused multiply-add at one of the two places and not at the other would break
+// "the same bits".  ilm == 0 (V = 2) gives (tot + arc) - 0: the fused instance's bits.
+template <bool ILM>
+__device__ __forceinline__ double fused_total(double tot, float arc, float mu, float ilm) {
+#pragma clang fp contract(off)
+  if constexpr (ILM) return (tot + (double)arc) - (double)mu * (double)ilm;
+  else return tot + (double)arc;
+}
 
 // int32 words of a stream's 256-byte workspace header (include/rnnt_hip.h: rnnt_beam_sync_stream_desc)
 enum { BSS_NA = 0, BSS_NNODES, BSS_COMMITTED, BSS_FRAMES, BSS_STATUS, BSS_NCOLLECT, BSS_NCOLLECT_IN, BSS_PEAK, BSS_WORDS };
@@ -159,8 +181,12 @@ inline size_t bs_step_floats(int L, int Hp, int O, int cell) {
 }
 
 // The members of `ls` (n of them) whose step is pending advance together: each gets a free slot, reads its parent's state and
-// writes (h', c', Cv') there.  Ends with a barrier.
-__device__ __forceinline__ void bs_step_pending(const BsK& p, BsShared& sh, BsList& ls, int n, float* slots, const BsStepLds& sl) {
+// writes (h', c', Cv') there.  Ends with a barrier.  ILM: then a wavefront per new slot reduces Cv + bias over v != blank to the
+// slot's pair (m, lse) in ilmp: lanes along v, wave_max / wave_sum as the row log-softmax below, so the order of the sums
+// depends neither on the group size nor on the hypothesis's place in a group.
+template <bool ILM>
+__device__ __forceinline__ void bs_step_pending(const BsK& p, BsShared& sh, BsList& ls, int n, float* slots, const BsStepLds& sl,
+                                                float* ilmp) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int Hp = p.Hp, L = p.L, LH = sl.LH, NG = sl.NG, SF = p.SF, V = p.V;
   const bool lstm = p.cell == RNNT_CELL_LSTM;
@@ -242,6 +268,23 @@ __device__ __forceinline__ void bs_step_pending(const BsK& p, BsShared& sh, BsLi
   if (tid == 0) sh.fpos += np;
   __threadfence_block();   // the slots are read through global memory by this workgroup's other waves
   __syncthreads();
+  if constexpr (ILM) {   // behind the fence: every Cv of this call is visible; gnew is not rewritten before the next call
+    for (int j = wave; j < np; j += BS_NW) {
+      const int s = clampi(sh.gnew[j], 0, p.NS - 1);   // (clamp: always in range)
+      const float* Cv = slots + (long)s * SF + (SF - V);
+      float m = -__builtin_huge_valf();
+      for (int v = lane; v < V; v += 64)
+        if (v != p.blank) m = fmaxf(m, Cv[v] + p.ilm_bias[v]);
+      m = wave_max(m);
+      float sum = 0.f;
+      for (int v = lane; v < V; v += 64)
+        if (v != p.blank) sum += expf((Cv[v] + p.ilm_bias[v]) - m);
+      sum = wave_sum(sum);
+      if (lane == 0) { ilmp[2 * s] = m; ilmp[2 * s + 1] = logf(sum); }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
 }
 
 // The free list: every slot the n members of c do not hold, in slot order; sh.fpos = 0.  Ends with a barrier.
@@ -379,9 +422,11 @@ __device__ __forceinline__ void bs_collect(BsShared& sh, const PrefixTree& nd, i
 
 // FUSE: the fusion policy (search_shared.hpp).  FUSE_DENSE reads farc / fnext at (state, token); FUSE_NGRAM asks ngram_lookup
 // for the same two values at the same two places, the candidate-key fill and the build of the selected children.
-template <int FUSE, bool STREAM>
+// ILM: internal-LM subtraction on top of a fusion policy (the term of fused_total at the same two places).
+template <int FUSE, bool STREAM, bool ILM = false>
 __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
   constexpr bool FUSED = FUSE != FUSE_NONE;
+  static_assert(!ILM || FUSED, "internal-LM subtraction rides on a fusion policy");
   __shared__ BsShared sh;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -402,6 +447,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
   u64* ck = STREAM ? reinterpret_cast<u64*>(wsb + p.off_keys) : p.keys + (long)b * W * V;
   float* slots = STREAM ? reinterpret_cast<float*>(wsb + p.off_slots) : p.slots + (long)b * NS * SF;
   const PrefixTree nd = tree_view(STREAM ? reinterpret_cast<int*>(wsb + p.off_nodes) : p.nodes + (long)b * 5 * maxn, maxn);
+  float* ilmp = !ILM ? nullptr : STREAM ? reinterpret_cast<float*>(wsb + p.off_ilm) : p.ilm + (long)b * NS * 2;
   BsStepLds sl;
   sl.NG = cell_gates(p.cell);
   sl.LH = p.L * p.Hp;
@@ -475,7 +521,7 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
       BsList& nx = sh.c[cur ^ 1];
       const bool last_round = r == S - 1;
       // round 0: the survivors among the last frame's last-round children (frame 0: the root); later: this frame's children
-      bs_step_pending(p, sh, c, n, slots, sl);
+      bs_step_pending<ILM>(p, sh, c, n, slots, sl, ilmp);
       if (r == 0) bs_free_list(sh, c, n, NS);   // the free list of this frame: every slot the beam does not hold
       if (tid == 0) { select_reset(sh.sel); sh.nnext = 0; }
       // ---- log-softmax of every member row and its candidate keys: a wavefront per row, lanes along v
@@ -491,6 +537,8 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
         if (lane == 0) { c.mx[i] = m; c.ls[i] = lse; }
         const double sc = c.score[i], tt = FUSED ? c.tot[i] : 0.0;
         const int st = FUSED ? c.st[i] : 0;
+        float im = 0.f, il = 0.f;   // ILM: the pair of the member's slot
+        if constexpr (ILM) { im = ilmp[2 * clampi(c.slot[i], 0, NS - 1)]; il = ilmp[2 * clampi(c.slot[i], 0, NS - 1) + 1]; }
         for (int v = lane; v < V; v += 64) {
           const float lp = ((At[v] + Cv[v]) - m) - lse;
           u64 key = 0ull;
@@ -499,8 +547,11 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
             double k = val;
             if constexpr (FUSE == FUSE_NGRAM) {   // only a candidate that passed the prune walks the tables
               int unused;
-              k = val + (v == blank ? tt : tt + (double)ngram_lookup(p.ng, st, v, unused));
-            } else if (FUSED) k = val + (v == blank ? tt : tt + (double)p.farc[(long)st * V + v]);
+              k = val + (v == blank ? tt : fused_total<ILM>(tt, ngram_lookup(p.ng, st, v, unused), p.ilm_w,
+                                                            ILM ? ilm_logp(Cv, p.ilm_bias, im, il, v) : 0.f));
+            } else if (FUSED)
+              k = val + (v == blank ? tt : fused_total<ILM>(tt, p.farc[(long)st * V + v], p.ilm_w,
+                                                            ILM ? ilm_logp(Cv, p.ilm_bias, im, il, v) : 0.f));
             if (val > NEG_INF && k > NEG_INF) key = sortable_key(k);   // (NaN compares false: dropped)
           }
           ck[(long)i * V + v] = key;
@@ -531,14 +582,19 @@ __global__ void __launch_bounds__(DEC_THREADS) beam_sync_kernel(const BsK p) {
           sh.rpar[rank] = -1;
           sh.tod[rank] = 1;
         } else {
+          float ilm = 0.f;   // ILM: the fill's value, from the same pair: the same bits
+          if constexpr (ILM) {
+            const float* ip = ilmp + 2 * clampi(c.slot[i], 0, NS - 1);
+            ilm = ilm_logp(Cv, p.ilm_bias, ip[0], ip[1], v);
+          }
           if constexpr (FUSE == FUSE_NGRAM) {
             int ns;
             const float arc = ngram_lookup(p.ng, c.st[i], v, ns);   // the fill's value: the same walk, the same bits
-            sh.rtot[rank] = c.tot[i] + (double)arc;
+            sh.rtot[rank] = fused_total<ILM>(c.tot[i], arc, p.ilm_w, ilm);
             sh.rst[rank] = ns;
           } else if (FUSED) {
             const long o = (long)c.st[i] * V + v;
-            sh.rtot[rank] = c.tot[i] + (double)p.farc[o];
+            sh.rtot[rank] = fused_total<ILM>(c.tot[i], p.farc[o], p.ilm_w, ilm);
             sh.rst[rank] = clampi(p.fnext[o], 0, p.n_states - 1);
           } else {
             sh.rtot[rank] = 0.0;
@@ -705,6 +761,17 @@ int bs_check_step(const D* d, const char* who) {
   if ((rc = prednet_check_dims<true>(d, who, RNNT_ERR_INVALID)) != RNNT_OK) return rc;
   RNNT_CHECK_ARG(bs_group(d) >= 1, "%s: one hypothesis's step needs %zu B of LDS beside %zu B of search state (> 160 KiB)", who,
                  bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float), sizeof(BsShared));
+  return RNNT_OK;
+}
+
+// an *_ilm entry's arguments, before any device work: the struct, and exactly one of the two automaton forms
+inline int bs_check_ilm(const rnnt_beam_ilm* ilm, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm, const char* who) {
+  RNNT_CHECK_ARG(ilm != nullptr, "%s: null ilm struct", who);
+  RNNT_CHECK_ARG(ilm->bias != nullptr, "%s: null ilm bias (fc.bias, V floats on the device)", who);
+  RNNT_CHECK_ARG(ilm->weight > 0.f && ilm->weight < __builtin_huge_valf(), "%s: ilm weight must be finite and > 0, got %g", who,
+                 (double)ilm->weight);
+  RNNT_CHECK_ARG((fusion != nullptr) != (lm != nullptr), "%s: takes exactly one of fusion and lm, got %s", who,
+                 fusion ? "both" : "neither");
   return RNNT_OK;
 }
 

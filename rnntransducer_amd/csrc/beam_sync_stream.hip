@@ -29,11 +29,12 @@ __global__ void __launch_bounds__(64) beam_sync_stream_reset_kernel(const BsK p)
 }
 
 struct BssLayout {
-  size_t table_bytes, stride, off_beam, off_slots, off_keys, off_nodes, off_mark, off_remap;
+  size_t table_bytes, stride, off_beam, off_slots, off_keys, off_nodes, off_mark, off_remap, off_ilm;
   int SF, NS;
 };
 
-BssLayout bss_layout(const rnnt_beam_sync_stream_desc* d) {
+// ilm: the layout of the *_ilm entries, one more carried part per stream behind the others: the (NS, 2) pairs of the state slots
+BssLayout bss_layout(const rnnt_beam_sync_stream_desc* d, bool ilm = false) {
   BssLayout l;
   const size_t W = d->beam, S = d->max_symbols, V = d->V, N = d->max_nodes;
   l.SF = slot_floats(d->L, d->Hp, d->cell, d->V);
@@ -46,6 +47,7 @@ BssLayout bss_layout(const rnnt_beam_sync_stream_desc* d) {
   l.off_nodes = off; off += align_up(5 * N * sizeof(int), 256);
   l.off_mark = off;  off += align_up(N * sizeof(int), 256);              // the collection's two scratch arrays
   l.off_remap = off; off += align_up(N * sizeof(int), 256);
+  l.off_ilm = off;   if (ilm) off += align_up((size_t)l.NS * 2 * sizeof(float), 256);
   l.stride = off;
   return l;
 }
@@ -63,15 +65,15 @@ int bss_check_dims(const rnnt_beam_sync_stream_desc* d, const char* who) {
 }
 
 // everything but A, lens and the outputs: the reset entry needs no more
-int bss_fill(const rnnt_beam_sync_stream_desc* d, BsK& k, const char* who) {
+int bss_fill(const rnnt_beam_sync_stream_desc* d, BsK& k, const char* who, bool ilm = false) {
   int rc = bss_check_dims(d, who);
   if (rc != RNNT_OK) return rc;
   if ((rc = fill_prednet<true>(d, k, who)) != RNNT_OK) return rc;
-  const BssLayout l = bss_layout(d);
+  const BssLayout l = bss_layout(d, ilm);
   RNNT_CHECK_ARG(d->workspace && (reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0 &&
                  d->workspace_bytes >= l.table_bytes + l.stride * (size_t)d->B,
-                 "%s: workspace must be 256-byte aligned and hold rnnt_hip_beam_sync_stream_workspace_bytes() = %zu bytes", who,
-                 l.table_bytes + l.stride * (size_t)d->B);
+                 "%s: workspace must be 256-byte aligned and hold rnnt_hip_beam_sync_stream%s_workspace_bytes() = %zu bytes", who,
+                 ilm ? "_ilm" : "", l.table_bytes + l.stride * (size_t)d->B);
   k.T = d->T; k.B = d->B; k.W = d->beam; k.S = d->max_symbols; k.G = bs_group(d);
   k.min_logp = d->token_min_logp;
   k.A = nullptr; k.a_st = 0; k.a_sb = 0; k.t_lens = nullptr;
@@ -84,6 +86,7 @@ int bss_fill(const rnnt_beam_sync_stream_desc* d, BsK& k, const char* who) {
   k.ws_stride = l.stride;
   k.off_beam = l.off_beam; k.off_slots = l.off_slots; k.off_keys = l.off_keys; k.off_nodes = l.off_nodes;
   k.off_mark = l.off_mark; k.off_remap = l.off_remap;
+  k.off_ilm = l.off_ilm; k.ilm = nullptr; k.ilm_bias = nullptr; k.ilm_w = 0.f;
   k.status = nullptr; k.commit = nullptr; k.commit_frames = nullptr; k.ncommit = nullptr; k.commit_ld = 0; k.rows = nullptr;
   return RNNT_OK;
 }
@@ -99,11 +102,12 @@ extern "C" size_t rnnt_hip_beam_sync_stream_workspace_bytes(const rnnt_beam_sync
   return l.table_bytes + l.stride * (size_t)d->B;
 }
 
-extern "C" int rnnt_hip_beam_sync_stream_reset(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows,
-                                               int32_t build_table, void* stream) {
-  const char* who = "beam_sync_stream_reset";
+// the reset behind both entries: the two differ in the workspace's layout alone (the pairs need no seed: a slot's pair is
+// written by the step that fills the slot, before anything reads it)
+static int bss_reset(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows, int32_t build_table, bool ilm,
+                     void* stream, const char* who) {
   BsK k;
-  const int rc = bss_fill(d, k, who);
+  const int rc = bss_fill(d, k, who, ilm);
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(n_rows >= 0 && (rows || n_rows == 0), "%s: bad row list", who);
   hipStream_t s = (hipStream_t)stream;
@@ -123,11 +127,16 @@ extern "C" int rnnt_hip_beam_sync_stream_reset(const rnnt_beam_sync_stream_desc*
   return RNNT_OK;
 }
 
-// the chunk call behind both entries: fusion (dense tables), lm (backoff tables), or neither
+extern "C" int rnnt_hip_beam_sync_stream_reset(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows,
+                                               int32_t build_table, void* stream) {
+  return bss_reset(d, rows, n_rows, build_table, false, stream, "beam_sync_stream_reset");
+}
+
+// the chunk call behind every entry: fusion (dense tables), lm (backoff tables), or neither; ilm on top of either of the two
 static int bss_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion, const rnnt_beam_ngram* lm, bool ngram,
-                     const rnnt_beam_timing* timing, void* stream, const char* who) {
+                     const rnnt_beam_ilm* ilm, const rnnt_beam_timing* timing, void* stream, const char* who) {
   BsK k;
-  int rc = bss_fill(d, k, who);
+  int rc = bss_fill(d, k, who, ilm != nullptr);
   if (rc != RNNT_OK) return rc;
   RNNT_CHECK_ARG(d->T >= 1 && d->A && d->lens, "%s: needs T >= 1 frames, A and lens", who);
   RNNT_CHECK_ARG(d->a_st >= 1 && d->a_sb >= 1, "%s: A strides (a_st = %lld, a_sb = %lld) must be positive", who, (long long)d->a_st,
@@ -146,14 +155,19 @@ static int bss_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion
   k.fnext = fusion ? fusion->next : nullptr; k.farc = fusion ? fusion->arc : nullptr; k.ffinal = fusion ? fusion->final : nullptr;
   k.n_states = fusion ? fusion->n_states : 1; k.fused = fusion ? fusion->fused_scores : nullptr;
   if (ngram) { k.ffinal = lm->final; k.n_states = lm->n_states; k.fused = lm->fused_scores; }
+  if (ilm) { k.ilm_bias = ilm->bias; k.ilm_w = ilm->weight; }
   const size_t lds = (size_t)k.G * bs_step_floats(d->L, d->Hp, d->O, d->cell) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  const void* fn = ngram    ? (const void*)beam_sync_kernel<FUSE_NGRAM, true>
+  const void* fn = ilm      ? (ngram ? (const void*)beam_sync_kernel<FUSE_NGRAM, true, true>
+                                     : (const void*)beam_sync_kernel<FUSE_DENSE, true, true>)
+                   : ngram  ? (const void*)beam_sync_kernel<FUSE_NGRAM, true>
                    : fusion ? (const void*)beam_sync_kernel<FUSE_DENSE, true>
                             : (const void*)beam_sync_kernel<FUSE_NONE, true>;
   if (lds + sizeof(BsShared) > 64 * 1024) RNNT_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)d->T * d->B * d->V * d->beam, s);
-  if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  if (ilm && ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, true, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (ilm) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, true, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
+  else if (ngram) hipLaunchKernelGGL((beam_sync_kernel<FUSE_NGRAM, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   else if (fusion) hipLaunchKernelGGL((beam_sync_kernel<FUSE_DENSE, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   else hipLaunchKernelGGL((beam_sync_kernel<FUSE_NONE, true>), dim3(d->B), dim3(DEC_THREADS), lds, s, k);
   RNNT_CHECK_LAUNCH();
@@ -162,10 +176,32 @@ static int bss_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion
 
 extern "C" int rnnt_hip_beam_sync_stream_chunk(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion,
                                                const rnnt_beam_timing* timing, void* stream) {
-  return bss_chunk(d, fusion, nullptr, false, timing, stream, "beam_sync_stream_chunk");
+  return bss_chunk(d, fusion, nullptr, false, nullptr, timing, stream, "beam_sync_stream_chunk");
 }
 
 extern "C" int rnnt_hip_beam_sync_stream_chunk_ngram(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_ngram* lm,
                                                      const rnnt_beam_timing* timing, void* stream) {
-  return bss_chunk(d, nullptr, lm, true, timing, stream, "beam_sync_stream_chunk_ngram");
+  return bss_chunk(d, nullptr, lm, true, nullptr, timing, stream, "beam_sync_stream_chunk_ngram");
+}
+
+// internal-LM subtraction: a stream opened for it carries the pairs of its state slots, so its workspace has
+// its own size and the reset that knows that layout
+extern "C" size_t rnnt_hip_beam_sync_stream_ilm_workspace_bytes(const rnnt_beam_sync_stream_desc* d) {
+  if (bss_check_dims(d, "beam_sync_stream_ilm") != RNNT_OK) return 0;
+  const BssLayout l = bss_layout(d, true);
+  return l.table_bytes + l.stride * (size_t)d->B;
+}
+
+extern "C" int rnnt_hip_beam_sync_stream_reset_ilm(const rnnt_beam_sync_stream_desc* d, const int32_t* rows, int32_t n_rows,
+                                                   int32_t build_table, void* stream) {
+  return bss_reset(d, rows, n_rows, build_table, true, stream, "beam_sync_stream_reset_ilm");
+}
+
+extern "C" int rnnt_hip_beam_sync_stream_chunk_ilm(const rnnt_beam_sync_stream_desc* d, const rnnt_beam_fusion* fusion,
+                                                   const rnnt_beam_ngram* lm, const rnnt_beam_ilm* ilm, const rnnt_beam_timing* timing,
+                                                   void* stream) {
+  const char* who = "beam_sync_stream_chunk_ilm";
+  const int rc = bs_check_ilm(ilm, fusion, lm, who);
+  if (rc != RNNT_OK) return rc;
+  return bss_chunk(d, fusion, lm, lm != nullptr, ilm, timing, stream, who);
 }

@@ -204,12 +204,14 @@ class RNNTransducer(_Base):
 
     def recognize_ctc_beams(self, inputs, inputs_lengths, beam_widths: int = 16, **kw):
         """JointNet.recognize_ctc_beams with this model's blank: the encoder-only CTC prefix beam search through the CTC head
-        (token_min_logp=, fusion=, return_scores=, return_frames=)."""
+        (token_min_logp=, fusion=, return_scores=, return_frames=; ilm_weight= is refused: no prediction net runs here)."""
         return self.jointnet.recognize_ctc_beams(inputs, inputs_lengths, self.blank_token_id, beam_widths, **kw)
 
     def recognize_beams_sync(self, inputs, inputs_lengths, **kw):
         """JointNet.recognize_beams_sync with this model's blank: the frame-synchronous transducer beam search with batched
-        hypothesis steps (beam_widths=, max_symbols=, token_min_logp=, fusion=, return_scores=, return_frames=)."""
+        hypothesis steps (beam_widths=, max_symbols=, token_min_logp=, fusion=, ilm_weight=, return_scores=, return_frames=).
+        ilm_weight > 0 subtracts the prediction net's internal language model per emitted token (ILME; JointNet.ilm_score
+        scores a token sequence under it)."""
         return self.jointnet.recognize_beams_sync(inputs, inputs_lengths, self.blank_token_id, **kw)
 
     def init_stream(self, batch_size: int, device=None):
@@ -224,7 +226,7 @@ class RNNTransducer(_Base):
     def init_beam_stream(self, batch_size: int, beam_widths: int = 100, improved: bool = False, state_beam: float = 4.6,
                          expand_beam: float = 2.3, device=None, fusion=None, **caps):
         """JointNet.init_beam_stream with this model's blank: per-stream state for recognize_beams_stream (fusion: a
-        TokenFusion, fixed for the life of the state)."""
+        TokenFusion, fixed for the life of the state; ilm_weight= is refused: the frame-synchronous searches take it)."""
         return self.jointnet.init_beam_stream(batch_size, self.blank_token_id, beam_widths, improved, state_beam, expand_beam,
                                               device, fusion=fusion, **caps)
 
@@ -236,7 +238,7 @@ class RNNTransducer(_Base):
 
     def init_beam_sync_stream(self, batch_size: int, beam_widths: int = 16, max_symbols: int = 1, **kw):
         """JointNet.init_beam_sync_stream with this model's blank: per-stream state for recognize_beams_sync_stream
-        (token_min_logp=, fusion=, device=, max_nodes=, max_len=; all fixed for the life of the state)."""
+        (token_min_logp=, fusion=, ilm_weight=, device=, max_nodes=, max_len=; all fixed for the life of the state)."""
         return self.jointnet.init_beam_sync_stream(batch_size, self.blank_token_id, beam_widths, max_symbols, **kw)
 
     def recognize_beams_sync_stream(self, chunk, chunk_lengths, state, *, return_scores: bool = False, return_frames: bool = False):

@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from ..ops import (MWER_MAX_LEN, CtcLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens, beam_search,
                    beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args, check_emit_windows,
-                   check_fastemit_lambda,
+                   check_fastemit_lambda, check_ilm_weight, refuse_ilm_weight,
                    check_fusion, ctc_beam_search, ctc_greedy, edit_distance, greedy_decode, nbest_pack, nbest_umax, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
@@ -261,7 +261,7 @@ class JointNet(nn.Module):
     @torch.no_grad()
     def recognize_ctc_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16, *,
                             token_min_logp: float = -math.inf, fusion=None, return_scores: bool = False,
-                            return_frames: bool = False):
+                            return_frames: bool = False, ilm_weight=None):
         """Encoder-only CTC prefix beam search through the CTC head (csrc/ctc_beam.hip): up to `beam_widths`
         (<= 128) token lists per utterance (no blanks, no leading blank), best first by the CTC log-probability mass the search
         kept for each labelling; no length normalisation.  The prediction net is not run, so this works before it is trained
@@ -273,7 +273,9 @@ class JointNet(nn.Module):
         total, the output by score + total + final; with return_scores the entries are (tokens, score, fused_score).  A CTC hypothesis has
         no leading blank: its totals are fusion.score([blank] + tokens).  Limitation: TokenFusion.from_hotwords refuses a phrase
         that repeats a token back to back (the transducer's y_star never holds one), although a CTC hypothesis can.
+        ilm_weight: refused with a ValueError: no prediction net runs here, so there is no internal LM to subtract.
         eval() mode only; ValueError for a missing head, training mode or bad arguments, before anything is launched."""
+        refuse_ilm_weight(ilm_weight, "recognize_ctc_beams", "the CTC search runs no prediction net: there is no internal LM")
         self._need_ctc_head("recognize_ctc_beams")
         if self.training:
             raise ValueError("recognize_ctc_beams expects eval() mode (dropout inactive), like recognize_ctc_greedy")
@@ -360,7 +362,7 @@ class JointNet(nn.Module):
     def recognize_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 100,
                         improved: bool = False, state_beam: float = 4.6, expand_beam: float = 2.3, lm=None, tokenizer=None,
                         hotwords=None, hotword_weight: float = 10.0, *, visit_padded_frames: bool = False,
-                        return_scores: bool = False, return_frames: bool = False, fusion=None, **caps):
+                        return_scores: bool = False, return_frames: bool = False, fusion=None, ilm_weight=None, **caps):
         """Beam search, same result as transducer.py:215-361 with lm=None and hotwords=None: a list of up to `beam_widths`
         y_star token lists (leading blank included), best first by asr_score / len(y_star), duplicates kept.  `tokenizer` is
         accepted and ignored: without an LM or hotwords the reference only uses it for lm_score, which never decides anything.
@@ -380,7 +382,10 @@ class JointNet(nn.Module):
         asr_score (what it is without fusion: the sum of the ASR log-probabilities) and then fused_score = asr_score + total +
         final, both fp64.  A positive bonus can make a frame's pop loop run away (so can the reference's hotwords): the
         max_pops cap ends it in RnntHipError naming max_pops, and the next call succeeds.  A backoff n-gram model (NgramFusion)
-        is refused here with a ValueError that names the searches that take one: those whose cost per frame is bounded."""
+        is refused here with a ValueError that names the searches that take one: those whose cost per frame is bounded.
+        ilm_weight (internal-LM subtraction) is refused the same way: it is a bonus for every emitted token, the kind of score
+        that makes this search's pop loop run away; the frame-synchronous searches take it."""
+        refuse_ilm_weight(ilm_weight, "recognize_beams", "a per-token bonus can make the best-first pop loop run away")
         if lm is not None or hotwords is not None:
             raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
                                       "lm=None and hotwords=None, and give token-level hotwords or an LM table as fusion= "
@@ -404,7 +409,7 @@ class JointNet(nn.Module):
     @torch.no_grad()
     def recognize_beams_sync(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16,
                              max_symbols: int = 1, *, token_min_logp: float = -math.inf, fusion=None,
-                             return_scores: bool = False, return_frames: bool = False):
+                             return_scores: bool = False, return_frames: bool = False, ilm_weight: float = 0.0):
         """Frame-synchronous beam search (csrc/beam_sync.hip), the search other transducer toolkits decode with:
         per frame the whole beam (beam_widths <= 64) expands at once, at most max_symbols (<= 4) tokens are emitted,
         hypotheses with the same token sequence are merged by logaddexp (a score is probability mass, not one path), and the
@@ -419,10 +424,17 @@ class JointNet(nn.Module):
         fusion (a TokenFusion, or an NgramFusion: a backoff n-gram model built from an ARPA file or from token-id n-grams, on
         the model's device): the search ranks by score + the automaton's total, the output by score + total + final; with
         return_scores the entries carry score and then fused_score.
+        ilm_weight = mu > 0: internal-LM subtraction (ILME).  The prediction net is itself a language model of
+        the training transcripts, so plain fusion counts a language prior twice; with mu every emitted token v also adds
+        -mu * ilm(v | y) to the total, ilm = the log-softmax over the non-blank tokens of the joint with the encoder's
+        contribution zeroed (`ilm_score` gives its sum over a sequence).  fused_score = score + the automaton's part -
+        mu * ilm_score(y).  With fusion=None the all-zero automaton is used: subtraction alone, and entries carry fused_score
+        like any fused call.  0 (the default): the search above, untouched.  Finite and >= 0, ValueError otherwise.
         Any encoder direction.  eval() mode only; ValueError for training mode or bad arguments, before anything is launched."""
         if self.training:
             raise ValueError("recognize_beams_sync expects eval() mode (dropout inactive), like recognize_beams")
         check_beam_sync_args(beam_widths, max_symbols, token_min_logp, "recognize_beams_sync")
+        check_ilm_weight(ilm_weight, "recognize_beams_sync")
         check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams_sync", ngram=True)
         if not 0 <= int(blank_token_id) < self.num_classes:
             raise ValueError(f"recognize_beams_sync: blank {blank_token_id} outside [0,{self.num_classes})")
@@ -431,12 +443,49 @@ class JointNet(nn.Module):
         dec = self.decoder
         res = beam_search_sync(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
                                dec.out_proj.weight, dec.out_proj.bias, int(blank_token_id), beam_widths, max_symbols, t_lens,
-                               token_min_logp=token_min_logp, frames=return_frames, fusion=fusion)
+                               token_min_logp=token_min_logp, frames=return_frames, fusion=fusion, ilm_weight=ilm_weight)
         if return_frames:   # an entry is (y, score[, fused_score], frames)
             outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
         else:
             outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
         return outs[0] if len(outs) == 1 else outs
+
+    @torch.no_grad()
+    def ilm_score(self, targets: torch.Tensor, target_lengths, blank: int) -> torch.Tensor:
+        """The internal LM's log-probability of given token sequences: targets (B, U) token ids without the
+        leading blank, target_lengths B values in [0, U] -> (B,) float64 on targets' device,
+            sum over u < target_lengths[b] of ilm(y_u | y_<u),
+        ilm(. | y_<u) = the log-softmax over the NON-BLANK tokens of gelu(dec_u) W_d^T + fc.bias: the joint with the encoder's
+        contribution zeroed, dec_u the prediction net's output after blank, y_0 .. y_{u-1} (started on blank from the zero state,
+        as the searches prime an utterance).  It is what recognize_beams_sync(ilm_weight=mu) subtracts mu times per hypothesis
+        (fused_score = score + the automaton's part - mu * ilm_score(y[1:])), and exp(-ilm_score / length) is the internal LM's
+        perplexity on a text.  fp32 network arithmetic, the sum in fp64.  eval() mode only; ValueError for a blank among the
+        counted tokens or bad shapes."""
+        if self.training:
+            raise ValueError("ilm_score expects eval() mode (dropout inactive), like recognize_beams_sync")
+        V = self.num_classes
+        if not 0 <= int(blank) < V:
+            raise ValueError(f"ilm_score: blank {blank} outside [0,{V})")
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.dtype not in (torch.int32, torch.int64):
+            raise ValueError("ilm_score: targets must be a (B, U) integer tensor")
+        B, U = targets.shape
+        dev = targets.device
+        u_lens = lengths_to_device(target_lengths, dev).to(torch.int64)
+        if tuple(u_lens.shape) != (B,) or bool(((u_lens < 0) | (u_lens > U)).any()):
+            raise ValueError(f"ilm_score: target_lengths must be {B} values in [0, {U}]")
+        tok = targets.to(torch.int64)
+        valid = torch.arange(U, device=dev)[None, :] < u_lens[:, None]
+        if bool((((tok == int(blank)) | (tok < 0) | (tok >= V)) & valid).any()):
+            raise ValueError("ilm_score: a counted token is the blank or outside the vocabulary")
+        if U == 0:
+            return torch.zeros(B, dtype=torch.float64, device=dev)
+        tok = torch.where(valid, tok, torch.full_like(tok, int(blank)))
+        text = torch.cat((torch.full((B, 1), int(blank), dtype=torch.int64, device=dev), tok), dim=1)   # blank first: U + 1 steps
+        dec = self.decoder.forward_time_major(text, torch.full((B,), U + 1, dtype=torch.int32, device=dev))   # (U+1, B, O_d)
+        z = torch.nn.functional.gelu(dec[:U].float(), approximate="tanh") @ self.fc.weight[:, self.enc_out:].t() + self.fc.bias
+        z[..., int(blank)] = -math.inf   # the blank is no word of the internal LM
+        lp = torch.log_softmax(z, dim=-1).gather(2, tok.t().unsqueeze(-1)).squeeze(-1)   # (U, B)
+        return torch.where(valid.t(), lp.double(), torch.zeros((), dtype=torch.float64, device=dev)).sum(0)   # (padding: -inf)
 
     def init_stream(self, batch_size: int, blank_token_id: int, device=None):
         """A GreedyStreamState for `batch_size` streams, each starting as recognize_greedy starts an utterance
@@ -489,7 +538,7 @@ class JointNet(nn.Module):
         return [tokens[b, :n[b]] for b in range(B)]
 
     def init_beam_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 100, improved: bool = False,
-                         state_beam: float = 4.6, expand_beam: float = 2.3, device=None, fusion=None, **caps):
+                         state_beam: float = 4.6, expand_beam: float = 2.3, device=None, fusion=None, ilm_weight=None, **caps):
         """A streaming.BeamStreamState for `batch_size` streams, each starting as recognize_beams starts an utterance
         (transducer.py:276-284): y_star = [blank], score 0, no prediction-net state.  The search options are fixed here: they
         size the workspace and belong to the utterance.  `caps`: max_pops / max_candidates / max_states / max_nodes / max_len as
@@ -498,8 +547,10 @@ class JointNet(nn.Module):
         given, must be the model's.  The weights must not change while the state is open.
         fusion (a TokenFusion on the model's device): the streams search as recognize_beams(fusion=...) does; the automaton is
         fixed here, its state and total are carried with every hypothesis, and recognize_beams_stream(return_scores=True)
-        returns asr_score and then fused_score per hypothesis."""
+        returns asr_score and then fused_score per hypothesis.  ilm_weight is refused (ValueError), as recognize_beams
+        refuses it."""
         from ..streaming import BeamStreamState
+        refuse_ilm_weight(ilm_weight, "init_beam_stream", "a per-token bonus can make the best-first pop loop run away")
         self.encoder.check_streamable("init_beam_stream")
         return BeamStreamState(self, batch_size, blank_token_id, beam_widths, improved, state_beam, expand_beam, device,
                                fusion=fusion, **caps)
@@ -542,20 +593,23 @@ class JointNet(nn.Module):
 
     def init_beam_sync_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 16, max_symbols: int = 1, *,
                               token_min_logp: float = -math.inf, fusion=None, device=None, max_nodes: int = 8192,
-                              max_len: int = 256):
+                              max_len: int = 256, ilm_weight: float = 0.0):
         """A streaming.BeamSyncStreamState for `batch_size` streams, each starting as recognize_beams_sync starts an utterance:
         the root [blank] with score 0 and one prediction-net step on blank pending.  The search options (beam_widths <= 64,
         max_symbols <= 4, token_min_logp, fusion: a TokenFusion or NgramFusion on the model's device) and the two caps are fixed here: max_nodes
         bounds the LIVE prefix tree (>= 1 + 4 * beam_widths * max_symbols), max_len the uncommitted tail of a returned sequence;
         `state.workspace_bytes` / `state.bytes_per_stream` tell what they cost.  `device`, if given, must be the model's.  The
         weights must not change while the state is open.  Unidirectional encoders only.  ValueError for bad arguments, before
-        anything is allocated or launched."""
+        anything is allocated or launched.
+        ilm_weight > 0: internal-LM subtraction as in recognize_beams_sync, fixed for the life of the state (`state.ilm_weight`);
+        the streams then search as recognize_beams_sync(ilm_weight=...) does, with the same bits whatever the chunking."""
         from ..streaming import BeamSyncStreamState
+        check_ilm_weight(ilm_weight, "init_beam_sync_stream")
         if self.training:
             raise ValueError("init_beam_sync_stream expects eval() mode (dropout inactive), like recognize_beams_sync")
         self.encoder.check_streamable("init_beam_sync_stream")
         return BeamSyncStreamState(self, batch_size, blank_token_id, beam_widths, max_symbols, token_min_logp=token_min_logp,
-                                   fusion=fusion, device=device, max_nodes=max_nodes, max_len=max_len)
+                                   fusion=fusion, device=device, max_nodes=max_nodes, max_len=max_len, ilm_weight=ilm_weight)
 
     @torch.no_grad()
     def recognize_beams_sync_stream(self, chunk: torch.Tensor, chunk_lengths, state, *, return_scores: bool = False,

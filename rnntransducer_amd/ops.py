@@ -1418,6 +1418,31 @@ def check_fusion(fusion, V: int, device, what: str, ngram: bool = False) -> None
         raise ValueError(f"{what}: the fusion tables are on {fusion.device}, the search runs on {device}; use fusion.to(device)")
 
 
+ILM_SEARCHES = "recognize_beams_sync and init_beam_sync_stream / recognize_beams_sync_stream"
+
+
+def check_ilm_weight(ilm_weight, what: str) -> float:
+    """ValueError unless ilm_weight is a finite number >= 0 (0: no internal-LM subtraction): before anything runs.  -> float"""
+    if isinstance(ilm_weight, bool) or not isinstance(ilm_weight, (int, float)) or not math.isfinite(ilm_weight) or ilm_weight < 0:
+        raise ValueError(f"{what}: ilm_weight must be a finite number >= 0 (0: off), got {ilm_weight!r}")
+    return float(ilm_weight)
+
+
+def refuse_ilm_weight(ilm_weight, what: str, why: str) -> None:
+    """The searches that cannot subtract the internal LM: ValueError naming the two that can, unless ilm_weight is None or 0."""
+    if ilm_weight is not None and not (isinstance(ilm_weight, (int, float)) and ilm_weight == 0):
+        raise ValueError(f"{what}: ilm_weight is not taken here ({why}); internal-LM subtraction is taken by {ILM_SEARCHES}")
+
+
+def ilm_fusion(fusion, V: int, device):
+    """The automaton an internal-LM call runs with: `fusion`, or without one the all-zero one-state TokenFusion (subtraction
+    alone)."""
+    if fusion is not None:
+        return fusion
+    from .fusion import TokenFusion
+    return TokenFusion(torch.zeros(1, V, dtype=torch.int32), torch.zeros(1, V), torch.zeros(1)).to(device)
+
+
 def fusion_struct(fusion, fused_scores: torch.Tensor):
     """rnnt_beam_fusion of a checked TokenFusion, or rnnt_beam_ngram of a checked NgramFusion (raw pointers: the caller keeps
     `fusion` and `fused_scores` alive)."""
@@ -1522,7 +1547,7 @@ def check_beam_sync_args(beam_width, max_symbols, token_min_logp, what: str) -> 
 def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                      cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam_width: int, max_symbols: int = 1,
                      t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf, frames: bool = False,
-                     fusion=None, step_group: int = 0):
+                     fusion=None, step_group: int = 0, ilm_weight: float = 0.0):
     """Frame-synchronous transducer beam search (include/rnnt_hip.h: rnnt_hip_beam_sync_search, csrc/beam_sync.hip, DESIGN.md
     §20) on enc_tm (T,B,Oe) encoder outputs (time-major): per frame the whole beam (beam_width <= 64) expands at once, at most
     max_symbols (<= 4) tokens are emitted, hypotheses with the same token sequence merge by logaddexp, and the prediction net
@@ -1534,11 +1559,15 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
     score + total + final; every entry is then (y, score, fused_score).  frames=True appends `frames`: per token the frame at which its prefix's
     node was created (-1 for the leading blank).  step_group: 0, or a smaller number of hypotheses per step group than the
     kernel would take (results do not depend on it).
+    ilm_weight = mu > 0 (rnnt_hip_beam_sync_search_ilm): internal-LM subtraction.  Every emitted token v also adds
+    -mu * ilm_h[v] to the total, ilm_h = the fp32 log-softmax over the non-blank tokens of Cv_h + fc_b (the joint with the
+    encoder zeroed); fused_score carries it.  Without fusion the all-zero automaton is used: subtraction alone, entries still
+    (y, score, fused_score).  0: the entries above, untouched.
     The cost per frame is bounded by beam_width, V and max_symbols: no cap can overflow.  One search launch, then one host copy
     of the counts and lengths (and one per returned array).  Argument errors raise ValueError before anything runs."""
     tokens, lens, counts, scores, host, fused, fr = _beam_search_sync_run(
         enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens, token_min_logp, frames,
-        fusion, step_group)
+        fusion, step_group, ilm_weight)
     B, W = lens.shape
     return _hyps_to_host(host[:B].tolist(), host[B:].reshape(B, W).tolist(), tokens, scores, fused, fr)
 
@@ -1546,21 +1575,23 @@ def beam_search_sync(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tenso
 @torch.no_grad()
 def beam_search_sync_device(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                             cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam_width: int, max_symbols: int = 1,
-                            t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf, fusion=None):
+                            t_lens: Optional[torch.Tensor] = None, *, token_min_logp: float = -math.inf, fusion=None,
+                            ilm_weight: float = 0.0):
     """beam_search_sync with its results left on the device (MWER training packs them into loss inputs there):
     -> (tokens (B, W, 1 + max_symbols*T) int32 with the leading blank, lens (B, W) int32, counts (B,) int32, scores (B, W) fp64,
     host): `host` is the search's one host copy, a CPU int32 tensor counts | lens.  Entries of rank >= counts[b] are unwritten.
     fusion (a TokenFusion or NgramFusion): the search ranks with it as beam_search_sync does, and the tuple gains a sixth entry,
-    fused (B, W) fp64."""
+    fused (B, W) fp64.  ilm_weight > 0: internal-LM subtraction as in beam_search_sync; the sixth entry is then always there."""
     out = _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
-                                token_min_logp, False, fusion, 0)
-    return out[:5] if fusion is None else out[:6]
+                                token_min_logp, False, fusion, 0, ilm_weight)
+    return out[:5] if out[5] is None else out[:6]
 
 
 def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, beam_width, max_symbols, t_lens,
-                          token_min_logp, frames, fusion, step_group):
+                          token_min_logp, frames, fusion, step_group, ilm_weight=0.0):
     """The launch behind beam_search_sync and beam_search_sync_device -> (tokens, lens, counts, scores, host, fused, frames)."""
     check_beam_sync_args(beam_width, max_symbols, token_min_logp, "beam_search_sync")
+    mu = check_ilm_weight(ilm_weight, "beam_search_sync")
     if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
         raise ValueError(f"beam_search_sync: step_group must be an integer >= 0, got {step_group!r}")
     if enc_tm.dim() != 3 or fc_w.dim() != 2:
@@ -1585,6 +1616,8 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
     dev, W, S, L = enc_tm.device, beam_width, max_symbols, _lib.lib()
+    if mu > 0.0:
+        fusion, fc_b = ilm_fusion(fusion, V, dev), _f32c(fc_b, "fc bias")
     A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
     gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
     max_len = 1 + S * T
@@ -1594,7 +1627,7 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     d.T, d.B, d.beam, d.max_symbols, d.step_group, d.token_min_logp = T, B, W, S, step_group, float(token_min_logp)
     d.A, d.a_st, d.a_sb = _addr(A), B * V, V
     d.t_lens = _addr(t_lens.contiguous()) if t_lens is not None else None
-    nws = L.rnnt_hip_beam_sync_workspace_bytes(C.byref(d))
+    nws = (L.rnnt_hip_beam_sync_ilm_workspace_bytes if mu > 0.0 else L.rnnt_hip_beam_sync_workspace_bytes)(C.byref(d))
     if nws == 0:
         raise ValueError("beam_search_sync: " + L.rnnt_hip_last_error().decode("utf-8", "replace"))
     ws = torch.empty(nws + 256, device=dev, dtype=torch.uint8)
@@ -1604,9 +1637,15 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     tm = _lib.BeamTiming(_addr(fr), None) if frames else None
     fused = torch.empty(B, W, device=dev, dtype=torch.float64) if fusion is not None else None
     fs = fusion_struct(fusion, fused) if fusion is not None else None
-    entry = "rnnt_hip_beam_sync_search_ngram" if isinstance(fs, _lib.BeamNgram) else "rnnt_hip_beam_sync_search"
-    check(getattr(L, entry)(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None, _stream()),
-          entry)
+    if mu > 0.0:
+        entry, ngram = "rnnt_hip_beam_sync_search_ilm", isinstance(fs, _lib.BeamNgram)
+        ilm = _lib.BeamIlm(_addr(fc_b), mu)
+        check(L.rnnt_hip_beam_sync_search_ilm(C.byref(d), None if ngram else C.byref(fs), C.byref(fs) if ngram else None, C.byref(ilm),
+                                              C.byref(tm) if tm is not None else None, _stream()), entry)
+    else:
+        entry = "rnnt_hip_beam_sync_search_ngram" if isinstance(fs, _lib.BeamNgram) else "rnnt_hip_beam_sync_search"
+        check(getattr(L, entry)(C.byref(d), C.byref(fs) if fs is not None else None, C.byref(tm) if tm is not None else None,
+                                _stream()), entry)
     host = small.cpu()   # the only host sync of the search
     return tokens, small[B:].view(B, W), small[:B], scores, host, fused, fr
 
@@ -1988,30 +2027,33 @@ def beam_sync_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, ou
     return d, keep
 
 
-def beam_sync_stream_workspace_bytes(d) -> int:
-    """Bytes of the carried workspace (ValueError with the library's message for sizes outside its limits)."""
+def beam_sync_stream_workspace_bytes(d, ilm: bool = False) -> int:
+    """Bytes of the carried workspace (ValueError with the library's message for sizes outside its limits).  ilm: of a stream
+    opened with internal-LM subtraction, which also carries the (m, lse) pair of every state slot."""
     L = _lib.lib()
-    n = L.rnnt_hip_beam_sync_stream_workspace_bytes(C.byref(d))
+    n = (L.rnnt_hip_beam_sync_stream_ilm_workspace_bytes if ilm else L.rnnt_hip_beam_sync_stream_workspace_bytes)(C.byref(d))
     if n == 0:
         raise ValueError("streaming frame-synchronous beam search: " + L.rnnt_hip_last_error().decode("utf-8", "replace"))
     return n
 
 
-def beam_sync_stream_reset(d, rows: torch.Tensor, build_table: bool) -> None:
-    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to."""
+def beam_sync_stream_reset(d, rows: torch.Tensor, build_table: bool, ilm: bool = False) -> None:
+    """rows (int32 on device, each in [0, B): the caller checks) start a new utterance in the workspace d points to (ilm: a
+    workspace of the internal-LM layout)."""
     _need_gpu(rows)
     _check_buffer("rows", rows, (rows.numel(),), torch.int32, rows.device)
-    check(_lib.lib().rnnt_hip_beam_sync_stream_reset(C.byref(d), _addr(rows), rows.numel(), int(build_table), _stream()),
-          "rnnt_hip_beam_sync_stream_reset")
+    entry = "rnnt_hip_beam_sync_stream_reset_ilm" if ilm else "rnnt_hip_beam_sync_stream_reset"
+    check(getattr(_lib.lib(), entry)(C.byref(d), _addr(rows), rows.numel(), int(build_table), _stream()), entry)
 
 
 def beam_sync_stream_chunk(d, A: torch.Tensor, lens_dev: torch.Tensor, commit: torch.Tensor, frames: Optional[torch.Tensor] = None,
-                           commit_frames: Optional[torch.Tensor] = None, fusion=None) -> None:
+                           commit_frames: Optional[torch.Tensor] = None, fusion=None, ilm=None) -> None:
     """One chunk: A (T,B,V) float32 (from stream_rnn_chunk; any positive frame and stream strides with contiguous rows), lens_dev
     (B) int32 on device, commit (B, max_nodes + max_symbols * T) int32; the outputs d points to are written.  frames
     (B, beam, max_len) and commit_frames (shaped as commit), int32 on device: the tails' and the committed tokens' absolute
     frames are written too.  fusion: the rnnt_beam_fusion or rnnt_beam_ngram struct of the stream's automaton (fusion_struct), the
-    same for every chunk."""
+    same for every chunk.  ilm: the rnnt_beam_ilm struct of a stream opened with internal-LM subtraction (fusion is then required;
+    d.workspace has the internal-LM layout)."""
     _need_gpu(A, lens_dev, commit)
     dev = A.device
     if A.dim() != 3 or tuple(A.shape[1:]) != (d.B, d.V) or A.dtype != torch.float32 or A.shape[0] < 1 or A.stride(2) != 1 \
@@ -2029,8 +2071,15 @@ def beam_sync_stream_chunk(d, A: torch.Tensor, lens_dev: torch.Tensor, commit: t
         tm = _lib.BeamTiming(_addr(frames), _addr(commit_frames))
     d.T, d.A, d.a_st, d.a_sb, d.lens, d.commit = T, _addr(A), A.stride(0), A.stride(1), _addr(lens_dev), _addr(commit)
     try:
-        entry = "rnnt_hip_beam_sync_stream_chunk_ngram" if isinstance(fusion, _lib.BeamNgram) else "rnnt_hip_beam_sync_stream_chunk"
-        check(getattr(_lib.lib(), entry)(C.byref(d), C.byref(fusion) if fusion is not None else None,
-                                         C.byref(tm) if tm is not None else None, _stream()), entry)
+        ngram = isinstance(fusion, _lib.BeamNgram)
+        if ilm is not None:
+            entry = "rnnt_hip_beam_sync_stream_chunk_ilm"
+            check(_lib.lib().rnnt_hip_beam_sync_stream_chunk_ilm(
+                C.byref(d), C.byref(fusion) if fusion is not None and not ngram else None, C.byref(fusion) if ngram else None,
+                C.byref(ilm), C.byref(tm) if tm is not None else None, _stream()), entry)
+        else:
+            entry = "rnnt_hip_beam_sync_stream_chunk_ngram" if ngram else "rnnt_hip_beam_sync_stream_chunk"
+            check(getattr(_lib.lib(), entry)(C.byref(d), C.byref(fusion) if fusion is not None else None,
+                                             C.byref(tm) if tm is not None else None, _stream()), entry)
     finally:
         d.T, d.A, d.lens, d.commit = 0, None, None, None

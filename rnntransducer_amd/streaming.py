@@ -381,6 +381,14 @@ class BeamStreamState:
                                "reset (state.reset(rows)) before they are fed again")
 
 
+def _lib_ilm(bias: torch.Tensor, weight: float):
+    """rnnt_beam_ilm over the joint's bias (a raw pointer: the model keeps the tensor alive)."""
+    from . import _lib
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError("internal-LM subtraction: fc.bias must be a contiguous float32 tensor")
+    return _lib.BeamIlm(bias.data_ptr(), weight)
+
+
 class BeamSyncStreamState:
     """Per-stream state of `JointNet.recognize_beams_sync_stream`.  On the device:
       enc_h / enc_c   (L_enc, B, H)   encoder state (enc_c None unless the encoder is an LSTM)
@@ -398,12 +406,16 @@ class BeamSyncStreamState:
     a returned sequence.  These two are the ONLY run-time error paths (RnntHipError naming the cap; the stream must be reset):
     the cost of a frame is fixed by beam_widths, V and max_symbols, there is no pop loop, and a hotword weight cannot reach
     either cap through the scores.  Bytes per stream (`bytes_per_stream`; all of them, `workspace_bytes`): 256 + 32 W +
-    4 (S + 2) W slot + 8 W V + 28 max_nodes, each part rounded up to 256, with slot = L * Hp * (2 if LSTM else 1) + V floats."""
+    4 (S + 2) W slot + 8 W V + 28 max_nodes, each part rounded up to 256, with slot = L * Hp * (2 if LSTM else 1) + V floats.
+    ilm_weight > 0 (internal-LM subtraction; fixed here like the fusion automaton, kept as `state.ilm_weight`): the
+    stream also carries the (m, lse) pair of every state slot, 8 (S + 2) W bytes more; without a fusion automaton the all-zero
+    one is used, and entries carry fused_score like any fused stream's."""
 
     def __init__(self, jointnet, batch_size: int, blank_token_id: int, beam_widths: int = 16, max_symbols: int = 1, *,
                  token_min_logp: float = float("-inf"), fusion=None, device=None, max_nodes: int = 8192, max_len: int = 256,
-                 step_group: int = 0):
+                 step_group: int = 0, ilm_weight: float = 0.0):
         what = "init_beam_sync_stream"
+        self.ilm_weight = ops.check_ilm_weight(ilm_weight, what)
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"{what}: batch_size must be an integer >= 1, got {batch_size!r}")
         ops.check_beam_sync_args(beam_widths, max_symbols, token_min_logp, what)
@@ -418,6 +430,8 @@ class BeamSyncStreamState:
         if not 0 <= int(blank_token_id) < jointnet.num_classes:
             raise ValueError(f"{what}: blank_token_id {blank_token_id} outside [0, {jointnet.num_classes})")
         ops.check_fusion(fusion, jointnet.num_classes, device, what, ngram=True)
+        if self.ilm_weight > 0.0:
+            fusion = ops.ilm_fusion(fusion, jointnet.num_classes, device)
         self.fusion = fusion
         self._net = jointnet
         self.batch_size, self.blank = int(batch_size), int(blank_token_id)
@@ -430,7 +444,7 @@ class BeamSyncStreamState:
         self.enc_h = z(enc.num_layers, enc.hidden_size)
         self.enc_c = z(enc.num_layers, enc.hidden_size) if enc.CELL == CELL_LSTM else None
         self.frames_seen = torch.zeros(B, device=device, dtype=torch.int64)
-        self.workspace_bytes = ops.beam_sync_stream_workspace_bytes(d)
+        self.workspace_bytes = ops.beam_sync_stream_workspace_bytes(d, ilm=self.ilm_weight > 0.0)
         self.workspace = torch.zeros(self.workspace_bytes + 256, device=device, dtype=torch.uint8)
         self._ws_off = -self.workspace.data_ptr() % 256
         ngate = {0: 4, 1: 3}.get(jointnet.decoder.rnn.CELL, 1)
@@ -537,7 +551,7 @@ class BeamSyncStreamState:
                 t.index_fill_(1, idx, 0.0)
         self.frames_seen.index_fill_(0, idx, 0)
         d, keep = self._descriptor()
-        ops.beam_sync_stream_reset(d, idx.to(torch.int32), build_table)
+        ops.beam_sync_stream_reset(d, idx.to(torch.int32), build_table, ilm=self.ilm_weight > 0.0)
         for r in rows:
             self.committed[r], self.committed_frames[r] = [self.blank], [-1]
             self.nbest[r], self.nbest_frames[r], self.failed[r] = [self._start_entry()], [[-1]], False
@@ -559,7 +573,10 @@ class BeamSyncStreamState:
             self._commit_frames = torch.empty_like(self._commit)
         d, keep = self._descriptor()
         fs = ops.fusion_struct(self.fusion, self._fused) if self.fusion is not None else None
-        ops.beam_sync_stream_chunk(d, A, lens_dev, self._commit, self._frames, self._commit_frames, fusion=fs)
+        ilm = None
+        if self.ilm_weight > 0.0:   # fc.bias is read at every chunk, like the other weights
+            ilm = _lib_ilm(self._net.fc.bias, self.ilm_weight)
+        ops.beam_sync_stream_chunk(d, A, lens_dev, self._commit, self._frames, self._commit_frames, fusion=fs, ilm=ilm)
         self.frames_seen += lens_dev   # (a stream that fails here is reset before it is fed again)
         host = self._small.cpu()   # the host sync of the chunk; the result slices below are copied from an idle stream
         count, status, ncommit = host[0].tolist(), host[1].tolist(), host[2].tolist()
