@@ -1194,6 +1194,44 @@ int rnnt_hip_beam_sync_stream_chunk_ilm(const rnnt_beam_sync_stream_desc* d, con
                                         const rnnt_beam_timing* timing /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Internal-LM training (ILMT; Meng et al. 2021, "Internal Language Model Training for Domain-Adaptive End-to-End Speech
+ * Recognition"; the same term on text alone: Meng et al. 2021, "Internal Language Model Adaptation with Text-Only Data for End-to-End
+ * Speech Recognition").  csrc/ilm_loss.hip, DESIGN.md §26.
+ * The cross-entropy of the internal LM of the ILME section above on the transcripts, as a training term.  C is the decoder half of
+ * the joint, the (U1, B, V) operand of the fused loss: C(u,b,v) = C[b*c_sb + u*c_su + v] (batch-major and time-major buffers both
+ * work, the inner stride is 1; c_su >= V), bias = fc.bias (V).  labels (B,U) int32 (U = U1-1), u_lens (B) int32 in [0,U] (clamped to
+ * that range on the device), blank in [0,V).  For v != blank:
+ *     z(u,b,v)   = C(u,b,v) + bias[v]
+ *     lse(u,b)   = m + log sum_{v != blank} exp(z(u,b,v) - m),   m = max_{v != blank} z(u,b,v)
+ *     ilm_nll[b] = sum_{u < u_lens[b]} (lse(u,b) - z(u,b,labels[b,u]))         evaluated as (m - z(u,b,y)) + log sum exp(z - m)
+ *     dC(u,b,v)  = gscale * gvec[b*gvec_stride] * (exp(z(u,b,v) - lse(u,b)) - [v == labels[b,u]])     u < u_lens[b], v != blank
+ *                = 0                                                 elsewhere (the blank column, u >= u_lens[b], row U1-1)
+ * ilm_nll[b] is minus JointNet.ilm_score of row b: a per-utterance sum over tokens, not length-normalised.  Per-token terms are fp32
+ * with the row maximum subtracted; the per-utterance sum is fp64 in a fixed order that depends on u_lens[b] alone, rounded once to
+ * fp32.  No float atomics: the same bits on every call, and a row gives the same bits alone as in any batch.
+ * V = 2 leaves one non-blank token: ilm_nll is exactly 0 and the gradient exactly zero.
+ * A counted label that is the blank or lies outside [0,V) is not checked on the host (that would cost a synchronisation): the row
+ * gets ilm_nll[b] = +inf and an exactly zero row of dC, every other row is bitwise what it is alone, and nothing is read out of
+ * bounds.  Labels at u >= u_lens[b] and rows u >= u_lens[b] of C are never read.
+ * rnnt_hip_ilm_loss_fwd: one launch.  lse, if given, receives lse(u,b) at lse[u*B + b] for u < u_lens[b] (other entries are not
+ *   written) for the backward.
+ * rnnt_hip_ilm_loss_bwd: one launch, on the SAME operands; lse = that buffer, or NULL: the rows' lse is recomputed (the same bits).
+ *   dC has C's strides.  accumulate = 0 writes the whole dC (V entries of every row; cells that are not counted become exact zeros);
+ *   accumulate != 0 adds into a dC that holds values already (the lattice gradient of rnnt_hip_joint_loss_bwd) as one rounded product
+ *   and one addition per cell, and leaves uncounted rows and the blank column untouched.  gscale, gvec, gvec_stride as in
+ *   rnnt_hip_joint_loss_bwd (gvec NULL = ones).
+ * Arguments are validated before any device work (RNNT_ERR_INVALID): a null pointer (lse and gvec may be NULL), B < 1, U1 < 1,
+ * V < 2, blank outside [0,V), c_su < V.  Nothing allocates or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+int rnnt_hip_ilm_loss_fwd(const float* C, int64_t c_sb, int64_t c_su, const float* bias, const int32_t* labels,
+                          const int32_t* u_lens, int32_t B, int32_t U1, int32_t V, int32_t blank,
+                          float* ilm_nll, float* lse /* (U1*B) or NULL */, void* stream);
+int rnnt_hip_ilm_loss_bwd(const float* C, int64_t c_sb, int64_t c_su, const float* bias, const int32_t* labels,
+                          const int32_t* u_lens, const float* lse /* or NULL: recompute */, int32_t B, int32_t U1,
+                          int32_t V, int32_t blank, float gscale, const float* gvec, int32_t gvec_stride,
+                          int32_t accumulate, float* dC, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Input side on device (datamodule.py:48-90, done offline on the host by the reference).
  * rnnt_hip_frontend_norm_pad: per utterance b (row b of wav, lens[b] samples): optional mean / population-variance
  *   normalisation (datamodule.py:87-90), reflect padding by `pad` samples at the utterance's own ends (torch.stft

@@ -347,6 +347,10 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnnt_hip_mwer_risk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "rnnt_hip_ilm_loss_fwd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rnnt_hip_ilm_loss_bwd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32,
+                                        c_i32, C.c_float, C.c_void_p, c_i32, c_i32, C.c_void_p, C.c_void_p]),
 }
 
 KERNEL_KINDS = ["gemm_f32_kernel", "lstm_fwd_kernel", "lstm_bwd_kernel", "lse_kernel", "alphabeta_kernel",

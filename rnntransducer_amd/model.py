@@ -32,7 +32,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
-from .ops import check_fastemit_lambda, emit_windows
+from .ops import check_fastemit_lambda, check_ilmt_weight, emit_windows
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -82,6 +82,11 @@ class RNNTransducer(_Base):
         self.mwer_nbest, self.mwer_max_symbols = (4 if nbest is None else nbest), (1 if max_symbols is None else max_symbols)
         self.mwer_weight = JointNet.check_mwer_args(self.mwer_nbest, self.mwer_max_symbols, 0.0, 511,
                                                     0.0 if mwer_weight is None else mwer_weight, "args.mwer_*")
+        # internal-LM training (JointNet.loss's ilmt_weight): off at 0; the MWER path has no such term
+        ilmt_weight = getattr(args, "ilmt_weight", 0.0)
+        self.ilmt_weight = check_ilmt_weight(0.0 if ilmt_weight is None else ilmt_weight)
+        if self.mwer_weight > 0.0 and self.ilmt_weight > 0.0:
+            raise ValueError("args.mwer_weight > 0 does not combine with args.ilmt_weight > 0: mwer_loss takes no internal-LM term")
 
     def forward(self, input_audios, audio_lengths, input_texts, text_lengths):
         # the reference hands these two as python lists (dataloader.py:20,37): validating them costs no device sync
@@ -186,7 +191,7 @@ class RNNTransducer(_Base):
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
                                   audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda,
-                                  emit_windows=windows)
+                                  emit_windows=windows, ilmt_weight=self.ilmt_weight)
         if logging:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}
@@ -197,6 +202,11 @@ class RNNTransducer(_Base):
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         return self.jointnet.align(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
                                    audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None)
+
+    def ilm_loss(self, input_texts, targets, target_lengths, reduction: str = "mean"):
+        """JointNet.ilm_loss with this model's blank: the internal-LM loss on text alone (text-only internal-LM adaptation; no
+        audio, no encoder call).  Freeze the encoder before building the optimizer: weight decay moves zero-gradient parameters."""
+        return self.jointnet.ilm_loss(input_texts, targets, target_lengths, self.blank_token_id, reduction)
 
     def recognize_ctc_greedy(self, inputs, inputs_lengths, return_frames: bool = False):
         """JointNet.recognize_ctc_greedy with this model's blank: the encoder-only greedy decode through the CTC head."""

@@ -24,15 +24,18 @@ training (`loss(..., ctc_weight=w)`, `ctc_loss` for CTC pre-training of the enco
 `mwer_loss` is minimum word error rate fine-tuning: the reference term of `loss` plus the expected number of token errors over
 the n-best list of the frame-synchronous search, with the hypotheses' losses from the fused loss over the shared encoder row
 (csrc/mwer.hip, ops.JointLossGroupedFn).
+`loss(..., ilmt_weight=w)` adds internal-LM training: w times the cross-entropy of the internal LM (the joint with the encoder half
+zeroed, minus `ilm_score`) on the transcripts, from the joint's decoder half the fused loss already holds; `ilm_loss` is that term
+alone on text, with no audio and no encoder call (csrc/ilm_loss.hip, ops.IlmLossFn).
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from ..ops import (MWER_MAX_LEN, CtcLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens, beam_search,
-                   beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args, check_emit_windows,
-                   check_fastemit_lambda, check_ilm_weight, refuse_ilm_weight,
+from ..ops import (MWER_MAX_LEN, CtcLossFn, IlmLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens,
+                   beam_search, beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args,
+                   check_emit_windows, check_fastemit_lambda, check_ilm_weight, check_ilmt_weight, refuse_ilm_weight,
                    check_fusion, ctc_beam_search, ctc_greedy, edit_distance, greedy_decode, nbest_pack, nbest_umax, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
@@ -106,7 +109,7 @@ class JointNet(nn.Module):
 
     def loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int,
              reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False,
-             fastemit_lambda: float = 0.0, emit_windows=None):
+             fastemit_lambda: float = 0.0, emit_windows=None, ilmt_weight: float = 0.0):
         """-log P(y|x) through the fused path (no (B,T,U+1,V) tensor): per utterance, shape (B,) (reduction "none"), or the 0-d
         "mean" / "sum" over the batch (model.py:39 builds the reference's loss with reduction="mean").
         `audio_lengths`: the python list of frame counts the reference's collate hands over next to the tensor (dataloader.py:20,49).
@@ -124,15 +127,25 @@ class JointNet(nn.Module):
         `emit_windows` = (lo, hi), two (B, U) int32 tensors in the CALLER's row order (they follow their rows through the ragged
         sort): the alignment-restricted transducer term, label u of row b only at frames lo[b,u] .. hi[b,u] (ops.emit_windows builds
         them around a reference alignment; include/rnnt_hip.h).  A row whose windows leave no path has loss +inf and a zero gradient.
-        The CTC term is untouched.  None: the unrestricted loss."""
+        The CTC term is untouched.  None: the unrestricted loss.
+        `ilmt_weight` > 0: internal-LM training (ILMT): the result is rnnt + ctc_weight * ctc + ilmt_weight * ilm,
+        ilm being the cross-entropy of the internal LM (the joint with the encoder half zeroed, over the non-blank tokens: minus
+        `ilm_score`) on `targets`, a per-utterance sum over tokens under the same reduction.  It costs one launch in the forward and
+        one in the backward on the joint's decoder half the loss already holds; the encoder gets no gradient from it.  FastEmit,
+        the windows and the CTC term do not touch it.  A counted target that is the blank gives that row +inf and a zero gradient
+        of the term.  With return_parts=True the tuple gains a last element: (total, rnnt, ctc, ilm).  Finite and >= 0; at 0 the
+        term is not computed and every result is bitwise that of a call without the argument."""
         return self._reference_terms(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
-                                     audio_lengths, ctc_weight, return_parts, fastemit_lambda, emit_windows=emit_windows)[0]
+                                     audio_lengths, ctc_weight, return_parts, fastemit_lambda, emit_windows=emit_windows,
+                                     ilmt_weight=ilmt_weight)[0]
 
     def _reference_terms(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
-                         audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False, emit_windows=None):
+                         audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False, emit_windows=None,
+                         ilmt_weight=0.0):
         """The body of loss(): -> (what loss() returns, (enc, targets, t_lens, u_lens, inv)) with the encoder output and the
         per-row tensors in the row order the encoder ran in (length-sorted for a ragged batch; `inv` restores the caller's order,
         None when nothing moved or nobody needs it).  mwer_loss builds its hypothesis term on the same encoder output."""
+        ilmt_weight = check_ilmt_weight(ilmt_weight)
         with_ctc = ctc_weight != 0.0 or return_parts
         if with_ctc:
             self._need_ctc_head("loss(ctc_weight != 0 or return_parts=True)")
@@ -147,7 +160,11 @@ class JointNet(nn.Module):
         input_audios, input_texts, targets = rows[:3]
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
-        if win is None:
+        ilm = None
+        if ilmt_weight > 0.0:
+            out, ilm = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
+                                         reduction, fastemit_lambda, None if win is None else (rows[3], rows[4]), ilmt_weight)
+        elif win is None:
             out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
                                     reduction, fastemit_lambda)
         else:
@@ -156,14 +173,40 @@ class JointNet(nn.Module):
         unsort = inv is not None and reduction == "none"
         shared = (enc, targets, t_lens, u_lens, inv)
         out = out.index_select(0, inv) if unsort else out
+        if ilm is not None:
+            ilm = ilm.index_select(0, inv) if unsort else ilm
         if not with_ctc:
-            return out, shared
+            return (out if ilm is None else out + ilmt_weight * ilm), shared
         track = ctc_weight != 0.0 and torch.is_grad_enabled()
         with torch.set_grad_enabled(track):
             ctc = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, track, reduction, True)
         ctc = ctc.index_select(0, inv) if unsort else ctc
         total = out + ctc_weight * ctc if ctc_weight != 0.0 else out
-        return ((total, out, ctc) if return_parts else total), shared
+        if ilm is not None:
+            total = total + ilmt_weight * ilm
+        parts = (total, out, ctc) if ilm is None else (total, out, ctc, ilm)
+        return (parts if return_parts else total), shared
+
+    def ilm_loss(self, input_texts, targets, target_lengths, blank: int, reduction: str = "none") -> torch.Tensor:
+        """The internal-LM term alone, on text (text-only internal-LM adaptation): no audio and no encoder call.
+        input_texts (B, U+1) int64 (the blank, then the tokens, as `loss` takes them), targets (B, U) int32, target_lengths B
+        values in [0, U] -> per utterance the cross-entropy of the internal LM on the targets, summed over tokens (shape (B,)),
+        or its "mean" / "sum" over the batch.  The prediction net, fc.weight[:, enc_out:] and fc.bias receive gradients; the
+        encoder's parameters receive none and fc.weight[:, :enc_out] exact zeros.  Freeze the encoder (requires_grad_(False))
+        BEFORE building the optimizer for text-only adaptation: a decoupled weight decay still moves a parameter whose gradient
+        is zero.  In eval() under torch.no_grad() this is -ilm_score(targets, target_lengths, blank) in fp32: the internal LM's
+        perplexity on a text is exp(ilm_loss / length), computed on the device.  A counted target that is the blank or outside
+        the vocabulary gives that row +inf and a zero gradient (no host check: it would cost a synchronisation)."""
+        if reduction not in ("none", "mean", "sum"):
+            raise ValueError(f"ilm_loss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        if not 0 <= int(blank) < self.num_classes:
+            raise ValueError(f"ilm_loss: blank {blank} outside [0,{self.num_classes})")
+        if input_texts.dim() != 2 or targets.dim() != 2 or tuple(input_texts.shape) != (targets.size(0), targets.size(1) + 1):
+            raise ValueError(f"ilm_loss: input_texts must be (B, U+1) and targets (B, U), got {tuple(input_texts.shape)} and "
+                             f"{tuple(targets.shape)}")
+        u_lens = lengths_to_device(target_lengths, input_texts.device)
+        dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1, as in loss()
+        return IlmLossFn.apply(dec, self.fc.weight, self.fc.bias, targets, u_lens, int(blank), torch.is_grad_enabled(), reduction)
 
     def ctc_loss(self, input_audios, tensor_audio_lengths, targets, target_lengths, blank: int, reduction: str = "none",
                  audio_lengths=None) -> torch.Tensor:

@@ -722,30 +722,35 @@ def _joint_ac(enc, dec, W, Oe, Od, V):
     return A, Cm
 
 
-def _joint_backward(enc, dec, W, dA, dC, needs, w_tgt=None, b_tgt=None):
+def _joint_backward(enc, dec, W, dA, dC, needs, w_tgt=None, b_tgt=None, db_from_c=False):
     """d_enc, d_dec, dW, db from dA (T,B,V), dC (U1,B,V).  w_tgt / b_tgt: flat-gradient views to add into (then None is
     returned for that gradient).  dec and dC may hold more rows than enc (JointLossGroupedFn: a group of label rows per
-    encoder row, dA already summed over the group)."""
-    T, B, Oe = enc.shape
+    encoder row, dA already summed over the group).
+    db_from_c: db = the column sums of dC instead of dA's.  z = A + C + bias, so the lattice's dA and dC have the same column sums;
+    a dC that also carries the internal-LM term (whose logits are C + bias) therefore holds the whole bias gradient.
+    enc = dA = None (IlmLossFn, with db_from_c): the decoder half alone; a fresh dW then has exact zeros in its encoder columns."""
     U1, Bd, Od = dec.shape
-    V = W.shape[0]
-    O = Oe + Od
+    V, O = W.shape
+    Oe = O - Od
     d_enc = d_dec = dW = db = None
     if needs[0]:
+        T, B = enc.shape[:2]
         d_enc = torch.empty_like(enc)
         gemm(T * B, Oe, V, dA, W, d_enc, b_sn=1, b_sk=O, aux=enc, flags=GEMM_MUL_DGELU)
     if needs[1]:
         d_dec = torch.empty_like(dec)
         gemm(U1 * Bd, Od, V, dC, W, d_dec, b_off=Oe, b_sn=1, b_sk=O, aux=dec, flags=GEMM_MUL_DGELU)
     if needs[2]:
-        dW = torch.empty_like(W) if w_tgt is None else None
+        dW = (torch.empty_like(W) if enc is not None else torch.zeros_like(W)) if w_tgt is None else None
         out = dW if w_tgt is None else w_tgt
         fl = GEMM_GELU_B | (0 if w_tgt is None else GEMM_ACCUM)
-        gemm(V, Oe, T * B, dA, enc, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Oe, c_div=1, c_so=O, c_si=0, flags=fl, split_k=True)
+        if enc is not None:
+            T, B = enc.shape[:2]
+            gemm(V, Oe, T * B, dA, enc, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Oe, c_div=1, c_so=O, c_si=0, flags=fl, split_k=True)
         gemm(V, Od, U1 * Bd, dC, dec, out, a_mc=True, a_sk=V, b_sn=1, b_sk=Od, c_off=Oe, c_div=1, c_so=O, c_si=0, flags=fl,
              split_k=True)
     if needs[3]:
-        db = colsum(dA, T * B, V, into=b_tgt)
+        db = colsum(dC, U1 * Bd, V, into=b_tgt) if db_from_c else colsum(dA, enc.shape[0] * enc.shape[1], V, into=b_tgt)
     return d_enc, d_dec, dW, db
 
 
@@ -755,6 +760,48 @@ def check_fastemit_lambda(fastemit_lambda) -> float:
     if not (math.isfinite(lam) and lam >= 0.0):
         raise ValueError(f"fastemit_lambda must be finite and >= 0, got {fastemit_lambda!r}")
     return lam
+
+
+def check_ilmt_weight(ilmt_weight) -> float:
+    """The weight of the internal-LM training term (ILMT; include/rnnt_hip.h): a finite number >= 0."""
+    if isinstance(ilmt_weight, bool) or not isinstance(ilmt_weight, (int, float)):
+        raise ValueError(f"ilmt_weight must be a number, finite and >= 0, got {ilmt_weight!r}")
+    w = float(ilmt_weight)
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"ilmt_weight must be finite and >= 0, got {ilmt_weight!r}")
+    return w
+
+
+def _ilm_forward(Cm, bias, labels, u_lens, blank: int, keep_lse: bool):
+    """The internal LM's per-utterance NLL (B,) on Cm (U1,B,V) time-major, and the rows' lse (U1*B) for the backward (or None).
+    (B, 0) labels have no storage to point at: u_lens stands in for them, and is never read as labels (every length clamps to 0)."""
+    U1, B, V = Cm.shape
+    labels = labels if labels.numel() else u_lens
+    ilm = torch.empty(B, device=Cm.device, dtype=torch.float32)
+    lse = torch.empty(U1 * B, device=Cm.device, dtype=torch.float32) if keep_lse else None
+    check(_lib.lib().rnnt_hip_ilm_loss_fwd(_addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(u_lens), B, U1, V, int(blank),
+                                           _addr(ilm), _addr(lse), _stream()), "rnnt_hip_ilm_loss_fwd")
+    return ilm, lse
+
+
+def _ilm_backward(Cm, bias, labels, u_lens, lse, blank: int, g, red_scale, accumulate: bool, dC) -> None:
+    """dC (+)= the internal-LM term's gradient under the upstream gradient g ((B,), or 0-d with the reduction's red_scale)."""
+    U1, B, V = Cm.shape
+    labels = labels if labels.numel() else u_lens
+    gvec = _f32c(g.to(torch.float32), "grad of the internal-LM loss")
+    scalar = red_scale is not None
+    check(_lib.lib().rnnt_hip_ilm_loss_bwd(_addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(u_lens), _addr(lse), B, U1, V,
+                                           int(blank), red_scale if scalar else 1.0, _addr(gvec), 0 if scalar else 1,
+                                           1 if accumulate else 0, _addr(dC), _stream()), "rnnt_hip_ilm_loss_bwd")
+
+
+def _reduce_loss(nll, red_scale):
+    """The (B,) losses themselves (red_scale None) or red_scale * their sum, 0-d, inside the library."""
+    if red_scale is None:
+        return nll
+    out = torch.empty((), device=nll.device, dtype=torch.float32)
+    check(_lib.lib().rnnt_hip_scaled_sum_f32(_addr(nll), nll.numel(), red_scale, _addr(out), _stream()), "rnnt_hip_scaled_sum_f32")
+    return out
 
 
 def check_emit_windows(emit_windows, B: int, U: int, device):
@@ -805,13 +852,18 @@ class JointLossFn(torch.autograd.Function):
     fastemit_lambda > 0: FastEmit regularisation of the GRADIENT (label log-probability gradients scaled by 1 + lambda, through the
     log-softmax exactly; include/rnnt_hip.h).  The returned loss stays the unregularised NLL, bit for bit that of lambda = 0.
     emit_windows = (lo, hi), two (B,U) int32 tensors: the alignment-restricted loss (label u only at frames lo[b,u] .. hi[b,u]; an
-    infeasible row has NLL +inf and a zero gradient; include/rnnt_hip.h).  None: the unrestricted loss, the entries without windows."""
+    infeasible row has NLL +inf and a zero gradient; include/rnnt_hip.h).  None: the unrestricted loss, the entries without windows.
+    ilmt_weight > 0 (internal-LM training; csrc/ilm_loss.hip): the function returns (nll, ilm_nll), the second the internal LM's NLL
+    of the labels under the same reduction, from one more launch on the C tensor the loss already holds.  The weight itself is the
+    caller's to apply: the upstream gradient of ilm_nll reaches the gradient kernel, which adds the term into the lattice's dC (one
+    launch); fc.bias's gradient is then the column sums of that dC.  At 0: one output, the launches and bits of a call without it."""
 
     @staticmethod
     def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0,
-                emit_windows=None):
+                emit_windows=None, ilmt_weight=0.0):
         _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
         ctx.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
+        ctx.ilmt = check_ilmt_weight(ilmt_weight) > 0.0
         win = check_emit_windows(emit_windows, enc.shape[1], dec.shape[0] - 1, enc.device)
         w_param, b_param = W, bias
         enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
@@ -843,20 +895,20 @@ class JointLossFn(torch.autograd.Function):
                                                                 _addr(nll), None, None, _addr(ws), nws, _stream()),
                   "rnnt_hip_joint_loss_fwd_bwd_window")
         ctx.windowed = win is not None   # the backward reads the band tables the forward left in the workspace
-        if want_grad and any(ctx.needs_input_grad[:4]):  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
-            ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws)
+        keep = want_grad and any(ctx.needs_input_grad[:4])  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
+        ilm, lse = _ilm_forward(Cm, bias, labels, u_lens, blank, keep) if ctx.ilmt else (None, None)
+        if keep:
+            ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws, *((lse,) if ctx.ilmt else ()))
             ctx.blank = int(blank)
             ctx.w_param, ctx.b_param = w_param, b_param
         ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
-        if ctx.red_scale is None:
-            return nll
-        out = torch.empty((), device=enc.device, dtype=torch.float32)   # reduction inside the library: no torch arithmetic on the path
-        check(_lib.lib().rnnt_hip_scaled_sum_f32(_addr(nll), B, ctx.red_scale, _addr(out), _stream()), "rnnt_hip_scaled_sum_f32")
-        return out
+        if ctx.ilmt:
+            return _reduce_loss(nll, ctx.red_scale), _reduce_loss(ilm, ctx.red_scale)
+        return _reduce_loss(nll, ctx.red_scale)   # reduction inside the library: no torch arithmetic on the path
 
     @staticmethod
-    def backward(ctx, g):
-        enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws = ctx.saved_tensors
+    def backward(ctx, g, g_ilm=None):
+        enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws = ctx.saved_tensors[:10]
         T, B, _ = enc.shape
         U1, V = dec.shape[0], W.shape[0]
         gvec = _f32c(g.to(torch.float32), "grad of the loss")
@@ -868,9 +920,11 @@ class JointLossFn(torch.autograd.Function):
         check(bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(t_lens), _addr(u_lens), B, T, U1, V,
                   ctx.blank, ctx.red_scale if scalar else 1.0, ctx.fastemit_lambda, _addr(gvec), 0 if scalar else 1, _addr(dA),
                   _addr(dC), _addr(ws), ws.numel(), _stream()), what)
+        if ctx.ilmt:   # the internal-LM term's gradient lands in the dC the lattice kernel has just written; db then comes from dC
+            _ilm_backward(Cm, bias, labels, u_lens, ctx.saved_tensors[10], ctx.blank, g_ilm, ctx.red_scale, True, dC)
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
-                                               _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
-        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None, None
+                                               _direct_grad(ctx.w_param), _direct_grad(ctx.b_param), db_from_c=ctx.ilmt)
+        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None, None, None
 
 
 class JointLossGroupedFn(torch.autograd.Function):
@@ -934,6 +988,51 @@ class JointLossGroupedFn(torch.autograd.Function):
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
                                                _direct_grad(ctx.w_param), _direct_grad(ctx.b_param))
         return d_enc, d_dec, dW, db, None, None, None, None, None, None
+
+
+class IlmLossFn(torch.autograd.Function):
+    """The internal-LM loss alone, on text (text-only internal-LM adaptation; include/rnnt_hip.h, csrc/ilm_loss.hip): dec (U1,B,Od)
+    time-major, fc.weight (V, Oe + Od), fc.bias -> per-utterance NLL (B,) of the internal LM on labels (B,U) int32, or its "sum" /
+    "mean" over the batch (0-d).  No encoder operand: the decoder half of the joint's pre-GEMM alone, the forward kernel, and in the
+    backward the gradient kernel (accumulate = 0) and the decoder half of the joint's own backward.  fc.weight's encoder columns get
+    exact zeros (nothing is added to them in a flat-gradient view).  Under torch.no_grad() nothing is kept."""
+
+    @staticmethod
+    def forward(ctx, dec, W, bias, labels, u_lens, blank, want_grad=True, reduction="none"):
+        _need_gpu(dec, W, bias, labels, u_lens)
+        w_param, b_param = W, bias
+        dec, W, bias = _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
+        for name, t in (("targets", labels), ("target lengths", u_lens)):
+            if t.dtype != torch.int32:
+                raise ValueError(f"{name} must be int32 (dataloader.py:21-24), got {t.dtype}")
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
+        labels, u_lens = labels.contiguous(), u_lens.contiguous()
+        U1, B, Od = dec.shape
+        V, O = W.shape
+        Oe = O - Od
+        if Oe < 0 or tuple(bias.shape) != (V,) or tuple(labels.shape) != (B, U1 - 1) or tuple(u_lens.shape) != (B,):
+            raise ValueError(f"shape mismatch: dec {tuple(dec.shape)} fc {tuple(W.shape)} bias {tuple(bias.shape)} targets "
+                             f"{tuple(labels.shape)} lengths {tuple(u_lens.shape)}")
+        Cm = torch.empty(U1, B, V, device=dec.device, dtype=torch.float32)
+        gemm(U1 * B, V, Od, dec, W, Cm, b_off=Oe, b_sn=O, b_sk=1, flags=GEMM_GELU_A)
+        keep = want_grad and any(ctx.needs_input_grad[:3])
+        ilm, lse = _ilm_forward(Cm, bias, labels, u_lens, blank, keep)
+        if keep:
+            ctx.save_for_backward(dec, W, bias, labels, u_lens, Cm, lse)
+            ctx.blank = int(blank)
+            ctx.w_param, ctx.b_param = w_param, b_param
+        ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
+        return _reduce_loss(ilm, ctx.red_scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        dec, W, bias, labels, u_lens, Cm, lse = ctx.saved_tensors
+        dC = torch.empty_like(Cm)
+        _ilm_backward(Cm, bias, labels, u_lens, lse, ctx.blank, g, ctx.red_scale, False, dC)
+        _, d_dec, dW, db = _joint_backward(None, dec, W, None, dC, (False,) + tuple(ctx.needs_input_grad[:3]),
+                                           _direct_grad(ctx.w_param), _direct_grad(ctx.b_param), db_from_c=True)
+        return d_dec, dW, db, None, None, None, None, None
 
 
 class JointLogitsFn(torch.autograd.Function):
