@@ -7,14 +7,20 @@
 // written: log p(blank) and log p(y_u).
 //
 // Kernels (all HBM/latency-bound integer+transcendental work; no MFMA here by design):
+//   band_kernel                       : emission windows -> the band tables L, R and the feasibility flag of every row
 //   lse_sep_kernel / lse_dense_kernel : per-cell log-sum-exp -> blk[b][u][t], emit[b][u][t] (u-major)
+//   lse_sepv_kernel                   : lse_sep_kernel for V >= 256, a lane per vocabulary entry
 //   alphabeta_kernel<K>               : one wavefront per (utterance, alpha|beta); lane l owns label
 //                                       positions [l*K, l*K+K) and sweeps t with a one-lane skew, so each
 //                                       step advances one anti-diagonal; neighbour hand-off by lane shuffle;
 //                                       accumulators in fp64 with an fp32 log1p(exp(.)) correction term
 //   grad_sep_kernel                   : dA[b,t,:] = sum_u dz, partial dC slabs per 32-frame tile (LDS adds)
 //   reduce_dc_kernel                  : fixed-order sum of the slabs (bitwise reproducible, no float atomics)
+//   grad_sepv_kernel                  : grad_sep_kernel with the vocabulary a grid dimension (V >= 256, or a table past LDS)
 //   grad_dense_kernel                 : warp-transducer-shaped d/d logits for rnnt_hip_loss_from_logits_*
+//   viterbi_kernel<K> / backtrace_kernel : forced alignment -- the max-plus sweep (one back-pointer bit per cell), the best path
+// The W / FE template flags select the emission-window / FastEmit instances; W = FE = false are the kernels without either.
+// The host half (from struct LossWs on): one LossCall per call, one check, four stages, three drivers behind the exported entries.
 #include "common.hpp"
 #include "lattice_shared.hpp"
 
@@ -1048,144 +1054,363 @@ struct LossWs {
   float *blk, *emit;
   double *alpha, *beta, *ll;
   float* dCp;
-  size_t total;
-};
-
-LossWs carve(void* ws, int B, int T, int U1, int V, bool with_slabs) {
-  LossWs w;
-  const size_t cells = (size_t)B * T * U1;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  w.alpha = reinterpret_cast<double*>(take(cells * 8));
-  w.beta = reinterpret_cast<double*>(take(cells * 8));
-  w.ll = reinterpret_cast<double*>(take((size_t)B * 2 * 8));
-  w.blk = reinterpret_cast<float*>(take(cells * 4));
-  w.emit = reinterpret_cast<float*>(take(cells * 4));
-  const size_t ntiles = ceil_div(T, TT);
-  w.dCp = reinterpret_cast<float*>(take(with_slabs ? (size_t)B * ntiles * U1 * V * 4 : 0));
-  w.total = off;
-  return w;
-}
-
-// the windowed loss: the plain workspace, then the band tables L, R ([B][U1] int32) and the feasibility flags ([B])
-struct WinWs {
-  LossWs w;
-  int *L, *R, *feas;
-  size_t total;
-};
-
-WinWs carve_window(void* ws, int B, int T, int U1, int V) {
-  WinWs x;
-  x.w = carve(ws, B, T, U1, V, true);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = x.w.total;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  x.L = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
-  x.R = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
-  x.feas = reinterpret_cast<int*>(take((size_t)B * 4));
-  x.total = off;
-  return x;
-}
-
-int check_window(const void* emit_lo, const void* emit_hi, int64_t win_stride, int U1, const char* who) {
-  RNNT_CHECK_ARG(emit_lo && emit_hi, "%s: null emit_lo / emit_hi", who);
-  RNNT_CHECK_ARG(win_stride >= 1 && win_stride >= U1 - 1, "%s: the window tables' row stride %lld must be positive and at least U = %d",
-                 who, (long long)win_stride, U1 - 1);
-  return RNNT_OK;
-}
-
-int launch_band(const WinWs& x, const int32_t* emit_lo, const int32_t* emit_hi, int64_t win_stride, const int* t_lens,
-                const int* u_lens, int B, int T, int U1, hipStream_t s) {
-  hipLaunchKernelGGL(band_kernel, dim3(B), dim3(256), 0, s, emit_lo, emit_hi, (long)win_stride, t_lens, u_lens, T, U1, x.L, x.R,
-                     x.feas);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-int check_common(const void* labels, const void* t_lens, const void* u_lens, int B, int T, int U1, int V, int blank,
-                 const void* nll) {
-  RNNT_CHECK_ARG(B >= 1 && T >= 1 && U1 >= 1 && V >= 1, "rnnt loss: dims must be positive (B=%d T=%d U1=%d V=%d)", B, T, U1, V);
-  RNNT_CHECK_ARG(blank >= 0 && blank < V, "rnnt loss: blank %d outside [0,%d)", blank, V);
-  RNNT_CHECK_ARG(U1 <= 64 * 8, "rnnt loss: U+1 = %d exceeds the 512 label positions one wavefront sweeps", U1);
-  RNNT_CHECK_ARG((int64_t)U1 * T * 8 < (1ll << 31), "rnnt loss: one utterance's lattice (T = %d x U+1 = %d, fp64) exceeds the 2 GB a buffer resource addresses", T, U1);
-  RNNT_CHECK_ARG(t_lens && u_lens && nll, "rnnt loss: null lengths/output");
-  RNNT_CHECK_ARG(U1 == 1 || labels, "rnnt loss: null labels");
-  return RNNT_OK;
-}
-
-int launch_alphabeta(const LossWs& w, const int* t_lens, const int* u_lens, int B, int T, int U1, hipStream_t s) {
-  const int K = (int)ceil_div(U1, 64);
-  ProfScope prof(RNNT_K_ALPHABETA, 2.0 * (8.0 + 8.0) * (double)B * T * U1, s);  // read blk+emit, write alpha|beta (fp64)
-  dim3 grid(B, 2), block(64);
-#define AB(KK) hipLaunchKernelGGL((alphabeta_kernel<KK>), grid, block, 0, s, w.blk, w.emit, t_lens, u_lens, T, U1, w.alpha, w.beta, w.ll)
-  switch (K) {
-    case 1: AB(1); break;
-    case 2: AB(2); break;
-    case 3: AB(3); break;
-    case 4: AB(4); break;
-    default: AB(8); break;
-  }
-#undef AB
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-// forced alignment: blk / emit as the loss lays them out, then the back-pointer table bp[B][U1][ceil(T/32)] (one bit per cell)
-struct AlignWs {
-  float *blk, *emit;
-  unsigned* bp;
+  int *L, *R, *feas;   // the band tables ([B][U1] int32) and feasibility flags ([B]) of the windowed loss: null without windows
+  unsigned* bp;        // forced alignment: the back-pointer table bp[B][U1][nw = ceil(T/32)], one bit per cell
   int nw;
   size_t total;
 };
 
-AlignWs carve_align(void* ws, int B, int T, int U1) {
-  AlignWs w;
-  const size_t cells = (size_t)B * T * U1;
-  char* p = reinterpret_cast<char*>(ws);
+// ------------------------------------------------------------------------------------------------
+// Host half.  Every exported loss / alignment entry fills ONE description of its call, a LossCall, and hands it to a driver:
+// run_loss (forward, and the backward when gradients are asked for), run_loss_bwd (the backward alone, on the workspace a forward
+// left) or run_align.  A driver checks the whole call before any device work (check_call, which also carves the workspace) and
+// then composes the stages: lse -> sweep (+ nll) -> grad, or lse -> viterbi.  A further variant of the loss is a field here.
+// ------------------------------------------------------------------------------------------------
+struct LossCall {
+  const char* who = "";   // the entry's name, for messages
+  // operands: separable (z = A + C + bias, element strides), or dense logits (B,T,U1,V) in `dtype` storage
+  bool dense = false;
+  const float *A = nullptr, *C = nullptr, *bias = nullptr;
+  int64_t a_sb = 0, a_st = 0, c_sb = 0, c_su = 0;
+  const void* logits = nullptr;
+  int dtype = RNNT_DTYPE_F32;
+  const int32_t *labels = nullptr, *t_lens = nullptr, *u_lens = nullptr;
+  int B = 0, T = 0, U1 = 0, V = 0, blank = 0;
+  // the gradient: upstream scale, FastEmit's weight, per-utterance upstream gradients (backward-only calls)
+  float gscale = 1.f, fastemit_lambda = 0.f;
+  const float* gvec = nullptr;
+  int gvec_stride = 0;
+  // emission windows.  windowed: the call works on the band tables of the workspace -- a forward builds them from emit_lo /
+  // emit_hi (rows win_stride apart), a backward-only call finds them there
+  bool windowed = false;
+  const int32_t *emit_lo = nullptr, *emit_hi = nullptr;
+  int64_t win_stride = 0;
+  // outputs: the loss (dA / dC separable, grad dense; null: no backward) or the alignment
+  float *nll = nullptr, *dA = nullptr, *dC = nullptr;
+  void* grad = nullptr;
+  int32_t* frames = nullptr;
+  double* score = nullptr;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+  hipStream_t stream = nullptr;
+};
+
+struct Carver {   // consecutive 256-byte aligned pieces of a workspace (a null base: sizes only)
+  char* p;
   size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  w.blk = reinterpret_cast<float*>(take(cells * 4));
-  w.emit = reinterpret_cast<float*>(take(cells * 4));
-  w.nw = (int)ceil_div(T, 32);
-  w.bp = reinterpret_cast<unsigned*>(take((size_t)B * U1 * w.nw * 4));
-  w.total = off;
+  template <typename T>
+  T* take(size_t bytes) {
+    char* q = p ? p + off : nullptr;
+    off += align_up(bytes, 256);
+    return reinterpret_cast<T*>(q);
+  }
+};
+
+// the loss: alpha | beta | logZ | blk | emit | the dC slabs, then (windowed) the band tables L, R and the feasibility flags
+LossWs carve(void* ws, int B, int T, int U1, int V, bool windowed) {
+  LossWs w{};
+  Carver c{reinterpret_cast<char*>(ws)};
+  const size_t cells = (size_t)B * T * U1, ntiles = ceil_div(T, TT);
+  w.alpha = c.take<double>(cells * 8);
+  w.beta = c.take<double>(cells * 8);
+  w.ll = c.take<double>((size_t)B * 2 * 8);
+  w.blk = c.take<float>(cells * 4);
+  w.emit = c.take<float>(cells * 4);
+  w.dCp = c.take<float>((size_t)B * ntiles * U1 * V * 4);
+  if (windowed) {
+    w.L = c.take<int>((size_t)B * U1 * 4);
+    w.R = c.take<int>((size_t)B * U1 * 4);
+    w.feas = c.take<int>((size_t)B * 4);
+  }
+  w.total = c.off;
   return w;
 }
 
-int check_align(const void* labels, const void* t_lens, const void* u_lens, int B, int T, int U1, int V, int blank,
-                const void* frames, const void* score) {
-  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, score)) return rc;
-  RNNT_CHECK_ARG(U1 == 1 || frames, "rnnt align: null frames");
+// forced alignment: blk / emit as the loss lays them out, then the back-pointer table
+LossWs carve_align(void* ws, int B, int T, int U1) {
+  LossWs w{};
+  Carver c{reinterpret_cast<char*>(ws)};
+  const size_t cells = (size_t)B * T * U1;
+  w.blk = c.take<float>(cells * 4);
+  w.emit = c.take<float>(cells * 4);
+  w.nw = (int)ceil_div(T, 32);
+  w.bp = c.take<unsigned>((size_t)B * U1 * w.nw * 4);
+  w.total = c.off;
+  return w;
+}
+
+// ---- dispatch helpers: a run-time choice handed to a generic lambda as a type ----
+template <bool X> struct BoolT { static constexpr bool value = X; };
+template <int X> struct IntT { static constexpr int value = X; };
+template <typename T> struct TypeT { using type = T; };
+
+// the storage type of dense logits: f(TypeT<float | __half | __hip_bfloat16>)
+template <typename F>
+int dispatch_dtype(int dtype, const char* who, F&& f) {
+  switch (dtype) {
+    case RNNT_DTYPE_F32: return f(TypeT<float>{});
+    case RNNT_DTYPE_F16: return f(TypeT<__half>{});
+    case RNNT_DTYPE_BF16: return f(TypeT<__hip_bfloat16>{});
+    default: set_error("%s: unknown dtype code %d", who, dtype); return RNNT_ERR_INVALID;
+  }
+}
+
+// K label positions per lane of the two sweep kernels (alphabeta_kernel, viterbi_kernel): f(IntT<K>), K in {1, 2, 3, 4, 8}
+template <typename F>
+void dispatch_k(int U1, F&& f) {
+  switch ((int)ceil_div(U1, 64)) {
+    case 1: f(IntT<1>{}); break;
+    case 2: f(IntT<2>{}); break;
+    case 3: f(IntT<3>{}); break;
+    case 4: f(IntT<4>{}); break;
+    default: f(IntT<8>{}); break;
+  }
+}
+
+// The kernel instance of a call.  W: f(BoolT<W>, tables...) -- the W = true instance and its one table struct with emission
+// windows, the W = false instance (the kernel without that feature) and no table without.
+template <typename Tab, typename F>
+int pick_w(bool windowed, const Tab& tab, F&& f) {
+  return windowed ? f(BoolT<true>{}, tab) : f(BoolT<false>{});
+}
+// <FE, W> of the gradient kernels: f(BoolT<FE>, BoolT<W>, lambda, tables...).  lambda = 0 launches the FE = false instances (the
+// kernels as they are without FastEmit), lambda > 0 the FE = true ones.
+template <typename F>
+int pick_fe_w(const LossCall& c, const LossWs& w, F&& f) {
+  return pick_w(w.L != nullptr, Band{w.L, w.R}, [&](auto win, auto... wt) {
+    return c.fastemit_lambda != 0.f ? f(BoolT<true>{}, win, c.fastemit_lambda, wt...) : f(BoolT<false>{}, win, 0.f, wt...);
+  });
+}
+
+// vocabularies from 256 entries take the lane-per-entry kernels (lse_sepv_kernel, grad_sepv_kernel); RNNT_LOSS_SMALLV_KERNELS=1 keeps
+// the round-1 kernels everywhere, RNNT_LOSS_LARGEV_KERNELS=1 takes the new ones for every V (A/B and tests)
+bool large_vocab(int V) {
+  if (getenv("RNNT_LOSS_SMALLV_KERNELS")) return false;
+  return V >= 256 || getenv("RNNT_LOSS_LARGEV_KERNELS") != nullptr;
+}
+
+unsigned dense_grid(long ncell) { return (unsigned)(ceil_div(ncell, 4) < 16384 ? ceil_div(ncell, 4) : 16384); }
+
+enum class Drive { Forward, Backward, Align };
+
+// Every argument check of every entry, before any device work; then the workspace, carved, and its size.
+int check_call(const LossCall& c, Drive drive, LossWs* w) {
+  const char* who = c.who;
+  RNNT_CHECK_ARG(c.B >= 1 && c.T >= 1 && c.U1 >= 1 && c.V >= 1, "%s: dims must be positive (B=%d T=%d U1=%d V=%d)", who, c.B, c.T, c.U1, c.V);
+  RNNT_CHECK_ARG(c.blank >= 0 && c.blank < c.V, "%s: blank %d outside [0,%d)", who, c.blank, c.V);
+  RNNT_CHECK_ARG(c.U1 <= 64 * 8, "%s: U+1 = %d exceeds the 512 label positions one wavefront sweeps", who, c.U1);
+  RNNT_CHECK_ARG((int64_t)c.U1 * c.T * 8 < (1ll << 31), "%s: one utterance's lattice (T = %d x U+1 = %d, fp64) exceeds the 2 GB a buffer resource addresses", who, c.T, c.U1);
+  RNNT_CHECK_ARG(c.t_lens && c.u_lens, "%s: null lengths", who);
+  RNNT_CHECK_ARG(c.U1 == 1 || c.labels, "%s: null labels", who);
+  if (c.dense) {
+    if (int rc = dispatch_dtype(c.dtype, who, [](auto) { return RNNT_OK; })) return rc;
+    RNNT_CHECK_ARG(c.logits, "%s: null logits", who);
+  } else {
+    RNNT_CHECK_ARG(c.A && c.C && c.bias, "%s: null A/C/bias", who);
+  }
+  // FastEmit's lambda is read by the backward only, but checked in every call that carries one: finite and >= 0
+  if (drive != Drive::Align)
+    RNNT_CHECK_ARG(c.fastemit_lambda >= 0.f && c.fastemit_lambda <= 3.4028234664e38f, "%s: fastemit_lambda must be finite and >= 0 (got %g)", who, (double)c.fastemit_lambda);
+  switch (drive) {
+    case Drive::Forward:
+      RNNT_CHECK_ARG(c.nll, "%s: null nll", who);
+      RNNT_CHECK_ARG((c.dA == nullptr) == (c.dC == nullptr), "%s: dA and dC must both be given or both be NULL", who);
+      if (c.windowed) {
+        RNNT_CHECK_ARG(c.emit_lo && c.emit_hi, "%s: null emit_lo / emit_hi", who);
+        RNNT_CHECK_ARG(c.win_stride >= 1 && c.win_stride >= c.U1 - 1, "%s: the window tables' row stride %lld must be positive and at least U = %d",
+                       who, (long long)c.win_stride, c.U1 - 1);
+      }
+      break;
+    case Drive::Backward:
+      // historical: the backward-only entries have always refused V = 1 and null labels (at U = 0 too), which the forward accepts
+      RNNT_CHECK_ARG(c.V >= 2 && c.labels, "%s: V must be at least 2 and labels given", who);
+      RNNT_CHECK_ARG(c.dA && c.dC, "%s: null dA/dC", who);
+      RNNT_CHECK_ARG(c.gvec_stride == 0 || c.gvec_stride == 1, "%s: gvec_stride must be 0 (one scalar) or 1 (per utterance)", who);
+      break;
+    case Drive::Align:
+      RNNT_CHECK_ARG(c.score, "%s: null score", who);
+      RNNT_CHECK_ARG(c.U1 == 1 || c.frames, "%s: null frames", who);
+      break;
+  }
+  *w = drive == Drive::Align ? carve_align(c.workspace, c.B, c.T, c.U1) : carve(c.workspace, c.B, c.T, c.U1, c.V, c.windowed);
+  RNNT_CHECK_ARG(c.workspace && c.workspace_bytes >= w->total, "%s: workspace too small (%zu < %zu)", who, c.workspace_bytes, w->total);
   return RNNT_OK;
 }
 
-int launch_viterbi(const AlignWs& w, const int* t_lens, const int* u_lens, int B, int T, int U1, int* frames, double* score,
-                   hipStream_t s) {
-  const int K = (int)ceil_div(U1, 64);
+// stage 1: blk / emit of every lattice cell, from the separable operands or from dense logits (the loss and the alignment share
+// it); with emission windows the band tables first, then the W = true instances
+int stage_lse(const LossCall& c, const LossWs& w) {
+  hipStream_t s = c.stream;
+  const bool windowed = w.L != nullptr;
+  if (windowed) {
+    hipLaunchKernelGGL(band_kernel, dim3(c.B), dim3(256), 0, s, c.emit_lo, c.emit_hi, (long)c.win_stride, c.t_lens, c.u_lens, c.T, c.U1,
+                       w.L, w.R, w.feas);
+    RNNT_CHECK_LAUNCH();
+  }
+  const Win win = {w.L, w.R, c.emit_lo, c.emit_hi, c.u_lens, (long)c.win_stride};
+  if (c.dense) {
+    const long ncell = (long)c.B * c.T * c.U1;
+    dispatch_dtype(c.dtype, c.who, [&](auto tz) {
+      using TZ = typename decltype(tz)::type;
+      ProfScope prof(RNNT_K_LSE, (double)sizeof(TZ) * (double)ncell * c.V + 8.0 * (double)ncell, s);
+      return pick_w(windowed, win, [&](auto W, auto... wt) {
+        hipLaunchKernelGGL((lse_dense_kernel<TZ, decltype(W)::value, decltype(wt)...>), dim3(dense_grid(ncell)), dim3(256), 0, s,
+                           (const TZ*)c.logits, c.labels, c.B, c.T, c.U1, c.V, c.blank, w.blk, w.emit, wt...);
+        return RNNT_OK;
+      });
+    });
+  } else {
+    const int ntiles = (int)ceil_div(c.T, TT);
+    const double cells = (double)c.B * c.T * c.U1;
+    ProfScope prof(RNNT_K_LSE, 4.0 * ((double)c.B * c.T * c.V + (double)c.B * c.U1 * c.V) + 8.0 * cells, s);
+    pick_w(windowed, win, [&](auto W, auto... wt) {
+      constexpr bool Wv = decltype(W)::value;
+      if (large_vocab(c.V))
+        hipLaunchKernelGGL((lse_sepv_kernel<Wv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSV_UT), c.B), dim3(256), 0, s, c.A,
+                           c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su, w.blk,
+                           w.emit, wt...);
+      else
+        hipLaunchKernelGGL((lse_sep_kernel<Wv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSE_UT), c.B), dim3(256), 0, s, c.A,
+                           c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su, w.blk,
+                           w.emit, wt...);
+      return RNNT_OK;
+    });
+  }
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// stage 2 of the loss: the alpha | beta sweep (it reads the masked tables of a windowed call as they are), then the NLL per row
+int stage_sweep(const LossCall& c, const LossWs& w) {
+  hipStream_t s = c.stream;
+  {
+    ProfScope prof(RNNT_K_ALPHABETA, 2.0 * (8.0 + 8.0) * (double)c.B * c.T * c.U1, s);  // read blk+emit, write alpha|beta (fp64)
+    dispatch_k(c.U1, [&](auto k) {
+      hipLaunchKernelGGL((alphabeta_kernel<decltype(k)::value>), dim3(c.B, 2), dim3(64), 0, s, w.blk, w.emit, c.t_lens, c.u_lens, c.T, c.U1,
+                         w.alpha, w.beta, w.ll);
+    });
+    RNNT_CHECK_LAUNCH();
+  }
+  const dim3 grid((unsigned)ceil_div(c.B, 64));
+  if (w.feas)
+    hipLaunchKernelGGL(nll_window_kernel, grid, dim3(64), 0, s, w.ll, w.feas, c.B, c.nll);
+  else
+    hipLaunchKernelGGL(nll_kernel, grid, dim3(64), 0, s, w.ll, c.B, c.nll);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// stage 3 of the loss, separable: dA and the per-tile dC slabs, then their fixed-order sum
+int stage_grad_sep(const LossCall& c, const LossWs& w) {
+  return pick_fe_w(c, w, [&](auto fe_t, auto w_t, float fe, auto... wt) -> int {
+    constexpr bool FE = decltype(fe_t)::value, W = decltype(w_t)::value;
+    hipStream_t s = c.stream;
+    const int T = c.T, U1 = c.U1, V = c.V, ntiles = (int)ceil_div(T, TT);
+    const double cells = (double)c.B * T * U1;
+    ProfScope prof(RNNT_K_LATGRAD, 4.0 * 2.0 * ((double)c.B * T * V + (double)c.B * U1 * V) + 24.0 * cells, s);
+    constexpr size_t LDS_MAX = 160 * 1024;
+    const size_t lds_sep = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 64 * 4 * 2 + (size_t)U1 * 4;   // 1028 (U+1): U+1 <= 159
+    // what every gradient kernel takes between its grid and the slab pitch
+#define GRAD_SEP_ARGS                                                                                                           \
+    c.A, c.C, c.bias, c.labels, c.t_lens, c.u_lens, w.blk, w.emit, w.alpha, w.beta, w.ll, T, U1, V, c.blank, (long)c.a_sb, (long)c.a_st, \
+        (long)c.c_sb, (long)c.c_su, c.gscale, c.gvec, c.gvec_stride, c.dA, w.dCp
+    // a lane per vocabulary entry, the vocabulary a grid dimension (grad_sepv_kernel): V >= 256, and every U+1 whose grad_sep_kernel
+    // table does not fit in LDS (any V)
+    if (large_vocab(V) || lds_sep > LDS_MAX) {
+      constexpr int NW = 4;   // 256 vocabulary entries per workgroup (8 waves per workgroup measured slower: 5.2 vs 4.6 ms at config 5)
+      const dim3 grid(ntiles, (unsigned)ceil_div(V, 64 * NW), c.B), block(64 * NW);
+      const size_t per_row = (size_t)TT * sizeof(CellS);
+      const size_t lds = (size_t)U1 * per_row + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
+      if (lds <= LDS_MAX) {
+        if (lds > 64 * 1024)
+          RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE, W, decltype(wt)...>), grid, block, lds, s, GRAD_SEP_ARGS, U1, fe, wt...);
+      } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
+        const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
+        const int nchunks = (int)ceil_div(U1, ul_max);
+        const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
+        const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+        hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE, W, decltype(wt)...>), grid, block, lds_c, s, GRAD_SEP_ARGS, ul, fe, wt...);
+      }
+    } else {
+      if (lds_sep > 64 * 1024)
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
+      hipLaunchKernelGGL((grad_sep_kernel<FE, W, decltype(wt)...>), dim3(ntiles, c.B), dim3(256), lds_sep, s, GRAD_SEP_ARGS, fe, wt...);
+    }
+#undef GRAD_SEP_ARGS
+    RNNT_CHECK_LAUNCH();
+    const long per_b = (long)U1 * V;
+    hipLaunchKernelGGL(reduce_dc_kernel, dim3((unsigned)ceil_div(per_b, 256), c.B), dim3(256), 0, s, w.dCp, ntiles, per_b, V, (long)c.c_sb,
+                       (long)c.c_su, c.gscale, c.gvec, c.gvec_stride, c.dC);
+    RNNT_CHECK_LAUNCH();
+    return RNNT_OK;
+  });
+}
+
+// stage 3 of the loss: the lattice gradient under the call's <FE, W> instance -- the separable dA / dC above, or dense d/d logits
+int stage_grad(const LossCall& c, const LossWs& w) {
+  if (!c.dense) return stage_grad_sep(c, w);
+  return dispatch_dtype(c.dtype, c.who, [&](auto tz) -> int {
+    using TZ = typename decltype(tz)::type;
+    hipStream_t s = c.stream;
+    const long ncell = (long)c.B * c.T * c.U1;
+    ProfScope prof(RNNT_K_LATGRAD, 2.0 * sizeof(TZ) * (double)ncell * c.V + 24.0 * (double)ncell, s);
+    pick_fe_w(c, w, [&](auto fe, auto win, float lam, auto... wt) {
+      hipLaunchKernelGGL((grad_dense_kernel<TZ, decltype(fe)::value, decltype(win)::value, decltype(wt)...>), dim3(dense_grid(ncell)), dim3(256),
+                         0, s, (const TZ*)c.logits, c.labels, c.t_lens, c.u_lens, w.blk, w.emit, w.alpha, w.beta, w.ll, c.B, c.T, c.U1, c.V,
+                         c.blank, c.gscale, (TZ*)c.grad, lam, wt...);
+      return RNNT_OK;
+    });
+    RNNT_CHECK_LAUNCH();
+    return RNNT_OK;
+  });
+}
+
+// stage 2 of the alignment: the max-plus sweep (one back-pointer bit per cell), then the back-trace
+int stage_viterbi(const LossCall& c, const LossWs& w) {
+  hipStream_t s = c.stream;
   // one scope over BOTH launches (sweep: read blk + emit, write one bit per cell; back-trace: read the bits back), booked under the
   // lattice-sweep kind of the loss: the profiler's kinds are part of the ABI (rnnt_hip_prof_collect), which this feature leaves as it
   // is, so a process that trains and aligns sees both sweeps summed in that slot
-  ProfScope prof(RNNT_K_ALPHABETA, (8.0 + 0.25) * (double)B * T * U1, s);
-  dim3 grid(B), block(64);
-#define VT(KK) hipLaunchKernelGGL((viterbi_kernel<KK>), grid, block, 0, s, w.blk, w.emit, t_lens, u_lens, T, U1, w.nw, w.bp, score)
-  switch (K) {
-    case 1: VT(1); break;
-    case 2: VT(2); break;
-    case 3: VT(3); break;
-    case 4: VT(4); break;
-    default: VT(8); break;
-  }
-#undef VT
+  ProfScope prof(RNNT_K_ALPHABETA, (8.0 + 0.25) * (double)c.B * c.T * c.U1, s);
+  dispatch_k(c.U1, [&](auto k) {
+    hipLaunchKernelGGL((viterbi_kernel<decltype(k)::value>), dim3(c.B), dim3(64), 0, s, w.blk, w.emit, c.t_lens, c.u_lens, c.T, c.U1, w.nw,
+                       w.bp, c.score);
+  });
   RNNT_CHECK_LAUNCH();
   constexpr size_t LDS_MAX = 160 * 1024;
-  const size_t lds = (size_t)U1 * w.nw * 4;   // U+1 = 512 label rows by T = 2560 frames fit
+  const size_t lds = (size_t)c.U1 * w.nw * 4;   // U+1 = 512 label rows by T = 2560 frames fit
   const int in_lds = lds <= LDS_MAX;
   if (in_lds && lds > 64 * 1024)
     RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)backtrace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(backtrace_kernel, grid, dim3(256), in_lds ? lds : 0, s, w.bp, t_lens, u_lens, T, U1, w.nw, in_lds, frames);
+  hipLaunchKernelGGL(backtrace_kernel, dim3(c.B), dim3(256), in_lds ? lds : 0, s, w.bp, c.t_lens, c.u_lens, c.T, c.U1, w.nw, in_lds, c.frames);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
+}
+
+// ---- the drivers ----
+int run_loss(const LossCall& c) {   // forward; the backward too when the call has somewhere to put it
+  LossWs w;
+  if (int rc = check_call(c, Drive::Forward, &w)) return rc;
+  if (int rc = stage_lse(c, w)) return rc;
+  if (int rc = stage_sweep(c, w)) return rc;
+  return (c.dense ? c.grad != nullptr : c.dA != nullptr) ? stage_grad(c, w) : RNNT_OK;
+}
+
+// the second half of a forward call made without gradients: the workspace still holds blk / emit / alpha / beta / logZ (and the band
+// tables of a windowed call) of that call on the SAME operands, labels, lengths and windows
+int run_loss_bwd(const LossCall& c) {
+  LossWs w;
+  if (int rc = check_call(c, Drive::Backward, &w)) return rc;
+  return stage_grad(c, w);
+}
+
+int run_align(const LossCall& c) {
+  LossWs w;
+  if (int rc = check_call(c, Drive::Align, &w)) return rc;
+  if (int rc = stage_lse(c, w)) return rc;
+  return stage_viterbi(c, w);
 }
 
 }  // namespace
@@ -1193,113 +1418,22 @@ int launch_viterbi(const AlignWs& w, const int* t_lens, const int* u_lens, int B
 
 using namespace rnnt;
 
-// vocabularies from 256 entries take the lane-per-entry kernels (lse_sepv_kernel, grad_sepv_kernel); RNNT_LOSS_SMALLV_KERNELS=1 keeps
-// the round-1 kernels everywhere, RNNT_LOSS_LARGEV_KERNELS=1 takes the new ones for every V (A/B and tests)
-static bool large_vocab(int V) {
-  if (getenv("RNNT_LOSS_SMALLV_KERNELS")) return false;
-  return V >= 256 || getenv("RNNT_LOSS_LARGEV_KERNELS") != nullptr;
-}
-
-// blk / emit of every lattice cell from the separable operands (the loss and the alignment share it)
-static int launch_lse_sep(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su, const float* bias,
-                          const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float* blk, float* emit,
-                          hipStream_t s, const Win* win = nullptr) {
-  const int ntiles = (int)ceil_div(T, TT);
-  const double cells = (double)B * T * U1;
-  {
-  ProfScope prof(RNNT_K_LSE, 4.0 * ((double)B * T * V + (double)B * U1 * V) + 8.0 * cells, s);
-  const dim3 gv(ntiles, (unsigned)ceil_div(U1, LSV_UT), B), gs(ntiles, (unsigned)ceil_div(U1, LSE_UT), B);
-  // win: emission windows, the W = true instances; without, the kernels as they are without that feature
-  if (large_vocab(V)) {
-    if (win)
-      hipLaunchKernelGGL((lse_sepv_kernel<true, Win>), gv, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
-                         (long)c_sb, (long)c_su, blk, emit, *win);
-    else
-      hipLaunchKernelGGL(lse_sepv_kernel<false>, gv, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
-                         (long)c_sb, (long)c_su, blk, emit);
-  } else {
-    if (win)
-      hipLaunchKernelGGL((lse_sep_kernel<true, Win>), gs, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
-                         (long)c_sb, (long)c_su, blk, emit, *win);
-    else
-      hipLaunchKernelGGL(lse_sep_kernel<false>, gs, dim3(256), 0, s, A, C, bias, labels, T, U1, V, blank, (long)a_sb, (long)a_st,
-                         (long)c_sb, (long)c_su, blk, emit);
-  }
-  }
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-// FastEmit's lambda is an argument of the backward only: finite and >= 0 (checked before any device work, like every argument)
-static int check_fastemit(float lambda, const char* who) {
-  RNNT_CHECK_ARG(lambda >= 0.f && lambda <= 3.4028234664e38f, "%s: fastemit_lambda must be finite and >= 0 (got %g)", who, (double)lambda);
-  return RNNT_OK;
-}
-
-// fe = 0 launches the FE = false instances (the kernels as they are without FastEmit), fe > 0 the FE = true ones; W with the band
-// tables of the windowed entries (wt: one Band for W = true, nothing for W = false)
-template <bool FE, bool W, typename... WT>
-static int launch_grad_sep_fe(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
-                           const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
-                           int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
-                           float* dC, float fe, hipStream_t s, WT... wt) {
-  const int ntiles = (int)ceil_div(T, TT);
-  const double cells = (double)B * T * U1;
-  ProfScope prof(RNNT_K_LATGRAD, 4.0 * 2.0 * ((double)B * T * V + (double)B * U1 * V) + 24.0 * cells, s);
-  constexpr size_t LDS_MAX = 160 * 1024;
-  const size_t lds_sep = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 64 * 4 * 2 + (size_t)U1 * 4;   // 1028 (U+1): U+1 <= 159
-  // a lane per vocabulary entry, the vocabulary a grid dimension (grad_sepv_kernel): V >= 256, and every U+1 whose grad_sep_kernel
-  // table does not fit in LDS (any V)
-  if (large_vocab(V) || lds_sep > LDS_MAX) {
-    constexpr int NW = 4;   // 256 vocabulary entries per workgroup (8 waves per workgroup measured slower: 5.2 vs 4.6 ms at config 5)
-    const dim3 grid(ntiles, (unsigned)ceil_div(V, 64 * NW), B), block(64 * NW);
-    const size_t lds = (size_t)TT * U1 * sizeof(CellS) + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
-    if (lds <= LDS_MAX) {
-      if (lds > 64 * 1024)
-        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE, W, WT...>), grid, block, lds, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
-                         w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, U1, fe, wt...);
-    } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
-      const size_t per_row = (size_t)TT * sizeof(CellS);
-      const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
-      const int nchunks = (int)ceil_div(U1, ul_max);
-      const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
-      const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-      hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE, W, WT...>), grid, block, lds_c, s, A, C, bias, labels, t_lens, u_lens, w.blk, w.emit, w.alpha,
-                         w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA,
-                         w.dCp, ul, fe, wt...);
-    }
-  } else {
-    if (lds_sep > 64 * 1024)
-      RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE, W, WT...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
-    hipLaunchKernelGGL((grad_sep_kernel<FE, W, WT...>), dim3(ntiles, B), dim3(256), lds_sep, s, A, C, bias, labels, t_lens, u_lens, w.blk,
-                       w.emit, w.alpha, w.beta, w.ll, T, U1, V, blank, (long)a_sb, (long)a_st, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dA, w.dCp, fe, wt...);
-  }
-  RNNT_CHECK_LAUNCH();
-  const long per_b = (long)U1 * V;
-  hipLaunchKernelGGL(reduce_dc_kernel, dim3((unsigned)ceil_div(per_b, 256), B), dim3(256), 0, s, w.dCp, ntiles, per_b,
-                     V, (long)c_sb, (long)c_su, gscale, gvec, gvec_stride, dC);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-static int launch_grad_sep(const LossWs& w, const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
-                           const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
-                           int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, const float* gvec, int gvec_stride, float* dA,
-                           float* dC, float fe, hipStream_t s, const int* wL = nullptr, const int* wR = nullptr) {
-#define GS(FE, W, LAM, ...)                                                                                                  \
-  launch_grad_sep_fe<FE, W>(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, \
-                            gvec_stride, dA, dC, LAM, s, ##__VA_ARGS__)
-  if (wL) return fe != 0.f ? GS(true, true, fe, Band{wL, wR}) : GS(false, true, 0.f, Band{wL, wR});
-  return fe != 0.f ? GS(true, false, fe) : GS(false, false, 0.f);
-#undef GS
-}
+// ---- the exported entries: each fills a LossCall from its positional arguments (the names below are the parameters') ----
+#define FILL_COMMON(c, WHO)                                                                                                  \
+  LossCall c;                                                                                                                \
+  c.who = WHO, c.labels = labels, c.t_lens = t_lens, c.u_lens = u_lens, c.B = B, c.T = T, c.U1 = U1, c.V = V, c.blank = blank; \
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream
+#define FILL_SEP(c, WHO) \
+  FILL_COMMON(c, WHO);   \
+  c.A = A, c.a_sb = a_sb, c.a_st = a_st, c.C = C, c.c_sb = c_sb, c.c_su = c_su, c.bias = bias
+#define FILL_DENSE(c, WHO) \
+  FILL_COMMON(c, WHO);     \
+  c.dense = true, c.logits = logits, c.dtype = dtype
+#define FILL_WINDOWS(c) c.windowed = true, c.emit_lo = emit_lo, c.emit_hi = emit_hi, c.win_stride = win_stride
 
 extern "C" size_t rnnt_hip_joint_loss_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
   if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
-  return carve(nullptr, B, T, U1, V, true).total;
+  return carve(nullptr, B, T, U1, V, false).total;
 }
 
 extern "C" int rnnt_hip_joint_loss_fwd_bwd_fastemit(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
@@ -1308,21 +1442,9 @@ extern "C" int rnnt_hip_joint_loss_fwd_bwd_fastemit(const float* A, int64_t a_sb
                                                     int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
                                                     float* nll, float* dA, float* dC, void* workspace, size_t workspace_bytes,
                                                     void* stream) {
-  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
-  if (int rc = check_fastemit(fastemit_lambda, "joint_loss")) return rc;
-  RNNT_CHECK_ARG(A && C && bias, "joint_loss: null A/C/bias");
-  RNNT_CHECK_ARG((dA == nullptr) == (dC == nullptr), "joint_loss: dA and dC must both be given or both be NULL");
-  const LossWs w = carve(workspace, B, T, U1, V, true);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_loss: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
-  if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
-  hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
-  RNNT_CHECK_LAUNCH();
-  if (dA)
-    return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nullptr, 0, dA, dC,
-                           fastemit_lambda, s);
-  return RNNT_OK;
+  FILL_SEP(c, "joint_loss");
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.nll = nll, c.dA = dA, c.dC = dC;
+  return run_loss(c);
 }
 
 extern "C" int rnnt_hip_joint_loss_fwd_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
@@ -1339,18 +1461,9 @@ extern "C" int rnnt_hip_joint_loss_bwd_fastemit(const float* A, int64_t a_sb, in
                                                 const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
                                                 float gscale, float fastemit_lambda, const float* gvec, int32_t gvec_stride,
                                                 float* dA, float* dC, void* workspace, size_t workspace_bytes, void* stream) {
-  // second half of rnnt_hip_joint_loss_fwd_bwd: the workspace still holds blk / emit / alpha / beta / logZ of a forward call
-  // (dA = dC = NULL) on the SAME A, C, bias, labels, lengths
-  RNNT_CHECK_ARG(labels && t_lens && u_lens && B >= 1 && T >= 1 && U1 >= 1 && V >= 2 && blank >= 0 && blank < V,
-                 "joint_loss_bwd: bad dims / null pointer");
-  RNNT_CHECK_ARG(A && C && bias && dA && dC, "joint_loss_bwd: null A/C/bias/dA/dC");
-  RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "joint_loss_bwd: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
-  RNNT_CHECK_ARG(U1 <= 64 * 8, "joint_loss_bwd: U+1 = %d exceeds the 512 label positions of the forward", U1);
-  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_bwd")) return rc;
-  const LossWs w = carve(workspace, B, T, U1, V, true);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_loss_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  return launch_grad_sep(w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, gvec_stride, dA,
-                         dC, fastemit_lambda, (hipStream_t)stream);
+  FILL_SEP(c, "joint_loss_bwd");
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.gvec = gvec, c.gvec_stride = gvec_stride, c.dA = dA, c.dC = dC;
+  return run_loss_bwd(c);
 }
 
 extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
@@ -1365,7 +1478,7 @@ extern "C" int rnnt_hip_joint_loss_bwd(const float* A, int64_t a_sb, int64_t a_s
 /* ---- emission windows (include/rnnt_hip.h): the entries above with the band tables and the W = true kernel instances ---- */
 extern "C" size_t rnnt_hip_joint_loss_window_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
   if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
-  return carve_window(nullptr, B, T, U1, V).total;
+  return carve(nullptr, B, T, U1, V, true).total;
 }
 
 extern "C" int rnnt_hip_joint_loss_fwd_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb,
@@ -1374,24 +1487,10 @@ extern "C" int rnnt_hip_joint_loss_fwd_bwd_window(const float* A, int64_t a_sb, 
                                                   float gscale, float fastemit_lambda, const int32_t* emit_lo,
                                                   const int32_t* emit_hi, int64_t win_stride, float* nll, float* dA, float* dC,
                                                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
-  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_window")) return rc;
-  if (int rc = check_window(emit_lo, emit_hi, win_stride, U1, "joint_loss_window")) return rc;
-  RNNT_CHECK_ARG(A && C && bias, "joint_loss_window: null A/C/bias");
-  RNNT_CHECK_ARG((dA == nullptr) == (dC == nullptr), "joint_loss_window: dA and dC must both be given or both be NULL");
-  const WinWs x = carve_window(workspace, B, T, U1, V);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= x.total, "joint_loss_window: workspace too small (%zu < %zu)", workspace_bytes, x.total);
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = launch_band(x, emit_lo, emit_hi, win_stride, t_lens, u_lens, B, T, U1, s)) return rc;
-  const Win win = {x.L, x.R, emit_lo, emit_hi, u_lens, (long)win_stride};
-  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, x.w.blk, x.w.emit, s, &win)) return rc;
-  if (int rc = launch_alphabeta(x.w, t_lens, u_lens, B, T, U1, s)) return rc;   // the sweep as it is: it reads the masked tables
-  hipLaunchKernelGGL(nll_window_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, x.w.ll, x.feas, B, nll);
-  RNNT_CHECK_LAUNCH();
-  if (dA)
-    return launch_grad_sep(x.w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, nullptr, 0, dA,
-                           dC, fastemit_lambda, s, x.L, x.R);
-  return RNNT_OK;
+  FILL_SEP(c, "joint_loss_window");
+  FILL_WINDOWS(c);
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.nll = nll, c.dA = dA, c.dC = dC;
+  return run_loss(c);
 }
 
 extern "C" int rnnt_hip_joint_loss_bwd_window(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
@@ -1399,18 +1498,10 @@ extern "C" int rnnt_hip_joint_loss_bwd_window(const float* A, int64_t a_sb, int6
                                               int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
                                               float fastemit_lambda, const float* gvec, int32_t gvec_stride, float* dA, float* dC,
                                               void* workspace, size_t workspace_bytes, void* stream) {
-  // second half of rnnt_hip_joint_loss_fwd_bwd_window: the workspace still holds the band tables and blk / emit / alpha / beta / logZ
-  // of a forward call (dA = dC = NULL) on the SAME operands and windows
-  RNNT_CHECK_ARG(labels && t_lens && u_lens && B >= 1 && T >= 1 && U1 >= 1 && V >= 2 && blank >= 0 && blank < V,
-                 "joint_loss_bwd_window: bad dims / null pointer");
-  RNNT_CHECK_ARG(A && C && bias && dA && dC, "joint_loss_bwd_window: null A/C/bias/dA/dC");
-  RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "joint_loss_bwd_window: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
-  RNNT_CHECK_ARG(U1 <= 64 * 8, "joint_loss_bwd_window: U+1 = %d exceeds the 512 label positions of the forward", U1);
-  if (int rc = check_fastemit(fastemit_lambda, "joint_loss_bwd_window")) return rc;
-  const WinWs x = carve_window(workspace, B, T, U1, V);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= x.total, "joint_loss_bwd_window: workspace too small (%zu < %zu)", workspace_bytes, x.total);
-  return launch_grad_sep(x.w, A, a_sb, a_st, C, c_sb, c_su, bias, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, gvec, gvec_stride,
-                         dA, dC, fastemit_lambda, (hipStream_t)stream, x.L, x.R);
+  FILL_SEP(c, "joint_loss_bwd_window");
+  c.windowed = true;
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.gvec = gvec, c.gvec_stride = gvec_stride, c.dA = dA, c.dC = dC;
+  return run_loss_bwd(c);
 }
 
 extern "C" int rnnt_hip_scaled_sum_f32(const float* x, int32_t n, float scale, float* out, void* stream) {
@@ -1433,91 +1524,15 @@ extern "C" int rnnt_hip_joint_logits_fwd(const float* A, int64_t a_sb, int64_t a
   return RNNT_OK;
 }
 
-// blk / emit of every lattice cell from dense logits in fp32 / f16 / bf16 storage (the loss and the alignment share it)
-static unsigned dense_grid(long ncell) { return (unsigned)(ceil_div(ncell, 4) < 16384 ? ceil_div(ncell, 4) : 16384); }
-
-template <typename TZ>
-static int launch_lse_dense(const void* logits, const int32_t* labels, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
-                            float* blk, float* emit, hipStream_t s, const Win* win = nullptr) {
-  const long ncell = (long)B * T * U1;
-  {
-  ProfScope prof(RNNT_K_LSE, (double)sizeof(TZ) * (double)ncell * V + 8.0 * (double)ncell, s);
-  if (win)
-    hipLaunchKernelGGL((lse_dense_kernel<TZ, true, Win>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V,
-                       blank, blk, emit, *win);
-  else
-    hipLaunchKernelGGL((lse_dense_kernel<TZ, false>), dim3(dense_grid(ncell)), dim3(256), 0, s, (const TZ*)logits, labels, B, T, U1, V,
-                       blank, blk, emit);
-  }
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
-}
-
-template <typename TZ>
-static int loss_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
-                                 int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fe,
-                                 float* nll, void* grad, void* workspace, size_t workspace_bytes, void* stream,
-                                 bool windowed = false, const int32_t* emit_lo = nullptr, const int32_t* emit_hi = nullptr,
-                                 int64_t win_stride = 0) {
-  if (int rc = check_common(labels, t_lens, u_lens, B, T, U1, V, blank, nll)) return rc;
-  if (int rc = check_fastemit(fe, "loss_from_logits")) return rc;
-  if (windowed)
-    if (int rc = check_window(emit_lo, emit_hi, win_stride, U1, "loss_from_logits_window")) return rc;
-  RNNT_CHECK_ARG(logits, "loss_from_logits: null logits");
-  // windowed: the plain workspace plus the band tables, and the W = true kernel instances (the sweep is the same)
-  const WinWs x = windowed ? carve_window(workspace, B, T, U1, V) : WinWs{carve(workspace, B, T, U1, V, true), nullptr, nullptr, nullptr, 0};
-  const LossWs& w = x.w;
-  const size_t need = windowed ? x.total : w.total;
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= need, "loss_from_logits: workspace too small (%zu < %zu)", workspace_bytes, need);
-  hipStream_t s = (hipStream_t)stream;
-  const long ncell = (long)B * T * U1;
-  const unsigned grid = dense_grid(ncell);
-  const Win win = {x.L, x.R, emit_lo, emit_hi, u_lens, (long)win_stride};
-  if (windowed)
-    if (int rc = launch_band(x, emit_lo, emit_hi, win_stride, t_lens, u_lens, B, T, U1, s)) return rc;
-  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s, windowed ? &win : nullptr)) return rc;
-  if (int rc = launch_alphabeta(w, t_lens, u_lens, B, T, U1, s)) return rc;
-  if (windowed)
-    hipLaunchKernelGGL(nll_window_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, x.feas, B, nll);
-  else
-    hipLaunchKernelGGL(nll_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, s, w.ll, B, nll);
-  RNNT_CHECK_LAUNCH();
-  if (grad) {
-    ProfScope prof(RNNT_K_LATGRAD, 2.0 * sizeof(TZ) * (double)ncell * V + 24.0 * (double)ncell, s);
-#define GD(KERNEL, LAM, ...)                                                                                                       \
-  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, s, (const TZ*)logits, labels, t_lens, u_lens, w.blk, w.emit, w.alpha, w.beta, \
-                     w.ll, B, T, U1, V, blank, gscale, (TZ*)grad, LAM, ##__VA_ARGS__)
-    const Band band = {x.L, x.R};
-    if (windowed) {
-      if (fe != 0.f) GD((grad_dense_kernel<TZ, true, true, Band>), fe, band); else GD((grad_dense_kernel<TZ, false, true, Band>), 0.f, band);
-    } else {
-      if (fe != 0.f) GD((grad_dense_kernel<TZ, true, false>), fe); else GD((grad_dense_kernel<TZ, false, false>), 0.f);
-    }
-#undef GD
-    RNNT_CHECK_LAUNCH();
-  }
-  return RNNT_OK;
-}
-
+/* ---- the loss on dense logits in fp32 / f16 / bf16 storage ---- */
 extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_fastemit(const void* logits, int32_t dtype, const int32_t* labels,
                                                           const int32_t* t_lens, const int32_t* u_lens, int32_t B, int32_t T,
                                                           int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
                                                           float* nll, void* grad, void* workspace, size_t workspace_bytes,
                                                           void* stream) {
-  switch (dtype) {
-    case RNNT_DTYPE_F32:
-      return loss_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream);
-    case RNNT_DTYPE_F16:
-      return loss_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream);
-    case RNNT_DTYPE_BF16:
-      return loss_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream);
-    default:
-      set_error("loss_from_logits: unknown dtype code %d", dtype);
-      return RNNT_ERR_INVALID;
-  }
+  FILL_DENSE(c, "loss_from_logits");
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.nll = nll, c.grad = grad;
+  return run_loss(c);
 }
 
 extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_window(const void* logits, int32_t dtype, const int32_t* labels,
@@ -1526,20 +1541,10 @@ extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_window(const void* logits, int3
                                                         const int32_t* emit_lo, const int32_t* emit_hi, int64_t win_stride,
                                                         float* nll, void* grad, void* workspace, size_t workspace_bytes,
                                                         void* stream) {
-  switch (dtype) {
-    case RNNT_DTYPE_F32:
-      return loss_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
-    case RNNT_DTYPE_F16:
-      return loss_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
-    case RNNT_DTYPE_BF16:
-      return loss_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, gscale, fastemit_lambda, nll, grad, workspace,
-                                          workspace_bytes, stream, true, emit_lo, emit_hi, win_stride);
-    default:
-      set_error("loss_from_logits_window: unknown dtype code %d", dtype);
-      return RNNT_ERR_INVALID;
-  }
+  FILL_DENSE(c, "loss_from_logits_window");
+  FILL_WINDOWS(c);
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.nll = nll, c.grad = grad;
+  return run_loss(c);
 }
 
 extern "C" int rnnt_hip_loss_from_logits_fwd_bwd_ex(const void* logits, int32_t dtype, const int32_t* labels,
@@ -1568,40 +1573,16 @@ extern "C" int rnnt_hip_joint_align(const float* A, int64_t a_sb, int64_t a_st, 
                                     const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
                                     int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, int32_t* frames, double* score,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_align(labels, t_lens, u_lens, B, T, U1, V, blank, frames, score)) return rc;
-  RNNT_CHECK_ARG(A && C && bias, "joint_align: null A/C/bias");
-  const AlignWs w = carve_align(workspace, B, T, U1);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "joint_align: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = launch_lse_sep(A, a_sb, a_st, C, c_sb, c_su, bias, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
-  return launch_viterbi(w, t_lens, u_lens, B, T, U1, frames, score, s);
-}
-
-template <typename TZ>
-static int align_from_logits_impl(const void* logits, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
-                                  int32_t T, int32_t U1, int32_t V, int32_t blank, int32_t* frames, double* score, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  if (int rc = check_align(labels, t_lens, u_lens, B, T, U1, V, blank, frames, score)) return rc;
-  RNNT_CHECK_ARG(logits, "align_from_logits: null logits");
-  const AlignWs w = carve_align(workspace, B, T, U1);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "align_from_logits: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = launch_lse_dense<TZ>(logits, labels, B, T, U1, V, blank, w.blk, w.emit, s)) return rc;
-  return launch_viterbi(w, t_lens, u_lens, B, T, U1, frames, score, s);
+  FILL_SEP(c, "joint_align");
+  c.frames = frames, c.score = score;
+  return run_align(c);
 }
 
 extern "C" int rnnt_hip_align_from_logits_ex(const void* logits, int32_t dtype, const int32_t* labels, const int32_t* t_lens,
                                              const int32_t* u_lens, int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank,
                                              int32_t* frames, double* score, void* workspace, size_t workspace_bytes, void* stream) {
-  switch (dtype) {
-    case RNNT_DTYPE_F32:
-      return align_from_logits_impl<float>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
-    case RNNT_DTYPE_F16:
-      return align_from_logits_impl<__half>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
-    case RNNT_DTYPE_BF16:
-      return align_from_logits_impl<__hip_bfloat16>(logits, labels, t_lens, u_lens, B, T, U1, V, blank, frames, score, workspace, workspace_bytes, stream);
-    default:
-      set_error("align_from_logits: unknown dtype code %d", dtype);
-      return RNNT_ERR_INVALID;
-  }
+  FILL_DENSE(c, "align_from_logits");
+  c.frames = frames, c.score = score;
+  return run_align(c);
 }
+

@@ -844,6 +844,62 @@ def emit_windows(frames, t_lens, u_lens, left: int, right: int):
     return fr - left, fr + right
 
 
+_LOGITS_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # RNNT_DTYPE_* of include/rnnt_hip.h
+
+
+def _logits_dtype_code(logits: torch.Tensor) -> int:
+    if logits.dtype not in _LOGITS_DTYPE_CODE:
+        raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    return _LOGITS_DTYPE_CODE[logits.dtype]
+
+
+def _i32(named, note: str = "") -> None:
+    """ValueError unless every tensor of the (name, tensor) pairs is int32."""
+    for name, t in named:
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32{note}, got {t.dtype}")
+
+
+def _loss_forward(entry: str, operands, B: int, T: int, U1: int, V: int, blank: int, win, lam: float, grads, device):
+    """One call of the library's loss with its workspace: the query, the allocation, the call.  entry + operands: the separable
+    "rnnt_hip_joint_loss_fwd_bwd" with _sep_operands(...), or the dense "rnnt_hip_loss_from_logits_fwd_bwd" with (logits, dtype
+    code, labels, t_lens, u_lens) -- its _fastemit form, or with win (check_emit_windows' triple, not None) its _window form and
+    the larger workspace.  grads: the entry's gradient pointers -- (None, None) for the separable forward, whose backward is
+    _sep_loss_backward on the workspace; (d/d logits or None,) for the dense one.  -> (nll (B,), workspace)."""
+    L = _lib.lib()
+    name = entry + ("_fastemit" if win is None else "_window")
+    nws = (L.rnnt_hip_joint_loss_workspace_bytes if win is None else L.rnnt_hip_joint_loss_window_workspace_bytes)(B, T, U1, V)
+    ws = torch.empty(nws, device=device, dtype=torch.uint8)
+    nll = torch.empty(B, device=device, dtype=torch.float32)
+    windows = () if win is None else (_addr(win[0]), _addr(win[1]), win[2])
+    check(getattr(L, name)(*operands, B, T, U1, V, int(blank), 1.0, lam, *windows, _addr(nll), *grads, _addr(ws), nws, _stream()), name)
+    return nll, ws
+
+
+def _sep_loss_forward(A, Cm, bias, labels, t_lens, u_lens, blank: int, win, lam: float):
+    """Forward of the separable loss on A (T,B,V), Cm (U1,B,V) time-major, without gradients -> (nll (B,), workspace)."""
+    (T, B, V), U1 = A.shape, Cm.shape[0]
+    return _loss_forward("rnnt_hip_joint_loss_fwd_bwd", _sep_operands(A, Cm, bias, labels, t_lens, u_lens), B, T, U1, V, blank, win, lam,
+                         (None, None), A.device)
+
+
+def _sep_operands(A, Cm, bias, labels, t_lens, u_lens):
+    """The separable operand block of the library's loss entries for A (T,B,V), Cm (U1,B,V) time-major."""
+    B, V = A.shape[1:]
+    return (_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(t_lens), _addr(u_lens))
+
+
+def _sep_loss_backward(A, Cm, bias, labels, t_lens, u_lens, blank: int, windowed: bool, lam: float, gscale: float, gvec, gvec_stride: int,
+                       ws):
+    """dA, dC of the loss whose forward (_loss_forward on the same operands) left `ws`, under the upstream gradient gvec."""
+    (T, B, V), U1 = A.shape, Cm.shape[0]
+    dA, dC = torch.empty_like(A), torch.empty_like(Cm)
+    name = "rnnt_hip_joint_loss_bwd_window" if windowed else "rnnt_hip_joint_loss_bwd_fastemit"
+    check(getattr(_lib.lib(), name)(*_sep_operands(A, Cm, bias, labels, t_lens, u_lens), B, T, U1, V, blank, gscale, lam, _addr(gvec),
+                                    gvec_stride, _addr(dA), _addr(dC), _addr(ws), ws.numel(), _stream()), name)
+    return dA, dC
+
+
 class JointLossFn(torch.autograd.Function):
     """enc (T,B,Oe), dec (U1,B,Od) time-major -> per-utterance NLL (B,).  Never builds (B,T,U1,V).
     forward: A/C pre-GEMMs + log-softmax terms + alpha/beta (kept in a workspace); backward: the lattice gradient kernel with
@@ -867,9 +923,7 @@ class JointLossFn(torch.autograd.Function):
         win = check_emit_windows(emit_windows, enc.shape[1], dec.shape[0] - 1, enc.device)
         w_param, b_param = W, bias
         enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
-        for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name} must be int32 (dataloader.py:21-24), got {t.dtype}")
+        _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)), " (dataloader.py:21-24)")
         labels = labels.contiguous()
         T, B, Oe = enc.shape
         U1, B2, Od = dec.shape
@@ -878,22 +932,7 @@ class JointLossFn(torch.autograd.Function):
             raise ValueError(f"shape mismatch: enc {tuple(enc.shape)} dec {tuple(dec.shape)} fc {tuple(W.shape)} "
                              f"targets {tuple(labels.shape)}")
         A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
-        nll = torch.empty(B, device=enc.device, dtype=torch.float32)
-        if win is None:
-            nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
-            ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
-            check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
-                                                         _addr(t_lens), _addr(u_lens), B, T, U1, V, int(blank), 1.0,
-                                                         _addr(nll), None, None, _addr(ws), nws, _stream()),
-                  "rnnt_hip_joint_loss_fwd_bwd")
-        else:
-            nws = _lib.lib().rnnt_hip_joint_loss_window_workspace_bytes(B, T, U1, V)
-            ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
-            check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd_window(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels),
-                                                                _addr(t_lens), _addr(u_lens), B, T, U1, V, int(blank), 1.0,
-                                                                ctx.fastemit_lambda, _addr(win[0]), _addr(win[1]), win[2],
-                                                                _addr(nll), None, None, _addr(ws), nws, _stream()),
-                  "rnnt_hip_joint_loss_fwd_bwd_window")
+        nll, ws = _sep_loss_forward(A, Cm, bias, labels, t_lens, u_lens, blank, win, ctx.fastemit_lambda)
         ctx.windowed = win is not None   # the backward reads the band tables the forward left in the workspace
         keep = want_grad and any(ctx.needs_input_grad[:4])  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
         ilm, lse = _ilm_forward(Cm, bias, labels, u_lens, blank, keep) if ctx.ilmt else (None, None)
@@ -909,17 +948,10 @@ class JointLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, g_ilm=None):
         enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws = ctx.saved_tensors[:10]
-        T, B, _ = enc.shape
-        U1, V = dec.shape[0], W.shape[0]
         gvec = _f32c(g.to(torch.float32), "grad of the loss")
         scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
-        dA, dC = torch.empty_like(A), torch.empty_like(Cm)
-        L = _lib.lib()
-        bwd, what = ((L.rnnt_hip_joint_loss_bwd_window, "rnnt_hip_joint_loss_bwd_window") if ctx.windowed else
-                     (L.rnnt_hip_joint_loss_bwd_fastemit, "rnnt_hip_joint_loss_bwd_fastemit"))
-        check(bwd(_addr(A), V, B * V, _addr(Cm), V, B * V, _addr(bias), _addr(labels), _addr(t_lens), _addr(u_lens), B, T, U1, V,
-                  ctx.blank, ctx.red_scale if scalar else 1.0, ctx.fastemit_lambda, _addr(gvec), 0 if scalar else 1, _addr(dA),
-                  _addr(dC), _addr(ws), ws.numel(), _stream()), what)
+        dA, dC = _sep_loss_backward(A, Cm, bias, labels, t_lens, u_lens, ctx.blank, ctx.windowed, ctx.fastemit_lambda,
+                                    ctx.red_scale if scalar else 1.0, gvec, 0 if scalar else 1, ws)
         if ctx.ilmt:   # the internal-LM term's gradient lands in the dC the lattice kernel has just written; db then comes from dC
             _ilm_backward(Cm, bias, labels, u_lens, ctx.saved_tensors[10], ctx.blank, g_ilm, ctx.red_scale, True, dC)
         d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
@@ -943,9 +975,7 @@ class JointLossGroupedFn(torch.autograd.Function):
         _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
         w_param, b_param = W, bias
         enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
-        for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name} must be int32 (dataloader.py:21-24), got {t.dtype}")
+        _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)), " (dataloader.py:21-24)")
         labels = labels.contiguous()
         T, B, Oe = enc.shape
         U1, R, Od = dec.shape
@@ -957,13 +987,7 @@ class JointLossGroupedFn(torch.autograd.Function):
         rows = torch.arange(R, device=enc.device, dtype=torch.int64) // group
         Ax = A.index_select(1, rows)   # (T, B*group, V): the gather
         del A
-        nll = torch.empty(R, device=enc.device, dtype=torch.float32)
-        nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(R, T, U1, V)
-        ws = torch.empty(nws, device=enc.device, dtype=torch.uint8)
-        check(_lib.lib().rnnt_hip_joint_loss_fwd_bwd(_addr(Ax), V, R * V, _addr(Cm), V, R * V, _addr(bias), _addr(labels),
-                                                     _addr(t_lens), _addr(u_lens), R, T, U1, V, int(blank), 1.0,
-                                                     _addr(nll), None, None, _addr(ws), nws, _stream()),
-              "rnnt_hip_joint_loss_fwd_bwd")
+        nll, ws = _sep_loss_forward(Ax, Cm, bias, labels, t_lens, u_lens, blank, None, 0.0)
         if want_grad and any(ctx.needs_input_grad[:4]):
             ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, Ax, Cm, ws)
             ctx.blank, ctx.group = int(blank), group
@@ -974,13 +998,9 @@ class JointLossGroupedFn(torch.autograd.Function):
     def backward(ctx, g):
         enc, dec, W, bias, labels, t_lens, u_lens, Ax, Cm, ws = ctx.saved_tensors
         T, B, _ = enc.shape
-        U1, R, V, G = dec.shape[0], dec.shape[1], W.shape[0], ctx.group
+        V, G = W.shape[0], ctx.group
         gvec = _f32c(g.to(torch.float32), "grad of the loss")
-        dAx, dC = torch.empty_like(Ax), torch.empty_like(Cm)
-        check(_lib.lib().rnnt_hip_joint_loss_bwd_fastemit(_addr(Ax), V, R * V, _addr(Cm), V, R * V, _addr(bias), _addr(labels),
-                                                          _addr(t_lens), _addr(u_lens), R, T, U1, V, ctx.blank, 1.0, 0.0,
-                                                          _addr(gvec), 1, _addr(dAx), _addr(dC), _addr(ws), ws.numel(), _stream()),
-              "rnnt_hip_joint_loss_bwd_fastemit")
+        dAx, dC = _sep_loss_backward(Ax, Cm, bias, labels, t_lens, u_lens, ctx.blank, False, 0.0, 1.0, gvec, 1, ws)
         dAg = dAx.view(T, B, G, V)
         dA = dAg[:, :, 0].contiguous()
         for n in range(1, G):   # rank order, one addition per rank: the same bits on every run
@@ -1002,9 +1022,7 @@ class IlmLossFn(torch.autograd.Function):
         _need_gpu(dec, W, bias, labels, u_lens)
         w_param, b_param = W, bias
         dec, W, bias = _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
-        for name, t in (("targets", labels), ("target lengths", u_lens)):
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name} must be int32 (dataloader.py:21-24), got {t.dtype}")
+        _i32((("targets", labels), ("target lengths", u_lens)), " (dataloader.py:21-24)")
         if reduction not in ("none", "sum", "mean"):
             raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
         labels, u_lens = labels.contiguous(), u_lens.contiguous()
@@ -1073,34 +1091,16 @@ class RnntLossFromLogitsFn(torch.autograd.Function):
         if logits.dim() != 4:
             raise ValueError("logits must be (B, T, U+1, V)")
         win = check_emit_windows(emit_windows, logits.shape[0], logits.shape[2] - 1, logits.device)
-        codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-        if logits.dtype not in codes:
-            raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+        code = _logits_dtype_code(logits)
         logits = logits if logits.is_contiguous() else logits.contiguous()
-        for name, t in (("targets", targets), ("logit lengths", t_lens), ("target lengths", u_lens)):
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name} must be int32, got {t.dtype}")
+        _i32((("targets", targets), ("logit lengths", t_lens), ("target lengths", u_lens)))
         B, T, U1, V = logits.shape
         if targets.shape != (B, U1 - 1):
             raise ValueError(f"targets must be (B, U) = ({B}, {U1 - 1}), got {tuple(targets.shape)}")
         targets = targets.contiguous()
-        nll = torch.empty(B, device=logits.device, dtype=torch.float32)
         grad = torch.empty_like(logits) if logits.requires_grad else None
-        if win is None:
-            nws = _lib.lib().rnnt_hip_joint_loss_workspace_bytes(B, T, U1, V)
-            ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
-            check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_fastemit(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
-                                                                        _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(nll),
-                                                                        _addr(grad), _addr(ws), nws, _stream()),
-                  "rnnt_hip_loss_from_logits_fwd_bwd_fastemit")
-        else:
-            nws = _lib.lib().rnnt_hip_joint_loss_window_workspace_bytes(B, T, U1, V)
-            ws = torch.empty(nws, device=logits.device, dtype=torch.uint8)
-            check(_lib.lib().rnnt_hip_loss_from_logits_fwd_bwd_window(_addr(logits), codes[logits.dtype], _addr(targets), _addr(t_lens),
-                                                                      _addr(u_lens), B, T, U1, V, int(blank), 1.0, lam, _addr(win[0]),
-                                                                      _addr(win[1]), win[2], _addr(nll), _addr(grad), _addr(ws), nws,
-                                                                      _stream()),
-                  "rnnt_hip_loss_from_logits_fwd_bwd_window")
+        nll, _ = _loss_forward("rnnt_hip_loss_from_logits_fwd_bwd", (_addr(logits), code, _addr(targets), _addr(t_lens), _addr(u_lens)),
+                               B, T, U1, V, blank, win, lam, (_addr(grad),), logits.device)
         ctx.grad = grad
         return nll
 
@@ -1311,9 +1311,7 @@ def _align_buffers(B, U1, device, frames, score):
 
 
 def _align_lengths(labels, t_lens, u_lens, B, U1):
-    for name, t in (("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)):
-        if t.dtype != torch.int32:
-            raise ValueError(f"{name} must be int32, got {t.dtype}")
+    _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)))
     if labels.shape != (B, U1 - 1) or t_lens.shape != (B,) or u_lens.shape != (B,):
         raise ValueError(f"targets must be (B, U) = ({B}, {U1 - 1}) and both lengths (B,), got {tuple(labels.shape)}, "
                          f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
@@ -1357,9 +1355,7 @@ def align_from_logits(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.
                       score: Optional[torch.Tensor] = None) -> Alignment:
     """joint_align for dense logits (B,T,U1,V) in float32, float16 or bfloat16 (arithmetic fp32 / fp64 whatever the storage)."""
     _need_gpu(logits, labels, t_lens, u_lens, workspace, frames, score)
-    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-    if logits.dtype not in codes:
-        raise ValueError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    code = _logits_dtype_code(logits)
     if logits.dim() != 4:
         raise ValueError("logits must be (B, T, U+1, V)")
     logits = logits if logits.is_contiguous() else logits.contiguous()
@@ -1368,7 +1364,7 @@ def align_from_logits(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.
     frames, score = _align_buffers(B, U1, logits.device, frames, score)
     nws = align_workspace_bytes(B, T, U1, V)
     ws = torch.empty(nws, device=logits.device, dtype=torch.uint8) if workspace is None else workspace
-    check(_lib.lib().rnnt_hip_align_from_logits_ex(_addr(logits), codes[logits.dtype], _addr(labels), _addr(t_lens), _addr(u_lens),
+    check(_lib.lib().rnnt_hip_align_from_logits_ex(_addr(logits), code, _addr(labels), _addr(t_lens), _addr(u_lens),
                                                    B, T, U1, V, int(blank), _addr(frames), _addr(score), _addr(ws),
                                                    ws.numel() * ws.element_size(), _stream()), "rnnt_hip_align_from_logits_ex")
     return Alignment(frames, score, u_lens)

@@ -71,6 +71,114 @@ def test_argument_validation_happens_before_any_device_work():
     assert L.rnnt_hip_hp_colmax(P, 8, 32, 31, Q, None) == -1 and L.rnnt_hip_hp_colmax(P, -1, 32, 32, Q, None) == -1
 
 
+# The loss / alignment entries of csrc/loss.hip: (name, argument names in ABI order).  SEP / DENSE: the operand block they share.
+_SEP = ("A", "a_sb", "a_st", "C", "c_sb", "c_su", "bias", "labels", "t_lens", "u_lens", "B", "T", "U1", "V", "blank")
+_DENSE = ("logits", "dtype", "labels", "t_lens", "u_lens", "B", "T", "U1", "V", "blank")
+_WS = ("workspace", "workspace_bytes", "stream")
+_WIN = ("emit_lo", "emit_hi", "win_stride")
+_BWD = ("gvec", "gvec_stride", "dA", "dC")
+_LOSS_ENTRIES = {
+    "joint_loss_fwd_bwd": _SEP + ("gscale", "nll", "dA", "dC") + _WS,
+    "joint_loss_fwd_bwd_fastemit": _SEP + ("gscale", "lam", "nll", "dA", "dC") + _WS,
+    "joint_loss_fwd_bwd_window": _SEP + ("gscale", "lam") + _WIN + ("nll", "dA", "dC") + _WS,
+    "joint_loss_bwd": _SEP + ("gscale",) + _BWD + _WS,
+    "joint_loss_bwd_fastemit": _SEP + ("gscale", "lam") + _BWD + _WS,
+    "joint_loss_bwd_window": _SEP + ("gscale", "lam") + _BWD + _WS,
+    "loss_from_logits_fwd_bwd": tuple(n for n in _DENSE if n != "dtype") + ("gscale", "nll", "grad") + _WS,
+    "loss_from_logits_fwd_bwd_ex": _DENSE + ("gscale", "nll", "grad") + _WS,
+    "loss_from_logits_fwd_bwd_fastemit": _DENSE + ("gscale", "lam", "nll", "grad") + _WS,
+    "loss_from_logits_fwd_bwd_window": _DENSE + ("gscale", "lam") + _WIN + ("nll", "grad") + _WS,
+    "joint_align": _SEP + ("frames", "score") + _WS,
+    "align_from_logits_ex": _DENSE + ("frames", "score") + _WS,
+}
+
+
+def _loss_refusals(name, fields):
+    """(why, overrides) for every argument set `name` must refuse; each changes ONE thing in an otherwise acceptable call."""
+    bwd_only, align, windowed = "_bwd" in name and "fwd" not in name, "align" in name, name.endswith("_window")
+    required = {"A", "C", "bias", "logits", "labels", "t_lens", "u_lens", "nll", "frames", "score", "workspace"}
+    if bwd_only:
+        required |= {"dA", "dC"}                     # "given singly" is "one of them missing" there
+    if windowed and not bwd_only:
+        required |= {"emit_lo", "emit_hi"}
+    rows = [(f"null {f}", {f: None}) for f in fields if f in required]
+    rows += [(f"{d} = {v}", {d: v}) for d in ("B", "T", "U1", "V") for v in (0, -1)]
+    rows += [("blank = -1", {"blank": -1}), ("blank = V", {"blank": 5}), ("U1 = 513", {"U1": 513, "workspace_bytes": 1 << 62})]
+    if not bwd_only:                                 # the backward-only entries took any lattice the forward had accepted
+        rows += [("T x U1 x 8 = 2^31", {"T": 1 << 20, "U1": 256, "workspace_bytes": 1 << 62}),
+                 ("T x U1 x 8 > 2^31", {"T": (1 << 28) + 1, "U1": 1, "labels": None, "frames": None, "workspace_bytes": 1 << 62})]
+    rows += [("workspace one byte short", {"workspace_bytes": "short"}), ("no workspace bytes", {"workspace_bytes": 0})]
+    if "dA" in fields and not bwd_only:
+        rows += [("dA alone", {"dC": None}), ("dC alone", {"dA": None})]
+    if bwd_only:
+        rows += [("gvec_stride = 2", {"gvec_stride": 2}), ("gvec_stride = -1", {"gvec_stride": -1}), ("V = 1", {"V": 1})]
+    if "lam" in fields:
+        rows += [(f"lambda = {v}", {"lam": v}) for v in (-0.5, float("inf"), -float("inf"), float("nan"))]
+    if "win_stride" in fields:
+        rows += [(f"win_stride = {v}", {"win_stride": v}) for v in (1, 0, -3)]          # U = 2
+    if "dtype" in fields:
+        rows += [(f"dtype code {v}", {"dtype": v}) for v in (7, -1, 3)]
+    return [(why, {k: v for k, v in over.items() if k in fields}) for why, over in rows]
+
+
+def test_loss_entries_refuse_bad_arguments_before_any_device_work():
+    """Every loss / alignment entry of csrc/loss.hip against one table of argument sets it must refuse: each returns -1 and leaves
+    a message, on the host.  The addresses are stand-ins that are never dereferenced; every call in here is a refused one, so nothing
+    reaches a launch.  Then the workspace queries at a grid of shapes, against the byte counts of the layout as it has always been."""
+    from rnntransducer_amd import _lib
+    L = _lib.lib()
+    P = 0x10000
+    B, T, U1, V = 2, 4, 3, 5
+    good = dict(A=P, a_sb=T * V, a_st=V, C=P, c_sb=U1 * V, c_su=V, bias=P, logits=P, dtype=0, labels=P, t_lens=P, u_lens=P,
+                B=B, T=T, U1=U1, V=V, blank=0, gscale=1.0, lam=0.0, emit_lo=P, emit_hi=P, win_stride=U1 - 1, gvec=P, gvec_stride=1,
+                nll=P, dA=P, dC=P, grad=P, frames=P, score=P, workspace=P, stream=None)
+    calls = 0
+    for name, fields in _LOSS_ENTRIES.items():
+        entry = getattr(L, "rnnt_hip_" + name)
+        query = (L.rnnt_hip_joint_align_workspace_bytes if "align" in name else
+                 L.rnnt_hip_joint_loss_window_workspace_bytes if name.endswith("_window") else L.rnnt_hip_joint_loss_workspace_bytes)
+        need = query(B, T, U1, V)
+        assert need > 0
+        for why, over in _loss_refusals(name, fields):
+            args = {**good, "workspace_bytes": need, **over}
+            if args["workspace_bytes"] == "short":
+                args["workspace_bytes"] = need - 1
+            rc = entry(*(args[f] for f in fields))
+            assert rc == -1, f"{name}: {why}: returned {rc}"
+            assert L.rnnt_hip_last_error(), f"{name}: {why}: no message"
+            calls += 1
+    assert calls > 11 * 20
+    # window tables of a wider row stride and of U = 0 are refused for their stride alone (labels may be null at U = 0)
+    n0 = L.rnnt_hip_joint_loss_window_workspace_bytes(B, T, 1, V)
+    for name in ("joint_loss_fwd_bwd_window", "loss_from_logits_fwd_bwd_window"):
+        fields = _LOSS_ENTRIES[name]
+        args = dict(good, U1=1, labels=None, win_stride=0, workspace_bytes=n0)
+        assert getattr(L, "rnnt_hip_" + name)(*(args[f] for f in fields)) == -1 and L.rnnt_hip_last_error()
+    # the queries: plain, windowed, align -- T on both sides of a 32-frame tile and word, U1 on both sides of 64, V = 1
+    recorded = _LOSS_WORKSPACE_BYTES
+    for (b, t, u1, v), want in recorded.items():
+        got = (L.rnnt_hip_joint_loss_workspace_bytes(b, t, u1, v), L.rnnt_hip_joint_loss_window_workspace_bytes(b, t, u1, v),
+               L.rnnt_hip_joint_align_workspace_bytes(b, t, u1, v))
+        assert got == want, ((b, t, u1, v), got, want)
+    for query in (L.rnnt_hip_joint_loss_workspace_bytes, L.rnnt_hip_joint_loss_window_workspace_bytes, L.rnnt_hip_joint_align_workspace_bytes):
+        for bad in ((0, 4, 3, 5), (2, 0, 3, 5), (2, 4, 0, 5), (2, 4, 3, 0), (-1, 4, 3, 5)):
+            assert query(*bad) == 0
+
+
+_LOSS_WORKSPACE_BYTES = {   # (B, T, U1, V): (loss, windowed loss, alignment), as the library has always answered
+    (1, 1, 1, 1): (1536, 2304, 768),
+    (2, 4, 3, 5): (1536, 2304, 768),
+    (3, 31, 63, 29): (163584, 165376, 47872),
+    (3, 32, 64, 29): (169984, 171776, 49920),
+    (3, 33, 65, 29): (200704, 203008, 53504),
+    (2, 100, 1, 260): (14336, 15104, 2304),
+    (1, 64, 512, 8): (819456, 823808, 266240),
+    (5, 97, 130, 3): (1545472, 1551360, 515328),
+    (2, 33, 5, 256): (29440, 30208, 3328),
+    (4, 2560, 20, 72): (6758656, 6759936, 1664000),
+}
+
+
 def test_gemm_hp_plan_is_the_workspace_query():
     """rnnt_hip_gemm_hp_plan (host only): the split rule at the shapes the GPU tests name, and its agreement with
     rnnt_hip_gemm_hp_workspace_bytes — both read the one function the launch takes its decisions from."""
