@@ -84,8 +84,19 @@ __device__ __forceinline__ void matvec(const float* __restrict__ W, long ld, int
         w[i] = *reinterpret_cast<const f32x4*>(W + (long)r * ld + k);
       }
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + k);
+      // One explicit fma chain per row: the rounding of a row's sum must not depend on which of the RU slots the row sits in.
+      // Written as `s += w0 x0 + w1 x1 + w2 x2 + w3 x3` the compiler contracts some slots into fma chains and packs the products
+      // of others in pairs (two rounded multiplies), so two rows with equal weights could differ in the last bit and a tie of
+      // the frame argmax went to the higher index (tests/test_gpu_search_shapes.py, the tie cases).
 #pragma unroll
-      for (int i = 0; i < RU; ++i) s[i] += w[i][0] * xv[0] + w[i][1] * xv[1] + w[i][2] * xv[2] + w[i][3] * xv[3];
+      for (int i = 0; i < RU; ++i) {
+        float a = s[i];
+        a = __builtin_fmaf(w[i][0], xv[0], a);
+        a = __builtin_fmaf(w[i][1], xv[1], a);
+        a = __builtin_fmaf(w[i][2], xv[2], a);
+        a = __builtin_fmaf(w[i][3], xv[3], a);
+        s[i] = a;
+      }
     }
 #pragma unroll
     for (int i = 0; i < RU; ++i) {
