@@ -482,6 +482,54 @@ int rnnt_hip_loss_from_logits_fwd_bwd_window(const void* logits, int32_t dtype, 
                                              void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Lattice knowledge distillation (Panchapagesan et al., ICASSP 2021, "Efficient knowledge distillation for RNN-Transducer models"):
+ * a teacher's per-cell distributions pull a student's, with three floats per lattice cell from each side and no (B,T,U+1,V) tensor.
+ * Per cell (t,u) both softmaxes are collapsed to three classes -- blank, the cell's label y_u (only where u < u_lens[b]), everything
+ * else -- and
+ *   kd[b] = sum_{t < t_lens[b], u <= u_lens[b]} sum_k P_T(k) (log P_T(k) - log P_S(k))        (>= 0; 0 iff the collapsed cells agree)
+ * The planes: blk, emit, rest (B,U1,T) fp32, plane(b,u,t) = plane[(b*U1 + u)*T + t]: log p(blank), log p(y_u) (0 at u = U1-1, the
+ * padded label's log-probability at u_lens[b] <= u < U1-1: not read by the term) and rest = log sum_{v not in {blank, y_u}} p(v), over
+ * every non-blank entry where u >= u_lens[b].  rest is a log-sum-exp over the entries themselves, exact to fp32 rounding down to
+ * -80 and FLOORED there: finite whatever the logits are (an entry more than ~87 below the cell's largest logit underflows in fp32).
+ *
+ * rnnt_hip_joint_cell_logprobs (the teacher's side): the three planes of the operands of rnnt_hip_joint_loss_fwd_bwd into the
+ * caller's buffers: one launch, no sweep, no workspace.  t_lens is not read (every frame of A is computed), u_lens ends the label
+ * class.  blk and emit are the bits the loss computes on the same operands.
+ *
+ * rnnt_hip_joint_loss_fwd_bwd_kd / _bwd_kd: the _fastemit entries plus the teacher's planes t_blk / t_emit / t_rest (from the call
+ * above on the teacher's operands with the SAME labels and lengths; entries outside a row's lattice are not used), the upstream
+ * gradient of the KD term (kd_gscale, and in the backward-only entry kd_gvec / kd_gvec_stride, read as gscale / gvec / gvec_stride
+ * are for the NLL) and the output kd (B).  Gradients: dA, dC = d(sum_b gscale gvec_b nll_b + kd_gscale kd_gvec_b kd_b)/dA,dC, the
+ * teacher's planes being constants.  Either upstream may be 0: gscale = 0 (or gvec_b = 0) is pure distillation.
+ *   - nll, and blk / emit / alpha / beta in the workspace, are bit for bit those of the _fastemit entries on the same operands.
+ *   - kd: fp32 class terms, fp64 sums in a fixed order, no atomics: a row gives the same bits alone as in any batch.  A class with
+ *     P_T(k) = 0 (a plane entry of -inf) contributes exactly 0; a row with t_lens[b] = 0 gives kd = 0 (and nll = +inf, zero gradients).
+ *   - The gradient of the term per cell is p[v] (1 - rho) - [v = blank] (a - rho p_b) - [v = y_u] (c - rho p_y) with (a, c, r) the
+ *     teacher's and (p_b, p_y, p_r) the student's collapsed probabilities and rho = r / p_r: the lattice gradient kernels' arithmetic
+ *     on changed per-cell scalars, so it costs no further pass over V.  fastemit_lambda acts on the transducer term as above.
+ *   - Workspace: rnnt_hip_joint_loss_kd_workspace_bytes (the plain layout followed by the student's rest plane).  The backward-only
+ *     entry takes the workspace of a forward call of rnnt_hip_joint_loss_fwd_bwd_kd (dA = dC = NULL) on the same operands and planes.
+ *   - RNNT_ERR_INVALID before any device work: null teacher planes, a null kd (forward), V < 3 (the third class would be empty), a
+ *     kd_gvec_stride other than 0 / 1, a kd_gscale that is not finite.  There is no windowed and no dense-logits form.
+ *   - Labels are non-blank by the loss's contract; a blank label is not detected.  The entries without KD are untouched.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_joint_loss_kd_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V);
+int rnnt_hip_joint_cell_logprobs(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                 const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
+                                 int32_t T, int32_t U1, int32_t V, int32_t blank, float* blk, float* emit, float* rest, void* stream);
+int rnnt_hip_joint_loss_fwd_bwd_kd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                   const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
+                                   int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda,
+                                   const float* t_blk, const float* t_emit, const float* t_rest, float kd_gscale, float* nll,
+                                   float* kd, float* dA, float* dC, void* workspace, size_t workspace_bytes, void* stream);
+int rnnt_hip_joint_loss_bwd_kd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                               const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens, int32_t B,
+                               int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale, float fastemit_lambda, const float* gvec,
+                               int32_t gvec_stride, const float* t_blk, const float* t_emit, const float* t_rest, float kd_gscale,
+                               const float* kd_gvec, int32_t kd_gvec_stride, float* dA, float* dC, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Forced alignment: the best (Viterbi) RNN-T path of a KNOWN transcript, per utterance, on the device.  No (B,T,U+1,V) tensor:
  * the same two numbers per lattice cell as the loss, blk(t,u) = log p(blank | t,u) and emit(t,u) = log p(y_u | t,u), then the
  * lattice sweep of the loss in the (max, +) semiring:

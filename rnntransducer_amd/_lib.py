@@ -270,6 +270,18 @@ SYMBOLS = {
     "rnnt_hip_loss_from_logits_fwd_bwd_window": (C.c_int, [C.c_void_p, c_i32, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32,
                                                             c_i32, c_i32, c_i32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                                             c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_joint_loss_kd_workspace_bytes": (C.c_size_t, [c_i32] * 4),
+    "rnnt_hip_joint_cell_logprobs": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "rnnt_hip_joint_loss_fwd_bwd_kd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnnt_hip_joint_loss_bwd_kd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float, C.c_float,
+                                              C.c_void_p, c_i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, c_i32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnnt_hip_joint_align_workspace_bytes": (C.c_size_t, [c_i32] * 4),
     "rnnt_hip_joint_align": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_void_p, C.c_void_p, C.c_void_p,

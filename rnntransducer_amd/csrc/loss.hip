@@ -19,12 +19,15 @@
 //   grad_sepv_kernel                  : grad_sep_kernel with the vocabulary a grid dimension (V >= 256, or a table past LDS)
 //   grad_dense_kernel                 : warp-transducer-shaped d/d logits for rnnt_hip_loss_from_logits_*
 //   viterbi_kernel<K> / backtrace_kernel : forced alignment -- the max-plus sweep (one back-pointer bit per cell), the best path
-// The W / FE template flags select the emission-window / FastEmit instances; W = FE = false are the kernels without either.
+//   kd_value_kernel                   : lattice distillation -- the collapsed KL per utterance, fp64 sums in a fixed order
+// The W / FE / KD template flags select the emission-window / FastEmit / distillation instances; all false: the kernels without them.
 // The host half (from struct LossWs on): one LossCall per call, one check, four stages, three drivers behind the exported entries.
 #include "common.hpp"
 #include "lattice_shared.hpp"
 
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -67,11 +70,42 @@ struct Band {   // what the gradient kernels read
   const int *L, *R;
 };
 // A kernel with the flag W takes its tables as a trailing parameter PACK: empty for W = false, so that instance has the parameter
-// list (and the kernel-argument block) of the kernel without this feature; one Win / Band for W = true.
-template <typename T>
-__device__ __forceinline__ T pick_tables(T t) { return t; }
+// list (and the kernel-argument block) of the kernel without this feature; one Win / Band for W = true.  The flag KD (lattice
+// distillation, below) adds its one struct to the same pack.  pick_tables<T>: the pack's member of type T, or an empty T.
 template <typename T>
 __device__ __forceinline__ T pick_tables() { return T{}; }
+template <typename T, typename H, typename... R>
+__device__ __forceinline__ T pick_tables(H h, R... r) {
+  if constexpr (std::is_same<T, H>::value) return h;
+  else return pick_tables<T>(r...);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Lattice knowledge distillation (Panchapagesan et al. 2021; include/rnnt_hip.h).  Per lattice cell the teacher's and
+// the student's distributions are collapsed to three classes -- blank, the cell's label y_u (u < U_b only), everything else -- and
+// the term is the sum over the cells of KL(teacher || student).  The third class needs a third per-cell plane next to blk / emit:
+//   rest[b][u][t] = log sum_{v not in {blank, y_u}} softmax(z)[v]        (u >= u_lens[b]: every non-blank entry)
+// a log-sum-exp over the entries themselves (1 - p_blank - p_label would lose everything once the blank dominates), which the KD
+// instances of the lse kernels take from the exponentials of the full sum: the same running maximum, a second accumulator that skips
+// the two entries.  blk / emit of a KD instance are the bits of the plain one (the full sum is accumulated in the same order).
+// FLOOR: an entry more than ~87 below the cell's largest logit underflows in fp32 (2^-126) and adds nothing; the plane is floored at
+// KD_REST_FLOOR = -80, above that gap, so rest is finite whatever the logits are (V >= 3: the class is never empty) and is the true
+// value to fp32 rounding wherever the true value is >= -80.  A student floored there has the class's gradient capped, not NaN.
+// ------------------------------------------------------------------------------------------------
+constexpr float KD_REST_FLOOR = -80.f;
+
+struct KdLse {   // what the KD instances of the lse kernels take: where rest goes, and the label counts that end the label class
+  float* rest;
+  const int* u_lens;
+};
+
+struct KdGrad {   // what the KD instances of the gradient kernels take
+  const float *t_blk, *t_emit, *t_rest;   // the teacher's planes, laid out as blk / emit
+  const float* rest;                      // the student's third plane (workspace)
+  float kscale;                           // upstream gradient of the KD term: kscale * kvec[b * kstride] (kvec null: kscale)
+  const float* kvec;
+  int kstride;
+};
 
 __global__ void __launch_bounds__(256) band_kernel(const int* __restrict__ lo, const int* __restrict__ hi, long stride,
                                                    const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T, int U1,
@@ -116,14 +150,15 @@ __global__ void __launch_bounds__(256) band_kernel(const int* __restrict__ lo, c
 // ------------------------------------------------------------------------------------------------
 constexpr int LSE_UT = 8, LSE_VC = 128;
 
-template <bool W, typename... WT>
+template <bool W, bool KD, typename... WT>
 __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                       const float* __restrict__ bias, const int* __restrict__ labels,
                                                       int T, int U1, int V, int blank, long a_sb, long a_st,
                                                       long c_sb, long c_su, float* __restrict__ blk,
                                                       float* __restrict__ emit, WT... wt) {
-  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Win");
+  static_assert(sizeof...(WT) == (W ? 1 : 0) + (KD ? 1 : 0) && !(W && KD), "W = true takes one Win, KD = true one KdLse");
   const Win win = pick_tables<Win>(wt...);
+  const KdLse kd = pick_tables<KdLse>(wt...);
   __shared__ float As[TT][LSE_VC + 1];
   __shared__ float Cs[LSE_UT][LSE_VC + 1];
   const int b = blockIdx.z, t0 = blockIdx.x * TT, u0 = blockIdx.y * LSE_UT;
@@ -131,6 +166,10 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
   const int t = t0 + tl, u = u0 + ul;
   const float* Ab = A + (long)b * a_sb;
   const float* Cb = C + (long)b * c_sb;
+  // KD: the cell's label entry (-1 where the row has no label: u >= u_lens[b]) and the second sum, without the blank and that entry
+  int ykd = -1;
+  float rs = 0.f;
+  if (KD && u < U1 - 1 && u < kd.u_lens[b]) ykd = labels[(long)b * (U1 - 1) + u];
   bool live = true;
   if (W) {
     live = t < T && u < U1;
@@ -163,7 +202,18 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
     for (int c = 0; c < vc; ++c) cm = fmaxf(cm, As[tl][c] + Cs[ul][c]);
     const float nm = fmaxf(m, cm);
     float cs = 0.f;
-    for (int c = 0; c < vc; ++c) cs += expf(As[tl][c] + Cs[ul][c] - nm);
+    if (KD) {   // the full sum as below (same order, same bits); the exponentials of the other entries go to the second sum too
+      const int cb = blank - v0, cy = ykd - v0;
+      float crs = 0.f;
+      for (int c = 0; c < vc; ++c) {
+        const float e = expf(As[tl][c] + Cs[ul][c] - nm);
+        cs += e;
+        crs += (c == cb || c == cy) ? 0.f : e;
+      }
+      rs = rs * expf(m - nm) + crs;
+    } else {
+      for (int c = 0; c < vc; ++c) cs += expf(As[tl][c] + Cs[ul][c] - nm);
+    }
     s = s * expf(m - nm) + cs;
     m = nm;
   }
@@ -176,6 +226,7 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
     }
     const float lse = m + logf(s);
     const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
+    if (KD) kd.rest[o] = fmaxf(logf(rs) - logf(s), KD_REST_FLOOR);   // both sums are relative to the same maximum
     blk[o] = zb - lse;
     float e = 0.f;
     if (u < U1 - 1) {
@@ -199,14 +250,15 @@ __global__ void __launch_bounds__(256) lse_sep_kernel(const float* __restrict__ 
 constexpr int LSV_UR = 4, LSV_UT = 8 * LSV_UR, LSV_VC = 128;
 constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
 
-template <bool W, typename... WT>
+template <bool W, bool KD, typename... WT>
 __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                        const float* __restrict__ bias, const int* __restrict__ labels,
                                                        int T, int U1, int V, int blank, long a_sb, long a_st,
                                                        long c_sb, long c_su, float* __restrict__ blk,
                                                        float* __restrict__ emit, WT... wt) {
-  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Win");
+  static_assert(sizeof...(WT) == (W ? 1 : 0) + (KD ? 1 : 0) && !(W && KD), "W = true takes one Win, KD = true one KdLse");
   const Win win = pick_tables<Win>(wt...);
+  const KdLse kd = pick_tables<KdLse>(wt...);
   __shared__ float As[TT][LSV_VC + 1];
   __shared__ float Cs[LSV_UT][LSV_VC + 1];
   const int b = blockIdx.z, t0 = blockIdx.x * TT, u0 = blockIdx.y * LSV_UT;
@@ -241,6 +293,17 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
   float m[LSV_UR], s[LSV_UR];   // running maximum (log2 domain) and sum of 2^(x - m)
 #pragma unroll
   for (int r = 0; r < LSV_UR; ++r) { m[r] = -__builtin_huge_valf(); s[r] = 0.f; }
+  int ykd[LSV_UR];   // KD: the cells' label entries (-1 where the row has no label) and the sums without the blank and that entry
+  float rs[LSV_UR];
+  if (KD) {
+    const int Ub = kd.u_lens[b];
+#pragma unroll
+    for (int r = 0; r < LSV_UR; ++r) {
+      const int u = u0 + ug * LSV_UR + r;
+      ykd[r] = (u < U1 - 1 && u < Ub) ? labels[(long)b * (U1 - 1) + u] : -1;
+      rs[r] = 0.f;
+    }
+  }
   for (int v0 = 0; v0 < V; v0 += LSV_VC) {
     const int vc = min(LSV_VC, V - v0);
     __syncthreads();
@@ -265,10 +328,29 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
     float nm[LSV_UR], cs[LSV_UR];
 #pragma unroll
     for (int r = 0; r < LSV_UR; ++r) { nm[r] = fmaxf(m[r], cm[r]); cs[r] = 0.f; }
-    for (int c = 0; c < vc; ++c) {
-      const float a = As[tl][c];
+    if (KD) {   // the full sums as below (same order, same bits); the exponentials of the other entries go to the second sums too
+      const int cb = blank - v0;
+      float crs[LSV_UR];
+      int cy[LSV_UR];
 #pragma unroll
-      for (int r = 0; r < LSV_UR; ++r) cs[r] += __builtin_amdgcn_exp2f(a + Cs[ug * LSV_UR + r][c] - nm[r]);
+      for (int r = 0; r < LSV_UR; ++r) { crs[r] = 0.f; cy[r] = ykd[r] - v0; }
+      for (int c = 0; c < vc; ++c) {
+        const float a = As[tl][c];
+#pragma unroll
+        for (int r = 0; r < LSV_UR; ++r) {
+          const float e = __builtin_amdgcn_exp2f(a + Cs[ug * LSV_UR + r][c] - nm[r]);
+          cs[r] += e;
+          crs[r] += (c == cb || c == cy[r]) ? 0.f : e;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < LSV_UR; ++r) rs[r] = rs[r] * __builtin_amdgcn_exp2f(m[r] - nm[r]) + crs[r];
+    } else {
+      for (int c = 0; c < vc; ++c) {
+        const float a = As[tl][c];
+#pragma unroll
+        for (int r = 0; r < LSV_UR; ++r) cs[r] += __builtin_amdgcn_exp2f(a + Cs[ug * LSV_UR + r][c] - nm[r]);
+      }
     }
 #pragma unroll
     for (int r = 0; r < LSV_UR; ++r) {
@@ -288,6 +370,7 @@ __global__ void __launch_bounds__(256) lse_sepv_kernel(const float* __restrict__
       }
       const float lse = (m[r] + __builtin_amdgcn_logf(s[r])) * LN2_F;   // v_log_f32 = log2
       const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
+      if (KD) kd.rest[o] = fmaxf((__builtin_amdgcn_logf(rs[r]) - __builtin_amdgcn_logf(s[r])) * LN2_F, KD_REST_FLOOR);
       blk[o] = zb - lse;
       float e = 0.f;
       if (u < U1 - 1) {
@@ -643,6 +726,27 @@ __device__ __forceinline__ void fastemit_cell(CellS& c, float lambda) {
   c.ce = (1.f + lambda) * c.ce;
 }
 
+// Lattice distillation in the gradient kernels (KD = true).  With p the student's softmax of a cell, (a, c, r) the
+// teacher's collapsed probabilities (blank, label, rest), (p_b, p_y, p_r) the student's and rho = r / p_r = exp(rest_T - rest_S),
+//   d KL / dz[v] = p[v] (1 - rho) - [v = blank] (a - rho p_b) - [v = y_u] (c - rho p_y)
+// which is again the plain kernels' arithmetic on changed per-cell scalars.  The two upstream gradients of a row (gn for the NLL,
+// gk for the KD term; either may be 0) enter the scalars here and the kernels' final scale is 1.  In fp32 the three-scalar form
+// cancels on the blank and label entries once rho is large (a peaked student: p[v] (1 - rho) + rho p_b against the p_b - a it should
+// leave), so the KD instances split the work: the inner loops see those two entries of a cell with a logit that sends the
+// exponential to 0 (kd_mask: they add exact zeros), and the cell's cb / ce slots carry the two entries COMPLETE,
+//   cb <- gn (cb - w p_b) + gk (a - p_b)            ce <- gn (ce - w p_y) + gk (c - p_y)   (0 without a label: u = U_b)
+// while every other entry is one product with w <- gn w + gk (1 - rho), of size at most gn + gk (p[v] rho <= r <= 1).
+// rest_S >= KD_REST_FLOOR and the exponent is capped, so rho (and w) stay finite; a teacher class of probability 0 (-inf) is fine.
+__device__ __forceinline__ void kd_cell(CellS& c, const KdGrad& kd, long o, float lb, float le, bool has_label, float gn, float gk) {
+  const float pb = expf(lb), py = has_label ? expf(le) : 0.f;
+  const float a = expf(kd.t_blk[o]), cl = has_label ? expf(kd.t_emit[o]) : 0.f;
+  const float rho = expf(fminf(kd.t_rest[o] - kd.rest[o], 85.f));
+  c.cb = gn * (c.cb - c.w * pb) + gk * (a - pb);
+  c.ce = has_label ? gn * (c.ce - c.w * py) + gk * (cl - py) : 0.f;
+  c.w = gn * c.w + gk * (1.f - rho);
+}
+constexpr float KD_MASKED = -1e30f;   // the logit of an entry the inner loop must not see: exp(x - lse) = 0
+
 // Emission windows in the gradient kernels (W = true): [ua, ub] = the label positions u <= Ub whose band [L[u], R[u]] meets the
 // frames [t0, t0 + TT) of this tile.  L and R are non-decreasing in u, so these positions are one interval; empty: ua > ub.
 // Called by every thread of the workgroup (two barriers).
@@ -666,7 +770,8 @@ constexpr float DEAD_LSE = 1e30f;   // the lse of a cell outside the band: exp(x
 // W: the u loop runs over the chunks of 8 (aligned as without windows, so that full windows keep every sum's order) that meet the
 // tile's interval; a dead cell inside them adds exact zeros, with no branch in the inner loop (a per-cell skip measured 1.9x slower
 // with full windows: it serialises the table reads)
-template <bool FE, bool W, typename... WT>
+// KD: kd_cell where the scalars are made, kd_mask on the staged C values of a cell's blank and label entries, no final scale
+template <bool FE, bool W, bool KD, typename... WT>
 __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                        const float* __restrict__ bias, const int* __restrict__ labels,
                                                        const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -677,8 +782,9 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
                                                        const float* __restrict__ gvec, int gvec_stride,
                                                        float* __restrict__ dA, float* __restrict__ dCp, float fe_lambda,
                                                        WT... wt) {
-  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Band");
+  static_assert(sizeof...(WT) == (W ? 1 : 0) + (KD ? 1 : 0) && !(W && KD), "W = true takes one Band, KD = true one KdGrad");
   const Band bt = pick_tables<Band>(wt...);
+  const KdGrad kd = pick_tables<KdGrad>(wt...);
   const int *wL = bt.L, *wR = bt.R;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   CellS* cells = reinterpret_cast<CellS*>(smem);
@@ -704,7 +810,9 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
     tile_band(wL, wR, t0, Ub, tid, 256, band, ua, ub);
   }
 
-  for (int i = tid; i < U1; i += 256) ys[i] = (i < U1 - 1) ? labels[(long)b * (U1 - 1) + i] : -1;
+  // (KD: a position without a label transition, u >= Ub, has no label entry: -1, so kd_mask leaves that entry to the inner loop)
+  for (int i = tid; i < U1; i += 256) ys[i] = (i < U1 - 1 && (!KD || i < Ub)) ? labels[(long)b * (U1 - 1) + i] : -1;
+  const float gk = KD ? (kd.kvec ? kd.kscale * kd.kvec[(long)b * kd.kstride] : kd.kscale) : 0.f;
   for (int i = tid; i < TT * U1; i += 256) {
     const int u = i / TT, tl = i % TT, t = t0 + tl;   // consecutive threads -> consecutive frames: alpha / beta / blk / emit rows are read coalesced
     CellS c = {0.f, W ? DEAD_LSE : 0.f, 0.f, 0.f};
@@ -712,6 +820,10 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
       const float zb = Ab[(long)t * a_st + blank] + Cb[(long)u * c_su + blank] + bias[blank];
       c = cell_scalars(blk, emit, alpha, beta, rowbase, T, t, u, Tb, Ub, logZ, zb);
       if (FE) fastemit_cell(c, fe_lambda);
+      if (KD) {
+        const long o = rowbase + (long)u * T + t;
+        kd_cell(c, kd, o, blk[o], emit[o], u < Ub, gscale, gk);
+      }
     }
     cells[tl * U1 + u] = c;
   }
@@ -749,6 +861,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
         accC[j] = 0.f;
         cs[j] = Cs[u * 64 + lane];
         yv[j] = ys[u];
+        if (KD && (v == blank || v == yv[j])) cs[j] = KD_MASKED;
       }
 #pragma unroll
       for (int i = 0; i < NF; ++i) {
@@ -783,7 +896,7 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
       const int t = t0 + wave + 4 * i;
-      if (t < T && vok) dA[(long)b * a_sb + (long)t * a_st + v] = accA[i] * gscale;
+      if (t < T && vok) dA[(long)b * a_sb + (long)t * a_st + v] = KD ? accA[i] : accA[i] * gscale;
     }
     __syncthreads();
     for (int i = tid; i < U1 * 64; i += 256) {
@@ -811,8 +924,10 @@ __global__ void __launch_bounds__(256) grad_sep_kernel(const float* __restrict__
 // unchunked kernel's.  Every wave stays to the end (the chunks' barriers), the ones beyond the vocabulary only help build the table.
 // W (emission windows): cells outside the band enter the table as cells outside the lattice do (exact zeros), and an 8-row block
 // that does not meet the tile's interval [ua, ub] skips its 32 x 8 x 64 exponentials and stores its zero dC rows.
+// KD (lattice distillation): kd_cell where the scalars are made, the masked logit in cs2 for a cell's blank and label entries (set
+// per 8-row block, outside the inner loop), whose complete values the correction pass then subtracts as it subtracts cb / ce; no final scale.
 // ------------------------------------------------------------------------------------------------
-template <int NW, bool CHUNKED, bool FE, bool W, typename... WT>
+template <int NW, bool CHUNKED, bool FE, bool W, bool KD, typename... WT>
 __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __restrict__ A, const float* __restrict__ C,
                                                             const float* __restrict__ bias, const int* __restrict__ labels,
                                                             const int* __restrict__ t_lens, const int* __restrict__ u_lens,
@@ -823,8 +938,9 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
                                                             const float* __restrict__ gvec, int gvec_stride,
                                                             float* __restrict__ dA, float* __restrict__ dCp, int ul,
                                                             float fe_lambda, WT... wt) {
-  static_assert(sizeof...(WT) == (W ? 1 : 0), "W = true takes one Band");
+  static_assert(sizeof...(WT) == (W ? 1 : 0) + (KD ? 1 : 0) && !(W && KD), "W = true takes one Band, KD = true one KdGrad");
   const Band bt = pick_tables<Band>(wt...);
+  const KdGrad kd = pick_tables<KdGrad>(wt...);
   const int *wL = bt.L, *wR = bt.R;
   const int UL = CHUNKED ? ul : U1;                      // label positions per table
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -855,7 +971,9 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
     tile_band(wL, wR, t0, Ub, tid, 64 * NW, band, ua, ub);
   }
 
-  for (int i = tid; i < U1; i += 64 * NW) ys[i] = (i < U1 - 1) ? labels[(long)b * (U1 - 1) + i] : -1;
+  // (KD: a position without a label transition, u >= Ub, has no label entry: -1)
+  for (int i = tid; i < U1; i += 64 * NW) ys[i] = (i < U1 - 1 && (!KD || i < Ub)) ? labels[(long)b * (U1 - 1) + i] : -1;
+  const float gk = KD ? (kd.kvec ? kd.kscale * kd.kvec[(long)b * kd.kstride] : kd.kscale) : 0.f;
   const float bias_blank = bias[blank];
   float a2[TT], accA[TT];
   const bool has_blank = blank >= vw0 && blank < vw0 + 64;   // uniform over the wave
@@ -880,6 +998,10 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
         const float zb = Ab[(long)tc * a_st + blank] + Cb[(long)uc * c_su + blank] + bias_blank;
         c[q] = cell_scalars(blk, emit, alpha, beta, rowbase, T, tc, uc, Tbc, Ub, logZ, zb);
         if (FE) fastemit_cell(c[q], fe_lambda);   // both tables carry the FastEmit values: wl its w, cbe its ce
+        if (KD) {   // (the clamped cell: inside the planes whatever (t, u) is)
+          const long o = rowbase + (long)uc * T + tc;
+          kd_cell(c[q], kd, o, blk[o], emit[o], uc < Ub, gscale, gk);
+        }
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -911,6 +1033,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
         const int u = min(u0 + j, U1 - 1);
         accC[j] = 0.f;
         cs2[j] = vok ? (Cb[(long)u * c_su + v] + bias_v) * LOG2E_F : 0.f;
+        if (KD) cs2[j] = (v == blank || v == ys[u]) ? KD_MASKED : cs2[j];
       }
       if (W ? (u0 <= ub && u0 + UC > ua) : (u0 <= Ub)) {
         // branch-free over the whole 32 x 8 block (cells outside the lattice contribute exact zeros; label positions beyond U1 - 1
@@ -961,7 +1084,7 @@ __global__ void __launch_bounds__(64 * NW, 3) grad_sepv_kernel(const float* __re
   if (vok) {
 #pragma unroll
     for (int tl = 0; tl < TT; ++tl)
-      if (t0 + tl < T) dA[(long)b * a_sb + (long)(t0 + tl) * a_st + v] = accA[tl] * gscale;
+      if (t0 + tl < T) dA[(long)b * a_sb + (long)(t0 + tl) * a_st + v] = KD ? accA[tl] : accA[tl] * gscale;
   }
 }
 
@@ -1042,6 +1165,41 @@ __global__ void nll_window_kernel(const double* __restrict__ ll, const int* __re
   if (b < B) nll[b] = feas[b] ? (float)(-ll[b]) : __builtin_huge_valf();
 }
 
+// lattice distillation, the value: kd[b] = sum over the cells (t < Tb, u <= Ub) and the classes k (blank, label -- u < Ub only --, rest) of
+// P_T(k) (log P_T(k) - log P_S(k)).  One workgroup per utterance.  The class terms are fp32, a class the teacher gives probability 0
+// adds exactly 0; thread i sums the cells i, i + 256, ... in fp64, then a tree over LDS: a fixed order that depends on the row's own
+// lengths alone, so a row gives the same bits alone as in any batch.  A row without cells gives 0.
+__global__ void __launch_bounds__(256) kd_value_kernel(const float* __restrict__ blk, const float* __restrict__ emit,
+                                                       const float* __restrict__ rest, const float* __restrict__ t_blk,
+                                                       const float* __restrict__ t_emit, const float* __restrict__ t_rest,
+                                                       const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T,
+                                                       int U1, float* __restrict__ kd) {
+  __shared__ double red[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Tb = max(min(t_lens[b], T), 0), Ub = max(min(u_lens[b], U1 - 1), 0);
+  const long rowbase = (long)b * U1 * T;
+  const int ncell = Tb * (Ub + 1);
+  auto term = [](float lt, float ls) -> float {
+    const float p = expf(lt);
+    return p > 0.f ? p * (lt - ls) : 0.f;
+  };
+  double s = 0.0;
+  for (int i = tid; i < ncell; i += 256) {
+    const int u = i / Tb, t = i - u * Tb;
+    const long o = rowbase + (long)u * T + t;
+    s += (double)term(t_blk[o], blk[o]);
+    if (u < Ub) s += (double)term(t_emit[o], emit[o]);
+    s += (double)term(t_rest[o], rest[o]);
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) kd[b] = (float)red[0];
+}
+
 // out[0] = scale * sum_i x[i]: one wavefront, fixed order (lane partial sums over i = lane, lane + 64, ... then a butterfly)
 __global__ void __launch_bounds__(64) scaled_sum_kernel(const float* __restrict__ x, int n, float scale, float* __restrict__ out) {
   float s = 0.f;
@@ -1054,6 +1212,7 @@ struct LossWs {
   float *blk, *emit;
   double *alpha, *beta, *ll;
   float* dCp;
+  float* rest;         // lattice distillation: the student's third plane, laid out as blk / emit; null without KD
   int *L, *R, *feas;   // the band tables ([B][U1] int32) and feasibility flags ([B]) of the windowed loss: null without windows
   unsigned* bp;        // forced alignment: the back-pointer table bp[B][U1][nw = ceil(T/32)], one bit per cell
   int nw;
@@ -1064,7 +1223,8 @@ struct LossWs {
 // Host half.  Every exported loss / alignment entry fills ONE description of its call, a LossCall, and hands it to a driver:
 // run_loss (forward, and the backward when gradients are asked for), run_loss_bwd (the backward alone, on the workspace a forward
 // left) or run_align.  A driver checks the whole call before any device work (check_call, which also carves the workspace) and
-// then composes the stages: lse -> sweep (+ nll) -> grad, or lse -> viterbi.  A further variant of the loss is a field here.
+// then composes the stages: lse -> sweep (+ nll) [-> kd] -> grad, lse -> viterbi, or lse alone into the caller's planes.  A further
+// variant of the loss is a field here.
 // ------------------------------------------------------------------------------------------------
 struct LossCall {
   const char* who = "";   // the entry's name, for messages
@@ -1085,6 +1245,16 @@ struct LossCall {
   bool windowed = false;
   const int32_t *emit_lo = nullptr, *emit_hi = nullptr;
   int64_t win_stride = 0;
+  // lattice distillation (KD): the teacher's three planes (B,U1,T), the upstream gradient of the KD term (as gscale / gvec are the
+  // NLL's) and where the per-utterance value goes (forward calls).  Separable operands only, no windows.
+  bool kd = false;
+  const float *t_blk = nullptr, *t_emit = nullptr, *t_rest = nullptr;
+  float kd_gscale = 1.f;
+  const float* kd_gvec = nullptr;
+  int kd_gvec_stride = 0;
+  float* kd_out = nullptr;
+  // the teacher's side: the three planes of the operands themselves, into the caller's buffers (Drive::Planes)
+  float *p_blk = nullptr, *p_emit = nullptr, *p_rest = nullptr;
   // outputs: the loss (dA / dC separable, grad dense; null: no backward) or the alignment
   float *nll = nullptr, *dA = nullptr, *dC = nullptr;
   void* grad = nullptr;
@@ -1106,8 +1276,9 @@ struct Carver {   // consecutive 256-byte aligned pieces of a workspace (a null 
   }
 };
 
-// the loss: alpha | beta | logZ | blk | emit | the dC slabs, then (windowed) the band tables L, R and the feasibility flags
-LossWs carve(void* ws, int B, int T, int U1, int V, bool windowed) {
+// the loss: alpha | beta | logZ | blk | emit | the dC slabs, then (windowed) the band tables L, R and the feasibility flags, or (KD)
+// the student's rest plane
+LossWs carve(void* ws, int B, int T, int U1, int V, bool windowed, bool kd = false) {
   LossWs w{};
   Carver c{reinterpret_cast<char*>(ws)};
   const size_t cells = (size_t)B * T * U1, ntiles = ceil_div(T, TT);
@@ -1122,6 +1293,7 @@ LossWs carve(void* ws, int B, int T, int U1, int V, bool windowed) {
     w.R = c.take<int>((size_t)B * U1 * 4);
     w.feas = c.take<int>((size_t)B * 4);
   }
+  if (kd) w.rest = c.take<float>(cells * 4);
   w.total = c.off;
   return w;
 }
@@ -1182,6 +1354,18 @@ int pick_fe_w(const LossCall& c, const LossWs& w, F&& f) {
   });
 }
 
+// <FE, W, KD> of the separable gradient kernels: f(BoolT<FE>, BoolT<W>, BoolT<KD>, lambda, tables...).  A KD call has no windows: its
+// pack is the one KdGrad; every other call takes the <FE, W> instances above with KD = false (the kernels without distillation).
+template <typename F>
+int pick_fe_w_kd(const LossCall& c, const LossWs& w, F&& f) {
+  if (c.kd) {
+    const KdGrad k = {c.t_blk, c.t_emit, c.t_rest, w.rest, c.kd_gscale, c.kd_gvec, c.kd_gvec_stride};
+    return c.fastemit_lambda != 0.f ? f(BoolT<true>{}, BoolT<false>{}, BoolT<true>{}, c.fastemit_lambda, k)
+                                    : f(BoolT<false>{}, BoolT<false>{}, BoolT<true>{}, 0.f, k);
+  }
+  return pick_fe_w(c, w, [&](auto fe, auto win, float lam, auto... wt) { return f(fe, win, BoolT<false>{}, lam, wt...); });
+}
+
 // vocabularies from 256 entries take the lane-per-entry kernels (lse_sepv_kernel, grad_sepv_kernel); RNNT_LOSS_SMALLV_KERNELS=1 keeps
 // the round-1 kernels everywhere, RNNT_LOSS_LARGEV_KERNELS=1 takes the new ones for every V (A/B and tests)
 bool large_vocab(int V) {
@@ -1191,7 +1375,7 @@ bool large_vocab(int V) {
 
 unsigned dense_grid(long ncell) { return (unsigned)(ceil_div(ncell, 4) < 16384 ? ceil_div(ncell, 4) : 16384); }
 
-enum class Drive { Forward, Backward, Align };
+enum class Drive { Forward, Backward, Align, Planes };
 
 // Every argument check of every entry, before any device work; then the workspace, carved, and its size.
 int check_call(const LossCall& c, Drive drive, LossWs* w) {
@@ -1209,11 +1393,26 @@ int check_call(const LossCall& c, Drive drive, LossWs* w) {
     RNNT_CHECK_ARG(c.A && c.C && c.bias, "%s: null A/C/bias", who);
   }
   // FastEmit's lambda is read by the backward only, but checked in every call that carries one: finite and >= 0
-  if (drive != Drive::Align)
+  if (drive != Drive::Align && drive != Drive::Planes)
     RNNT_CHECK_ARG(c.fastemit_lambda >= 0.f && c.fastemit_lambda <= 3.4028234664e38f, "%s: fastemit_lambda must be finite and >= 0 (got %g)", who, (double)c.fastemit_lambda);
+  if (c.kd || drive == Drive::Planes) {   // lattice distillation: three classes per cell, separable operands, no windows
+    RNNT_CHECK_ARG(!c.dense, "%s: distillation takes the separable operands, not dense logits", who);
+    RNNT_CHECK_ARG(!c.windowed, "%s: distillation does not combine with emission windows", who);
+    RNNT_CHECK_ARG(c.V >= 3, "%s: distillation needs V >= 3 (blank, label, rest), got %d", who, c.V);
+  }
+  if (c.kd) {
+    RNNT_CHECK_ARG(c.t_blk && c.t_emit && c.t_rest, "%s: null teacher planes", who);
+    RNNT_CHECK_ARG(c.kd_gscale >= -3.4028234664e38f && c.kd_gscale <= 3.4028234664e38f, "%s: kd_gscale must be finite (got %g)", who, (double)c.kd_gscale);
+  }
   switch (drive) {
+    case Drive::Planes:
+      RNNT_CHECK_ARG(c.p_blk && c.p_emit && c.p_rest, "%s: null output planes", who);
+      *w = LossWs{};
+      w->blk = c.p_blk, w->emit = c.p_emit, w->rest = c.p_rest;
+      return RNNT_OK;
     case Drive::Forward:
       RNNT_CHECK_ARG(c.nll, "%s: null nll", who);
+      RNNT_CHECK_ARG(!c.kd || c.kd_out, "%s: null kd", who);
       RNNT_CHECK_ARG((c.dA == nullptr) == (c.dC == nullptr), "%s: dA and dC must both be given or both be NULL", who);
       if (c.windowed) {
         RNNT_CHECK_ARG(c.emit_lo && c.emit_hi, "%s: null emit_lo / emit_hi", who);
@@ -1226,19 +1425,20 @@ int check_call(const LossCall& c, Drive drive, LossWs* w) {
       RNNT_CHECK_ARG(c.V >= 2 && c.labels, "%s: V must be at least 2 and labels given", who);
       RNNT_CHECK_ARG(c.dA && c.dC, "%s: null dA/dC", who);
       RNNT_CHECK_ARG(c.gvec_stride == 0 || c.gvec_stride == 1, "%s: gvec_stride must be 0 (one scalar) or 1 (per utterance)", who);
+      RNNT_CHECK_ARG(!c.kd || c.kd_gvec_stride == 0 || c.kd_gvec_stride == 1, "%s: kd_gvec_stride must be 0 (one scalar) or 1 (per utterance)", who);
       break;
     case Drive::Align:
       RNNT_CHECK_ARG(c.score, "%s: null score", who);
       RNNT_CHECK_ARG(c.U1 == 1 || c.frames, "%s: null frames", who);
       break;
   }
-  *w = drive == Drive::Align ? carve_align(c.workspace, c.B, c.T, c.U1) : carve(c.workspace, c.B, c.T, c.U1, c.V, c.windowed);
+  *w = drive == Drive::Align ? carve_align(c.workspace, c.B, c.T, c.U1) : carve(c.workspace, c.B, c.T, c.U1, c.V, c.windowed, c.kd);
   RNNT_CHECK_ARG(c.workspace && c.workspace_bytes >= w->total, "%s: workspace too small (%zu < %zu)", who, c.workspace_bytes, w->total);
   return RNNT_OK;
 }
 
 // stage 1: blk / emit of every lattice cell, from the separable operands or from dense logits (the loss and the alignment share
-// it); with emission windows the band tables first, then the W = true instances
+// it); with emission windows the band tables first, then the W = true instances; with a rest plane to fill (KD) the KD instances
 int stage_lse(const LossCall& c, const LossWs& w) {
   hipStream_t s = c.stream;
   const bool windowed = w.L != nullptr;
@@ -1263,18 +1463,22 @@ int stage_lse(const LossCall& c, const LossWs& w) {
     const int ntiles = (int)ceil_div(c.T, TT);
     const double cells = (double)c.B * c.T * c.U1;
     ProfScope prof(RNNT_K_LSE, 4.0 * ((double)c.B * c.T * c.V + (double)c.B * c.U1 * c.V) + 8.0 * cells, s);
-    pick_w(windowed, win, [&](auto W, auto... wt) {
-      constexpr bool Wv = decltype(W)::value;
+    auto launch = [&](auto W, auto KD, auto... wt) {
+      constexpr bool Wv = decltype(W)::value, KDv = decltype(KD)::value;
       if (large_vocab(c.V))
-        hipLaunchKernelGGL((lse_sepv_kernel<Wv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSV_UT), c.B), dim3(256), 0, s, c.A,
-                           c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su, w.blk,
-                           w.emit, wt...);
+        hipLaunchKernelGGL((lse_sepv_kernel<Wv, KDv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSV_UT), c.B), dim3(256), 0, s,
+                           c.A, c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su,
+                           w.blk, w.emit, wt...);
       else
-        hipLaunchKernelGGL((lse_sep_kernel<Wv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSE_UT), c.B), dim3(256), 0, s, c.A,
-                           c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su, w.blk,
-                           w.emit, wt...);
+        hipLaunchKernelGGL((lse_sep_kernel<Wv, KDv, decltype(wt)...>), dim3(ntiles, (unsigned)ceil_div(c.U1, LSE_UT), c.B), dim3(256), 0, s,
+                           c.A, c.C, c.bias, c.labels, c.T, c.U1, c.V, c.blank, (long)c.a_sb, (long)c.a_st, (long)c.c_sb, (long)c.c_su,
+                           w.blk, w.emit, wt...);
       return RNNT_OK;
-    });
+    };
+    if (w.rest)
+      launch(BoolT<false>{}, BoolT<true>{}, KdLse{w.rest, c.u_lens});
+    else
+      pick_w(windowed, win, [&](auto W, auto... wt) { return launch(W, BoolT<false>{}, wt...); });
   }
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
@@ -1300,10 +1504,20 @@ int stage_sweep(const LossCall& c, const LossWs& w) {
   return RNNT_OK;
 }
 
-// stage 3 of the loss, separable: dA and the per-tile dC slabs, then their fixed-order sum
+// the stage of a KD forward call: the distillation term's value per utterance, from the student's and the teacher's planes
+int stage_kd(const LossCall& c, const LossWs& w) {
+  ProfScope prof(RNNT_K_MISC, 24.0 * (double)c.B * c.T * c.U1, c.stream);
+  hipLaunchKernelGGL(kd_value_kernel, dim3(c.B), dim3(256), 0, c.stream, w.blk, w.emit, w.rest, c.t_blk, c.t_emit, c.t_rest, c.t_lens, c.u_lens,
+                     c.T, c.U1, c.kd_out);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// stage 3 of the loss, separable: dA and the per-tile dC slabs, then their fixed-order sum.  (KD: both upstream gradients are in the
+// cell scalars already, so the kernels and the slab sum scale by 1)
 int stage_grad_sep(const LossCall& c, const LossWs& w) {
-  return pick_fe_w(c, w, [&](auto fe_t, auto w_t, float fe, auto... wt) -> int {
-    constexpr bool FE = decltype(fe_t)::value, W = decltype(w_t)::value;
+  return pick_fe_w_kd(c, w, [&](auto fe_t, auto w_t, auto kd_t, float fe, auto... wt) -> int {
+    constexpr bool FE = decltype(fe_t)::value, W = decltype(w_t)::value, KD = decltype(kd_t)::value;
     hipStream_t s = c.stream;
     const int T = c.T, U1 = c.U1, V = c.V, ntiles = (int)ceil_div(T, TT);
     const double cells = (double)c.B * T * U1;
@@ -1323,26 +1537,26 @@ int stage_grad_sep(const LossCall& c, const LossWs& w) {
       const size_t lds = (size_t)U1 * per_row + (size_t)U1 * 4;   // 516 (U+1): the whole table up to U+1 = 317
       if (lds <= LDS_MAX) {
         if (lds > 64 * 1024)
-          RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE, W, decltype(wt)...>), grid, block, lds, s, GRAD_SEP_ARGS, U1, fe, wt...);
+          RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, false, FE, W, KD, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((grad_sepv_kernel<NW, false, FE, W, KD, decltype(wt)...>), grid, block, lds, s, GRAD_SEP_ARGS, U1, fe, wt...);
       } else {   // the table in chunks of label positions: as few chunks as fit, of equal size rounded up to the 8-row block
         const int ul_max = (int)((LDS_MAX - (size_t)U1 * 4) / per_row) & ~7;
         const int nchunks = (int)ceil_div(U1, ul_max);
         const int ul = (int)ceil_div(ceil_div(U1, nchunks), 8) * 8;
         const size_t lds_c = (size_t)ul * per_row + (size_t)U1 * 4;
-        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-        hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE, W, decltype(wt)...>), grid, block, lds_c, s, GRAD_SEP_ARGS, ul, fe, wt...);
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sepv_kernel<NW, true, FE, W, KD, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+        hipLaunchKernelGGL((grad_sepv_kernel<NW, true, FE, W, KD, decltype(wt)...>), grid, block, lds_c, s, GRAD_SEP_ARGS, ul, fe, wt...);
       }
     } else {
       if (lds_sep > 64 * 1024)
-        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE, W, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
-      hipLaunchKernelGGL((grad_sep_kernel<FE, W, decltype(wt)...>), dim3(ntiles, c.B), dim3(256), lds_sep, s, GRAD_SEP_ARGS, fe, wt...);
+        RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)grad_sep_kernel<FE, W, KD, decltype(wt)...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sep));
+      hipLaunchKernelGGL((grad_sep_kernel<FE, W, KD, decltype(wt)...>), dim3(ntiles, c.B), dim3(256), lds_sep, s, GRAD_SEP_ARGS, fe, wt...);
     }
 #undef GRAD_SEP_ARGS
     RNNT_CHECK_LAUNCH();
     const long per_b = (long)U1 * V;
     hipLaunchKernelGGL(reduce_dc_kernel, dim3((unsigned)ceil_div(per_b, 256), c.B), dim3(256), 0, s, w.dCp, ntiles, per_b, V, (long)c.c_sb,
-                       (long)c.c_su, c.gscale, c.gvec, c.gvec_stride, c.dC);
+                       (long)c.c_su, KD ? 1.f : c.gscale, KD ? nullptr : c.gvec, c.gvec_stride, c.dC);
     RNNT_CHECK_LAUNCH();
     return RNNT_OK;
   });
@@ -1395,6 +1609,8 @@ int run_loss(const LossCall& c) {   // forward; the backward too when the call h
   if (int rc = check_call(c, Drive::Forward, &w)) return rc;
   if (int rc = stage_lse(c, w)) return rc;
   if (int rc = stage_sweep(c, w)) return rc;
+  if (c.kd)
+    if (int rc = stage_kd(c, w)) return rc;
   return (c.dense ? c.grad != nullptr : c.dA != nullptr) ? stage_grad(c, w) : RNNT_OK;
 }
 
@@ -1404,6 +1620,13 @@ int run_loss_bwd(const LossCall& c) {
   LossWs w;
   if (int rc = check_call(c, Drive::Backward, &w)) return rc;
   return stage_grad(c, w);
+}
+
+// the teacher's side of the distillation: blk / emit / rest of the operands into the caller's planes -- no sweep, no workspace
+int run_planes(const LossCall& c) {
+  LossWs w;
+  if (int rc = check_call(c, Drive::Planes, &w)) return rc;
+  return stage_lse(c, w);
 }
 
 int run_align(const LossCall& c) {
@@ -1501,6 +1724,50 @@ extern "C" int rnnt_hip_joint_loss_bwd_window(const float* A, int64_t a_sb, int6
   FILL_SEP(c, "joint_loss_bwd_window");
   c.windowed = true;
   c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.gvec = gvec, c.gvec_stride = gvec_stride, c.dA = dA, c.dC = dC;
+  return run_loss_bwd(c);
+}
+
+/* ---- lattice knowledge distillation (include/rnnt_hip.h): the _fastemit entries with the teacher's planes and the KD instances ---- */
+#define FILL_KD(c) c.kd = true, c.t_blk = t_blk, c.t_emit = t_emit, c.t_rest = t_rest, c.kd_gscale = kd_gscale
+extern "C" size_t rnnt_hip_joint_loss_kd_workspace_bytes(int32_t B, int32_t T, int32_t U1, int32_t V) {
+  if (B < 1 || T < 1 || U1 < 1 || V < 1) return 0;
+  return carve(nullptr, B, T, U1, V, false, true).total;
+}
+
+extern "C" int rnnt_hip_joint_cell_logprobs(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                            const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                            int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float* blk, float* emit,
+                                            float* rest, void* stream) {
+  void* workspace = nullptr;
+  const size_t workspace_bytes = 0;
+  FILL_SEP(c, "joint_cell_logprobs");
+  c.p_blk = blk, c.p_emit = emit, c.p_rest = rest;
+  return run_planes(c);
+}
+
+extern "C" int rnnt_hip_joint_loss_fwd_bwd_kd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                              const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                              int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                              float fastemit_lambda, const float* t_blk, const float* t_emit, const float* t_rest,
+                                              float kd_gscale, float* nll, float* kd, float* dA, float* dC, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  FILL_SEP(c, "joint_loss_kd");
+  FILL_KD(c);
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.nll = nll, c.kd_out = kd, c.dA = dA, c.dC = dC;
+  return run_loss(c);
+}
+
+extern "C" int rnnt_hip_joint_loss_bwd_kd(const float* A, int64_t a_sb, int64_t a_st, const float* C, int64_t c_sb, int64_t c_su,
+                                          const float* bias, const int32_t* labels, const int32_t* t_lens, const int32_t* u_lens,
+                                          int32_t B, int32_t T, int32_t U1, int32_t V, int32_t blank, float gscale,
+                                          float fastemit_lambda, const float* gvec, int32_t gvec_stride, const float* t_blk,
+                                          const float* t_emit, const float* t_rest, float kd_gscale, const float* kd_gvec,
+                                          int32_t kd_gvec_stride, float* dA, float* dC, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  FILL_SEP(c, "joint_loss_bwd_kd");
+  FILL_KD(c);
+  c.gscale = gscale, c.fastemit_lambda = fastemit_lambda, c.gvec = gvec, c.gvec_stride = gvec_stride;
+  c.kd_gvec = kd_gvec, c.kd_gvec_stride = kd_gvec_stride, c.dA = dA, c.dC = dC;
   return run_loss_bwd(c);
 }
 

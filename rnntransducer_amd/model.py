@@ -22,6 +22,10 @@ Differences, all inside the hot path:
   * `args.mwer_weight` (default 0.0: off), `args.mwer_nbest` (4) and `args.mwer_max_symbols` (1) add minimum word error rate
     fine-tuning to `training_step`: loss = rnnt + ctc_weight * ctc + mwer_weight * risk, the risk being the expected number of token
     errors over the model's own n-best list (JointNet.mwer_loss).  With the weight at 0 the step is today's, bit for bit.
+  * `args.kd_weight` (default 0.0: off) with `set_teacher(teacher)` adds lattice knowledge distillation to `training_step`: loss =
+    rnnt + ctc_weight * ctc + ilmt_weight * ilm + kd_weight * kd, kd being the collapsed per-cell KL between a frozen teacher model
+    (say the bidirectional offline model, for a unidirectional streaming student) and this one (JointNet.loss's kd_teacher).  The
+    teacher is held outside the module tree: parameters, state_dict, optimizer and checkpoints are those of the student alone.
   * `validation_step` stays on the GPU (the reference moves the module to the CPU at model.py:65-72 because its
     decode is a host loop): fused loss + on-device greedy search; it returns token ids, and texts only if a
     tokenizer object was attached as `self.tokenizer`.
@@ -32,7 +36,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
-from .ops import check_fastemit_lambda, check_ilmt_weight, emit_windows
+from .ops import check_fastemit_lambda, check_ilmt_weight, check_kd_weight, emit_windows
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -87,6 +91,32 @@ class RNNTransducer(_Base):
         self.ilmt_weight = check_ilmt_weight(0.0 if ilmt_weight is None else ilmt_weight)
         if self.mwer_weight > 0.0 and self.ilmt_weight > 0.0:
             raise ValueError("args.mwer_weight > 0 does not combine with args.ilmt_weight > 0: mwer_loss takes no internal-LM term")
+        # lattice knowledge distillation (JointNet.loss's kd_teacher / kd_weight): off at 0; needs set_teacher() before the first step
+        kd_weight = getattr(args, "kd_weight", 0.0)
+        self.kd_weight = check_kd_weight(0.0 if kd_weight is None else kd_weight)
+        if self.kd_weight > 0.0 and self.ar_left is not None:
+            raise ValueError("args.kd_weight > 0 does not combine with args.ar_left / args.ar_right: the distillation term has no windowed form")
+        if self.kd_weight > 0.0 and self.mwer_weight > 0.0:
+            raise ValueError("args.kd_weight > 0 does not combine with args.mwer_weight > 0: mwer_loss takes no teacher")
+        object.__setattr__(self, "_kd_teacher", None)   # a plain attribute: never a submodule (set_teacher)
+
+    def set_teacher(self, teacher):
+        """The teacher of lattice knowledge distillation (args.kd_weight): another RNNTransducer with the same vocabulary and blank,
+        on the same device.  It is put in eval() and its parameters stop requiring grad; it is kept OUTSIDE the module tree, so
+        parameters(), state_dict(), the optimizer and checkpoints stay the student's alone (and .to() / .cuda() do not move it).
+        training_step asks it for its cell log-probabilities on each batch, without a graph.  None removes it.  Returns self."""
+        if teacher is not None:
+            if not isinstance(teacher, RNNTransducer):
+                raise ValueError(f"set_teacher takes an RNNTransducer (or None), got {type(teacher).__name__}")
+            if teacher is self:
+                raise ValueError("set_teacher: a model cannot be its own teacher")
+            if teacher.jointnet.num_classes != self.jointnet.num_classes or teacher.blank_token_id != self.blank_token_id:
+                raise ValueError(f"set_teacher: the teacher's vocabulary ({teacher.jointnet.num_classes} classes, blank "
+                                 f"{teacher.blank_token_id}) must be the student's ({self.jointnet.num_classes}, {self.blank_token_id})")
+            teacher.eval()
+            teacher.requires_grad_(False)
+        object.__setattr__(self, "_kd_teacher", teacher)
+        return self
 
     def forward(self, input_audios, audio_lengths, input_texts, text_lengths):
         # the reference hands these two as python lists (dataloader.py:20,37): validating them costs no device sync
@@ -177,6 +207,12 @@ class RNNTransducer(_Base):
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         lengths = audio_lengths if isinstance(audio_lengths, (list, tuple)) else None
         logging = pl is not None and getattr(self, "_trainer", None) is not None
+        teacher_planes = None
+        if self.kd_weight > 0.0:
+            if self._kd_teacher is None:
+                raise ValueError("args.kd_weight > 0 needs a teacher: call set_teacher(teacher) before training")
+            teacher_planes = self._kd_teacher.jointnet.cell_logprobs(input_audios, tensor_audio_lengths, input_texts, targets,
+                                                                     target_lengths, self.blank_token_id, audio_lengths=lengths)
         if windows is not None and self.mwer_weight > 0.0:
             raise ValueError("args.ar_left / args.ar_right do not combine with args.mwer_weight > 0: mwer_loss takes no emission windows")
         if self.mwer_weight > 0.0:   # rnnt + ctc_weight * ctc + mwer_weight * risk over the model's own n-best list
@@ -191,7 +227,8 @@ class RNNTransducer(_Base):
         loss = self.jointnet.loss(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths,
                                   self.blank_token_id, reduction="mean",   # reduction="mean" (model.py:39), inside the library
                                   audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda,
-                                  emit_windows=windows, ilmt_weight=self.ilmt_weight)
+                                  emit_windows=windows, ilmt_weight=self.ilmt_weight, kd_teacher=teacher_planes,
+                                  kd_weight=self.kd_weight)
         if logging:
             self.log("train_loss", loss, sync_dist=True)
         return {"loss": loss}

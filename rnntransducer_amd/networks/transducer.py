@@ -27,15 +27,21 @@ the n-best list of the frame-synchronous search, with the hypotheses' losses fro
 `loss(..., ilmt_weight=w)` adds internal-LM training: w times the cross-entropy of the internal LM (the joint with the encoder half
 zeroed, minus `ilm_score`) on the transcripts, from the joint's decoder half the fused loss already holds; `ilm_loss` is that term
 alone on text, with no audio and no encoder call (csrc/ilm_loss.hip, ops.IlmLossFn).
+`cell_logprobs` / `loss(..., kd_teacher=, kd_weight=w)` are lattice knowledge distillation: a teacher (any JointNet with the same
+vocabulary: a bidirectional offline model for a streaming student) hands over three floats per lattice cell, and w times the
+collapsed KL between its cells and the student's joins the loss, its gradient through the KD instances of the lattice gradient
+kernels (csrc/loss.hip).
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from ..ops import (MWER_MAX_LEN, CtcLossFn, IlmLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, MwerRiskFn, TimedTokens,
+from ..ops import (MWER_MAX_LEN, CtcLossFn, IlmLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, JointLossKdFn, MwerRiskFn,
+                   TimedTokens,
                    beam_search, beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args,
-                   check_emit_windows, check_fastemit_lambda, check_ilm_weight, check_ilmt_weight, refuse_ilm_weight,
+                   check_emit_windows, check_fastemit_lambda, check_ilm_weight, check_ilmt_weight, check_kd_teacher, check_kd_weight,
+                   refuse_ilm_weight,
                    check_fusion, ctc_beam_search, ctc_greedy, edit_distance, greedy_decode, nbest_pack, nbest_umax, stream_greedy)
 from .decoder import TextPredNet
 from .encoder import AudioTransNet, HipLinear, lengths_to_device
@@ -109,7 +115,7 @@ class JointNet(nn.Module):
 
     def loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int,
              reduction: str = "none", audio_lengths=None, ctc_weight: float = 0.0, return_parts: bool = False,
-             fastemit_lambda: float = 0.0, emit_windows=None, ilmt_weight: float = 0.0):
+             fastemit_lambda: float = 0.0, emit_windows=None, ilmt_weight: float = 0.0, kd_teacher=None, kd_weight: float = 0.0):
         """-log P(y|x) through the fused path (no (B,T,U+1,V) tensor): per utterance, shape (B,) (reduction "none"), or the 0-d
         "mean" / "sum" over the batch (model.py:39 builds the reference's loss with reduction="mean").
         `audio_lengths`: the python list of frame counts the reference's collate hands over next to the tensor (dataloader.py:20,49).
@@ -134,14 +140,23 @@ class JointNet(nn.Module):
         one in the backward on the joint's decoder half the loss already holds; the encoder gets no gradient from it.  FastEmit,
         the windows and the CTC term do not touch it.  A counted target that is the blank gives that row +inf and a zero gradient
         of the term.  With return_parts=True the tuple gains a last element: (total, rnnt, ctc, ilm).  Finite and >= 0; at 0 the
-        term is not computed and every result is bitwise that of a call without the argument."""
+        term is not computed and every result is bitwise that of a call without the argument.
+        `kd_teacher` (an ops.CellLogProbs: a teacher's `cell_logprobs` on THIS batch, rows in the caller's order -- they follow their
+        rows through the ragged sort) with `kd_weight` > 0: lattice knowledge distillation.  The result is rnnt +
+        ctc_weight * ctc + ilmt_weight * ilm + kd_weight * kd, kd being per utterance the sum over its lattice cells of the KL
+        divergence between the teacher's and this model's distributions collapsed to (blank, the cell's label, everything else),
+        under the same reduction.  One small launch in the forward; the gradient comes out of the lattice gradient kernels' KD
+        instances with the transducer term's, FastEmit included.  With return_parts=True the tuple gains a last element, kd.
+        ValueError for a teacher next to emit_windows, planes that are not (B, U+1, T) float32 on the inputs' device, or fewer than 3
+        classes.  Finite and >= 0; at 0, or without a teacher, nothing of it runs and every result is bitwise that of a call without
+        the arguments."""
         return self._reference_terms(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
                                      audio_lengths, ctc_weight, return_parts, fastemit_lambda, emit_windows=emit_windows,
-                                     ilmt_weight=ilmt_weight)[0]
+                                     ilmt_weight=ilmt_weight, kd_teacher=kd_teacher, kd_weight=kd_weight)[0]
 
     def _reference_terms(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction,
                          audio_lengths, ctc_weight, return_parts, fastemit_lambda, want_inv=False, emit_windows=None,
-                         ilmt_weight=0.0):
+                         ilmt_weight=0.0, kd_teacher=None, kd_weight=0.0):
         """The body of loss(): -> (what loss() returns, (enc, targets, t_lens, u_lens, inv)) with the encoder output and the
         per-row tensors in the row order the encoder ran in (length-sorted for a ragged batch; `inv` restores the caller's order,
         None when nothing moved or nobody needs it).  mwer_loss builds its hypothesis term on the same encoder output."""
@@ -154,14 +169,24 @@ class JointNet(nn.Module):
         u_lens = lengths_to_device(target_lengths, dev)
         T, B = input_audios.size(1), input_audios.size(0)
         win = check_emit_windows(emit_windows, B, targets.size(1), dev)
-        rows = (input_audios, input_texts, targets) + (() if win is None else (win[0], win[1]))   # the windows are sorted with their rows
+        kd_weight = check_kd_weight(kd_weight)
+        teacher = check_kd_teacher(kd_teacher, B, targets.size(1) + 1, T, self.num_classes, dev, emit_windows)
+        if kd_weight == 0.0:
+            teacher = None
+        # the windows, and a teacher's planes, are sorted with their rows
+        rows = (input_audios, input_texts, targets) + (() if win is None else (win[0], win[1])) + (() if teacher is None else tuple(teacher))
         rows, t_lens, u_lens, enc_lens, inv = self._ragged_rows(audio_lengths, T, B, dev, t_lens, u_lens, rows,
                                                                 reduction == "none" or want_inv)
         input_audios, input_texts, targets = rows[:3]
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
-        ilm = None
-        if ilmt_weight > 0.0:
+        ilm = kd = None
+        if teacher is not None:
+            outs = JointLossKdFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
+                                     reduction, fastemit_lambda, None, ilmt_weight, rows[-3:], kd_weight)
+            out, kd = outs[0], outs[-1]
+            ilm = outs[1] if ilmt_weight > 0.0 else None
+        elif ilmt_weight > 0.0:
             out, ilm = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
                                          reduction, fastemit_lambda, None if win is None else (rows[3], rows[4]), ilmt_weight)
         elif win is None:
@@ -175,8 +200,11 @@ class JointNet(nn.Module):
         out = out.index_select(0, inv) if unsort else out
         if ilm is not None:
             ilm = ilm.index_select(0, inv) if unsort else ilm
+        if kd is not None:
+            kd = kd.index_select(0, inv) if unsort else kd
         if not with_ctc:
-            return (out if ilm is None else out + ilmt_weight * ilm), shared
+            total = out if ilm is None else out + ilmt_weight * ilm
+            return (total if kd is None else total + kd_weight * kd), shared
         track = ctc_weight != 0.0 and torch.is_grad_enabled()
         with torch.set_grad_enabled(track):
             ctc = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, track, reduction, True)
@@ -184,7 +212,9 @@ class JointNet(nn.Module):
         total = out + ctc_weight * ctc if ctc_weight != 0.0 else out
         if ilm is not None:
             total = total + ilmt_weight * ilm
-        parts = (total, out, ctc) if ilm is None else (total, out, ctc, ilm)
+        if kd is not None:
+            total = total + kd_weight * kd
+        parts = (total, out, ctc) + (() if ilm is None else (ilm,)) + (() if kd is None else (kd,))
         return (parts if return_parts else total), shared
 
     def ilm_loss(self, input_texts, targets, target_lengths, blank: int, reduction: str = "none") -> torch.Tensor:
@@ -369,6 +399,31 @@ class JointNet(nn.Module):
         if inv is None:
             return res
         return Alignment(res.frames.index_select(0, inv), res.score.index_select(0, inv), u_lens.index_select(0, inv))
+
+    @torch.no_grad()
+    def cell_logprobs(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, audio_lengths=None):
+        """The teacher's side of lattice knowledge distillation: this model's distribution in every lattice cell of
+        the batch, collapsed to (blank, the cell's label, everything else).  Arguments as `loss`, with the same ragged handling
+        under `audio_lengths`.  Returns an ops.CellLogProbs of three (B, U+1, T) fp32 planes in the caller's row order, for another
+        model's `loss(..., kd_teacher=)` on the same batch: the encoder, the prediction net, the joint's two small products and one
+        launch; no lattice sweep, no (B,T,U+1,V) tensor, no graph.  Any encoder will do (a bidirectional one for a streaming
+        student); the vocabulary and the blank must be the student's.  eval() mode only, like align."""
+        from ..ops import CellLogProbs, joint_cell_logprobs, _need_gpu
+        if self.training:
+            raise RuntimeError("cell_logprobs expects eval() mode (dropout inactive), like align")
+        if not 0 <= int(blank) < self.num_classes:
+            raise ValueError(f"cell_logprobs: blank {blank} outside [0,{self.num_classes})")
+        _need_gpu(input_audios, input_texts, targets)
+        dev = input_audios.device
+        t_lens = lengths_to_device(tensor_audio_lengths, dev)
+        u_lens = lengths_to_device(target_lengths, dev)
+        T, B = input_audios.size(1), input_audios.size(0)
+        (input_audios, input_texts, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), True)
+        enc = self.encoder.forward_time_major(input_audios, enc_lens)
+        dec = self.decoder.forward_time_major(input_texts, u_lens + 1)
+        res = joint_cell_logprobs(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, int(blank))
+        return res if inv is None else CellLogProbs(*(x.index_select(0, inv) for x in res))
 
     @torch.no_grad()
     def recognize_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, max_iters: int = 3,

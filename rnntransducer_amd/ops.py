@@ -772,6 +772,51 @@ def check_ilmt_weight(ilmt_weight) -> float:
     return w
 
 
+def check_kd_weight(kd_weight) -> float:
+    """The weight of the lattice distillation term (KD; include/rnnt_hip.h): a finite number >= 0."""
+    if isinstance(kd_weight, bool) or not isinstance(kd_weight, (int, float)):
+        raise ValueError(f"kd_weight must be a number, finite and >= 0, got {kd_weight!r}")
+    w = float(kd_weight)
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"kd_weight must be finite and >= 0, got {kd_weight!r}")
+    return w
+
+
+class CellLogProbs(NamedTuple):
+    """A model's collapsed per-cell log-probabilities over a batch's lattices (include/rnnt_hip.h, lattice distillation): three
+    (B, U+1, T) fp32 planes, plane[b, u, t] -- log p(blank), log p(y_u), and log of everything else (every non-blank entry where the
+    row has no label left).  What a teacher hands to a student's loss (`kd_teacher=`)."""
+    blk: torch.Tensor
+    emit: torch.Tensor
+    rest: torch.Tensor
+
+
+def check_kd_teacher(kd_teacher, B: int, U1: int, T: int, V: int, device, emit_windows=None):
+    """The `kd_teacher` argument of the losses: None, or a CellLogProbs of three (B, U1, T) float32 tensors on `device` (made
+    contiguous here).  ValueError for anything else, for V < 3 (the third class would be empty) and for emission windows next to a
+    teacher, before anything runs."""
+    if kd_teacher is None:
+        return None
+    if not isinstance(kd_teacher, (tuple, list)) or len(kd_teacher) != 3:
+        raise ValueError(f"kd_teacher must be None or a CellLogProbs (blk, emit, rest), got {type(kd_teacher).__name__}")
+    if emit_windows is not None:
+        raise ValueError("kd_teacher does not combine with emit_windows: the distillation term has no windowed form")
+    if V < 3:
+        raise ValueError(f"kd_teacher needs a vocabulary of at least 3 entries (blank, label, rest), got V = {V}")
+    out = []
+    for name, t in zip(("kd_teacher.blk", "kd_teacher.emit", "kd_teacher.rest"), kd_teacher):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if tuple(t.shape) != (B, U1, T):
+            raise ValueError(f"{name} must be (B, U+1, T) = ({B}, {U1}, {T}), got {tuple(t.shape)}")
+        if t.device != torch.device(device):
+            raise ValueError(f"{name} must be on {device}, got {t.device}")
+        out.append(t.detach().contiguous())
+    return CellLogProbs(*out)
+
+
 def _ilm_forward(Cm, bias, labels, u_lens, blank: int, keep_lse: bool):
     """The internal LM's per-utterance NLL (B,) on Cm (U1,B,V) time-major, and the rows' lse (U1*B) for the backward (or None).
     (B, 0) labels have no storage to point at: u_lens stands in for them, and is never read as labels (every length clamps to 0)."""
@@ -900,6 +945,55 @@ def _sep_loss_backward(A, Cm, bias, labels, t_lens, u_lens, blank: int, windowed
     return dA, dC
 
 
+def _sep_loss_forward_kd(A, Cm, bias, labels, t_lens, u_lens, blank: int, lam: float, teacher):
+    """_sep_loss_forward with a teacher's planes: -> (nll (B,), kd (B,), workspace), the workspace with the student's third plane."""
+    (T, B, V), U1 = A.shape, Cm.shape[0]
+    L = _lib.lib()
+    nws = L.rnnt_hip_joint_loss_kd_workspace_bytes(B, T, U1, V)
+    ws = torch.empty(nws, device=A.device, dtype=torch.uint8)
+    nll, kd = torch.empty(B, device=A.device, dtype=torch.float32), torch.empty(B, device=A.device, dtype=torch.float32)
+    check(L.rnnt_hip_joint_loss_fwd_bwd_kd(*_sep_operands(A, Cm, bias, labels, t_lens, u_lens), B, T, U1, V, int(blank), 1.0, lam,
+                                           _addr(teacher.blk), _addr(teacher.emit), _addr(teacher.rest), 1.0, _addr(nll), _addr(kd), None,
+                                           None, _addr(ws), nws, _stream()), "rnnt_hip_joint_loss_fwd_bwd_kd")
+    return nll, kd, ws
+
+
+def _sep_loss_backward_kd(A, Cm, bias, labels, t_lens, u_lens, blank: int, lam: float, gscale: float, gvec, kvec, stride: int, teacher, ws):
+    """dA, dC of nll and kd together (_sep_loss_forward_kd left `ws`) under their upstream gradients gvec and kvec."""
+    (T, B, V), U1 = A.shape, Cm.shape[0]
+    dA, dC = torch.empty_like(A), torch.empty_like(Cm)
+    check(_lib.lib().rnnt_hip_joint_loss_bwd_kd(*_sep_operands(A, Cm, bias, labels, t_lens, u_lens), B, T, U1, V, blank, gscale, lam,
+                                                _addr(gvec), stride, _addr(teacher.blk), _addr(teacher.emit), _addr(teacher.rest), gscale,
+                                                _addr(kvec), stride, _addr(dA), _addr(dC), _addr(ws), ws.numel(), _stream()),
+          "rnnt_hip_joint_loss_bwd_kd")
+    return dA, dC
+
+
+def joint_cell_logprobs(enc, dec, W, bias, labels, t_lens, u_lens, blank: int) -> CellLogProbs:
+    """The teacher's side of lattice distillation: enc (T,B,Oe), dec (U1,B,Od) time-major, fc.weight, fc.bias, labels (B,U) int32 and
+    the int32 lengths, as JointLossFn takes them -> CellLogProbs of three (B, U1, T) fp32 planes.  The joint's two pre-GEMMs and one
+    launch; no lattice sweep, no graph (the result never requires grad)."""
+    _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
+    with torch.no_grad():
+        enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
+        _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)), " (dataloader.py:21-24)")
+        labels = labels.contiguous()
+        T, B, Oe = enc.shape
+        U1, B2, Od = dec.shape
+        V = W.shape[0]
+        if B2 != B or W.shape[1] != Oe + Od or labels.shape != (B, U1 - 1):
+            raise ValueError(f"shape mismatch: enc {tuple(enc.shape)} dec {tuple(dec.shape)} fc {tuple(W.shape)} "
+                             f"targets {tuple(labels.shape)}")
+        if V < 3:
+            raise ValueError(f"joint_cell_logprobs needs a vocabulary of at least 3 entries (blank, label, rest), got V = {V}")
+        A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
+        out = CellLogProbs(*(torch.empty(B, U1, T, device=enc.device, dtype=torch.float32) for _ in range(3)))
+        check(_lib.lib().rnnt_hip_joint_cell_logprobs(*_sep_operands(A, Cm, bias, labels, t_lens, u_lens), B, T, U1, V, int(blank),
+                                                      _addr(out.blk), _addr(out.emit), _addr(out.rest), _stream()),
+              "rnnt_hip_joint_cell_logprobs")
+    return out
+
+
 class JointLossFn(torch.autograd.Function):
     """enc (T,B,Oe), dec (U1,B,Od) time-major -> per-utterance NLL (B,).  Never builds (B,T,U1,V).
     forward: A/C pre-GEMMs + log-softmax terms + alpha/beta (kept in a workspace); backward: the lattice gradient kernel with
@@ -912,51 +1006,95 @@ class JointLossFn(torch.autograd.Function):
     ilmt_weight > 0 (internal-LM training; csrc/ilm_loss.hip): the function returns (nll, ilm_nll), the second the internal LM's NLL
     of the labels under the same reduction, from one more launch on the C tensor the loss already holds.  The weight itself is the
     caller's to apply: the upstream gradient of ilm_nll reaches the gradient kernel, which adds the term into the lattice's dC (one
-    launch); fc.bias's gradient is then the column sums of that dC.  At 0: one output, the launches and bits of a call without it."""
+    launch); fc.bias's gradient is then the column sums of that dC.  At 0: one output, the launches and bits of a call without it.
+    (Lattice distillation is JointLossKdFn below: this function's arguments plus a teacher's planes.  Both run _joint_loss_forward /
+    _joint_loss_backward.)"""
 
     @staticmethod
     def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0,
                 emit_windows=None, ilmt_weight=0.0):
-        _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
-        ctx.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
-        ctx.ilmt = check_ilmt_weight(ilmt_weight) > 0.0
-        win = check_emit_windows(emit_windows, enc.shape[1], dec.shape[0] - 1, enc.device)
-        w_param, b_param = W, bias
-        enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
-        _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)), " (dataloader.py:21-24)")
-        labels = labels.contiguous()
-        T, B, Oe = enc.shape
-        U1, B2, Od = dec.shape
-        V = W.shape[0]
-        if B2 != B or W.shape[1] != Oe + Od or labels.shape != (B, U1 - 1):
-            raise ValueError(f"shape mismatch: enc {tuple(enc.shape)} dec {tuple(dec.shape)} fc {tuple(W.shape)} "
-                             f"targets {tuple(labels.shape)}")
-        A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
-        nll, ws = _sep_loss_forward(A, Cm, bias, labels, t_lens, u_lens, blank, win, ctx.fastemit_lambda)
-        ctx.windowed = win is not None   # the backward reads the band tables the forward left in the workspace
-        keep = want_grad and any(ctx.needs_input_grad[:4])  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
-        ilm, lse = _ilm_forward(Cm, bias, labels, u_lens, blank, keep) if ctx.ilmt else (None, None)
-        if keep:
-            ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws, *((lse,) if ctx.ilmt else ()))
-            ctx.blank = int(blank)
-            ctx.w_param, ctx.b_param = w_param, b_param
-        ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
-        if ctx.ilmt:
-            return _reduce_loss(nll, ctx.red_scale), _reduce_loss(ilm, ctx.red_scale)
-        return _reduce_loss(nll, ctx.red_scale)   # reduction inside the library: no torch arithmetic on the path
+        return _joint_loss_forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad, reduction, fastemit_lambda,
+                                   emit_windows, ilmt_weight, None, 0.0)
 
     @staticmethod
-    def backward(ctx, g, g_ilm=None):
-        enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws = ctx.saved_tensors[:10]
-        gvec = _f32c(g.to(torch.float32), "grad of the loss")
-        scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
+    def backward(ctx, g, *g_more):
+        return _joint_loss_backward(ctx, g, *g_more) + (None,) * 9
+
+
+class JointLossKdFn(torch.autograd.Function):
+    """JointLossFn with lattice knowledge distillation: the same arguments, then kd_teacher (a CellLogProbs from a
+    teacher on the same batch, or None) and kd_weight.  With a teacher and kd_weight > 0 the function returns one more value, LAST:
+    kd, the collapsed KL between the teacher's and the student's cells per utterance, under the same reduction.  The weight is the
+    caller's to apply; the upstream gradients of nll and kd both reach the KD instances of the lattice gradient kernels (either may be
+    0).  Not with emit_windows.  Without a teacher or at weight 0 nothing of it runs: the outputs, launches and bits of JointLossFn."""
+
+    @staticmethod
+    def forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", fastemit_lambda=0.0,
+                emit_windows=None, ilmt_weight=0.0, kd_teacher=None, kd_weight=0.0):
+        return _joint_loss_forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad, reduction, fastemit_lambda,
+                                   emit_windows, ilmt_weight, kd_teacher, kd_weight)
+
+    @staticmethod
+    def backward(ctx, g, *g_more):
+        return _joint_loss_backward(ctx, g, *g_more) + (None,) * 11
+
+
+# the shared body of the two functions above
+def _joint_loss_forward(ctx, enc, dec, W, bias, labels, t_lens, u_lens, blank, want_grad, reduction, fastemit_lambda, emit_windows,
+                        ilmt_weight, kd_teacher, kd_weight):
+    _need_gpu(enc, dec, W, bias, labels, t_lens, u_lens)
+    ctx.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
+    ctx.ilmt = check_ilmt_weight(ilmt_weight) > 0.0
+    teacher = check_kd_teacher(kd_teacher, enc.shape[1], dec.shape[0], enc.shape[0], W.shape[0], enc.device, emit_windows)
+    ctx.kd = check_kd_weight(kd_weight) > 0.0 and teacher is not None
+    win = check_emit_windows(emit_windows, enc.shape[1], dec.shape[0] - 1, enc.device)
+    w_param, b_param = W, bias
+    enc, dec, W, bias = _f32c(enc, "enc"), _f32c(dec, "dec"), _f32c(W, "fc.weight"), _f32c(bias, "fc.bias")
+    _i32((("targets", labels), ("frame lengths", t_lens), ("target lengths", u_lens)), " (dataloader.py:21-24)")
+    labels = labels.contiguous()
+    T, B, Oe = enc.shape
+    U1, B2, Od = dec.shape
+    V = W.shape[0]
+    if B2 != B or W.shape[1] != Oe + Od or labels.shape != (B, U1 - 1):
+        raise ValueError(f"shape mismatch: enc {tuple(enc.shape)} dec {tuple(dec.shape)} fc {tuple(W.shape)} "
+                         f"targets {tuple(labels.shape)}")
+    A, Cm = _joint_ac(enc, dec, W, Oe, Od, V)
+    kd = None
+    if ctx.kd:
+        nll, kd, ws = _sep_loss_forward_kd(A, Cm, bias, labels, t_lens, u_lens, blank, ctx.fastemit_lambda, teacher)
+    else:
+        nll, ws = _sep_loss_forward(A, Cm, bias, labels, t_lens, u_lens, blank, win, ctx.fastemit_lambda)
+    ctx.windowed = win is not None   # the backward reads the band tables the forward left in the workspace
+    keep = want_grad and any(ctx.needs_input_grad[:4])  # want_grad: the caller's torch.is_grad_enabled() (always off in here)
+    ilm, lse = _ilm_forward(Cm, bias, labels, u_lens, blank, keep) if ctx.ilmt else (None, None)
+    if keep:
+        ctx.save_for_backward(enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws, *((lse,) if ctx.ilmt else ()),
+                              *(teacher if ctx.kd else ()))
+        ctx.blank = int(blank)
+        ctx.w_param, ctx.b_param = w_param, b_param
+    ctx.red_scale = {"none": None, "sum": 1.0, "mean": 1.0 / B}[reduction]
+    if ctx.ilmt or ctx.kd:
+        return tuple(_reduce_loss(x, ctx.red_scale) for x in (nll, ilm, kd) if x is not None)
+    return _reduce_loss(nll, ctx.red_scale)   # reduction inside the library: no torch arithmetic on the path
+
+def _joint_loss_backward(ctx, g, *g_more):
+    """-> (d_enc, d_dec, dW, db)"""
+    enc, dec, W, bias, labels, t_lens, u_lens, A, Cm, ws = ctx.saved_tensors[:10]
+    gvec = _f32c(g.to(torch.float32), "grad of the loss")
+    scalar = ctx.red_scale is not None   # reduced loss: ONE upstream scalar, the 1/B of "mean" rides in gscale
+    if ctx.kd:   # both upstream gradients, of nll and of kd (the last output), in one pass of the KD gradient instances
+        kvec = _f32c(g_more[-1].to(torch.float32), "grad of the distillation term")
+        dA, dC = _sep_loss_backward_kd(A, Cm, bias, labels, t_lens, u_lens, ctx.blank, ctx.fastemit_lambda,
+                                       ctx.red_scale if scalar else 1.0, gvec, kvec, 0 if scalar else 1,
+                                       CellLogProbs(*ctx.saved_tensors[-3:]), ws)
+    else:
         dA, dC = _sep_loss_backward(A, Cm, bias, labels, t_lens, u_lens, ctx.blank, ctx.windowed, ctx.fastemit_lambda,
                                     ctx.red_scale if scalar else 1.0, gvec, 0 if scalar else 1, ws)
-        if ctx.ilmt:   # the internal-LM term's gradient lands in the dC the lattice kernel has just written; db then comes from dC
-            _ilm_backward(Cm, bias, labels, u_lens, ctx.saved_tensors[10], ctx.blank, g_ilm, ctx.red_scale, True, dC)
-        d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
-                                               _direct_grad(ctx.w_param), _direct_grad(ctx.b_param), db_from_c=ctx.ilmt)
-        return d_enc, d_dec, dW, db, None, None, None, None, None, None, None, None, None
+    if ctx.ilmt:   # the internal-LM term's gradient lands in the dC the lattice kernel has just written; db then comes from dC
+        _ilm_backward(Cm, bias, labels, u_lens, ctx.saved_tensors[10], ctx.blank, g_more[0], ctx.red_scale, True, dC)
+    d_enc, d_dec, dW, db = _joint_backward(enc, dec, W, dA, dC, ctx.needs_input_grad[:4],
+                                           _direct_grad(ctx.w_param), _direct_grad(ctx.b_param), db_from_c=ctx.ilmt)
+    return d_enc, d_dec, dW, db
 
 
 class JointLossGroupedFn(torch.autograd.Function):
