@@ -591,6 +591,42 @@ int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_st, const i
                         int32_t blank, int32_t* tokens, int32_t* counts, int32_t* frames, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CTC forced alignment: the best (Viterbi) CTC path of a KNOWN transcript, per utterance, on the device.  csrc/ctc.hip, DESIGN.md §28.
+ * Operands and limits are those of rnnt_hip_ctc_loss_fwd: strides z_sb, z_st >= V (batch- and time-major buffers both work),
+ * U <= 511, any V, U = 0 allowed (labels, first, last and token_logp may then be NULL); frames t >= t_lens[b] and labels past
+ * u_lens[b] are never read; t_lens / u_lens are clamped to [0,T] / [0,U].
+ *   lp[t,v] is the fp32 log-softmax the CTC loss computes (the same emission rows em[b][r][t] of the same kernel: the all-path loss
+ *   and the best path are functions of the same fp32 numbers).  The (max, +) form of the alpha recurrence above, over l' of
+ *   S = 2 U_b + 1 states:
+ *     v_0(0) = lp[0,blank], v_0(1) = lp[0,y_0], everything else -inf
+ *     v_t(s) = lp[t,l'_s] + max( v_{t-1}(s), v_{t-1}(s-1), [l'_s != blank and l'_s != l'_{s-2}] v_{t-1}(s-2) )
+ *     score  = max( v_{T_b-1}(S-1), v_{T_b-1}(S-2) )
+ *   accumulated in fp64 from the fp32 terms: no transcendental after the log-softmax, as in rnnt_hip_joint_align.
+ * Tie rule: candidates are taken in the order written: stay, s-1, s-2.  A later candidate wins only when strictly greater.  At the
+ *   end the last label state S-2 wins only when strictly greater than the trailing blank S-1.  The path is then a pure function of lp.
+ * Outputs: first, last (B,U) int32: the first and last frame the best path spends in label u's state;
+ *     first[u] <= last[u] < first[u+1], all inside [0, t_lens[b]); -1 for u >= u_lens[b].
+ *   path (B,T) int32 or NULL: the token of the path's state at frame t (the blank id in blank states), -1 for t >= t_lens[b].
+ *   token_logp (B,U) fp64 or NULL: sum_{t=first..last} lp[t,y_u], summed in ascending t; 0 for u >= u_lens[b].
+ *   score (B) fp64 (<= -nll of rnnt_hip_ctc_loss_fwd, which sums over all paths).
+ * Edge rows: a row with no path (t_lens[b] < u_lens[b] + number of k with y_k = y_{k+1}; also t_lens[b] = 0) gives score = -inf,
+ *   first = last = -1, path = -1, token_logp = 0, and every other row is untouched by it.  u_lens[b] = 0 is the all-blank path:
+ *   finite score, no frames.  Row b gives the same bits alone as in any batch; two calls give the same bits.
+ * Workspace, rnnt_hip_ctc_align_workspace_bytes(B, T, U, V) bytes (0 for B, T or V < 1 or U < 0), with r(x) = x rounded up to 256:
+ *     r(4 B (U+1) T)  emission rows em[b][r][t] (r = 0: blank, r = k+1: y_k), at offset 0
+ *   + r(4 B T)        the frames' log-sum-exp
+ *   + r(4 B (U+1))    the terms kernel's label chains (not used by the alignment)
+ *   + r(12 B (U+1) ceil(T/32))   back-pointers: three bits per (frame, label position), in three planes of 32-frame words
+ *   + r(4 B)          the end state of each row.
+ * Three launches (terms, sweep, back-trace); arguments are validated before any device work; nothing allocates or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t U, int32_t V);
+int rnnt_hip_ctc_align(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
+                       const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, int32_t* first,
+                       int32_t* last, int32_t* path, double* token_logp, double* score, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CTC prefix beam search on per-frame logits (the encoder's CTC head), optionally with token fusion.  csrc/ctc_beam.hip, DESIGN.md §19.
  * Logits, strides and t_lens as for the CTC entries above (t_lens[b] is clamped to [0,T]; frames t >= t_lens[b] are never read).
  * Per utterance, lp[t,v] is the fp32 log-softmax of the logits row, as the CTC loss computes it.  A hypothesis is a prefix l (a token

@@ -295,6 +295,10 @@ SYMBOLS = {
                                         c_i32, C.c_float, C.c_void_p, c_i32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnnt_hip_ctc_greedy": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "rnnt_hip_ctc_align_workspace_bytes": (C.c_size_t, [c_i32] * 4),
+    "rnnt_hip_ctc_align": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32, c_i32,
+                                     c_i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "rnnt_hip_ctc_beam_workspace_bytes": (C.c_size_t, [c_i32] * 4),
     "rnnt_hip_ctc_beam_search": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_float,
                                            C.POINTER(BeamFusion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,4 +1,5 @@
-// CTC loss on the encoder's logits, and the greedy (best-path) CTC decode, for gfx950.  DESIGN.md §16.
+// CTC loss on the encoder's logits, the greedy (best-path) CTC decode, and the forced alignment of a known transcript, for gfx950.
+// DESIGN.md §16, §28.
 //
 // Per utterance b: frames t < T_b, labels y_0..y_{U_b-1}, extended sequence l' of S = 2 U_b + 1 states (l'_{2k} = blank,
 // l'_{2k+1} = y_k), lp[t,v] = z[t,v] - logsumexp_v z[t,:].
@@ -21,6 +22,10 @@
 //   ctc_grad_kernel      : grid (32-frame tile, utterance); occupancies of the tile in LDS, then softmax - sum occ per frame; equal
 //                          labels are summed along their chain by the lane of the first occurrence: fixed order, no float atomics
 //   ctc_greedy_kernel    : a workgroup per utterance: argmax per frame (ties to the lowest index), collapse, ballot compaction
+//   ctc_viterbi_kernel<K>: forced alignment: the alpha sweep in the (max, +) semiring on the same emission rows, one wavefront per
+//                          utterance, three back-pointer bits per (frame, position) packed into 32-frame words
+//   ctc_backtrace_kernel : a workgroup per utterance: the best path walked backwards a word at a time, then first / last / path /
+//                          token_logp
 #include "common.hpp"
 #include "lattice_shared.hpp"
 
@@ -446,6 +451,262 @@ int check_ctc(const char* what, const void* logits, int64_t z_sb, int64_t z_st, 
   return RNNT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// forced alignment: the alpha sweep above in the (max, +) semiring, one wavefront per utterance, same lane ownership.
+//   v_t(s) = lp[t,l'_s] + max( v_{t-1}(s), v_{t-1}(s-1), [l'_s != blank and l'_s != l'_{s-2}] v_{t-1}(s-2) )
+// fp64 sums of the fp32 emission rows, no transcendental.  TIE RULE: the candidates are taken in the order written (stay, s-1, s-2)
+// and a later one wins only when strictly greater, so a -inf candidate never beats a -inf incumbent and the path is a pure function
+// of lp.  Back-pointers: three bits per (frame, position) in three planes of 32-frame words, bp[b][plane][u][t >> 5] bit (t & 31):
+//   plane 0: the blank state of position u was entered from the label state of position u-1
+//   plane 1: the label state of position u was entered from its own blank state (s-1)
+//   plane 2: the label state of position u was entered from the label state of position u-1 (s-2)
+// (no bit: the state stayed; frame 0 has no predecessor and never a bit).  A lane collects the bits of its K positions in registers
+// and stores the words when the step ends a 32-frame block or the utterance; like every memory operation of the loop the stores go
+// through a buffer resource, with an out-of-range offset when there is nothing to store.
+// ------------------------------------------------------------------------------------------------
+template <int K>
+__global__ void __launch_bounds__(64) ctc_viterbi_kernel(const float* __restrict__ em, const int* __restrict__ labels,
+                                                         const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T,
+                                                         int U, int NW, unsigned* __restrict__ bp, double* __restrict__ score,
+                                                         int* __restrict__ fin) {
+  const int b = blockIdx.x, lane = threadIdx.x, U1 = U + 1;
+  const int Tb = clampi(t_lens[b], 0, T), Ub = clampi(u_lens[b], 0, U);
+  const long rowbase = (long)b * U1 * T;
+  const int cells = U1 * T, pwords = U1 * NW;
+  const int ulo = lane * K;
+  const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(em + rowbase), 0, cells * 4, AB_RSRC);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bp + (long)b * 3 * pwords, 0, 3 * pwords * 4, AB_RSRC);
+  auto ld = [&](int c) -> float {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(re, c >= 0 ? c * 4 : AB_OOB, 0, 0));
+  };
+  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, rw, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
+  auto cellB = [&](int t) -> int { return (t >= 0 && t < Tb) ? t : -1; };
+  auto cellL = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u < Ub) ? (u + 1) * T + t : -1; };
+  const int* yb = labels + (long)b * U;
+  bool skip[K];   // the label state of position u may be entered from the label state of position u-1
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int lo = ulo + k - 1;
+    skip[k] = (lo >= 0 && lo + 1 < Ub) ? (yb[lo] != yb[lo + 1]) : false;
+  }
+  const int nrounds = (Tb + PF - 1) / PF;   // steps beyond Tb touch nothing
+  double sB[K], sL[K];
+  unsigned w0[K], w1[K], w2[K];   // back-pointer bits of the current 32-frame block, one word per plane
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    sB[k] = sL[k] = NEG_INF;
+    w0[k] = w1[k] = w2[k] = 0u;
+  }
+  float pb[PF], pl[PF][K];
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+    pb[j] = ld(cellB(j));
+#pragma unroll
+    for (int k = 0; k < K; ++k) pl[j][k] = ld(cellL(ulo + k, j));
+  }
+  for (int r = 0; r < nrounds; ++r) {
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int t = r * PF + j;
+      const double carry = shfl_up1(sL[K - 1], lane);   // v_{t-1} of the label state before this lane's first blank
+      const float cb = pb[j];
+      float cl[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) cl[k] = pl[j][k];
+      pb[j] = ld(cellB(t + PF));
+#pragma unroll
+      for (int k = 0; k < K; ++k) pl[j][k] = ld(cellL(ulo + k, t + PF));
+      const bool row = t < Tb;
+      const int sh = t & 31, wi = t >> 5;
+      const bool flush = row && (sh == 31 || t == Tb - 1);   // (uniform)
+#pragma unroll
+      for (int k = K - 1; k >= 0; --k) {
+        const int u = ulo + k;
+        const double prevL = k > 0 ? sL[k - 1] : carry;
+        const bool okB = row && u <= Ub, okL = row && u < Ub;
+        double nB, nL;
+        bool c0 = false, c1 = false, c2 = false;
+        if (t == 0) {   // (uniform)
+          nB = u == 0 ? (double)cb : NEG_INF;
+          nL = u == 0 ? (double)cl[k] : NEG_INF;
+        } else {
+          c0 = prevL > sB[k];
+          nB = (double)cb + (c0 ? prevL : sB[k]);
+          c1 = sB[k] > sL[k];
+          double m = c1 ? sB[k] : sL[k];
+          c2 = skip[k] && prevL > m;
+          m = c2 ? prevL : m;
+          c1 = c1 && !c2;
+          nL = (double)cl[k] + m;
+        }
+        const unsigned n0 = (sh == 0 ? 0u : w0[k]) | ((unsigned)c0 << sh);
+        const unsigned n1 = (sh == 0 ? 0u : w1[k]) | ((unsigned)c1 << sh);
+        const unsigned n2 = (sh == 0 ? 0u : w2[k]) | ((unsigned)c2 << sh);
+        w0[k] = n0;
+        w1[k] = n1;
+        w2[k] = n2;
+        stw(n0, (okB && flush) ? u * NW + wi : -1);
+        stw(n1, (okL && flush) ? pwords + u * NW + wi : -1);
+        stw(n2, (okL && flush) ? 2 * pwords + u * NW + wi : -1);
+        sB[k] = okB ? nB : sB[k];
+        sL[k] = okL ? nL : sL[k];
+      }
+    }
+  }
+  // score = max(v(S-1), v(S-2)): the trailing blank of position Ub and the label state before it, which wins only when strictly greater
+  const double prevL = shfl_up1(sL[K - 1], lane);
+  double vB = NEG_INF, vL = NEG_INF;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (ulo + k == Ub) {
+      vB = sB[k];
+      vL = k > 0 ? sL[k - 1] : prevL;
+    }
+  }
+  if (lane == Ub / K) {
+    const bool lab = vL > vB;
+    score[b] = lab ? vL : vB;   // -inf for a row without any path
+    fin[b] = lab ? 1 : 0;
+  }
+}
+
+// Back-trace and outputs of the alignment: one workgroup per utterance.  Thread 0 walks the path backwards a WORD at a time: inside a
+// state the next event is the highest set bit at or below the current frame (a zero word is up to 32 stay steps at once, a set bit is
+// found by a leading-zero count): about 2 U_b + T_b / 32 dependent loads instead of T_b.  The utterance's part of the three planes is
+// first copied to LDS (coalesced) when the host found room for it; otherwise the walk reads the workspace.  Then every thread writes
+// outputs: first / last from the walk, path by a binary search of the frame among the spans, token_logp as the ascending fp64 sum of
+// the label's emission row over its span.  dynamic LDS: first[U1] | last[U1] | ys[U1] | table (in_lds)
+__global__ void __launch_bounds__(256) ctc_backtrace_kernel(const unsigned* __restrict__ bp, const float* __restrict__ em,
+                                                            const int* __restrict__ labels, const int* __restrict__ t_lens,
+                                                            const int* __restrict__ u_lens, const double* __restrict__ score,
+                                                            const int* __restrict__ fin, int T, int U, int NW, int in_lds,
+                                                            int blank, int* __restrict__ first, int* __restrict__ last,
+                                                            int* __restrict__ path, double* __restrict__ token_logp) {
+  extern __shared__ int bt_s[];
+  const int b = blockIdx.x, tid = threadIdx.x, U1 = U + 1;
+  const int Tb = clampi(t_lens[b], 0, T), Ub = clampi(u_lens[b], 0, U);
+  int* first_s = bt_s;
+  int* last_s = first_s + U1;
+  int* ys = last_s + U1;
+  unsigned* tab = reinterpret_cast<unsigned*>(ys + U1);
+  if (score[b] == NEG_INF) {   // (uniform) no path: also Tb = 0
+    for (int u = tid; u < U; u += 256) {
+      first[(long)b * U + u] = -1;
+      last[(long)b * U + u] = -1;
+      if (token_logp) token_logp[(long)b * U + u] = 0.0;
+    }
+    if (path)
+      for (int t = tid; t < T; t += 256) path[(long)b * T + t] = -1;
+    return;
+  }
+  for (int u = tid; u < Ub; u += 256) ys[u] = labels[(long)b * U + u];
+  const unsigned* tp = bp + (long)b * 3 * U1 * NW;
+  int stride = NW, pstride = U1 * NW;
+  if (in_lds) {
+    const int nwb = ((Tb - 1) >> 5) + 1, per = (Ub + 1) * nwb;   // words per row, per plane, this utterance wrote or may read
+    for (int i = tid; i < 3 * per; i += 256) {
+      const int p = i / per, rem = i % per;
+      tab[i] = tp[(long)p * U1 * NW + (rem / nwb) * NW + rem % nwb];
+    }
+    tp = tab;
+    stride = nwb;
+    pstride = per;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int t = Tb - 1, inlab = fin[b] != 0 && Ub > 0, u = inlab ? Ub - 1 : Ub;
+    if (inlab) last_s[u] = t;
+    while (t >= 0) {
+      const int wi = t >> 5;
+      const unsigned mask = 0xffffffffu >> (31 - (t & 31));   // frames <= t of the block
+      if (inlab) {
+        const unsigned b1 = tp[pstride + u * stride + wi] & mask, b2 = tp[2 * pstride + u * stride + wi] & mask;
+        const unsigned w = b1 | b2;
+        if (w == 0u) {
+          t = (t & ~31) - 1;
+          if (t < 0) first_s[u] = 0;   // the path starts in this label state (u = 0)
+          continue;
+        }
+        const int bit = 31 - __clz(w);
+        const int te = (t & ~31) + bit;   // the frame at which the path entered the state: >= 1, frame 0 never carries a bit
+        first_s[u] = te;
+        t = te - 1;
+        if ((b2 >> bit) & 1u) {
+          if (u == 0) break;   // (never on bits this call wrote)
+          last_s[--u] = t;
+        } else {
+          inlab = 0;
+        }
+      } else {
+        const unsigned w = tp[u * stride + wi] & mask;
+        if (w == 0u) {
+          t = (t & ~31) - 1;
+          continue;
+        }
+        if (u == 0) break;   // (never on bits this call wrote)
+        t = (t & ~31) + 31 - __clz(w) - 1;
+        inlab = 1;
+        last_s[--u] = t;
+      }
+    }
+  }
+  __syncthreads();
+  for (int u = tid; u < U; u += 256) {
+    const bool ok = u < Ub;
+    const int f = ok ? clampi(first_s[u], 0, Tb - 1) : -1, l = ok ? clampi(last_s[u], 0, Tb - 1) : -1;
+    first[(long)b * U + u] = f;
+    last[(long)b * U + u] = l;
+    if (token_logp) {
+      double s = 0.0;
+      if (ok) {
+        const float* row = em + ((long)b * U1 + u + 1) * T;
+        for (int t = f; t <= l; ++t) s += (double)row[t];
+      }
+      token_logp[(long)b * U + u] = s;
+    }
+  }
+  if (path) {
+    for (int t = tid; t < T; t += 256) {
+      int tok = -1;
+      if (t < Tb) {
+        int lo = 0, hi = Ub;   // the number of labels whose span starts at or before t
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (first_s[mid] <= t) lo = mid + 1;
+          else hi = mid;
+        }
+        tok = (lo > 0 && t <= last_s[lo - 1]) ? ys[lo - 1] : blank;
+      }
+      path[(long)b * T + t] = tok;
+    }
+  }
+}
+
+struct CtcAlignWs {
+  float *em, *lse;
+  int* chain;
+  unsigned* bp;
+  int* fin;
+  int NW;
+  size_t total;
+};
+
+CtcAlignWs carve_ctc_align(void* ws, int B, int T, int U) {
+  CtcAlignWs w;
+  const size_t U1 = (size_t)U + 1;
+  w.NW = (int)ceil_div(T, 32);
+  char* p = reinterpret_cast<char*>(ws);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
+  w.em = reinterpret_cast<float*>(take((size_t)B * U1 * T * 4));
+  w.lse = reinterpret_cast<float*>(take((size_t)B * T * 4));
+  w.chain = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
+  w.bp = reinterpret_cast<unsigned*>(take((size_t)B * 3 * U1 * w.NW * 4));
+  w.fin = reinterpret_cast<int*>(take((size_t)B * 4));
+  w.total = off;
+  return w;
+}
+
 }  // namespace
 }  // namespace rnnt
 
@@ -521,6 +782,54 @@ extern "C" int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_
   ProfScope prof(RNNT_K_MISC, 4.0 * (double)B * T * V, s);
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(GR_T), 0, s, logits, (long)z_sb, (long)z_st, t_lens, T, V, blank, tokens, counts,
                      frames);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+/* ---- forced alignment under CTC (include/rnnt_hip.h): the terms kernel of the loss, max-plus sweep, back-trace ---- */
+extern "C" size_t rnnt_hip_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t U, int32_t V) {
+  if (B < 1 || T < 1 || U < 0 || V < 1) return 0;
+  return carve_ctc_align(nullptr, B, T, U).total;
+}
+
+extern "C" int rnnt_hip_ctc_align(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
+                                  const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, int32_t* first,
+                                  int32_t* last, int32_t* path, double* token_logp, double* score, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  if (int rc = check_ctc("ctc_align", logits, z_sb, z_st, labels, t_lens, u_lens, B, T, U, V, blank)) return rc;
+  RNNT_CHECK_ARG(score, "ctc_align: null score");
+  RNNT_CHECK_ARG(U == 0 || (first && last), "ctc_align: null first/last");
+  const CtcAlignWs w = carve_ctc_align(workspace, B, T, U);
+  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_align: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  const double cells = (double)B * T * (U + 1);
+  {
+    ProfScope prof(RNNT_K_LSE, 4.0 * (double)B * T * V + 4.0 * cells, s);
+    hipLaunchKernelGGL(ctc_terms_kernel, dim3((unsigned)ceil_div(T, TT), B), dim3(256), 0, s, logits, (long)z_sb, (long)z_st, labels,
+                       t_lens, u_lens, T, U, V, blank, w.em, w.lse, w.chain);
+  }
+  RNNT_CHECK_LAUNCH();
+  // the sweep (read the emission rows, write three bits per position) is booked under the lattice-sweep kind like the sweeps of the
+  // loss, the back-trace under the kind of the small kernels, so that a profile shows its share: the kinds are part of the ABI
+  const int K = (int)ceil_div(U + 1, 64);
+  {
+    ProfScope prof(RNNT_K_ALPHABETA, (4.0 + 3.0 / 8.0) * cells, s);
+#define VT(KK) hipLaunchKernelGGL((ctc_viterbi_kernel<KK>), dim3(B), dim3(64), 0, s, w.em, labels, t_lens, u_lens, T, U, w.NW, w.bp, score, w.fin)
+    switch (K) {
+      case 1: VT(1); break;
+      case 2: VT(2); break;
+      case 3: VT(3); break;
+      case 4: VT(4); break;
+      default: VT(8); break;
+    }
+#undef VT
+  }
+  RNNT_CHECK_LAUNCH();
+  ProfScope prof(RNNT_K_MISC, 3.0 / 8.0 * cells + 4.0 * (double)B * (T + 2 * U), s);
+  const size_t small = (size_t)3 * (U + 1) * 4, table = (size_t)3 * (U + 1) * w.NW * 4;
+  const int in_lds = small + table <= 64 * 1024;
+  hipLaunchKernelGGL(ctc_backtrace_kernel, dim3(B), dim3(256), in_lds ? small + table : small, s, w.bp, w.em, labels, t_lens, u_lens,
+                     score, w.fin, T, U, w.NW, in_lds, blank, first, last, path, token_logp);
   RNNT_CHECK_LAUNCH();
   return RNNT_OK;
 }

@@ -19,6 +19,10 @@ Differences, all inside the hot path:
   * `args.ar_left` / `args.ar_right` (default None: off) make `training_step` train the alignment-restricted loss (Ar-RNN-T): the batch
     then carries an 8th element, a (B, U) int32 table of reference frames (a teacher's `align`, `recognize_ctc_greedy(...,
     return_frames=True)`, an external aligner), and label u may be emitted only at frames [frame - ar_left, frame + ar_right].
+    `args.ar_source = "ctc"` (default "frames": the 8-element contract above) takes the reference from the model's own CTC head
+    instead, on the ordinary 7-element batch: each step aligns ctc_head(encoder output) to the transcript on the device
+    (JointNet.ctc_align's kernels, no second encoder call, no host sync) and label u may be emitted at frames
+    [first[u] - ar_left, last[u] + ar_right] of that best CTC path.  It needs `aux_ctc` and both ar knobs.
   * `args.mwer_weight` (default 0.0: off), `args.mwer_nbest` (4) and `args.mwer_max_symbols` (1) add minimum word error rate
     fine-tuning to `training_step`: loss = rnnt + ctc_weight * ctc + mwer_weight * risk, the risk being the expected number of token
     errors over the model's own n-best list (JointNet.mwer_loss).  With the weight at 0 the step is today's, bit for bit.
@@ -36,7 +40,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
-from .ops import check_fastemit_lambda, check_ilmt_weight, check_kd_weight, emit_windows
+from .ops import CtcEmitWindows, check_fastemit_lambda, check_ilmt_weight, check_kd_weight, emit_windows
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -77,6 +81,16 @@ class RNNTransducer(_Base):
         for name, v in (("args.ar_left", self.ar_left), ("args.ar_right", self.ar_right)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
                 raise ValueError(f"{name} must be an integer >= 0 or None, got {v!r}")
+        # where the windows' reference comes from: "frames" (the batch's 8th element) or "ctc" (the model's own CTC head, every step)
+        ar_source = getattr(args, "ar_source", None)
+        self.ar_source = "frames" if ar_source is None else ar_source
+        if self.ar_source not in ("frames", "ctc"):
+            raise ValueError(f"args.ar_source must be 'frames' or 'ctc', got {ar_source!r}")
+        if self.ar_source == "ctc":
+            if self.ar_left is None:
+                raise ValueError("args.ar_source = 'ctc' needs args.ar_left and args.ar_right")
+            if not self.jointnet.aux_ctc:
+                raise ValueError("args.ar_source = 'ctc' needs the CTC head: set jointnet_params['aux_ctc'] = True")
         self.ctc_weight = float(getattr(args, "ctc_weight", 0.0) or 0.0)
         if self.ctc_weight > 0.0 and not self.jointnet.aux_ctc:
             raise ValueError("args.ctc_weight > 0 needs the CTC head: set jointnet_params['aux_ctc'] = True")
@@ -198,7 +212,11 @@ class RNNTransducer(_Base):
     def training_step(self, batch, batch_idx):
         assert not getattr(self.args, "move_metrics_to_cpu", False), "DDP only (model.py:53)"
         windows = None
-        if self.ar_left is not None:   # alignment-restricted loss: the batch's 8th element is the (B, U) reference frame table
+        if self.ar_left is not None and self.ar_source == "ctc":   # alignment-restricted loss around the CTC head's own best path
+            if len(batch) != 7:
+                raise ValueError(f"args.ar_source = 'ctc': training_step takes the ordinary 7-element batch, got {len(batch)} elements")
+            windows = CtcEmitWindows(self.ar_left, self.ar_right)
+        elif self.ar_left is not None:   # alignment-restricted loss: the batch's 8th element is the (B, U) reference frame table
             if len(batch) != 8:
                 raise ValueError(f"args.ar_left / args.ar_right are set: training_step takes an 8-element batch whose last element is "
                                  f"the (B, U) int32 reference frame table, got {len(batch)} elements")
@@ -239,6 +257,13 @@ class RNNTransducer(_Base):
         input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
         return self.jointnet.align(input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
                                    audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None)
+
+    def ctc_align(self, batch, **kw):
+        """JointNet.ctc_align on the 7-tuple batch of training_step with this model's blank: per utterance the first and last frame of
+        each label on the CTC head's best path, and that path's score (ops.CtcAlignment; return_path=, return_token_logp=)."""
+        input_audios, audio_lengths, tensor_audio_lengths, input_texts, text_lengths, targets, target_lengths = batch
+        return self.jointnet.ctc_align(input_audios, tensor_audio_lengths, targets, target_lengths, self.blank_token_id,
+                                       audio_lengths=audio_lengths if isinstance(audio_lengths, (list, tuple)) else None, **kw)
 
     def ilm_loss(self, input_texts, targets, target_lengths, reduction: str = "mean"):
         """JointNet.ilm_loss with this model's blank: the internal-LM loss on text alone (text-only internal-LM adaptation; no

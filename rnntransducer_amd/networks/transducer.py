@@ -31,6 +31,9 @@ alone on text, with no audio and no encoder call (csrc/ilm_loss.hip, ops.IlmLoss
 vocabulary: a bidirectional offline model for a streaming student) hands over three floats per lattice cell, and w times the
 collapsed KL between its cells and the student's joins the loss, its gradient through the KD instances of the lattice gradient
 kernels (csrc/loss.hip).
+`ctc_align` is the forced alignment of a known transcript under the CTC head: per label the span of frames it holds on the best CTC
+path, the path's score, on request the token per frame and per-label log-probabilities, from the encoder alone (csrc/ctc.hip,
+DESIGN.md §28); `loss(..., emit_windows=ops.CtcEmitWindows(left, right))` feeds the alignment-restricted loss from it every step.
 """
 import math
 
@@ -38,7 +41,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import (MWER_MAX_LEN, CtcLossFn, IlmLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, JointLossKdFn, MwerRiskFn,
-                   TimedTokens,
+                   TimedTokens, CtcEmitWindows, check_ctc_emit_windows, ctc_align, ctc_emit_windows,
                    beam_search, beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args,
                    check_emit_windows, check_fastemit_lambda, check_ilm_weight, check_ilmt_weight, check_kd_teacher, check_kd_weight,
                    refuse_ilm_weight,
@@ -134,6 +137,12 @@ class JointNet(nn.Module):
         sort): the alignment-restricted transducer term, label u of row b only at frames lo[b,u] .. hi[b,u] (ops.emit_windows builds
         them around a reference alignment; include/rnnt_hip.h).  A row whose windows leave no path has loss +inf and a zero gradient.
         The CTC term is untouched.  None: the unrestricted loss.
+        `emit_windows` = ops.CtcEmitWindows(left, right) (aux_ctc=True only): the windows come from the model's own CTC head.  After
+        the one encoder forward, ctc_head(encoder output) is computed once (shared with the CTC term when that is on), its detached
+        values are aligned to `targets` without a graph (ops.ctc_align), and label u may be emitted at frames first[u] - left ..
+        last[u] + right of the head's best path; a row without a CTC path gets the full window.  No host sync, no second encoder
+        call.  This cannot produce +inf on a row that has a CTC path: there first[u] <= last[u] < first[u+1], so the transducer
+        path that emits label u at frame first[u] is monotone, inside every window and inside [0, T_b).
         `ilmt_weight` > 0: internal-LM training (ILMT): the result is rnnt + ctc_weight * ctc + ilmt_weight * ilm,
         ilm being the cross-entropy of the internal LM (the joint with the encoder half zeroed, over the non-blank tokens: minus
         `ilm_score`) on `targets`, a per-utterance sum over tokens under the same reduction.  It costs one launch in the forward and
@@ -168,7 +177,11 @@ class JointNet(nn.Module):
         t_lens = lengths_to_device(tensor_audio_lengths, dev)
         u_lens = lengths_to_device(target_lengths, dev)
         T, B = input_audios.size(1), input_audios.size(0)
-        win = check_emit_windows(emit_windows, B, targets.size(1), dev)
+        ctc_win = None
+        if isinstance(emit_windows, CtcEmitWindows):   # windows from the CTC head's own alignment, built below on the encoder output
+            self._need_ctc_head("loss(emit_windows=CtcEmitWindows(...))")
+            ctc_win = check_ctc_emit_windows(emit_windows)
+        win = None if ctc_win is not None else check_emit_windows(emit_windows, B, targets.size(1), dev)
         kd_weight = check_kd_weight(kd_weight)
         teacher = check_kd_teacher(kd_teacher, B, targets.size(1) + 1, T, self.num_classes, dev, emit_windows)
         if kd_weight == 0.0:
@@ -181,6 +194,12 @@ class JointNet(nn.Module):
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)  # text length = label length + 1 (dataloader.py:39-40)
         ilm = kd = None
+        track = ctc_weight != 0.0 and torch.is_grad_enabled()
+        head, win_pair = None, (None if win is None else (rows[3], rows[4]))
+        if ctc_win is not None:   # ONE ctc_head(enc), shared with the CTC term; its detached values are aligned without a graph
+            with torch.set_grad_enabled(track):
+                head = self.ctc_head(enc)
+            win_pair = ctc_emit_windows(head, targets, t_lens, u_lens, blank, ctc_win)
         if teacher is not None:
             outs = JointLossKdFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
                                      reduction, fastemit_lambda, None, ilmt_weight, rows[-3:], kd_weight)
@@ -188,13 +207,13 @@ class JointNet(nn.Module):
             ilm = outs[1] if ilmt_weight > 0.0 else None
         elif ilmt_weight > 0.0:
             out, ilm = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
-                                         reduction, fastemit_lambda, None if win is None else (rows[3], rows[4]), ilmt_weight)
-        elif win is None:
+                                         reduction, fastemit_lambda, win_pair, ilmt_weight)
+        elif win_pair is None:
             out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
                                     reduction, fastemit_lambda)
         else:
             out = JointLossFn.apply(enc, dec, self.fc.weight, self.fc.bias, targets, t_lens, u_lens, blank, torch.is_grad_enabled(),
-                                    reduction, fastemit_lambda, (rows[3], rows[4]))
+                                    reduction, fastemit_lambda, win_pair)
         unsort = inv is not None and reduction == "none"
         shared = (enc, targets, t_lens, u_lens, inv)
         out = out.index_select(0, inv) if unsort else out
@@ -205,9 +224,8 @@ class JointNet(nn.Module):
         if not with_ctc:
             total = out if ilm is None else out + ilmt_weight * ilm
             return (total if kd is None else total + kd_weight * kd), shared
-        track = ctc_weight != 0.0 and torch.is_grad_enabled()
         with torch.set_grad_enabled(track):
-            ctc = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, track, reduction, True)
+            ctc = CtcLossFn.apply(self.ctc_head(enc) if head is None else head, targets, t_lens, u_lens, blank, track, reduction, True)
         ctc = ctc.index_select(0, inv) if unsort else ctc
         total = out + ctc_weight * ctc if ctc_weight != 0.0 else out
         if ilm is not None:
@@ -252,6 +270,31 @@ class JointNet(nn.Module):
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         out = CtcLossFn.apply(self.ctc_head(enc), targets, t_lens, u_lens, blank, torch.is_grad_enabled(), reduction, True)
         return out if inv is None else out.index_select(0, inv)
+
+    @torch.no_grad()
+    def ctc_align(self, input_audios, tensor_audio_lengths, targets, target_lengths, blank: int, audio_lengths=None,
+                  return_path: bool = False, return_token_logp: bool = False):
+        """CTC forced alignment through the CTC head (csrc/ctc.hip): the best CTC path of the KNOWN transcript
+        `targets` per utterance on ctc_head(encoder output); the prediction net and the joint are not run and no (T, U) lattice is
+        built, so this works with bidirectional encoders and before the transducer is trained.  Arguments and the ragged handling
+        as in `ctc_loss`; results come back in the caller's row order.  Returns an ops.CtcAlignment: `first`, `last` (B,U) int32,
+        the first and last encoder frame each label's state holds on the best path (-1 past target_lengths[b] and in a row
+        without a path), `score` (B,) float64 (-inf without a path), and on request `path` (B,T) int32 (the token per frame, the
+        blank in blank states, -1 past the row's frames) and `token_logp` (B,U) float64 (per label the sum of its
+        log-probabilities over its span).  No host sync."""
+        self._need_ctc_head("ctc_align")
+        dev = input_audios.device
+        t_lens = lengths_to_device(tensor_audio_lengths, dev)
+        u_lens = lengths_to_device(target_lengths, dev)
+        T, B = input_audios.size(1), input_audios.size(0)
+        (input_audios, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, targets), True)
+        enc = self.encoder.forward_time_major(input_audios, enc_lens)
+        res = ctc_align(self.ctc_head(enc), targets, t_lens, u_lens, blank, time_major=True, return_path=return_path,
+                        return_token_logp=return_token_logp)
+        if inv is None:
+            return res
+        return type(res)(*(None if x is None else x.index_select(0, inv) for x in res))
 
     @staticmethod
     def check_mwer_args(nbest, max_symbols, token_min_logp, max_hyp_len, mwer_weight, what: str) -> float:

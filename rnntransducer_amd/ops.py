@@ -1339,6 +1339,85 @@ def ctc_greedy(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, *, time_m
     return [tokens[b, :n[b]].long() for b in range(B)]
 
 
+class CtcAlignment(NamedTuple):
+    """Result of ctc_align, on the device (nothing here has synchronised with the host): `first`, `last` (B,U) int32 — the first and
+    last frame the best CTC path spends in label u's state, -1 for u >= target_lengths[b] and in a row without any path —, `score`
+    (B,) float64 — the log-probability of that path, -inf without one —, `path` (B,T) int32 or None — the token of the path's state
+    per frame, the blank id in blank states, -1 past the row's frames —, `token_logp` (B,U) float64 or None — per label the sum of
+    its log-probabilities over its span."""
+    first: torch.Tensor
+    last: torch.Tensor
+    score: torch.Tensor
+    path: Optional[torch.Tensor]
+    token_logp: Optional[torch.Tensor]
+
+
+class CtcEmitWindows(NamedTuple):
+    """`emit_windows=` of JointNet.loss from the model's own CTC head instead of a (lo, hi) pair: the head's best path of the
+    transcript gives every label a span [first, last], and label u may be emitted at frames first - left .. last + right."""
+    left: int
+    right: int
+
+
+def check_ctc_emit_windows(w: "CtcEmitWindows") -> "CtcEmitWindows":
+    for name, v in (("left", w.left), ("right", w.right)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"CtcEmitWindows: {name} must be an integer >= 0, got {v!r}")
+    return w
+
+
+def ctc_align_workspace_bytes(B: int, T: int, U: int, V: int) -> int:
+    n = _lib.lib().rnnt_hip_ctc_align_workspace_bytes(B, T, U, V)
+    if n == 0:
+        raise ValueError(f"ctc_align: B, T, V must be positive and U >= 0 (B={B} T={T} U={U} V={V})")
+    return n
+
+
+@torch.no_grad()
+def ctc_align(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.Tensor, u_lens: torch.Tensor, blank: int, *,
+              time_major: bool = False, return_path: bool = False, return_token_logp: bool = False,
+              workspace: Optional[torch.Tensor] = None) -> CtcAlignment:
+    """Best CTC path of the known transcripts `labels` (B,U) int32 on logits (B,T,V) (time_major: (T,B,V)) fp32, t_lens / u_lens
+    (B,) int32 (include/rnnt_hip.h: rnnt_hip_ctc_align, csrc/ctc.hip): the CTC loss's per-frame terms, its sweep in the (max, +)
+    semiring, a back-trace.  `workspace` (uint8, >= ctc_align_workspace_bytes): the caller's buffer, allocated here when None; it
+    holds the emission rows afterwards (layout in the header).  -> CtcAlignment; absent outputs are None.  No host sync."""
+    _need_gpu(logits, labels, t_lens, u_lens, workspace)
+    logits = _f32c(logits, "logits")
+    _i32((("targets", labels), ("logit lengths", t_lens), ("target lengths", u_lens)))
+    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    if labels.dim() != 2 or labels.shape[0] != B or t_lens.shape != (B,) or u_lens.shape != (B,):
+        raise ValueError(f"targets must be (B, U) with B = {B} and both lengths (B,), got {tuple(labels.shape)}, "
+                         f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
+    labels, t_lens, u_lens = labels.contiguous(), t_lens.contiguous(), u_lens.contiguous()
+    U, dev, L = labels.shape[1], logits.device, _lib.lib()
+    first = torch.empty(B, U, device=dev, dtype=torch.int32)
+    last = torch.empty(B, U, device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float64)
+    path = torch.empty(B, T, device=dev, dtype=torch.int32) if return_path else None
+    token_logp = torch.empty(B, U, device=dev, dtype=torch.float64) if return_token_logp else None
+    nws = ctc_align_workspace_bytes(B, T, U, V)
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8) if workspace is None else workspace
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous():
+        raise ValueError(f"workspace: expected a contiguous uint8 tensor on {dev}")
+    check(L.rnnt_hip_ctc_align(_addr(logits), z_sb, z_st, _addr(labels) if U else None, _addr(t_lens), _addr(u_lens), B, T, U, V,
+                               int(blank), _addr(first) if U else None, _addr(last) if U else None, _addr(path),
+                               _addr(token_logp) if U else None, _addr(score), _addr(ws), ws.numel() * ws.element_size(), _stream()),
+          "rnnt_hip_ctc_align")
+    return CtcAlignment(first, last, score, path, token_logp)
+
+
+def ctc_emit_windows(logits_tm: torch.Tensor, labels: torch.Tensor, t_lens: torch.Tensor, u_lens: torch.Tensor, blank: int,
+                     w: "CtcEmitWindows"):
+    """(lo, hi) int32 (B, U) for the alignment-restricted loss from the CTC head's logits (T,B,V): lo = first - left, hi = last +
+    right around the head's best path (ctc_align on the detached values); a row without a CTC path gets the full window
+    [0, T-1].  Entries past u_lens[b] are not read by the loss.  No host sync."""
+    al = ctc_align(logits_tm.detach(), labels, t_lens, u_lens, blank, time_major=True)
+    nopath = torch.isinf(al.score).unsqueeze(1)
+    lo = torch.where(nopath, torch.zeros_like(al.first), al.first - w.left)
+    hi = torch.where(nopath, torch.full_like(al.last, logits_tm.shape[0] - 1), al.last + w.right)
+    return lo, hi
+
+
 CTC_BEAM_MAX_WIDTH = 128
 
 
