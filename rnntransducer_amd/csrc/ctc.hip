@@ -15,17 +15,18 @@
 //   ctc_terms_kernel     : row log-sum-exp of every valid frame (a wavefront per frame, lanes along v) and the U_b + 1 emission rows the
 //                          sweep reads, label-major over t: em[b][0][t] = lp[t,blank], em[b][k+1][t] = lp[t,y_k]; the tile-0
 //                          workgroup of an utterance also links equal labels into chains (for the gradient's fixed-order sums)
-//   ctc_sweep_kernel<K>  : one wavefront per (utterance, alpha|beta); lane l owns label positions [l*K, l*K+K), each a blank state
+//   ctc_sweep_kernel<K, MAX> : one wavefront per (utterance, alpha|beta); lane l owns label positions [l*K, l*K+K), each a blank state
 //                          and the label state behind it (position U_b: the trailing blank only); every state steps at every t, the
 //                          neighbour lane's boundary states arrive by DPP; memory operations unconditional through buffer
-//                          resources, per-row values prefetched PF steps ahead (loss.hip explains why)
+//                          resources, per-row values prefetched PF steps ahead (loss.hip explains why).  MAX = true: forced
+//                          alignment, the same alpha sweep in the (max, +) semiring, one wavefront per utterance, three
+//                          back-pointer bits per (frame, position) packed into 32-frame words instead of the cell stores
 //   ctc_grad_kernel      : grid (32-frame tile, utterance); occupancies of the tile in LDS, then softmax - sum occ per frame; equal
 //                          labels are summed along their chain by the lane of the first occurrence: fixed order, no float atomics
 //   ctc_greedy_kernel    : a workgroup per utterance: argmax per frame (ties to the lowest index), collapse, ballot compaction
-//   ctc_viterbi_kernel<K>: forced alignment: the alpha sweep in the (max, +) semiring on the same emission rows, one wavefront per
-//                          utterance, three back-pointer bits per (frame, position) packed into 32-frame words
 //   ctc_backtrace_kernel : a workgroup per utterance: the best path walked backwards a word at a time, then first / last / path /
 //                          token_logp
+// The host half (from struct CtcCall on): one CtcCall per call, one check, four stages behind the exported entries.
 #include "common.hpp"
 #include "lattice_shared.hpp"
 
@@ -97,21 +98,48 @@ __global__ void __launch_bounds__(256) ctc_terms_kernel(const float* __restrict_
 // alpha / beta: one wavefront per (b, which).  Position u of a lane = blank state 2u and label state 2u+1.
 // sB / sL hold alpha_{t-1} (beta_{t+1}) of the lane's states when step t starts; a lane walks its positions against the direction of
 // the dependence, so the neighbour's value it reads is still the previous step's.
+//
+// The semiring is the template flag MAX.  MAX = false, the loss: the sums of the file's header, both directions picked by
+// blockIdx.y, both states of every position stored in fp64, logZ and the NLL at the end of the alpha direction.
+// MAX = true, forced alignment: the alpha direction alone (grid (B, 1); the beta branch is not compiled) in the
+// (max, +) semiring on the same emission rows, same lane ownership:
+//   v_t(s) = lp[t,l'_s] + max( v_{t-1}(s), v_{t-1}(s-1), [l'_s != blank and l'_s != l'_{s-2}] v_{t-1}(s-2) )
+// fp64 sums of the fp32 emission rows, no transcendental.  TIE RULE: the candidates are taken in the order written (stay, s-1, s-2)
+// and a later one wins only when strictly greater, so a -inf candidate never beats a -inf incumbent and the path is a pure function
+// of lp.  Back-pointers in place of the cell stores: three bits per (frame, position) in three planes of 32-frame words,
+// bp[b][plane][u][t >> 5] bit (t & 31):
+//   plane 0: the blank state of position u was entered from the label state of position u-1
+//   plane 1: the label state of position u was entered from its own blank state (s-1)
+//   plane 2: the label state of position u was entered from the label state of position u-1 (s-2)
+// (no bit: the state stayed; frame 0 has no predecessor and never a bit).  A lane collects the bits of its K positions in registers
+// and stores the words when the step ends a 32-frame block or the utterance; like every memory operation of the loop the stores go
+// through a buffer resource, with an out-of-range offset when there is nothing to store.  At the end score = max(v(S-1), v(S-2))
+// goes to ll[b] (-inf for a row without any path) and fin[b] says which of the two it was (the label state wins only when strictly
+// greater).  The MAX instance takes its tables as a trailing CtcBackPtr (the pack is empty for the loss, whose instances keep their
+// kernel-argument block); aB / aL / bB / bL / nll are not read then.
 // ------------------------------------------------------------------------------------------------
-template <int K>
+struct CtcBackPtr {
+  unsigned* bp;   // bp[B][3][U + 1][nw]
+  int nw;         // words per position: ceil(T / 32)
+  int* fin;       // [B]: 1 when the best path ends in the last label state, 0 in the trailing blank
+};
+
+template <int K, bool MAX = false, typename... BT>
 __global__ void __launch_bounds__(64) ctc_sweep_kernel(const float* __restrict__ em, const int* __restrict__ labels,
                                                        const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T,
                                                        int U, double* __restrict__ aB, double* __restrict__ aL,
                                                        double* __restrict__ bB, double* __restrict__ bL,
-                                                       double* __restrict__ ll, float* __restrict__ nll) {
-  const int b = blockIdx.x, which = blockIdx.y, lane = threadIdx.x, U1 = U + 1;
+                                                       double* __restrict__ ll, float* __restrict__ nll, BT... bt) {
+  const int b = blockIdx.x, which = MAX ? 0 : blockIdx.y, lane = threadIdx.x, U1 = U + 1;
+  const CtcBackPtr bk = pick_tables<CtcBackPtr>(bt...);
   const int Tb = clampi(t_lens[b], 0, T), Ub = clampi(u_lens[b], 0, U);
   const long rowbase = (long)b * U1 * T;
-  const int cells = U1 * T;
+  const int cells = U1 * T, NW = bk.nw, pwords = U1 * NW;
   const int ulo = lane * K;
   const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(em + rowbase), 0, cells * 4, AB_RSRC);
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((which == 0 ? aB : bB) + rowbase, 0, cells * 8, AB_RSRC);
   const __amdgpu_buffer_rsrc_t rL = __builtin_amdgcn_make_buffer_rsrc((which == 0 ? aL : bL) + rowbase, 0, cells * 8, AB_RSRC);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bk.bp + (long)b * 3 * pwords, 0, 3 * pwords * 4, AB_RSRC);   // MAX
   auto ld = [&](int c) -> float {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(re, c >= 0 ? c * 4 : AB_OOB, 0, 0));
   };
@@ -119,6 +147,7 @@ __global__ void __launch_bounds__(64) ctc_sweep_kernel(const float* __restrict__
     typedef int i32x2 __attribute__((ext_vector_type(2)));
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, v), r, c >= 0 ? c * 8 : AB_OOB, 0, 0);
   };
+  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, rw, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
   // emission rows: row 0 = blank (the same value for every lane), row u + 1 = label u
   auto cellB = [&](int t) -> int { return (t >= 0 && t < Tb) ? t : -1; };
   auto cellL = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u < Ub) ? (u + 1) * T + t : -1; };
@@ -133,8 +162,12 @@ __global__ void __launch_bounds__(64) ctc_sweep_kernel(const float* __restrict__
   }
   const int nrounds = (Tb + PF - 1) / PF;   // steps beyond Tb touch nothing
   double sB[K], sL[K];
+  [[maybe_unused]] unsigned w0[K], w1[K], w2[K];   // MAX: back-pointer bits of the current 32-frame block, one word per plane
 #pragma unroll
-  for (int k = 0; k < K; ++k) sB[k] = sL[k] = NEG_INF;
+  for (int k = 0; k < K; ++k) {
+    sB[k] = sL[k] = NEG_INF;
+    w0[k] = w1[k] = w2[k] = 0u;
+  }
   float pb[PF], pl[PF][K];
 
   if (which == 0) {
@@ -157,29 +190,54 @@ __global__ void __launch_bounds__(64) ctc_sweep_kernel(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < K; ++k) pl[j][k] = ld(cellL(ulo + k, t + PF));
         const bool row = t < Tb;
+        const int sh = t & 31, wi = t >> 5;
+        const bool flush = row && (sh == 31 || t == Tb - 1);   // (uniform)
 #pragma unroll
         for (int k = K - 1; k >= 0; --k) {
           const int u = ulo + k;
           const double prevL = k > 0 ? sL[k - 1] : carry;
           const bool okB = row && u <= Ub, okL = row && u < Ub;
           double nB, nL;
+          bool c0 = false, c1 = false, c2 = false;   // MAX: the back-pointer bits of this step
           if (t == 0) {   // (uniform)
             nB = u == 0 ? (double)cb : NEG_INF;
             nL = u == 0 ? (double)cl[k] : NEG_INF;
+          } else if constexpr (MAX) {
+            c0 = prevL > sB[k];
+            nB = (double)cb + (c0 ? prevL : sB[k]);
+            c1 = sB[k] > sL[k];
+            double m = c1 ? sB[k] : sL[k];
+            c2 = skip[k] && prevL > m;
+            m = c2 ? prevL : m;
+            c1 = c1 && !c2;
+            nL = (double)cl[k] + m;
           } else {
             nB = (double)cb + logaddexp_d(sB[k], prevL);
             double x = logaddexp_d(sL[k], sB[k]);
             x = skip[k] ? logaddexp_d(x, prevL) : x;
             nL = (double)cl[k] + x;
           }
-          st(rB, nB, okB ? u * T + t : -1);
-          st(rL, nL, okL ? u * T + t : -1);
+          if constexpr (MAX) {
+            const unsigned n0 = (sh == 0 ? 0u : w0[k]) | ((unsigned)c0 << sh);
+            const unsigned n1 = (sh == 0 ? 0u : w1[k]) | ((unsigned)c1 << sh);
+            const unsigned n2 = (sh == 0 ? 0u : w2[k]) | ((unsigned)c2 << sh);
+            w0[k] = n0;
+            w1[k] = n1;
+            w2[k] = n2;
+            stw(n0, (okB && flush) ? u * NW + wi : -1);
+            stw(n1, (okL && flush) ? pwords + u * NW + wi : -1);
+            stw(n2, (okL && flush) ? 2 * pwords + u * NW + wi : -1);
+          } else {
+            st(rB, nB, okB ? u * T + t : -1);
+            st(rL, nL, okL ? u * T + t : -1);
+          }
           sB[k] = okB ? nB : sB[k];
           sL[k] = okL ? nL : sL[k];
         }
       }
     }
     // logZ = logaddexp(alpha(S-1), alpha(S-2)): the trailing blank of position Ub and the label state before it
+    // (MAX: score = max of the two, the label state only when strictly greater)
     const double prevL = shfl_up1(sL[K - 1], lane);
     double vB = NEG_INF, vL = NEG_INF;
 #pragma unroll
@@ -190,11 +248,17 @@ __global__ void __launch_bounds__(64) ctc_sweep_kernel(const float* __restrict__
       }
     }
     if (lane == Ub / K) {
-      const double z = logaddexp_d(vB, vL);
-      ll[b] = z;
-      nll[b] = (float)(-z);
+      if constexpr (MAX) {
+        const bool lab = vL > vB;
+        ll[b] = lab ? vL : vB;
+        bk.fin[b] = lab ? 1 : 0;
+      } else {
+        const double z = logaddexp_d(vB, vL);
+        ll[b] = z;
+        nll[b] = (float)(-z);
+      }
     }
-  } else {
+  } else if constexpr (!MAX) {
 #pragma unroll
     for (int j = 0; j < PF; ++j) {
       pb[j] = ld(cellB(Tb - 1 - j));
@@ -408,168 +472,6 @@ __global__ void __launch_bounds__(GR_T) ctc_greedy_kernel(const float* __restric
   if (tid == 0) counts[b] = base;
 }
 
-struct CtcWs {
-  float *em, *lse;
-  double *aB, *aL, *bB, *bL, *ll;
-  int* chain;
-  size_t total;
-};
-
-CtcWs carve_ctc(void* ws, int B, int T, int U) {
-  CtcWs w;
-  const size_t cells = (size_t)B * T * (U + 1);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  w.aB = reinterpret_cast<double*>(take(cells * 8));
-  w.aL = reinterpret_cast<double*>(take(cells * 8));
-  w.bB = reinterpret_cast<double*>(take(cells * 8));
-  w.bL = reinterpret_cast<double*>(take(cells * 8));
-  w.ll = reinterpret_cast<double*>(take((size_t)B * 8));
-  w.em = reinterpret_cast<float*>(take(cells * 4));
-  w.lse = reinterpret_cast<float*>(take((size_t)B * T * 4));
-  w.chain = reinterpret_cast<int*>(take((size_t)B * (U + 1) * 4));
-  w.total = off;
-  return w;
-}
-
-constexpr size_t LDS_MAX = 160 * 1024;
-size_t grad_lds_bytes(int U, int V) {
-  return (size_t)TT * (U + 1) * 4 + (8 * TT + 2 * TT) * 4 + (size_t)(U + 1) * 8 + (size_t)ceil_div(V, 32) * 4;
-}
-
-int check_ctc(const char* what, const void* logits, int64_t z_sb, int64_t z_st, const void* labels, const void* t_lens,
-              const void* u_lens, int B, int T, int U, int V, int blank) {
-  RNNT_CHECK_ARG(B >= 1 && T >= 1 && U >= 0 && V >= 1, "%s: B, T, V must be positive and U >= 0 (B=%d T=%d U=%d V=%d)", what, B, T, U, V);
-  RNNT_CHECK_ARG(blank >= 0 && blank < V, "%s: blank %d outside [0,%d)", what, blank, V);
-  RNNT_CHECK_ARG(U <= 511, "%s: U = %d exceeds the 511 labels one wavefront sweeps", what, U);
-  RNNT_CHECK_ARG((int64_t)(U + 1) * T * 8 < (1ll << 31), "%s: one utterance's lattice (T = %d x U+1 = %d, fp64) exceeds the 2 GB a buffer resource addresses", what, T, U + 1);
-  RNNT_CHECK_ARG(grad_lds_bytes(U, V) <= LDS_MAX, "%s: V = %d with U = %d does not fit the gradient kernel's LDS tables", what, V, U);
-  RNNT_CHECK_ARG(logits && t_lens && u_lens, "%s: null logits/lengths", what);
-  RNNT_CHECK_ARG(U == 0 || labels, "%s: null labels", what);
-  RNNT_CHECK_ARG(z_sb >= 1 && z_st >= V, "%s: logits strides (z_sb = %lld, z_st = %lld) must be positive, z_st >= V", what, (long long)z_sb, (long long)z_st);
-  return RNNT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// forced alignment: the alpha sweep above in the (max, +) semiring, one wavefront per utterance, same lane ownership.
-//   v_t(s) = lp[t,l'_s] + max( v_{t-1}(s), v_{t-1}(s-1), [l'_s != blank and l'_s != l'_{s-2}] v_{t-1}(s-2) )
-// fp64 sums of the fp32 emission rows, no transcendental.  TIE RULE: the candidates are taken in the order written (stay, s-1, s-2)
-// and a later one wins only when strictly greater, so a -inf candidate never beats a -inf incumbent and the path is a pure function
-// of lp.  Back-pointers: three bits per (frame, position) in three planes of 32-frame words, bp[b][plane][u][t >> 5] bit (t & 31):
-//   plane 0: the blank state of position u was entered from the label state of position u-1
-//   plane 1: the label state of position u was entered from its own blank state (s-1)
-//   plane 2: the label state of position u was entered from the label state of position u-1 (s-2)
-// (no bit: the state stayed; frame 0 has no predecessor and never a bit).  A lane collects the bits of its K positions in registers
-// and stores the words when the step ends a 32-frame block or the utterance; like every memory operation of the loop the stores go
-// through a buffer resource, with an out-of-range offset when there is nothing to store.
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__global__ void __launch_bounds__(64) ctc_viterbi_kernel(const float* __restrict__ em, const int* __restrict__ labels,
-                                                         const int* __restrict__ t_lens, const int* __restrict__ u_lens, int T,
-                                                         int U, int NW, unsigned* __restrict__ bp, double* __restrict__ score,
-                                                         int* __restrict__ fin) {
-  const int b = blockIdx.x, lane = threadIdx.x, U1 = U + 1;
-  const int Tb = clampi(t_lens[b], 0, T), Ub = clampi(u_lens[b], 0, U);
-  const long rowbase = (long)b * U1 * T;
-  const int cells = U1 * T, pwords = U1 * NW;
-  const int ulo = lane * K;
-  const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(em + rowbase), 0, cells * 4, AB_RSRC);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bp + (long)b * 3 * pwords, 0, 3 * pwords * 4, AB_RSRC);
-  auto ld = [&](int c) -> float {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(re, c >= 0 ? c * 4 : AB_OOB, 0, 0));
-  };
-  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, rw, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
-  auto cellB = [&](int t) -> int { return (t >= 0 && t < Tb) ? t : -1; };
-  auto cellL = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u < Ub) ? (u + 1) * T + t : -1; };
-  const int* yb = labels + (long)b * U;
-  bool skip[K];   // the label state of position u may be entered from the label state of position u-1
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int lo = ulo + k - 1;
-    skip[k] = (lo >= 0 && lo + 1 < Ub) ? (yb[lo] != yb[lo + 1]) : false;
-  }
-  const int nrounds = (Tb + PF - 1) / PF;   // steps beyond Tb touch nothing
-  double sB[K], sL[K];
-  unsigned w0[K], w1[K], w2[K];   // back-pointer bits of the current 32-frame block, one word per plane
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    sB[k] = sL[k] = NEG_INF;
-    w0[k] = w1[k] = w2[k] = 0u;
-  }
-  float pb[PF], pl[PF][K];
-#pragma unroll
-  for (int j = 0; j < PF; ++j) {
-    pb[j] = ld(cellB(j));
-#pragma unroll
-    for (int k = 0; k < K; ++k) pl[j][k] = ld(cellL(ulo + k, j));
-  }
-  for (int r = 0; r < nrounds; ++r) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j) {
-      const int t = r * PF + j;
-      const double carry = shfl_up1(sL[K - 1], lane);   // v_{t-1} of the label state before this lane's first blank
-      const float cb = pb[j];
-      float cl[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) cl[k] = pl[j][k];
-      pb[j] = ld(cellB(t + PF));
-#pragma unroll
-      for (int k = 0; k < K; ++k) pl[j][k] = ld(cellL(ulo + k, t + PF));
-      const bool row = t < Tb;
-      const int sh = t & 31, wi = t >> 5;
-      const bool flush = row && (sh == 31 || t == Tb - 1);   // (uniform)
-#pragma unroll
-      for (int k = K - 1; k >= 0; --k) {
-        const int u = ulo + k;
-        const double prevL = k > 0 ? sL[k - 1] : carry;
-        const bool okB = row && u <= Ub, okL = row && u < Ub;
-        double nB, nL;
-        bool c0 = false, c1 = false, c2 = false;
-        if (t == 0) {   // (uniform)
-          nB = u == 0 ? (double)cb : NEG_INF;
-          nL = u == 0 ? (double)cl[k] : NEG_INF;
-        } else {
-          c0 = prevL > sB[k];
-          nB = (double)cb + (c0 ? prevL : sB[k]);
-          c1 = sB[k] > sL[k];
-          double m = c1 ? sB[k] : sL[k];
-          c2 = skip[k] && prevL > m;
-          m = c2 ? prevL : m;
-          c1 = c1 && !c2;
-          nL = (double)cl[k] + m;
-        }
-        const unsigned n0 = (sh == 0 ? 0u : w0[k]) | ((unsigned)c0 << sh);
-        const unsigned n1 = (sh == 0 ? 0u : w1[k]) | ((unsigned)c1 << sh);
-        const unsigned n2 = (sh == 0 ? 0u : w2[k]) | ((unsigned)c2 << sh);
-        w0[k] = n0;
-        w1[k] = n1;
-        w2[k] = n2;
-        stw(n0, (okB && flush) ? u * NW + wi : -1);
-        stw(n1, (okL && flush) ? pwords + u * NW + wi : -1);
-        stw(n2, (okL && flush) ? 2 * pwords + u * NW + wi : -1);
-        sB[k] = okB ? nB : sB[k];
-        sL[k] = okL ? nL : sL[k];
-      }
-    }
-  }
-  // score = max(v(S-1), v(S-2)): the trailing blank of position Ub and the label state before it, which wins only when strictly greater
-  const double prevL = shfl_up1(sL[K - 1], lane);
-  double vB = NEG_INF, vL = NEG_INF;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    if (ulo + k == Ub) {
-      vB = sB[k];
-      vL = k > 0 ? sL[k - 1] : prevL;
-    }
-  }
-  if (lane == Ub / K) {
-    const bool lab = vL > vB;
-    score[b] = lab ? vL : vB;   // -inf for a row without any path
-    fin[b] = lab ? 1 : 0;
-  }
-}
-
 // Back-trace and outputs of the alignment: one workgroup per utterance.  Thread 0 walks the path backwards a WORD at a time: inside a
 // state the next event is the highest set bit at or below the current frame (a zero word is up to 32 stay steps at once, a set bit is
 // found by a leading-zero count): about 2 U_b + T_b / 32 dependent loads instead of T_b.  The utterance's part of the three planes is
@@ -682,29 +584,161 @@ __global__ void __launch_bounds__(256) ctc_backtrace_kernel(const unsigned* __re
   }
 }
 
-struct CtcAlignWs {
+// ------------------------------------------------------------------------------------------------
+// Host half, after the pattern of loss.hip.  Every exported loss / alignment entry fills ONE description of its call, a CtcCall,
+// checks the whole call before any device work (check_ctc, which also carves the workspace) and then composes the stages:
+// terms -> sweep (forward), grad (backward, on the workspace the forward left), terms -> viterbi + back-trace (alignment).
+// ------------------------------------------------------------------------------------------------
+struct CtcCall {
+  const char* who = "";   // the entry's name, for messages
+  const float* logits = nullptr;
+  int64_t z_sb = 0, z_st = 0;
+  const int32_t *labels = nullptr, *t_lens = nullptr, *u_lens = nullptr;
+  int B = 0, T = 0, U = 0, V = 0, blank = 0;
+  float* nll = nullptr;   // forward
+  // backward: upstream scale, per-utterance upstream gradients, the gradient
+  float gscale = 1.f;
+  const float* gvec = nullptr;
+  int gvec_stride = 0;
+  float* dlogits = nullptr;
+  // alignment
+  int32_t *first = nullptr, *last = nullptr, *path = nullptr;
+  double *token_logp = nullptr, *score = nullptr;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+  hipStream_t stream = nullptr;
+};
+
+struct CtcWs {
   float *em, *lse;
   int* chain;
-  unsigned* bp;
+  double *aB, *aL, *bB, *bL, *ll;   // the loss
+  unsigned* bp;                     // the alignment: back-pointer planes bp[B][3][U + 1][nw = ceil(T/32)] and the final states
   int* fin;
-  int NW;
+  int nw;
   size_t total;
 };
 
-CtcAlignWs carve_ctc_align(void* ws, int B, int T, int U) {
-  CtcAlignWs w;
-  const size_t U1 = (size_t)U + 1;
-  w.NW = (int)ceil_div(T, 32);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align_up(bytes, 256); return q; };
-  w.em = reinterpret_cast<float*>(take((size_t)B * U1 * T * 4));
-  w.lse = reinterpret_cast<float*>(take((size_t)B * T * 4));
-  w.chain = reinterpret_cast<int*>(take((size_t)B * U1 * 4));
-  w.bp = reinterpret_cast<unsigned*>(take((size_t)B * 3 * U1 * w.NW * 4));
-  w.fin = reinterpret_cast<int*>(take((size_t)B * 4));
-  w.total = off;
+enum class CtcDrive { Forward, Backward, Align };
+
+// the loss: alpha (blank, label states) | beta (the same) | logZ | em | lse | chain;  the alignment: em | lse | chain | bp | fin
+CtcWs carve_ctc(void* ws, int B, int T, int U, bool align) {
+  CtcWs w{};
+  Carver c{reinterpret_cast<char*>(ws)};
+  const size_t U1 = (size_t)U + 1, cells = (size_t)B * T * U1;
+  if (!align) {
+    w.aB = c.take<double>(cells * 8);
+    w.aL = c.take<double>(cells * 8);
+    w.bB = c.take<double>(cells * 8);
+    w.bL = c.take<double>(cells * 8);
+    w.ll = c.take<double>((size_t)B * 8);
+  }
+  w.em = c.take<float>(cells * 4);
+  w.lse = c.take<float>((size_t)B * T * 4);
+  w.chain = c.take<int>((size_t)B * U1 * 4);
+  if (align) {
+    w.nw = (int)ceil_div(T, 32);
+    w.bp = c.take<unsigned>((size_t)B * 3 * U1 * w.nw * 4);
+    w.fin = c.take<int>((size_t)B * 4);
+  }
+  w.total = c.off;
   return w;
+}
+
+constexpr size_t LDS_MAX = 160 * 1024;
+size_t grad_lds_bytes(int U, int V) {
+  return (size_t)TT * (U + 1) * 4 + (8 * TT + 2 * TT) * 4 + (size_t)(U + 1) * 8 + (size_t)ceil_div(V, 32) * 4;
+}
+
+// Every argument check of every entry, before any device work; then the workspace, carved, and its size.
+int check_ctc(const CtcCall& c, CtcDrive drive, CtcWs* w) {
+  const char* what = c.who;
+  const int B = c.B, T = c.T, U = c.U, V = c.V;
+  RNNT_CHECK_ARG(B >= 1 && T >= 1 && U >= 0 && V >= 1, "%s: B, T, V must be positive and U >= 0 (B=%d T=%d U=%d V=%d)", what, B, T, U, V);
+  RNNT_CHECK_ARG(c.blank >= 0 && c.blank < V, "%s: blank %d outside [0,%d)", what, c.blank, V);
+  RNNT_CHECK_ARG(U <= 511, "%s: U = %d exceeds the 511 labels one wavefront sweeps", what, U);
+  RNNT_CHECK_ARG((int64_t)(U + 1) * T * 8 < (1ll << 31), "%s: one utterance's lattice (T = %d x U+1 = %d, fp64) exceeds the 2 GB a buffer resource addresses", what, T, U + 1);
+  RNNT_CHECK_ARG(grad_lds_bytes(U, V) <= LDS_MAX, "%s: V = %d with U = %d does not fit the gradient kernel's LDS tables", what, V, U);
+  RNNT_CHECK_ARG(c.logits && c.t_lens && c.u_lens, "%s: null logits/lengths", what);
+  RNNT_CHECK_ARG(U == 0 || c.labels, "%s: null labels", what);
+  RNNT_CHECK_ARG(c.z_sb >= 1 && c.z_st >= V, "%s: logits strides (z_sb = %lld, z_st = %lld) must be positive, z_st >= V", what, (long long)c.z_sb, (long long)c.z_st);
+  switch (drive) {
+    case CtcDrive::Forward:
+      RNNT_CHECK_ARG(c.nll, "%s: null nll", what);
+      break;
+    case CtcDrive::Backward:
+      RNNT_CHECK_ARG(c.dlogits, "%s: null dlogits", what);
+      RNNT_CHECK_ARG(c.gvec_stride == 0 || c.gvec_stride == 1, "%s: gvec_stride must be 0 (one scalar) or 1 (per utterance)", what);
+      break;
+    case CtcDrive::Align:
+      RNNT_CHECK_ARG(c.score, "%s: null score", what);
+      RNNT_CHECK_ARG(U == 0 || (c.first && c.last), "%s: null first/last", what);
+      break;
+  }
+  *w = carve_ctc(c.workspace, B, T, U, drive == CtcDrive::Align);
+  RNNT_CHECK_ARG(c.workspace && c.workspace_bytes >= w->total, "%s: workspace too small (%zu < %zu)", what, c.workspace_bytes, w->total);
+  return RNNT_OK;
+}
+
+// stage 1 of the loss and of the alignment: the row log-sum-exp, the emission rows and the label chains
+int stage_terms(const CtcCall& c, const CtcWs& w) {
+  {
+    ProfScope prof(RNNT_K_LSE, 4.0 * (double)c.B * c.T * c.V + 4.0 * (double)c.B * c.T * (c.U + 1), c.stream);
+    hipLaunchKernelGGL(ctc_terms_kernel, dim3((unsigned)ceil_div(c.T, TT), c.B), dim3(256), 0, c.stream, c.logits, (long)c.z_sb, (long)c.z_st,
+                       c.labels, c.t_lens, c.u_lens, c.T, c.U, c.V, c.blank, w.em, w.lse, w.chain);
+  }
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// stage 2 of the loss: the alpha | beta sweep, logZ and the NLL.  Booked under the lattice-sweep kind of the RNN-T loss: the
+// profiler's kinds are part of the ABI, which CTC leaves as it is
+int stage_sweep(const CtcCall& c, const CtcWs& w) {
+  // read the emission rows, write both states of a position (fp64)
+  ProfScope prof(RNNT_K_ALPHABETA, 2.0 * (4.0 + 16.0) * (double)c.B * c.T * (c.U + 1), c.stream);
+  dispatch_k(c.U + 1, [&](auto k) {
+    hipLaunchKernelGGL((ctc_sweep_kernel<decltype(k)::value>), dim3(c.B, 2), dim3(64), 0, c.stream, w.em, c.labels, c.t_lens, c.u_lens, c.T,
+                       c.U, w.aB, w.aL, w.bB, w.bL, w.ll, c.nll);
+  });
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// the backward: the workspace still holds the emission rows, alpha, beta and logZ of rnnt_hip_ctc_loss_fwd on the SAME operands
+int stage_grad(const CtcCall& c, const CtcWs& w) {
+  const size_t lds = grad_lds_bytes(c.U, c.V);
+  if (lds > 64 * 1024)
+    RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)ctc_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ProfScope prof(RNNT_K_LATGRAD, 2.0 * 4.0 * (double)c.B * c.T * c.V + 36.0 * (double)c.B * c.T * (c.U + 1), c.stream);
+  hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)ceil_div(c.T, TT), c.B), dim3(256), lds, c.stream, c.logits, (long)c.z_sb, (long)c.z_st,
+                     c.labels, c.t_lens, c.u_lens, w.em, w.lse, w.chain, w.aB, w.aL, w.bB, w.bL, w.ll, c.T, c.U, c.V, c.blank, c.gscale, c.gvec,
+                     c.gvec_stride, c.dlogits);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
+}
+
+// stage 2 of the alignment: the max-plus sweep (read the emission rows, write three bits per position), booked under the
+// lattice-sweep kind like the sweeps of the loss, then the back-trace under the kind of the small kernels, so that a profile shows
+// its share: the kinds are part of the ABI
+int stage_viterbi(const CtcCall& c, const CtcWs& w) {
+  hipStream_t s = c.stream;
+  const double cells = (double)c.B * c.T * (c.U + 1);
+  {
+    ProfScope prof(RNNT_K_ALPHABETA, (4.0 + 3.0 / 8.0) * cells, s);
+    dispatch_k(c.U + 1, [&](auto k) {
+      hipLaunchKernelGGL((ctc_sweep_kernel<decltype(k)::value, true, CtcBackPtr>), dim3(c.B, 1), dim3(64), 0, s, w.em, c.labels, c.t_lens,
+                         c.u_lens, c.T, c.U, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, c.score,
+                         (float*)nullptr, CtcBackPtr{w.bp, w.nw, w.fin});
+    });
+  }
+  RNNT_CHECK_LAUNCH();
+  ProfScope prof(RNNT_K_MISC, 3.0 / 8.0 * cells + 4.0 * (double)c.B * (c.T + 2 * c.U), s);
+  const size_t small = (size_t)3 * (c.U + 1) * 4, table = (size_t)3 * (c.U + 1) * w.nw * 4;
+  const int in_lds = small + table <= 64 * 1024;
+  hipLaunchKernelGGL(ctc_backtrace_kernel, dim3(c.B), dim3(256), in_lds ? small + table : small, s, w.bp, w.em, c.labels, c.t_lens, c.u_lens,
+                     c.score, w.fin, c.T, c.U, w.nw, in_lds, c.blank, c.first, c.last, c.path, c.token_logp);
+  RNNT_CHECK_LAUNCH();
+  return RNNT_OK;
 }
 
 }  // namespace
@@ -712,64 +746,37 @@ CtcAlignWs carve_ctc_align(void* ws, int B, int T, int U) {
 
 using namespace rnnt;
 
+// ---- the exported entries: each fills a CtcCall from its positional arguments (the names below are the parameters') ----
+#define FILL_CTC(c, WHO)                                                                                                          \
+  CtcCall c;                                                                                                                      \
+  c.who = WHO, c.logits = logits, c.z_sb = z_sb, c.z_st = z_st, c.labels = labels, c.t_lens = t_lens, c.u_lens = u_lens, c.B = B, \
+  c.T = T, c.U = U, c.V = V, c.blank = blank, c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream
+
 extern "C" size_t rnnt_hip_ctc_loss_workspace_bytes(int32_t B, int32_t T, int32_t U, int32_t V) {
   if (B < 1 || T < 1 || U < 0 || V < 1) return 0;
-  return carve_ctc(nullptr, B, T, U).total;
+  return carve_ctc(nullptr, B, T, U, false).total;
 }
 
 extern "C" int rnnt_hip_ctc_loss_fwd(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
                                      const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, float* nll,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_ctc("ctc_loss_fwd", logits, z_sb, z_st, labels, t_lens, u_lens, B, T, U, V, blank)) return rc;
-  RNNT_CHECK_ARG(nll, "ctc_loss_fwd: null nll");
-  const CtcWs w = carve_ctc(workspace, B, T, U);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_loss_fwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  const int ntiles = (int)ceil_div(T, TT);
-  const double cells = (double)B * T * (U + 1);
-  {
-    ProfScope prof(RNNT_K_LSE, 4.0 * (double)B * T * V + 4.0 * cells, s);
-    hipLaunchKernelGGL(ctc_terms_kernel, dim3(ntiles, B), dim3(256), 0, s, logits, (long)z_sb, (long)z_st, labels, t_lens, u_lens, T, U,
-                       V, blank, w.em, w.lse, w.chain);
-  }
-  RNNT_CHECK_LAUNCH();
-  // booked under the lattice-sweep kind of the RNN-T loss: the profiler's kinds are part of the ABI, which this feature leaves as it is
-  ProfScope prof(RNNT_K_ALPHABETA, 2.0 * (4.0 + 16.0) * cells, s);   // read the emission rows, write both states of a position (fp64)
-  const dim3 grid(B, 2), block(64);
-  const int K = (int)ceil_div(U + 1, 64);
-#define SW(KK) hipLaunchKernelGGL((ctc_sweep_kernel<KK>), grid, block, 0, s, w.em, labels, t_lens, u_lens, T, U, w.aB, w.aL, w.bB, w.bL, w.ll, nll)
-  switch (K) {
-    case 1: SW(1); break;
-    case 2: SW(2); break;
-    case 3: SW(3); break;
-    case 4: SW(4); break;
-    default: SW(8); break;
-  }
-#undef SW
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
+  FILL_CTC(c, "ctc_loss_fwd");
+  c.nll = nll;
+  CtcWs w;
+  if (int rc = check_ctc(c, CtcDrive::Forward, &w)) return rc;
+  if (int rc = stage_terms(c, w)) return rc;
+  return stage_sweep(c, w);
 }
 
 extern "C" int rnnt_hip_ctc_loss_bwd(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
                                      const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, float gscale,
                                      const float* gvec, int32_t gvec_stride, float* dlogits, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-  // the workspace still holds the emission rows, alpha, beta and logZ of rnnt_hip_ctc_loss_fwd on the SAME operands
-  if (int rc = check_ctc("ctc_loss_bwd", logits, z_sb, z_st, labels, t_lens, u_lens, B, T, U, V, blank)) return rc;
-  RNNT_CHECK_ARG(dlogits, "ctc_loss_bwd: null dlogits");
-  RNNT_CHECK_ARG(gvec_stride == 0 || gvec_stride == 1, "ctc_loss_bwd: gvec_stride must be 0 (one scalar) or 1 (per utterance)");
-  const CtcWs w = carve_ctc(workspace, B, T, U);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_loss_bwd: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = grad_lds_bytes(U, V);
-  if (lds > 64 * 1024)
-    RNNT_CHECK_HIP(hipFuncSetAttribute((const void*)ctc_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  ProfScope prof(RNNT_K_LATGRAD, 2.0 * 4.0 * (double)B * T * V + 36.0 * (double)B * T * (U + 1), s);
-  hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)ceil_div(T, TT), B), dim3(256), lds, s, logits, (long)z_sb, (long)z_st, labels,
-                     t_lens, u_lens, w.em, w.lse, w.chain, w.aB, w.aL, w.bB, w.bL, w.ll, T, U, V, blank, gscale, gvec, gvec_stride,
-                     dlogits);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
+  FILL_CTC(c, "ctc_loss_bwd");
+  c.gscale = gscale, c.gvec = gvec, c.gvec_stride = gvec_stride, c.dlogits = dlogits;
+  CtcWs w;
+  if (int rc = check_ctc(c, CtcDrive::Backward, &w)) return rc;
+  return stage_grad(c, w);
 }
 
 extern "C" int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T,
@@ -789,47 +796,17 @@ extern "C" int rnnt_hip_ctc_greedy(const float* logits, int64_t z_sb, int64_t z_
 /* ---- forced alignment under CTC (include/rnnt_hip.h): the terms kernel of the loss, max-plus sweep, back-trace ---- */
 extern "C" size_t rnnt_hip_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t U, int32_t V) {
   if (B < 1 || T < 1 || U < 0 || V < 1) return 0;
-  return carve_ctc_align(nullptr, B, T, U).total;
+  return carve_ctc(nullptr, B, T, U, true).total;
 }
 
 extern "C" int rnnt_hip_ctc_align(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* labels, const int32_t* t_lens,
                                   const int32_t* u_lens, int32_t B, int32_t T, int32_t U, int32_t V, int32_t blank, int32_t* first,
                                   int32_t* last, int32_t* path, double* token_logp, double* score, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  if (int rc = check_ctc("ctc_align", logits, z_sb, z_st, labels, t_lens, u_lens, B, T, U, V, blank)) return rc;
-  RNNT_CHECK_ARG(score, "ctc_align: null score");
-  RNNT_CHECK_ARG(U == 0 || (first && last), "ctc_align: null first/last");
-  const CtcAlignWs w = carve_ctc_align(workspace, B, T, U);
-  RNNT_CHECK_ARG(workspace && workspace_bytes >= w.total, "ctc_align: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  const double cells = (double)B * T * (U + 1);
-  {
-    ProfScope prof(RNNT_K_LSE, 4.0 * (double)B * T * V + 4.0 * cells, s);
-    hipLaunchKernelGGL(ctc_terms_kernel, dim3((unsigned)ceil_div(T, TT), B), dim3(256), 0, s, logits, (long)z_sb, (long)z_st, labels,
-                       t_lens, u_lens, T, U, V, blank, w.em, w.lse, w.chain);
-  }
-  RNNT_CHECK_LAUNCH();
-  // the sweep (read the emission rows, write three bits per position) is booked under the lattice-sweep kind like the sweeps of the
-  // loss, the back-trace under the kind of the small kernels, so that a profile shows its share: the kinds are part of the ABI
-  const int K = (int)ceil_div(U + 1, 64);
-  {
-    ProfScope prof(RNNT_K_ALPHABETA, (4.0 + 3.0 / 8.0) * cells, s);
-#define VT(KK) hipLaunchKernelGGL((ctc_viterbi_kernel<KK>), dim3(B), dim3(64), 0, s, w.em, labels, t_lens, u_lens, T, U, w.NW, w.bp, score, w.fin)
-    switch (K) {
-      case 1: VT(1); break;
-      case 2: VT(2); break;
-      case 3: VT(3); break;
-      case 4: VT(4); break;
-      default: VT(8); break;
-    }
-#undef VT
-  }
-  RNNT_CHECK_LAUNCH();
-  ProfScope prof(RNNT_K_MISC, 3.0 / 8.0 * cells + 4.0 * (double)B * (T + 2 * U), s);
-  const size_t small = (size_t)3 * (U + 1) * 4, table = (size_t)3 * (U + 1) * w.NW * 4;
-  const int in_lds = small + table <= 64 * 1024;
-  hipLaunchKernelGGL(ctc_backtrace_kernel, dim3(B), dim3(256), in_lds ? small + table : small, s, w.bp, w.em, labels, t_lens, u_lens,
-                     score, w.fin, T, U, w.NW, in_lds, blank, first, last, path, token_logp);
-  RNNT_CHECK_LAUNCH();
-  return RNNT_OK;
+  FILL_CTC(c, "ctc_align");
+  c.first = first, c.last = last, c.path = path, c.token_logp = token_logp, c.score = score;
+  CtcWs w;
+  if (int rc = check_ctc(c, CtcDrive::Align, &w)) return rc;
+  if (int rc = stage_terms(c, w)) return rc;
+  return stage_viterbi(c, w);
 }

@@ -10,15 +10,17 @@
 //   band_kernel                       : emission windows -> the band tables L, R and the feasibility flag of every row
 //   lse_sep_kernel / lse_dense_kernel : per-cell log-sum-exp -> blk[b][u][t], emit[b][u][t] (u-major)
 //   lse_sepv_kernel                   : lse_sep_kernel for V >= 256, a lane per vocabulary entry
-//   alphabeta_kernel<K>               : one wavefront per (utterance, alpha|beta); lane l owns label
+//   alphabeta_kernel<K, MAX>          : one wavefront per (utterance, alpha|beta); lane l owns label
 //                                       positions [l*K, l*K+K) and sweeps t with a one-lane skew, so each
 //                                       step advances one anti-diagonal; neighbour hand-off by lane shuffle;
-//                                       accumulators in fp64 with an fp32 log1p(exp(.)) correction term
+//                                       accumulators in fp64 with an fp32 log1p(exp(.)) correction term.
+//                                       MAX = true: the same alpha sweep in the (max, +) semiring, for forced
+//                                       alignment -- one back-pointer bit per cell instead of the cell store
 //   grad_sep_kernel                   : dA[b,t,:] = sum_u dz, partial dC slabs per 32-frame tile (LDS adds)
 //   reduce_dc_kernel                  : fixed-order sum of the slabs (bitwise reproducible, no float atomics)
 //   grad_sepv_kernel                  : grad_sep_kernel with the vocabulary a grid dimension (V >= 256, or a table past LDS)
 //   grad_dense_kernel                 : warp-transducer-shaped d/d logits for rnnt_hip_loss_from_logits_*
-//   viterbi_kernel<K> / backtrace_kernel : forced alignment -- the max-plus sweep (one back-pointer bit per cell), the best path
+//   backtrace_kernel                  : forced alignment -- the best path, walked back through the MAX sweep's back-pointer bits
 //   kd_value_kernel                   : lattice distillation -- the collapsed KL per utterance, fp64 sums in a fixed order
 // The W / FE / KD template flags select the emission-window / FastEmit / distillation instances; all false: the kernels without them.
 // The host half (from struct LossWs on): one LossCall per call, one check, four stages, three drivers behind the exported entries.
@@ -71,14 +73,8 @@ struct Band {   // what the gradient kernels read
 };
 // A kernel with the flag W takes its tables as a trailing parameter PACK: empty for W = false, so that instance has the parameter
 // list (and the kernel-argument block) of the kernel without this feature; one Win / Band for W = true.  The flag KD (lattice
-// distillation, below) adds its one struct to the same pack.  pick_tables<T>: the pack's member of type T, or an empty T.
-template <typename T>
-__device__ __forceinline__ T pick_tables() { return T{}; }
-template <typename T, typename H, typename... R>
-__device__ __forceinline__ T pick_tables(H h, R... r) {
-  if constexpr (std::is_same<T, H>::value) return h;
-  else return pick_tables<T>(r...);
-}
+// distillation, below) adds its one struct to the same pack.  pick_tables<T> (lattice_shared.hpp): the pack's member of type T, or
+// an empty T.
 
 // ------------------------------------------------------------------------------------------------
 // Lattice knowledge distillation (Panchapagesan et al. 2021; include/rnnt_hip.h).  Per lattice cell the teacher's and
@@ -440,13 +436,34 @@ __global__ void __launch_bounds__(256) lse_dense_kernel(const TZ* __restrict__ Z
 // (`s_waitcnt vmcnt(n)`, n > 0).  With the loads and stores inside `if (cell exists)` branches — the round-1 form — it could not, fell
 // back to vmcnt(0) after every step and each step waited out the loads it had just issued for 8 steps later: 950 cycles per step at
 // config 2 (0.41 ms per training step for a 1 040-step chain) against the ~300 the arithmetic takes.
-template <int K>
+//
+// The semiring is the template flag MAX.  MAX = false, the loss: the (logaddexp, +) sums above, both directions picked by blockIdx.y,
+// every cell stored in fp64, logZ of each direction to ll; the lengths are taken as they come (the loss's check is the caller's).
+// MAX = true, forced alignment: the alpha direction alone (grid (B, 1); the beta branch is not compiled) in the (max, +) semiring,
+//   v(t,u) = max( v(t-1,u) + blk(t-1,u), v(t,u-1) + emit(t,u-1) ),  v(0,0) = 0,  score = v(Tb-1,Ub) + blk(Tb-1,Ub)  -> ll[b]
+// fp64 sums of the fp32 cell terms, no transcendental: the score is exact (-inf when the utterance has no frame).  TIE RULE: on
+// exactly equal candidates the blank predecessor (t-1,u) wins (the label predecessor is taken only when it is strictly greater), so
+// the path is a pure function of blk / emit.  Back-pointers in place of the cell store: ONE BIT per cell (1 = came from (t,u-1),
+// i.e. label u-1 is emitted at frame t), 32 consecutive frames of one label row per word: bp[b][u][t >> 5] bit (t & 31).  A lane
+// collects the bits of its K rows in registers and stores a word when its row reaches the end of a 32-frame block or the
+// utterance's last frame; like every memory operation of the loop the store goes through the buffer resource with an out-of-range
+// offset when there is nothing to store.  The lengths are the caller's: CLAMPED into the lattice (as backtrace_kernel clamps them),
+// so a wrong length can neither reach another label row through u * T + t nor leave the score unwritten.
+// The MAX instance has no alpha / beta to write, so the two kernel arguments before ll are its table instead: the words per label
+// row and bp[B][U1][NW].  (Left unused beside a table of their own they cost the K = 2 instance 0.8 % of its time at config-5
+// size: same loop, other registers.  As below each mode compiles to the instructions it had as a kernel of its own:
+// profiles/lattice_sweeps_resource_usage.txt.)
+template <bool MAX> using SweepOut0 = std::conditional_t<MAX, int, double* __restrict__>;                        // alpha | NW
+template <bool MAX> using SweepOut1 = std::conditional_t<MAX, unsigned* __restrict__, double* __restrict__>;   // beta  | bp
+
+template <int K, bool MAX = false>
 __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__ blk, const float* __restrict__ emit,
                                                        const int* __restrict__ t_lens, const int* __restrict__ u_lens,
-                                                       int T, int U1, double* __restrict__ alpha,
-                                                       double* __restrict__ beta, double* __restrict__ ll) {
-  const int b = blockIdx.x, which = blockIdx.y, lane = threadIdx.x;
-  const int Tb = t_lens[b], Ub = u_lens[b];  // valid cells: t < Tb, u <= Ub
+                                                       int T, int U1, SweepOut0<MAX> alpha, SweepOut1<MAX> beta,
+                                                       double* __restrict__ ll) {
+  const int b = blockIdx.x, which = MAX ? 0 : blockIdx.y, lane = threadIdx.x;
+  // valid cells: t < Tb, u <= Ub
+  const int Tb = MAX ? min(t_lens[b], T) : t_lens[b], Ub = MAX ? max(min(u_lens[b], U1 - 1), 0) : u_lens[b];
   const long rowbase = (long)b * U1 * T;
   const int ulo = lane * K;
   const int lastlane = Ub / K;
@@ -454,7 +471,15 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
   const int cells = U1 * T;
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(blk + rowbase), 0, cells * 4, AB_RSRC);
   const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(emit + rowbase), 0, cells * 4, AB_RSRC);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((which == 0 ? alpha : beta) + rowbase, 0, cells * 8, AB_RSRC);
+  // what the sweep writes: the cells of alpha | beta, or (MAX) the utterance's back-pointer words
+  [[maybe_unused]] int NW = 0;
+  __amdgpu_buffer_rsrc_t ro;
+  if constexpr (MAX) {
+    NW = alpha;
+    ro = __builtin_amdgcn_make_buffer_rsrc(beta + (long)b * U1 * NW, 0, U1 * NW * 4, AB_RSRC);
+  } else {
+    ro = __builtin_amdgcn_make_buffer_rsrc((which == 0 ? alpha : beta) + rowbase, 0, cells * 8, AB_RSRC);
+  }
   auto cell = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u <= Ub) ? u * T + t : -1; };
   auto ld = [&](const __amdgpu_buffer_rsrc_t& r, int c) -> float {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, c >= 0 ? c * 4 : AB_OOB, 0, 0));
@@ -463,13 +488,15 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
     typedef int i32x2 __attribute__((ext_vector_type(2)));
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, v), ro, c >= 0 ? c * 8 : AB_OOB, 0, 0);
   };
+  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, ro, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
   const int nrounds = (nsteps + PF - 1) / PF;   // steps beyond nsteps touch no cell (every lane is past its last row)
   double llv = NEG_INF;
 
   if (which == 0) {
     double down[K];  // alpha[t-1][u] + blk[t-1][u]
+    [[maybe_unused]] unsigned bits[K];  // MAX: back-pointer bits of the current 32-frame block of row ulo + k
 #pragma unroll
-    for (int k = 0; k < K; ++k) down[k] = NEG_INF;
+    for (int k = 0; k < K; ++k) { down[k] = NEG_INF; bits[k] = 0u; }
     double eout = NEG_INF;  // alpha[t][uhi] + emit[t][uhi] of this lane's last cell at its current row
     // a row's blk/emit values are fetched PF steps ahead into a register ring
     float pb[PF][K], pe[PF][K];
@@ -497,13 +524,24 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
           pe[j][k] = ld(re, c);
         }
         const bool row = t >= 0 && t < Tb;
+        const int sh = t & 31;
+        const bool flush = sh == 31 || t == Tb - 1;
         double left = carry;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           const int u = ulo + k;
           const bool ok = row && u <= Ub;
-          const double a = (t == 0 && u == 0) ? 0.0 : logaddexp_d(down[k], left);
-          st(a, ok ? u * T + t : -1);
+          double a;
+          if constexpr (MAX) {
+            const bool from_label = left > down[k];   // strict: a tie keeps the blank predecessor; (0,0) and u = 0 see left = -inf
+            a = (t == 0 && u == 0) ? 0.0 : (from_label ? left : down[k]);
+            const unsigned nb = (sh == 0 ? 0u : bits[k]) | ((unsigned)from_label << sh);
+            bits[k] = ok ? nb : bits[k];
+            stw(nb, (ok && flush) ? u * NW + (t >> 5) : -1);
+          } else {
+            a = (t == 0 && u == 0) ? 0.0 : logaddexp_d(down[k], left);
+            st(a, ok ? u * T + t : -1);
+          }
           const double nd = a + (double)cb[k];
           down[k] = ok ? nd : down[k];
           left = ok ? ((u < Ub) ? a + (double)ce[k] : NEG_INF) : left;
@@ -512,8 +550,8 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
         eout = row ? left : eout;
       }
     }
-    if (lane == lastlane) ll[b] = llv;   // the lane that owns cell (Tb - 1, Ub)
-  } else {
+    if (lane == lastlane) ll[b] = llv;   // the lane that owns cell (Tb - 1, Ub): logZ, or (MAX) the best path's score
+  } else if constexpr (!MAX) {
     double down[K];  // beta[t+1][u]
 #pragma unroll
     for (int k = 0; k < K; ++k) down[k] = NEG_INF;
@@ -561,93 +599,6 @@ __global__ void __launch_bounds__(64) alphabeta_kernel(const float* __restrict__
     }
     if (lane == 0) ll[gridDim.x + b] = llv;   // the lane that owns cell (0, 0)
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// forced alignment: the alpha sweep above in the (max, +) semiring, one wavefront per utterance.
-//   v(t,u) = max( v(t-1,u) + blk(t-1,u), v(t,u-1) + emit(t,u-1) ),  v(0,0) = 0,  score = v(Tb-1,Ub) + blk(Tb-1,Ub)
-// fp64 sums of the fp32 cell terms, no transcendental: the score is exact.  TIE RULE: on exactly equal candidates the blank
-// predecessor (t-1,u) wins (the label predecessor is taken only when it is strictly greater), so the path is a pure function of
-// blk / emit.  Back-pointers: ONE BIT per cell (1 = came from (t,u-1), i.e. label u-1 is emitted at frame t), 32 consecutive frames
-// of one label row per word: bp[b][u][t >> 5] bit (t & 31).  A lane collects the bits of its K rows in registers and stores a word
-// when its row reaches the end of a 32-frame block or the utterance's last frame; like every memory operation of the loop the store
-// goes through a buffer resource with an out-of-range offset when there is nothing to store.
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__global__ void __launch_bounds__(64) viterbi_kernel(const float* __restrict__ blk, const float* __restrict__ emit,
-                                                     const int* __restrict__ t_lens, const int* __restrict__ u_lens,
-                                                     int T, int U1, int NW, unsigned* __restrict__ bp,
-                                                     double* __restrict__ score) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  // valid cells: t < Tb, u <= Ub.  The lengths are the caller's: clamped into the lattice (as backtrace_kernel clamps them), so a wrong
-  // length can neither reach another label row through u * T + t nor leave score[b] unwritten
-  const int Tb = min(t_lens[b], T), Ub = max(min(u_lens[b], U1 - 1), 0);
-  const long rowbase = (long)b * U1 * T;
-  const int ulo = lane * K;
-  const int lastlane = Ub / K;
-  const int nsteps = Tb + lastlane;
-  const int cells = U1 * T;
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(blk + rowbase), 0, cells * 4, AB_RSRC);
-  const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(emit + rowbase), 0, cells * 4, AB_RSRC);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(bp + (long)b * U1 * NW, 0, U1 * NW * 4, AB_RSRC);
-  auto cell = [&](int u, int t) -> int { return (t >= 0 && t < Tb && u <= Ub) ? u * T + t : -1; };
-  auto ld = [&](const __amdgpu_buffer_rsrc_t& r, int c) -> float {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, c >= 0 ? c * 4 : AB_OOB, 0, 0));
-  };
-  auto stw = [&](unsigned v, int w) { __builtin_amdgcn_raw_buffer_store_b32((int)v, rw, w >= 0 ? w * 4 : AB_OOB, 0, 0); };
-  const int nrounds = (nsteps + PF - 1) / PF;
-  double best = NEG_INF;
-
-  double down[K];    // v[t-1][u] + blk[t-1][u]
-  unsigned bits[K];  // back-pointer bits of the current 32-frame block of row ulo + k
-#pragma unroll
-  for (int k = 0; k < K; ++k) { down[k] = NEG_INF; bits[k] = 0u; }
-  double eout = NEG_INF;  // v[t][uhi] + emit[t][uhi] of this lane's last cell at its current row
-  float pb[PF][K], pe[PF][K];
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int c = cell(ulo + k, j - lane);
-      pb[j][k] = ld(rb, c);
-      pe[j][k] = ld(re, c);
-    }
-  for (int r = 0; r < nrounds; ++r) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j) {
-      const int t = r * PF + j - lane;
-      const double carry = shfl_up1(eout, lane);
-      float cb[K], ce[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) { cb[k] = pb[j][k]; ce[k] = pe[j][k]; }
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int c = cell(ulo + k, t + PF);
-        pb[j][k] = ld(rb, c);
-        pe[j][k] = ld(re, c);
-      }
-      const bool row = t >= 0 && t < Tb;
-      const int sh = t & 31;
-      const bool flush = sh == 31 || t == Tb - 1;
-      double left = carry;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int u = ulo + k;
-        const bool ok = row && u <= Ub;
-        const bool from_label = left > down[k];   // strict: a tie keeps the blank predecessor; (0,0) and u = 0 see left = -inf
-        const double v = (t == 0 && u == 0) ? 0.0 : (from_label ? left : down[k]);
-        const unsigned nb = (sh == 0 ? 0u : bits[k]) | ((unsigned)from_label << sh);
-        bits[k] = ok ? nb : bits[k];
-        stw(nb, (ok && flush) ? u * NW + (t >> 5) : -1);
-        const double nd = v + (double)cb[k];
-        down[k] = ok ? nd : down[k];
-        left = ok ? ((u < Ub) ? v + (double)ce[k] : NEG_INF) : left;
-        best = (ok && t == Tb - 1 && u == Ub) ? nd : best;
-      }
-      eout = row ? left : eout;
-    }
-  }
-  if (lane == lastlane) score[b] = best;   // the lane that owns cell (Tb - 1, Ub); -inf when the utterance has no frame
 }
 
 // Back-trace from (Tb-1, Ub) to label row 0: one workgroup per utterance.  A zero word (below the current frame) is 32 blank steps
@@ -1265,17 +1216,6 @@ struct LossCall {
   hipStream_t stream = nullptr;
 };
 
-struct Carver {   // consecutive 256-byte aligned pieces of a workspace (a null base: sizes only)
-  char* p;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align_up(bytes, 256);
-    return reinterpret_cast<T*>(q);
-  }
-};
-
 // the loss: alpha | beta | logZ | blk | emit | the dC slabs, then (windowed) the band tables L, R and the feasibility flags, or (KD)
 // the student's rest plane
 LossWs carve(void* ws, int B, int T, int U1, int V, bool windowed, bool kd = false) {
@@ -1311,11 +1251,8 @@ LossWs carve_align(void* ws, int B, int T, int U1) {
   return w;
 }
 
-// ---- dispatch helpers: a run-time choice handed to a generic lambda as a type ----
-template <bool X> struct BoolT { static constexpr bool value = X; };
-template <int X> struct IntT { static constexpr int value = X; };
-template <typename T> struct TypeT { using type = T; };
-
+// ---- dispatch helpers: a run-time choice handed to a generic lambda as a type (BoolT / IntT / TypeT, and dispatch_k for the K of
+// the sweep kernel, are in lattice_shared.hpp) ----
 // the storage type of dense logits: f(TypeT<float | __half | __hip_bfloat16>)
 template <typename F>
 int dispatch_dtype(int dtype, const char* who, F&& f) {
@@ -1324,18 +1261,6 @@ int dispatch_dtype(int dtype, const char* who, F&& f) {
     case RNNT_DTYPE_F16: return f(TypeT<__half>{});
     case RNNT_DTYPE_BF16: return f(TypeT<__hip_bfloat16>{});
     default: set_error("%s: unknown dtype code %d", who, dtype); return RNNT_ERR_INVALID;
-  }
-}
-
-// K label positions per lane of the two sweep kernels (alphabeta_kernel, viterbi_kernel): f(IntT<K>), K in {1, 2, 3, 4, 8}
-template <typename F>
-void dispatch_k(int U1, F&& f) {
-  switch ((int)ceil_div(U1, 64)) {
-    case 1: f(IntT<1>{}); break;
-    case 2: f(IntT<2>{}); break;
-    case 3: f(IntT<3>{}); break;
-    case 4: f(IntT<4>{}); break;
-    default: f(IntT<8>{}); break;
   }
 }
 
@@ -1589,8 +1514,8 @@ int stage_viterbi(const LossCall& c, const LossWs& w) {
   // is, so a process that trains and aligns sees both sweeps summed in that slot
   ProfScope prof(RNNT_K_ALPHABETA, (8.0 + 0.25) * (double)c.B * c.T * c.U1, s);
   dispatch_k(c.U1, [&](auto k) {
-    hipLaunchKernelGGL((viterbi_kernel<decltype(k)::value>), dim3(c.B), dim3(64), 0, s, w.blk, w.emit, c.t_lens, c.u_lens, c.T, c.U1, w.nw,
-                       w.bp, c.score);
+    hipLaunchKernelGGL((alphabeta_kernel<decltype(k)::value, true>), dim3(c.B, 1), dim3(64), 0, s, w.blk, w.emit, c.t_lens, c.u_lens, c.T, c.U1,
+                       w.nw, w.bp, c.score);
   });
   RNNT_CHECK_LAUNCH();
   constexpr size_t LDS_MAX = 160 * 1024;

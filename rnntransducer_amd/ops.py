@@ -1263,6 +1263,28 @@ def _ctc_strides(logits: torch.Tensor, time_major: bool):
     return B, T, V, T * V, V
 
 
+def _ctc_operands(logits, time_major: bool, t_lens, labels=None, u_lens=None):
+    """The checked operands of a CTC entry: fp32 contiguous logits, int32 contiguous lengths (B,) and, for the entries that take a
+    transcript, labels (B, U) and u_lens (B,) (None, None otherwise).
+    -> (logits, labels, t_lens, u_lens, B, T, V, z_sb, z_st)."""
+    _need_gpu(logits, labels, t_lens, u_lens)
+    logits = _f32c(logits, "logits")
+    if labels is None:
+        _i32((("logit lengths", t_lens),))
+    else:
+        _i32((("targets", labels), ("logit lengths", t_lens), ("target lengths", u_lens)))
+    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    if labels is None:
+        if t_lens.shape != (B,):
+            raise ValueError(f"logit lengths must be (B,) = ({B},), got {tuple(t_lens.shape)}")
+    elif labels.dim() != 2 or labels.shape[0] != B or t_lens.shape != (B,) or u_lens.shape != (B,):
+        raise ValueError(f"targets must be (B, U) with B = {B} and both lengths (B,), got {tuple(labels.shape)}, "
+                         f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
+    else:
+        labels, u_lens = labels.contiguous(), u_lens.contiguous()
+    return logits, labels, t_lens.contiguous(), u_lens, B, T, V, z_sb, z_st
+
+
 class CtcLossFn(torch.autograd.Function):
     """logits (B,T,V) (time_major: (T,B,V)) fp32 -> per-utterance CTC NLL (B,), or its "sum" / "mean" over the batch (0-d).
     forward: per-frame terms + alpha/beta (kept in a workspace); backward: the gradient kernel with the upstream gradient folded
@@ -1271,20 +1293,10 @@ class CtcLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, t_lens, u_lens, blank, want_grad=True, reduction="none", time_major=False, zero_infinity=False):
-        _need_gpu(logits, labels, t_lens, u_lens)
-        logits = _f32c(logits, "logits")
-        for name, t in (("targets", labels), ("logit lengths", t_lens), ("target lengths", u_lens)):
-            if t.dtype != torch.int32:
-                raise ValueError(f"{name} must be int32, got {t.dtype}")
-        B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
-        if labels.dim() != 2 or labels.shape[0] != B or t_lens.shape != (B,) or u_lens.shape != (B,):
-            raise ValueError(f"targets must be (B, U) with B = {B} and both lengths (B,), got {tuple(labels.shape)}, "
-                             f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
+        logits, labels, t_lens, u_lens, B, T, V, z_sb, z_st = _ctc_operands(logits, time_major, t_lens, labels, u_lens)
         if reduction not in ("none", "sum", "mean"):
             raise ValueError(f"reduction must be mean|sum|none, got {reduction!r}")
-        labels, t_lens, u_lens = labels.contiguous(), t_lens.contiguous(), u_lens.contiguous()
-        U = labels.shape[1]
-        L = _lib.lib()
+        U, L = labels.shape[1], _lib.lib()
         nll = torch.empty(B, device=logits.device, dtype=torch.float32)
         nws = L.rnnt_hip_ctc_loss_workspace_bytes(B, T, U, V)
         ws = torch.empty(max(nws, 16), device=logits.device, dtype=torch.uint8)
@@ -1320,14 +1332,7 @@ def ctc_greedy(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, *, time_m
     """Greedy CTC decode of logits (B,T,V) (time_major: (T,B,V)) fp32, t_lens (B,) int32: per frame the argmax (ties to the
     lowest index), repeats collapsed, blanks dropped.  One launch, then one host copy (the counts).  Returns a list of B 1-D
     LongTensors; with return_frames a list of (tokens, frames) pairs, frames int32: the first frame of each token's run."""
-    _need_gpu(logits, t_lens)
-    logits = _f32c(logits, "logits")
-    if t_lens.dtype != torch.int32:
-        raise ValueError(f"logit lengths must be int32, got {t_lens.dtype}")
-    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
-    if t_lens.shape != (B,):
-        raise ValueError(f"logit lengths must be (B,) = ({B},), got {tuple(t_lens.shape)}")
-    t_lens = t_lens.contiguous()
+    logits, _, t_lens, _, B, T, V, z_sb, z_st = _ctc_operands(logits, time_major, t_lens)
     tokens = torch.empty(B, T, device=logits.device, dtype=torch.int32)
     counts = torch.empty(B, device=logits.device, dtype=torch.int32)
     frames = torch.empty(B, T, device=logits.device, dtype=torch.int32) if return_frames else None
@@ -1381,14 +1386,8 @@ def ctc_align(logits: torch.Tensor, labels: torch.Tensor, t_lens: torch.Tensor, 
     (B,) int32 (include/rnnt_hip.h: rnnt_hip_ctc_align, csrc/ctc.hip): the CTC loss's per-frame terms, its sweep in the (max, +)
     semiring, a back-trace.  `workspace` (uint8, >= ctc_align_workspace_bytes): the caller's buffer, allocated here when None; it
     holds the emission rows afterwards (layout in the header).  -> CtcAlignment; absent outputs are None.  No host sync."""
-    _need_gpu(logits, labels, t_lens, u_lens, workspace)
-    logits = _f32c(logits, "logits")
-    _i32((("targets", labels), ("logit lengths", t_lens), ("target lengths", u_lens)))
-    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
-    if labels.dim() != 2 or labels.shape[0] != B or t_lens.shape != (B,) or u_lens.shape != (B,):
-        raise ValueError(f"targets must be (B, U) with B = {B} and both lengths (B,), got {tuple(labels.shape)}, "
-                         f"{tuple(t_lens.shape)}, {tuple(u_lens.shape)}")
-    labels, t_lens, u_lens = labels.contiguous(), t_lens.contiguous(), u_lens.contiguous()
+    _need_gpu(workspace)
+    logits, labels, t_lens, u_lens, B, T, V, z_sb, z_st = _ctc_operands(logits, time_major, t_lens, labels, u_lens)
     U, dev, L = labels.shape[1], logits.device, _lib.lib()
     first = torch.empty(B, U, device=dev, dtype=torch.int32)
     last = torch.empty(B, U, device=dev, dtype=torch.int32)
@@ -1466,19 +1465,13 @@ def ctc_beam_search(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, beam
     `frames`: per token the frame at which its prefix first entered the beam.  One launch, then one host copy of the counts and
     lengths (and one per returned array).  Argument errors raise ValueError before anything is launched."""
     check_ctc_beam_args(beam_width, token_min_logp, "ctc_beam_search")
-    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    V = _ctc_strides(logits, time_major)[2]   # the search's own arguments are checked first, before the operands and the GPU
     if V < 2 or not 0 <= int(blank) < V:
         raise ValueError(f"ctc_beam_search: V = {V} < 2 or blank {blank} outside [0, {V})")
     if beam_width * (V + 1) > 1 << 24:
         raise ValueError(f"ctc_beam_search: beam_width * (V + 1) = {beam_width * (V + 1)} exceeds 2^24 candidates per frame")
     check_fusion(fusion, V, logits.device, "ctc_beam_search", ngram=True)
-    _need_gpu(logits, t_lens)
-    logits = _f32c(logits, "logits")
-    if t_lens.dtype != torch.int32:
-        raise ValueError(f"logit lengths must be int32, got {t_lens.dtype}")
-    if t_lens.shape != (B,):
-        raise ValueError(f"logit lengths must be (B,) = ({B},), got {tuple(t_lens.shape)}")
-    t_lens = t_lens.contiguous()
+    logits, _, t_lens, _, B, T, V, z_sb, z_st = _ctc_operands(logits, time_major, t_lens)
     dev, W, L = logits.device, beam_width, _lib.lib()
     tokens = torch.empty(B, W, T, device=dev, dtype=torch.int32)
     small = torch.empty(B + B * W, device=dev, dtype=torch.int32)   # counts | lens: one transfer

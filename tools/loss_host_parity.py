@@ -1,4 +1,4 @@
-"""Bitwise comparison of the loss / alignment entries of csrc/loss.hip under two builds of the library (the in-tree one against
+"""Bitwise comparison of the loss / alignment entries of csrc/loss.hip and the CTC entries of csrc/ctc.hip under two builds of the library (the in-tree one against
 OTHER, e.g. the parent commit built in a git worktree): one fresh process per library, every output as a .npy file, compared byte
 for byte.  The method of tools/gemm_hp_epilogue_parity.py.
    python tools/loss_host_parity.py OTHER.so OUTDIR [--bench]
@@ -8,6 +8,11 @@ for byte.  The method of tools/gemm_hp_epilogue_parity.py.
              Every entry: fused fwd+bwd; forward then _bwd with gvec_stride 0 and 1; the windowed pairs; the dense entries in
              fp32 / fp16 / bf16 at (5,7) and (70,72); both alignment entries.  Outputs: nll, dA, dC, grad, frames, score and the
              workspace's logZ slice.
+   CTC (csrc/ctc.hip), in the same child: B = 3, blank in {0, V-1}, (U, V, T) in CTC_SHAPES -- no labels, then the K = 1, 2, 3, 4 and
+             8 instances of the sweep with T = U + 41; row 0 full without equal neighbours, row 1 ragged with equal neighbours,
+             row 2 with fewer frames than labels (no path); logits batch- and time-major.  ctc_loss_fwd then ctc_loss_bwd with
+             gvec_stride 0 and 1 (nll, dlogits, the workspace's logZ slice); ctc_align (first, last, path, token_logp, score, the
+             workspace's emission rows); ctc_greedy (tokens, counts, frames).
    --bench:  also `bench.py --config c2 --steps 3 --warmup 1 --dump-outputs`
 Exit status 1 when a file differs or is missing on one side, or a child fails (nothing more is started then)."""
 import os, subprocess, sys
@@ -16,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(5, 7), (70, 72), (130, 8), (160, 8), (200, 8), (320, 8), (5, 260), (1, 3)]
 DENSE_SHAPES = [(5, 7), (70, 72)]
 B, T, T_ALIGN = 3, 33, 40
+CTC_SHAPES = [(0, 3, 9), (4, 7, 33), (69, 8, 110), (129, 8, 170), (199, 8, 240), (319, 8, 360), (511, 8, 552)]   # (U, V, T)
 
 
 def dump(out):
@@ -115,8 +121,69 @@ def dump(out):
                             check(L.rnnt_hip_loss_from_logits_fwd_bwd(dense[0], *dense[2:], *tail), "dense")
                         for n, t in (("nll", nll), ("grad", grad), ("ll", ll(ws))):
                             save(f"{cname}_dense{code}_{n}", t)
+    dump_ctc(L, save)
     torch.cuda.synchronize()
     print(f"dumped {len(os.listdir(out))} files under {_lib.LIB_PATH}")
+
+
+def dump_ctc(L, save):
+    """The CTC entries of csrc/ctc.hip (same child, files ctc_*): every output buffer is pre-filled, so what a call leaves alone
+    compares equal too."""
+    import numpy as np, torch
+    from rnntransducer_amd._lib import check
+    from rnntransducer_amd.ops import _addr, _stream
+    dev = "cuda"
+
+    def i32(a):
+        return torch.tensor(np.asarray(a), dtype=torch.int32, device=dev)
+
+    def up(n):
+        return (n + 255) // 256 * 256
+
+    for U, V, T in CTC_SHAPES:
+        for blank in (0, V - 1):
+            rng = np.random.default_rng(100000 * U + 10 * V + (blank != 0))
+            tag = f"ctc_u{U}_v{V}_t{T}_bl{blank}"
+            z = torch.tensor(rng.normal(size=(B, T, V)), dtype=torch.float32, device=dev)
+            nonblank = np.array([v for v in range(V) if v != blank])
+            lab = rng.integers(0, V - 1, size=(B, max(U, 1)))
+            for u in range(1, lab.shape[1]):   # row 0, full length: no equal neighbours, so T = U + 41 leaves it a path
+                lab[0, u] = (lab[0, u - 1] + 1 + rng.integers(0, V - 2)) % (V - 1)
+            lab[1, 1::2] = lab[1, 0:lab.shape[1] - 1:2]   # row 1: equal neighbours
+            labels = i32(nonblank[lab])[:, :U].contiguous()
+            # row 2: fewer frames than labels, no path (U = 0: one frame)
+            t_lens, u_lens = i32([T, T - 5, max(1, min(T, U - 1))]), i32([U, U // 2, U])
+            lab_p = _addr(labels) if U else None
+            cells = B * T * (U + 1)
+            gvec = torch.tensor(rng.normal(size=B), dtype=torch.float32, device=dev)
+            for layout, zz, z_sb, z_st in (("bm", z, T * V, V), ("tm", z.transpose(0, 1).contiguous(), V, B * V)):
+                head = (_addr(zz), z_sb, z_st, lab_p, _addr(t_lens), _addr(u_lens), B, T, U, V, blank)
+                nws = L.rnnt_hip_ctc_loss_workspace_bytes(B, T, U, V)
+                for stride in (0, 1):
+                    ws = torch.zeros(nws, dtype=torch.uint8, device=dev)
+                    nll, dz = torch.full((B,), -7.0, dtype=torch.float32, device=dev), torch.full_like(zz, -7.0)
+                    check(L.rnnt_hip_ctc_loss_fwd(*head, _addr(nll), _addr(ws), nws, _stream()), "ctc_loss_fwd")
+                    check(L.rnnt_hip_ctc_loss_bwd(*head, 0.25, _addr(gvec), stride, _addr(dz), _addr(ws), nws, _stream()), "ctc_loss_bwd")
+                    off = 4 * up(cells * 8)   # logZ: after the four alpha / beta planes, each 256-byte aligned
+                    for n, t in (("nll", nll), ("dlogits", dz), ("ll", ws[off:off + B * 8].view(torch.float64))):
+                        save(f"{tag}_{layout}_g{stride}_{n}", t)
+                nws = L.rnnt_hip_ctc_align_workspace_bytes(B, T, U, V)
+                ws = torch.zeros(nws, dtype=torch.uint8, device=dev)
+                first, last = (torch.full((B, max(U, 1)), -7, dtype=torch.int32, device=dev) for _ in range(2))
+                path = torch.full((B, T), -7, dtype=torch.int32, device=dev)
+                tlp = torch.full((B, max(U, 1)), -7.0, dtype=torch.float64, device=dev)
+                score = torch.full((B,), -7.0, dtype=torch.float64, device=dev)
+                check(L.rnnt_hip_ctc_align(*head, _addr(first), _addr(last), _addr(path), _addr(tlp), _addr(score), _addr(ws), nws, _stream()),
+                      "ctc_align")
+                for n, t in (("first", first), ("last", last), ("path", path), ("token_logp", tlp), ("score", score),
+                             ("em", ws[:cells * 4].view(torch.float32))):   # the emission rows: offset 0 of the workspace
+                    save(f"{tag}_{layout}_align_{n}", t)
+                tokens, frames = (torch.full((B, T), -7, dtype=torch.int32, device=dev) for _ in range(2))
+                counts = torch.full((B,), -7, dtype=torch.int32, device=dev)
+                check(L.rnnt_hip_ctc_greedy(_addr(zz), z_sb, z_st, _addr(t_lens), B, T, V, blank, _addr(tokens), _addr(counts), _addr(frames),
+                                            _stream()), "ctc_greedy")
+                for n, t in (("tokens", tokens), ("counts", counts), ("frames", frames)):
+                    save(f"{tag}_{layout}_greedy_{n}", t)
 
 
 def run(cmd, env_extra, limit):
