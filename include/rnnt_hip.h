@@ -1362,6 +1362,32 @@ int rnnt_hip_nbest_pack(const int32_t* tokens, int64_t max_len, const int32_t* c
 int rnnt_hip_mwer_risk(const float* nll, const int32_t* dist, const int32_t* valid, int32_t B, int32_t N, double gscale, float* risk,
                        float* weights, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTC-guided blank-frame skipping in front of the transducer searches.  csrc/ctc_skip.hip, DESIGN.md §29.
+ * logits(b,t,v) = logits[b*z_sb + t*z_st + v] are the CTC head's fp32 logits (any layout through the strides, z_st >= V);
+ * enc(b,t,o) = enc[b*e_sb + t*e_st + o] and enc_out(b,j,o) = enc_out[b*o_sb + j*o_st + o] are rows of O fp32 values
+ * (e_st, o_st >= O).  Per utterance b, with T_b = t_lens[b] clamped to [0,T]:
+ *   lp[t] = z[t,blank] - logsumexp_v z[t,:]   for t < T_b, in fp32 with the row maximum subtracted (the arithmetic, and the bits,
+ *           of the CTC loss's per-frame terms);
+ *   frame t is SKIPPED exactly when lp[t] > log_threshold (log_threshold = log p of a blank posterior p; 0 skips nothing, and a
+ *           row whose lp is NaN is kept);
+ *   the kept frames k_0 < k_1 < ... : enc_out(b,j,:) = enc(b,k_j,:) as a bitwise copy, frame_map[b*T + j] = k_j, for
+ *           j < new_lens[b] = their number;  frame_map[b*T + j] = -1 for new_lens[b] <= j < T;  rows j >= new_lens[b] of enc_out
+ *           are not written.
+ *   blank_logp (B,T) fp32 or NULL: lp[t] for t < T_b (entries t >= T_b are not written).
+ * Frames t >= T_b of logits and enc are never read (padding may hold anything).  enc_out must not overlap enc.  Two launches, no
+ * atomics, no host sync, nothing allocated; row b gives the same bits alone as in any batch, and two calls give the same bits.
+ * 16-byte copies when O % 4 == 0 and both buffers' addresses and strides are multiples of 16 bytes, 4-byte copies otherwise.
+ * Checked on the host before any launch (RNNT_ERR_INVALID): B in [1,65535], T, O >= 1, V >= 2, 0 <= blank < V, log_threshold <= 0
+ * and not NaN, the strides above, non-NULL pointers, no overlap, and a workspace (4-byte aligned) of
+ * rnnt_hip_ctc_frame_skip_workspace_bytes(B, T) bytes (0 for B or T < 1): one 32-frame keep word per (utterance, tile).
+ * ---------------------------------------------------------------------------------------------- */
+size_t rnnt_hip_ctc_frame_skip_workspace_bytes(int32_t B, int32_t T);
+int rnnt_hip_ctc_frame_skip(const float* logits, int64_t z_sb, int64_t z_st, const int32_t* t_lens, int32_t B, int32_t T, int32_t V,
+                            int32_t blank, float log_threshold, const float* enc, int64_t e_sb, int64_t e_st, int32_t O,
+                            float* enc_out, int64_t o_sb, int64_t o_st, int32_t* new_lens, int32_t* frame_map, float* blank_logp,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

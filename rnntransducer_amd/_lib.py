@@ -367,6 +367,10 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnnt_hip_ilm_loss_bwd": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32, c_i32,
                                         c_i32, C.c_float, C.c_void_p, c_i32, c_i32, C.c_void_p, C.c_void_p]),
+    "rnnt_hip_ctc_frame_skip_workspace_bytes": (C.c_size_t, [c_i32] * 2),
+    "rnnt_hip_ctc_frame_skip": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, c_i32, c_i32, c_i32, c_i32, C.c_float, C.c_void_p,
+                                          c_i64, c_i64, c_i32, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 KERNEL_KINDS = ["gemm_f32_kernel", "lstm_fwd_kernel", "lstm_bwd_kernel", "lse_kernel", "alphabeta_kernel",

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = ["api.hip", "gemm.hip", "gemm_hp.hip", "loss.hip", "lstm.hip", "lstm5.hip", "lstm_layer.hip", "colsum_embedding.hip",
            "decode.hip", "beam.hip", "frontend.hip", "stream.hip", "beam_stream.hip", "ctc.hip", "ctc_beam.hip", "beam_sync.hip",
-           "beam_sync_stream.hip", "mwer.hip", "ilm_loss.hip"]
+           "beam_sync_stream.hip", "mwer.hip", "ilm_loss.hip", "ctc_skip.hip"]
 HEADERS = ["common.hpp", "lstm_shared.hpp", "decode_shared.hpp", "beam_shared.hpp", "lattice_shared.hpp",
            "search_shared.hpp", "beam_sync_shared.hpp"]
 LIB = os.path.join(HERE, "librnnt_hip.so")

@@ -40,7 +40,7 @@ import torch
 
 from .loss import RNNTLoss
 from .networks import JointNet
-from .ops import CtcEmitWindows, check_fastemit_lambda, check_ilmt_weight, check_kd_weight, emit_windows
+from .ops import CtcEmitWindows, check_ctc_skip, check_fastemit_lambda, check_ilmt_weight, check_kd_weight, emit_windows
 
 try:  # pragma: no cover - not installed in the build image
     import pytorch_lightning as pl
@@ -100,6 +100,14 @@ class RNNTransducer(_Base):
         self.mwer_nbest, self.mwer_max_symbols = (4 if nbest is None else nbest), (1 if max_symbols is None else max_symbols)
         self.mwer_weight = JointNet.check_mwer_args(self.mwer_nbest, self.mwer_max_symbols, 0.0, 511,
                                                     0.0 if mwer_weight is None else mwer_weight, "args.mwer_*")
+        # CTC-guided blank-frame skipping (ctc_skip= of JointNet.mwer_loss / recognize_greedy): a blank-posterior threshold in (0, 1]
+        # for MWER's n-best search and for validation_step's greedy search; None (the default) leaves both as they are
+        self.mwer_ctc_skip, self.val_ctc_skip = getattr(args, "mwer_ctc_skip", None), getattr(args, "val_ctc_skip", None)
+        for name, p in (("args.mwer_ctc_skip", self.mwer_ctc_skip), ("args.val_ctc_skip", self.val_ctc_skip)):
+            if p is not None:
+                check_ctc_skip(p, name)
+                if not self.jointnet.aux_ctc:
+                    raise ValueError(f"{name} needs the CTC head: set jointnet_params['aux_ctc'] = True")
         # internal-LM training (JointNet.loss's ilmt_weight): off at 0; the MWER path has no such term
         ilmt_weight = getattr(args, "ilmt_weight", 0.0)
         self.ilmt_weight = check_ilmt_weight(0.0 if ilmt_weight is None else ilmt_weight)
@@ -237,7 +245,8 @@ class RNNTransducer(_Base):
             out = self.jointnet.mwer_loss(
                 input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, self.blank_token_id,
                 nbest=self.mwer_nbest, max_symbols=self.mwer_max_symbols, mwer_weight=self.mwer_weight, reduction="mean",
-                audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda, return_parts=logging)
+                audio_lengths=lengths, ctc_weight=self.ctc_weight, fastemit_lambda=self.fastemit_lambda, return_parts=logging,
+                ctc_skip=self.mwer_ctc_skip)
             if logging:   # the parts are (total, rnnt[, ctc], risk, err1)
                 self.log("train_loss", out[0], sync_dist=True)
                 self.log("train_mwer_risk", out[-2].detach(), sync_dist=True)
@@ -334,7 +343,8 @@ class RNNTransducer(_Base):
         was_training = self.jointnet.training
         self.jointnet.eval()
         try:
-            pred = self.jointnet.recognize_greedy(input_audios, tensor_audio_lengths, self.blank_token_id, 3)
+            pred = self.jointnet.recognize_greedy(input_audios, tensor_audio_lengths, self.blank_token_id, 3,
+                                                  ctc_skip=self.val_ctc_skip)
             if aux:
                 ctc_pred = self.jointnet.recognize_ctc_greedy(input_audios, tensor_audio_lengths, self.blank_token_id)
         finally:

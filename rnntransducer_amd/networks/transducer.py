@@ -34,6 +34,9 @@ kernels (csrc/loss.hip).
 `ctc_align` is the forced alignment of a known transcript under the CTC head: per label the span of frames it holds on the best CTC
 path, the path's score, on request the token per frame and per-label log-probabilities, from the encoder alone (csrc/ctc.hip,
 DESIGN.md §28); `loss(..., emit_windows=ops.CtcEmitWindows(left, right))` feeds the alignment-restricted loss from it every step.
+`ctc_skip=p` of `recognize_greedy` / `recognize_beams` / `recognize_beams_sync` / `mwer_loss` is CTC-guided blank-frame skipping:
+the frames whose CTC blank posterior exceeds p are dropped in one pass on the device and the unchanged search runs on the rest,
+its frames reported in the encoder's numbering (csrc/ctc_skip.hip, ops.ctc_frame_skip).
 """
 import math
 
@@ -41,7 +44,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import (MWER_MAX_LEN, CtcLossFn, IlmLossFn, JointLogitsFn, JointLossFn, JointLossGroupedFn, JointLossKdFn, MwerRiskFn,
-                   TimedTokens, CtcEmitWindows, check_ctc_emit_windows, ctc_align, ctc_emit_windows,
+                   TimedTokens, CtcEmitWindows, check_ctc_emit_windows, ctc_align, ctc_emit_windows, check_ctc_skip, ctc_frame_skip,
+                   map_frames,
                    beam_search, beam_search_sync, beam_search_sync_device, check_beam_sync_args, check_ctc_beam_args,
                    check_emit_windows, check_fastemit_lambda, check_ilm_weight, check_ilmt_weight, check_kd_teacher, check_kd_weight,
                    refuse_ilm_weight,
@@ -69,6 +73,31 @@ class JointNet(nn.Module):
     def _need_ctc_head(self, what: str) -> None:
         if not self.aux_ctc:
             raise ValueError(f"{what} needs the CTC head: build the JointNet with aux_ctc=True (jointnet_params['aux_ctc'])")
+
+    def _check_ctc_skip(self, ctc_skip, blank, what: str, visit_padded_frames: bool = False) -> None:
+        """The argument checks of `ctc_skip=p` (not None), before anything runs: p a probability in (0, 1], the CTC head present,
+        the blank inside the vocabulary, and no visit_padded_frames (a skipped utterance has no padded frames to visit)."""
+        check_ctc_skip(ctc_skip, what)
+        self._need_ctc_head(f"{what}(ctc_skip=)")
+        if visit_padded_frames:
+            raise ValueError(f"{what}: visit_padded_frames=True cannot be combined with ctc_skip (the compacted rows behind an "
+                             "utterance's kept frames hold nothing)")
+        if isinstance(blank, bool) or not 0 <= int(blank) < self.num_classes:
+            raise ValueError(f"{what}: blank {blank!r} outside [0,{self.num_classes})")
+
+    def _skip_blank_frames(self, enc, t_lens, blank, ctc_skip):
+        """ctc_skip=p of the searches: ctc_head(enc) once, then ops.ctc_frame_skip -> FrameSkip(enc, t_lens,
+        frame_map): the search's operands and the table that turns its frames back into encoder frames.  No graph, no host sync."""
+        with torch.no_grad():
+            enc = enc.detach()
+            return ctc_frame_skip(self.ctc_head(enc), t_lens, int(blank), ctc_skip, enc)
+
+    @staticmethod
+    def _original_frames(res, frame_map):
+        """The beam searches' host lists (entries end in `frames`) with every frame >= 0 mapped through frame_map (B, T): one
+        host copy, behind the search's own."""
+        fm = frame_map.cpu().tolist()
+        return [[(*e[:-1], [f if f < 0 else fm[b][f] for f in e[-1]]) for e in hyps] for b, hyps in enumerate(res)]
 
     @staticmethod
     def _ragged_rows(audio_lengths, T, B, dev, t_lens, u_lens, rows, want_inv):
@@ -311,7 +340,7 @@ class JointNet(nn.Module):
     def mwer_loss(self, input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank: int, *, nbest: int = 4,
                   max_symbols: int = 1, token_min_logp: float = -math.inf, max_hyp_len: int = MWER_MAX_LEN,
                   mwer_weight: float = 1.0, reduction: str = "mean", audio_lengths=None, ctc_weight: float = 0.0,
-                  fastemit_lambda: float = 0.0, return_parts: bool = False):
+                  fastemit_lambda: float = 0.0, return_parts: bool = False, ctc_skip=None):
         """Minimum word error rate fine-tuning: rnnt + ctc_weight * ctc + mwer_weight * risk, where risk is the
         expected number of TOKEN errors over the model's own n-best list, relative to the list's mean:
             risk_b = sum_i P^_i (W_i - mean W),   P^_i = softmax_i(-nll_i)   over the valid hypotheses i of utterance b,
@@ -327,6 +356,8 @@ class JointNet(nn.Module):
         No emission windows (loss()'s emit_windows): the rows of the risk term are hypotheses and have no reference alignment.
         A hypothesis longer than max_hyp_len (<= 511) tokens is left out, as are the ranks the search did not fill; an utterance
         with fewer than two valid hypotheses has risk 0.  No host sync beyond the search's one copy of counts and lengths.
+        ctc_skip=p (needs the CTC head): the n-best search alone runs on the frames whose CTC blank posterior
+        (the head on the detached encoder output, without a graph) is at most p; every loss term stays on all frames.
         reduction: "none" (B,), "mean" or "sum" over B, for every term.  return_parts=True -> (total, rnnt[, ctc], risk,
         err1) with ctc present when the module has the CTC head, err1 the mean edit distance of the 1-best hypotheses (fp32, 0-d).
         ValueError for bad arguments before anything runs."""
@@ -337,14 +368,19 @@ class JointNet(nn.Module):
             raise ValueError(f"{what}: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
         if not 0 <= int(blank) < self.num_classes:
             raise ValueError(f"{what}: blank {blank} outside [0,{self.num_classes})")
+        if ctc_skip is not None:
+            self._check_ctc_skip(ctc_skip, blank, what)
         parts = return_parts and self.aux_ctc
         ref, (enc, targets, t_lens, u_lens, inv) = self._reference_terms(
             input_audios, tensor_audio_lengths, input_texts, targets, target_lengths, blank, reduction, audio_lengths, ctc_weight,
             parts, fastemit_lambda, want_inv=True)
         dec, B, N = self.decoder, enc.shape[1], nbest
+        s_enc, s_lens = enc.detach(), t_lens
+        if ctc_skip is not None:   # the search alone sees the kept frames; nbest_pack and the losses below keep the originals
+            s_enc, s_lens = self._skip_blank_frames(enc, t_lens, blank, ctc_skip)[:2]
         tokens, lens, counts, _, host = beam_search_sync_device(
-            enc.detach(), self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-            dec.out_proj.weight, dec.out_proj.bias, int(blank), N, max_symbols, t_lens, token_min_logp=token_min_logp)
+            s_enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+            dec.out_proj.weight, dec.out_proj.bias, int(blank), N, max_symbols, s_lens, token_min_logp=token_min_logp)
         texts, labels, hu_lens, ht_lens, valid = nbest_pack(tokens, lens, counts, t_lens, nbest_umax(host, B, N, max_hyp_len),
                                                             int(blank), max_hyp_len)
         hdec = dec.forward_time_major(texts, hu_lens + 1)
@@ -470,7 +506,7 @@ class JointNet(nn.Module):
 
     @torch.no_grad()
     def recognize_greedy(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, max_iters: int = 3,
-                         visit_padded_frames: bool = False, return_timing: bool = False, max_out=None):
+                         visit_padded_frames: bool = False, return_timing: bool = False, max_out=None, ctc_skip=None):
         """Greedy search, same result as transducer.py:95-145: per frame up to `max_iters` non-blank symbols, a symbol
         equal to the previously appended one is dropped (but still advances the prediction net).  Returns a LongTensor
         (1, n) for a single utterance, as the reference's `torch.stack` does.  For B > 1 (where the reference's stack
@@ -481,16 +517,28 @@ class JointNet(nn.Module):
         tensors of equal length, instead of the tokens alone (one tuple for a single utterance, else a list): for every
         appended token the encoder frame at which the search chose it and the log-softmax of the joint at that evaluation,
         at that token (fp32).  A symbol dropped as a repeat has no entry.  `LogMelFrontend.frame_seconds` turns frames into
-        seconds.  max_out caps the entries kept per utterance (default: max_iters per frame, which never truncates)."""
+        seconds.  max_out caps the entries kept per utterance (default: max_iters per frame, which never truncates).
+        ctc_skip=p (a probability in (0, 1]; needs the CTC head): the search walks only the frames whose CTC blank
+        posterior is at most p (ctc_head on the encoder output, one pass on the device, no host sync); the frames of
+        return_timing still count the encoder's frames.  None (the default): every frame, the head is not evaluated.  1.0 skips
+        nothing.  ValueError with visit_padded_frames=True, without the head or for p outside (0, 1], before anything runs."""
         if self.training:
             raise RuntimeError("recognize_greedy expects eval() mode (dropout inactive), like the reference's validation_step")
+        if ctc_skip is not None:
+            self._check_ctc_skip(ctc_skip, blank_token_id, "recognize_greedy", visit_padded_frames)
         dev = inputs.device
         t_lens = lengths_to_device(inputs_lengths, dev)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         dec = self.decoder
+        skip = None
+        if ctc_skip is not None:
+            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
+            enc, t_lens = skip.enc, skip.t_lens
         res = greedy_decode(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(),
                             dec.rnn.CELL, dec.out_proj.weight, dec.out_proj.bias, blank_token_id, max_iters,
                             None if visit_padded_frames else t_lens, timing=return_timing, max_out=max_out)
+        if skip is not None and return_timing:   # one device gather: compacted frame -> encoder frame
+            res = (res[0], res[1], map_frames(res[2], skip.frame_map), res[3])
         tokens, ntok = res[0], res[1]
         n = ntok.tolist()  # the only host sync of the decode
         if return_timing:
@@ -503,7 +551,8 @@ class JointNet(nn.Module):
     def recognize_beams(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 100,
                         improved: bool = False, state_beam: float = 4.6, expand_beam: float = 2.3, lm=None, tokenizer=None,
                         hotwords=None, hotword_weight: float = 10.0, *, visit_padded_frames: bool = False,
-                        return_scores: bool = False, return_frames: bool = False, fusion=None, ilm_weight=None, **caps):
+                        return_scores: bool = False, return_frames: bool = False, fusion=None, ilm_weight=None, ctc_skip=None,
+                        **caps):
         """Beam search, same result as transducer.py:215-361 with lm=None and hotwords=None: a list of up to `beam_widths`
         y_star token lists (leading blank included), best first by asr_score / len(y_star), duplicates kept.  `tokenizer` is
         accepted and ignored: without an LM or hotwords the reference only uses it for lm_score, which never decides anything.
@@ -525,8 +574,12 @@ class JointNet(nn.Module):
         max_pops cap ends it in RnntHipError naming max_pops, and the next call succeeds.  A backoff n-gram model (NgramFusion)
         is refused here with a ValueError that names the searches that take one: those whose cost per frame is bounded.
         ilm_weight (internal-LM subtraction) is refused the same way: it is a bonus for every emitted token, the kind of score
-        that makes this search's pop loop run away; the frame-synchronous searches take it."""
+        that makes this search's pop loop run away; the frame-synchronous searches take it.
+        ctc_skip=p: as in recognize_greedy, the search walks only the frames whose CTC blank posterior is at most p; the frames
+        of return_frames still count the encoder's frames (mapped on the host behind the search's own copy)."""
         refuse_ilm_weight(ilm_weight, "recognize_beams", "a per-token bonus can make the best-first pop loop run away")
+        if ctc_skip is not None:
+            self._check_ctc_skip(ctc_skip, blank_token_id, "recognize_beams", visit_padded_frames)
         if lm is not None or hotwords is not None:
             raise NotImplementedError("recognize_beams: LM / hotword rescoring (pyctcdecode, KenLM) is not implemented; pass "
                                       "lm=None and hotwords=None, and give token-level hotwords or an LM table as fusion= "
@@ -538,9 +591,15 @@ class JointNet(nn.Module):
         t_lens = lengths_to_device(inputs_lengths, dev)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         dec = self.decoder
+        skip = None
+        if ctc_skip is not None:
+            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
+            enc, t_lens = skip.enc, skip.t_lens
         res = beam_search(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
                           dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
                           expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, fusion=fusion, **caps)
+        if skip is not None and return_frames:
+            res = self._original_frames(res, skip.frame_map)
         if return_frames:   # an entry is (y_star, asr_score[, fused_score], frames)
             outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
         else:
@@ -550,7 +609,7 @@ class JointNet(nn.Module):
     @torch.no_grad()
     def recognize_beams_sync(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16,
                              max_symbols: int = 1, *, token_min_logp: float = -math.inf, fusion=None,
-                             return_scores: bool = False, return_frames: bool = False, ilm_weight: float = 0.0):
+                             return_scores: bool = False, return_frames: bool = False, ilm_weight: float = 0.0, ctc_skip=None):
         """Frame-synchronous beam search (csrc/beam_sync.hip), the search other transducer toolkits decode with:
         per frame the whole beam (beam_widths <= 64) expands at once, at most max_symbols (<= 4) tokens are emitted,
         hypotheses with the same token sequence are merged by logaddexp (a score is probability mass, not one path), and the
@@ -571,6 +630,8 @@ class JointNet(nn.Module):
         contribution zeroed (`ilm_score` gives its sum over a sequence).  fused_score = score + the automaton's part -
         mu * ilm_score(y).  With fusion=None the all-zero automaton is used: subtraction alone, and entries carry fused_score
         like any fused call.  0 (the default): the search above, untouched.  Finite and >= 0, ValueError otherwise.
+        ctc_skip=p: as in recognize_greedy, the search walks only the frames whose CTC blank posterior is at most p; the frames
+        of return_frames still count the encoder's frames.
         Any encoder direction.  eval() mode only; ValueError for training mode or bad arguments, before anything is launched."""
         if self.training:
             raise ValueError("recognize_beams_sync expects eval() mode (dropout inactive), like recognize_beams")
@@ -579,12 +640,20 @@ class JointNet(nn.Module):
         check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams_sync", ngram=True)
         if not 0 <= int(blank_token_id) < self.num_classes:
             raise ValueError(f"recognize_beams_sync: blank {blank_token_id} outside [0,{self.num_classes})")
+        if ctc_skip is not None:
+            self._check_ctc_skip(ctc_skip, blank_token_id, "recognize_beams_sync")
         t_lens = lengths_to_device(inputs_lengths, inputs.device)
         enc = self.encoder.forward_time_major(inputs, t_lens)
         dec = self.decoder
+        skip = None
+        if ctc_skip is not None:
+            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
+            enc, t_lens = skip.enc, skip.t_lens
         res = beam_search_sync(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
                                dec.out_proj.weight, dec.out_proj.bias, int(blank_token_id), beam_widths, max_symbols, t_lens,
                                token_min_logp=token_min_logp, frames=return_frames, fusion=fusion, ilm_weight=ilm_weight)
+        if skip is not None and return_frames:
+            res = self._original_frames(res, skip.frame_map)
         if return_frames:   # an entry is (y, score[, fused_score], frames)
             outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
         else:

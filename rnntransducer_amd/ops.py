@@ -1417,6 +1417,78 @@ def ctc_emit_windows(logits_tm: torch.Tensor, labels: torch.Tensor, t_lens: torc
     return lo, hi
 
 
+# --------------------------------------------------------------------------------------------------
+# CTC-guided blank-frame skipping in front of the transducer searches (include/rnnt_hip.h: rnnt_hip_ctc_frame_skip, csrc/ctc_skip.hip)
+# --------------------------------------------------------------------------------------------------
+class FrameSkip(NamedTuple):
+    """Result of ctc_frame_skip, on the device (nothing here has synchronised with the host): `enc` (T, B, O) fp32 — per utterance its
+    kept frames' rows of the input, in order, in rows 0 .. t_lens[b]-1 (the rows behind them are not written) —, `t_lens` (B,)
+    int32 — the number of kept frames —, `frame_map` (B, T) int32 — the original frame of kept frame j, -1 for j >= t_lens[b] —,
+    `blank_logp` (B, T) fp32 or None — the head's log-softmax at the blank per valid frame (frames past the input's t_lens[b] are
+    not written)."""
+    enc: torch.Tensor
+    t_lens: torch.Tensor
+    frame_map: torch.Tensor
+    blank_logp: Optional[torch.Tensor] = None
+
+
+def check_ctc_skip(threshold, what: str) -> float:
+    """ValueError unless threshold is a probability in (0, 1]; -> float32(log threshold), the entry's log_threshold."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or math.isnan(threshold) or not 0.0 < threshold <= 1.0:
+        raise ValueError(f"{what}: the blank-posterior threshold must be a probability in (0, 1], got {threshold!r}")
+    return torch.tensor(math.log(threshold), dtype=torch.float32).item()
+
+
+@torch.no_grad()
+def ctc_frame_skip(logits: torch.Tensor, t_lens: torch.Tensor, blank: int, threshold: float, enc_tm: torch.Tensor, *,
+                   time_major: bool = True, return_blank_logp: bool = False) -> FrameSkip:
+    """Drops the frames the CTC head calls blank (include/rnnt_hip.h: rnnt_hip_ctc_frame_skip, csrc/ctc_skip.hip):
+    logits (T,B,V) (time_major=False: (B,T,V)) fp32 are the head's, t_lens (B,) int32, enc_tm (T,B,O) fp32 the rows to compact
+    (the encoder's output).  Frame t < t_lens[b] is skipped exactly when the head's fp32 log-softmax at `blank` exceeds
+    float32(log threshold); threshold is a probability in (0, 1], and 1.0 skips nothing.  -> FrameSkip(enc, t_lens, frame_map[,
+    blank_logp]): a new (T,B,O) tensor holding the kept rows, the new lengths and the original frame of every kept frame, for the
+    searches that take (enc_tm, t_lens).  Two launches, no host sync.  ValueError for bad arguments before anything runs."""
+    what = "ctc_frame_skip"
+    log_thr = check_ctc_skip(threshold, what)
+    for name, t, dt in (("logits", logits, torch.float32), ("enc_tm", enc_tm, torch.float32), ("t_lens", t_lens, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"{what}: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+    if enc_tm.dim() != 3:
+        raise ValueError(f"{what}: enc_tm must be (T, B, O), got {tuple(enc_tm.shape)}")
+    B, T, V, z_sb, z_st = _ctc_strides(logits, time_major)
+    if tuple(enc_tm.shape[:2]) != (T, B) or tuple(t_lens.shape) != (B,):
+        raise ValueError(f"{what}: logits give T = {T}, B = {B}; enc_tm must be (T, B, O) and t_lens (B,), got {tuple(enc_tm.shape)}, "
+                         f"{tuple(t_lens.shape)}")
+    if V < 2 or isinstance(blank, bool) or not 0 <= int(blank) < V:
+        raise ValueError(f"{what}: V = {V} < 2 or blank {blank!r} outside [0, {V})")
+    if T < 1 or B < 1 or enc_tm.shape[2] < 1:
+        raise ValueError(f"{what}: T, B and O must be positive, got logits {tuple(logits.shape)} and enc_tm {tuple(enc_tm.shape)}")
+    for name, t in (("logits", logits), ("enc_tm", enc_tm), ("t_lens", t_lens)):
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} is a CPU tensor; there is no CPU path")
+    if not (logits.device == enc_tm.device == t_lens.device):
+        raise ValueError(f"{what}: logits, enc_tm and t_lens must be on one device")
+    logits, enc_tm, t_lens = logits.contiguous(), enc_tm.contiguous(), t_lens.contiguous()
+    O, dev, L = enc_tm.shape[2], enc_tm.device, _lib.lib()
+    out = torch.empty_like(enc_tm)
+    small = torch.empty(B + B * T, device=dev, dtype=torch.int32)   # new lengths | frame map
+    lp = torch.empty(B, T, device=dev, dtype=torch.float32) if return_blank_logp else None
+    nws = L.rnnt_hip_ctc_frame_skip_workspace_bytes(B, T)
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    check(L.rnnt_hip_ctc_frame_skip(_addr(logits), z_sb, z_st, _addr(t_lens), B, T, V, int(blank), log_thr, _addr(enc_tm), O, B * O, O,
+                                    _addr(out), O, B * O, _addr(small), _addr(small, B), _addr(lp), _addr(ws), nws, _stream()),
+          "rnnt_hip_ctc_frame_skip")
+    return FrameSkip(out, small[:B], small[B:].view(B, T), lp)
+
+
+def map_frames(frames: torch.Tensor, frame_map: torch.Tensor) -> torch.Tensor:
+    """frames (B, ...) integer frame numbers of a compacted encoder output -> the original frames through frame_map (B, T) of
+    ctc_frame_skip, on the tensors' device; -1 stays -1."""
+    flat = frames.reshape(frames.shape[0], -1).long()
+    orig = frame_map.gather(1, flat.clamp(min=0)).to(frames.dtype)
+    return torch.where(flat < 0, flat.to(frames.dtype), orig).view(frames.shape)
+
+
 CTC_BEAM_MAX_WIDTH = 128
 
 
