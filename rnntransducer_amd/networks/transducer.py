@@ -92,6 +92,47 @@ class JointNet(nn.Module):
             enc = enc.detach()
             return ctc_frame_skip(self.ctc_head(enc), t_lens, int(blank), ctc_skip, enc)
 
+    def search_weights(self, fc_bias: bool = True) -> tuple:
+        """The prediction-net / joint weights in the order the ops searches take them: fc.weight, fc.bias, the embedding, the
+        prediction net's flat weights and cell, out_proj's weight and bias.  fc_bias=False: without fc.bias, as the streaming
+        entries take them (their encoder step has added it)."""
+        dec = self.decoder
+        return (self.fc.weight, *((self.fc.bias,) if fc_bias else ()), dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
+                dec.out_proj.weight, dec.out_proj.bias)
+
+    def _search_encoder(self, inputs, inputs_lengths, blank, ctc_skip):
+        """The prologue of the offline searches, behind their argument checks: lengths to the device, the encoder, and with
+        ctc_skip the blank frames dropped.  -> (the search's encoder output, its t_lens, the FrameSkip record or None)"""
+        t_lens = lengths_to_device(inputs_lengths, inputs.device)
+        enc = self.encoder.forward_time_major(inputs, t_lens)
+        if ctc_skip is None:
+            return enc, t_lens, None
+        skip = self._skip_blank_frames(enc, t_lens, blank, ctc_skip)
+        return skip.enc, skip.t_lens, skip
+
+    def _nbest_lists(self, res, skip, return_scores: bool, return_frames: bool):
+        """The beam searches' host lists (an entry is (y, score[, fused_score][, frames])) as recognize_beams and
+        recognize_beams_sync return them: frames back in the encoder's numbering after a skip, frames second in an entry,
+        scores on request, the list itself for a single utterance."""
+        if skip is not None and return_frames:
+            res = self._original_frames(res, skip.frame_map)
+        if return_frames:
+            outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
+        else:
+            outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
+        return outs[0] if len(outs) == 1 else outs
+
+    def _stream_encoder(self, chunk, lens, T_run: int, state):
+        """The encoder step of the three streaming searches over the first T_run = max(lens) frames of a chunk, in place on the
+        state's encoder rows.  -> (A (T_run, B, V), the encoder half of the joint; lens on the device, int32: one copy, shared by
+        the encoder's and the search's launches)"""
+        B = chunk.shape[0]
+        lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
+        enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
+        A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
+                                      (self.fc.weight, self.fc.bias))
+        return A, lens_dev
+
     @staticmethod
     def _original_frames(res, frame_map):
         """The beam searches' host lists (entries end in `frames`) with every frame >= 0 mapped through frame_map (B, T): one
@@ -378,9 +419,8 @@ class JointNet(nn.Module):
         s_enc, s_lens = enc.detach(), t_lens
         if ctc_skip is not None:   # the search alone sees the kept frames; nbest_pack and the losses below keep the originals
             s_enc, s_lens = self._skip_blank_frames(enc, t_lens, blank, ctc_skip)[:2]
-        tokens, lens, counts, _, host = beam_search_sync_device(
-            s_enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-            dec.out_proj.weight, dec.out_proj.bias, int(blank), N, max_symbols, s_lens, token_min_logp=token_min_logp)
+        tokens, lens, counts, _, host = beam_search_sync_device(s_enc, *self.search_weights(), int(blank), N, max_symbols, s_lens,
+                                                                token_min_logp=token_min_logp)
         texts, labels, hu_lens, ht_lens, valid = nbest_pack(tokens, lens, counts, t_lens, nbest_umax(host, B, N, max_hyp_len),
                                                             int(blank), max_hyp_len)
         hdec = dec.forward_time_major(texts, hu_lens + 1)
@@ -457,20 +497,9 @@ class JointNet(nn.Module):
         dev = input_audios.device
         t_lens = lengths_to_device(tensor_audio_lengths, dev)
         u_lens = lengths_to_device(target_lengths, dev)
-        enc_lens, inv = t_lens, None
         T, B = input_audios.size(1), input_audios.size(0)
-        if audio_lengths is not None and len(audio_lengths) == B and B > 1 and min(audio_lengths) < T:
-            from ..ops import RaggedPlan
-            host = [int(n) for n in audio_lengths]
-            order = sorted(range(B), key=lambda b: (-host[b], b))
-            if order != list(range(B)):   # length-sorted rows, as in loss(); frames and scores are un-sorted below
-                perm = torch.tensor(order, dtype=torch.int64, device=dev)
-                input_audios, input_texts, targets = (x.index_select(0, perm) for x in (input_audios, input_texts, targets))
-                t_lens, u_lens = t_lens.index_select(0, perm), u_lens.index_select(0, perm)
-                host = [host[b] for b in order]
-                inv = torch.empty_like(perm)
-                inv[perm] = torch.arange(B, dtype=torch.int64, device=dev)
-            enc_lens = RaggedPlan(host, T, dev)
+        (input_audios, input_texts, targets), t_lens, u_lens, enc_lens, inv = self._ragged_rows(
+            audio_lengths, T, B, dev, t_lens, u_lens, (input_audios, input_texts, targets), True)   # frames and scores are un-sorted below
         enc = self.encoder.forward_time_major(input_audios, enc_lens)
         dec = self.decoder.forward_time_major(input_texts, u_lens + 1)
         A, Cm = _joint_ac(enc, dec, self.fc.weight, self.enc_out, self.dec_out, self.num_classes)
@@ -526,17 +555,9 @@ class JointNet(nn.Module):
             raise RuntimeError("recognize_greedy expects eval() mode (dropout inactive), like the reference's validation_step")
         if ctc_skip is not None:
             self._check_ctc_skip(ctc_skip, blank_token_id, "recognize_greedy", visit_padded_frames)
-        dev = inputs.device
-        t_lens = lengths_to_device(inputs_lengths, dev)
-        enc = self.encoder.forward_time_major(inputs, t_lens)
-        dec = self.decoder
-        skip = None
-        if ctc_skip is not None:
-            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
-            enc, t_lens = skip.enc, skip.t_lens
-        res = greedy_decode(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(),
-                            dec.rnn.CELL, dec.out_proj.weight, dec.out_proj.bias, blank_token_id, max_iters,
-                            None if visit_padded_frames else t_lens, timing=return_timing, max_out=max_out)
+        enc, t_lens, skip = self._search_encoder(inputs, inputs_lengths, blank_token_id, ctc_skip)
+        res = greedy_decode(enc, *self.search_weights(), blank_token_id, max_iters, None if visit_padded_frames else t_lens,
+                            timing=return_timing, max_out=max_out)
         if skip is not None and return_timing:   # one device gather: compacted frame -> encoder frame
             res = (res[0], res[1], map_frames(res[2], skip.frame_map), res[3])
         tokens, ntok = res[0], res[1]
@@ -587,24 +608,10 @@ class JointNet(nn.Module):
         if self.training:
             raise RuntimeError("recognize_beams expects eval() mode (dropout inactive), like the reference's inference script")
         check_fusion(fusion, self.num_classes, self.fc.weight.device, "recognize_beams")   # before anything is launched
-        dev = inputs.device
-        t_lens = lengths_to_device(inputs_lengths, dev)
-        enc = self.encoder.forward_time_major(inputs, t_lens)
-        dec = self.decoder
-        skip = None
-        if ctc_skip is not None:
-            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
-            enc, t_lens = skip.enc, skip.t_lens
-        res = beam_search(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-                          dec.out_proj.weight, dec.out_proj.bias, blank_token_id, beam_widths, improved, state_beam,
-                          expand_beam, None if visit_padded_frames else t_lens, frames=return_frames, fusion=fusion, **caps)
-        if skip is not None and return_frames:
-            res = self._original_frames(res, skip.frame_map)
-        if return_frames:   # an entry is (y_star, asr_score[, fused_score], frames)
-            outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
-        else:
-            outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
-        return outs[0] if len(outs) == 1 else outs
+        enc, t_lens, skip = self._search_encoder(inputs, inputs_lengths, blank_token_id, ctc_skip)
+        res = beam_search(enc, *self.search_weights(), blank_token_id, beam_widths, improved, state_beam, expand_beam,
+                          None if visit_padded_frames else t_lens, frames=return_frames, fusion=fusion, **caps)
+        return self._nbest_lists(res, skip, return_scores, return_frames)
 
     @torch.no_grad()
     def recognize_beams_sync(self, inputs: torch.Tensor, inputs_lengths, blank_token_id: int, beam_widths: int = 16,
@@ -642,23 +649,10 @@ class JointNet(nn.Module):
             raise ValueError(f"recognize_beams_sync: blank {blank_token_id} outside [0,{self.num_classes})")
         if ctc_skip is not None:
             self._check_ctc_skip(ctc_skip, blank_token_id, "recognize_beams_sync")
-        t_lens = lengths_to_device(inputs_lengths, inputs.device)
-        enc = self.encoder.forward_time_major(inputs, t_lens)
-        dec = self.decoder
-        skip = None
-        if ctc_skip is not None:
-            skip = self._skip_blank_frames(enc, t_lens, blank_token_id, ctc_skip)
-            enc, t_lens = skip.enc, skip.t_lens
-        res = beam_search_sync(enc, self.fc.weight, self.fc.bias, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-                               dec.out_proj.weight, dec.out_proj.bias, int(blank_token_id), beam_widths, max_symbols, t_lens,
+        enc, t_lens, skip = self._search_encoder(inputs, inputs_lengths, blank_token_id, ctc_skip)
+        res = beam_search_sync(enc, *self.search_weights(), int(blank_token_id), beam_widths, max_symbols, t_lens,
                                token_min_logp=token_min_logp, frames=return_frames, fusion=fusion, ilm_weight=ilm_weight)
-        if skip is not None and return_frames:
-            res = self._original_frames(res, skip.frame_map)
-        if return_frames:   # an entry is (y, score[, fused_score], frames)
-            outs = [[(e[0], e[-1], *e[1:-1]) if return_scores else (e[0], e[-1]) for e in hyps] for hyps in res]
-        else:
-            outs = [hyps if return_scores else [e[0] for e in hyps] for hyps in res]
-        return outs[0] if len(outs) == 1 else outs
+        return self._nbest_lists(res, skip, return_scores, return_frames)
 
     @torch.no_grad()
     def ilm_score(self, targets: torch.Tensor, target_lengths, blank: int) -> torch.Tensor:
@@ -732,13 +726,8 @@ class JointNet(nn.Module):
             if return_timing:
                 return [TimedTokens(empty(torch.int64), empty(torch.int32), empty(torch.float32)) for _ in range(B)]
             return [empty(torch.int64) for _ in range(B)]
-        lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)   # one copy, shared by both launches' reads
-        enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
-        A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
-                                      (self.fc.weight, self.fc.bias))
-        dec = self.decoder
-        res = stream_greedy(A, lens_dev, self.fc.weight, dec.embedding.weight, dec.rnn.flat_weights(), dec.rnn.CELL,
-                            dec.out_proj.weight, dec.out_proj.bias, state.blank, max_iters, state.pred_h, state.pred_c,
+        A, lens_dev = self._stream_encoder(chunk, lens, T_run, state)
+        res = stream_greedy(A, lens_dev, *self.search_weights(fc_bias=False), state.blank, max_iters, state.pred_h, state.pred_c,
                             state.pred_joint, state.last_token, frame_base=state.frames_seen if return_timing else None)
         tokens, ntok = res[0], res[1]
         state.frames_seen += lens_dev   # after the search's launch on this stream: the kernel read the count before the chunk
@@ -794,11 +783,7 @@ class JointNet(nn.Module):
             state.check_frames_known()   # before the encoder runs: a refused call leaves the state untouched
         T_run = max(lens)
         if T_run > 0:
-            lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
-            enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
-            A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
-                                          (self.fc.weight, self.fc.bias))
-            state.run_chunk(A, lens_dev, return_frames)
+            state.run_chunk(*self._stream_encoder(chunk, lens, T_run, state), return_frames)
         return state.results(return_scores, return_frames)
 
     def init_beam_sync_stream(self, batch_size: int, blank_token_id: int, beam_widths: int = 16, max_symbols: int = 1, *,
@@ -851,9 +836,5 @@ class JointNet(nn.Module):
         state.check_feedable(lens)
         T_run = max(lens)
         if T_run > 0:
-            lens_dev = torch.tensor(lens, dtype=torch.int32, device=chunk.device)
-            enc = torch.empty(T_run, B, self.enc_out, device=chunk.device)
-            A = self.encoder.stream_chunk(chunk, lens_dev, T_run, state.enc_h, state.enc_c, enc, (self.enc_out, B * self.enc_out),
-                                          (self.fc.weight, self.fc.bias))
-            state.run_chunk(A, lens_dev, lens)
+            state.run_chunk(*self._stream_encoder(chunk, lens, T_run, state), lens)
         return state.results(return_scores, return_frames)

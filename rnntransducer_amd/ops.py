@@ -1708,6 +1708,41 @@ def _fill_prednet(d, fc_w, emb_w, rnn_weights, cell: int, out_w, out_b, blank: i
     return keep
 
 
+def _search_fit(d, enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell: int, out_w, out_b, blank: int, what: str):
+    """The host half of the opening of the three offline searches on enc_tm (T,B,Oe): _fill_prednet on the search's descriptor
+    d, then the joint's weights against the encoder's width.  Nothing here touches a device, so each search keeps its own
+    argument checks where they were, around this call.  -> (keep, T, B, V)"""
+    T, B, Oe = enc_tm.shape
+    V, Ocat = fc_w.shape
+    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, what)
+    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
+        raise ValueError(f"{what}: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
+                         f"encoder width {Oe}")
+    return keep, T, B, V
+
+
+def _joint_half(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor) -> torch.Tensor:
+    """The device half of that opening: A (T,B,V) = gelu(enc_tm) W_e^T + fc_b, the encoder half of the joint, in one product
+    (fc_w: the float32 contiguous (V, Oe + Od) weight _search_fit kept, its encoder columns first)."""
+    T, B, Oe = enc_tm.shape
+    V, Ocat = fc_w.shape
+    A = torch.empty(T, B, V, device=enc_tm.device, dtype=torch.float32)
+    gemm(T * B, V, Oe, enc_tm, fc_w, A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    return A
+
+
+def _aligned_workspace(nbytes: int, device):
+    """A search's workspace of nbytes at a 256-byte boundary: nbytes + 256 are allocated and the address is rounded up.
+    -> (the tensor that owns it, the aligned address)"""
+    ws = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
+    return ws, (_addr(ws) + 255) // 256 * 256
+
+
+def _check_step_group(step_group, what: str) -> None:
+    if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
+        raise ValueError(f"{what}: step_group must be an integer >= 0, got {step_group!r}")
+
+
 def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                   cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, max_iters: int,
                   t_lens: Optional[torch.Tensor] = None, timing: bool = False, max_out: Optional[int] = None):
@@ -1718,28 +1753,22 @@ def greedy_decode(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, 
     joint there.  max_out (default T*max_iters, which never truncates) caps the stored entries per utterance."""
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
-    T, B, Oe = enc_tm.shape
-    V, Ocat = fc_w.shape
-    d = _lib.DecodeDesc()
-    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "greedy decode")
-    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
-        raise ValueError(f"greedy decode: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
-                         f"encoder width {Oe}")
+    d, dev = _lib.DecodeDesc(), enc_tm.device
+    keep, T, B, V = _search_fit(d, enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, "greedy decode")
     if max_iters < 1:
         raise ValueError(f"greedy decode: max_iters {max_iters} < 1")
-    A = torch.empty(T, B, V, device=enc_tm.device, dtype=torch.float32)
-    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    A = _joint_half(enc_tm, keep[-1], fc_b)
     max_out = T * max_iters if max_out is None else int(max_out)
     if max_out < 1:
         raise ValueError(f"greedy decode: max_out {max_out} < 1")
-    tokens = torch.full((B, max_out), blank, device=enc_tm.device, dtype=torch.int64)
-    ntok = torch.zeros(B, device=enc_tm.device, dtype=torch.int32)
+    tokens = torch.full((B, max_out), blank, device=dev, dtype=torch.int64)
+    ntok = torch.zeros(B, device=dev, dtype=torch.int32)
     d.T, d.B, d.max_iters, d.max_out = T, B, max_iters, max_out
     d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.ntok = _addr(tokens), _addr(ntok)
     if timing:
-        frames = torch.full((B, max_out), -1, device=enc_tm.device, dtype=torch.int32)
-        logp = torch.zeros(B, max_out, device=enc_tm.device, dtype=torch.float32)
+        frames = torch.full((B, max_out), -1, device=dev, dtype=torch.int32)
+        logp = torch.zeros(B, max_out, device=dev, dtype=torch.float32)
         tm = _lib.GreedyTiming(_addr(frames), _addr(logp), None)
         check(_lib.lib().rnnt_hip_greedy_decode_timed(C.byref(d), C.byref(tm), _stream()), "rnnt_hip_greedy_decode_timed")
         return tokens, ntok, frames, logp
@@ -1831,6 +1860,13 @@ def fusion_struct(fusion, fused_scores: torch.Tensor):
     return _lib.BeamFusion(_addr(fusion.next), _addr(fusion.arc), _addr(fusion.final), fusion.n_states, _addr(fused_scores))
 
 
+def ilm_struct(bias: torch.Tensor, weight: float):
+    """rnnt_beam_ilm over the joint's bias (a raw pointer: the caller keeps the tensor alive)."""
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError("internal-LM subtraction: fc.bias must be a contiguous float32 tensor")
+    return _lib.BeamIlm(_addr(bias), weight)
+
+
 def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, emb_w: torch.Tensor, rnn_weights,
                 cell: int, out_w: torch.Tensor, out_b: torch.Tensor, blank: int, beam: int, improved: bool = False,
                 state_beam: float = 4.6, expand_beam: float = 2.3, t_lens: Optional[torch.Tensor] = None, *,
@@ -1851,22 +1887,15 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     fused_score = asr_score + total + final, fp64.  Positive arcs can make a frame's pop loop run away: max_pops bounds it."""
     _need_gpu(enc_tm, fc_w, emb_w)
     enc_tm = _f32c(enc_tm, "encoder outputs")
-    T, B, Oe = enc_tm.shape
-    V, Ocat = fc_w.shape
-    d = _lib.BeamDesc()
-    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, blank, "beam search")
-    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
-        raise ValueError(f"beam search: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
-                         f"encoder width {Oe}")
+    d, dev = _lib.BeamDesc(), enc_tm.device
+    keep, T, B, V = _search_fit(d, enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, blank, "beam search")
     if V < 2 or beam < 1:
         raise ValueError(f"beam search: V {V} < 2 or beam {beam} < 1")
-    check_fusion(fusion, V, enc_tm.device, "beam search")
+    check_fusion(fusion, V, dev, "beam search")
     max_candidates = max_pops * V if max_candidates is None else max_candidates
     max_states = 3 * max_pops if max_states is None else max_states
     max_len = 4 * T + 64 if max_len is None else max_len
-    dev = enc_tm.device
-    A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
-    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    A = _joint_half(enc_tm, keep[-1], fc_b)
     tokens = torch.empty(B, beam, max_len, device=dev, dtype=torch.int32)
     lens = torch.empty(B, beam, device=dev, dtype=torch.int32)
     scores = torch.empty(B, beam, device=dev, dtype=torch.float64)
@@ -1878,8 +1907,8 @@ def beam_search(enc_tm: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, em
     ws_bytes = ws_query(C.byref(d))
     if ws_bytes == 0:
         raise ValueError("beam search: invalid sizes or caps (all caps must be >= 1)")
-    ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
-    d.workspace, d.workspace_bytes = (_addr(ws) + 255) // 256 * 256, ws_bytes
+    ws, d.workspace = _aligned_workspace(ws_bytes, dev)
+    d.workspace_bytes = ws_bytes
     d.A, d.t_lens = _addr(A), _addr(t_lens)
     d.tokens, d.lens, d.scores = _addr(tokens), _addr(lens), _addr(scores)
     d.count, d.status, d.stats = _addr(small), _addr(small, B), _addr(small, 2 * B)
@@ -1969,13 +1998,11 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     """The launch behind beam_search_sync and beam_search_sync_device -> (tokens, lens, counts, scores, host, fused, frames)."""
     check_beam_sync_args(beam_width, max_symbols, token_min_logp, "beam_search_sync")
     mu = check_ilm_weight(ilm_weight, "beam_search_sync")
-    if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
-        raise ValueError(f"beam_search_sync: step_group must be an integer >= 0, got {step_group!r}")
+    _check_step_group(step_group, "beam_search_sync")
     if enc_tm.dim() != 3 or fc_w.dim() != 2:
         raise ValueError(f"beam_search_sync: encoder outputs must be (T,B,Oe) and fc (V,Oe+Od), got {tuple(enc_tm.shape)} / "
                          f"{tuple(fc_w.shape)}")
-    T, B, Oe = enc_tm.shape
-    V, Ocat = fc_w.shape
+    (T, B, _), V = enc_tm.shape, fc_w.shape[0]
     if V < 2:
         raise ValueError(f"beam_search_sync: V = {V} < 2 (a blank and at least one token)")
     if beam_width * V > 1 << 24:
@@ -1983,20 +2010,16 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     if T < 1 or B < 1:
         raise ValueError(f"beam_search_sync: T and B must be positive, got T={T} B={B}")
     d = _lib.BeamSyncDesc()
-    keep = _fill_prednet(d, fc_w, emb_w, rnn_weights, cell, out_w, out_b, int(blank), "beam_search_sync")
-    if Ocat - d.O != Oe or tuple(fc_b.shape) != (V,):
-        raise ValueError(f"beam_search_sync: fc {tuple(fc_w.shape)} / {tuple(fc_b.shape)} / out_proj {tuple(out_w.shape)} do not fit "
-                         f"encoder width {Oe}")
+    keep = _search_fit(d, enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, out_b, int(blank), "beam_search_sync")[0]
     check_fusion(fusion, V, enc_tm.device, "beam_search_sync", ngram=True)
     if t_lens is not None and (t_lens.dtype != torch.int32 or tuple(t_lens.shape) != (B,)):
         raise ValueError(f"beam_search_sync: t_lens must be (B,) = ({B},) int32, got {tuple(t_lens.shape)} {t_lens.dtype}")
-    _need_gpu(enc_tm, fc_w, emb_w)
+    _need_gpu(enc_tm, fc_w, emb_w)   # every argument check above runs without a device
     enc_tm = _f32c(enc_tm, "encoder outputs")
     dev, W, S, L = enc_tm.device, beam_width, max_symbols, _lib.lib()
     if mu > 0.0:
         fusion, fc_b = ilm_fusion(fusion, V, dev), _f32c(fc_b, "fc bias")
-    A = torch.empty(T, B, V, device=dev, dtype=torch.float32)
-    gemm(T * B, V, Oe, enc_tm, keep[-1], A, b_sn=Ocat, b_sk=1, bias=fc_b, flags=GEMM_GELU_A)
+    A = _joint_half(enc_tm, keep[-1], fc_b)
     max_len = 1 + S * T
     tokens = torch.empty(B, W, max_len, device=dev, dtype=torch.int32)
     small = torch.empty(B + B * W, device=dev, dtype=torch.int32)   # counts | lens: one transfer
@@ -2007,8 +2030,8 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     nws = (L.rnnt_hip_beam_sync_ilm_workspace_bytes if mu > 0.0 else L.rnnt_hip_beam_sync_workspace_bytes)(C.byref(d))
     if nws == 0:
         raise ValueError("beam_search_sync: " + L.rnnt_hip_last_error().decode("utf-8", "replace"))
-    ws = torch.empty(nws + 256, device=dev, dtype=torch.uint8)
-    d.workspace, d.workspace_bytes = (_addr(ws) + 255) // 256 * 256, nws
+    ws, d.workspace = _aligned_workspace(nws, dev)
+    d.workspace_bytes = nws
     d.tokens, d.lens, d.scores, d.count = _addr(tokens), _addr(small, B), _addr(scores), _addr(small)
     fr = torch.empty(B, W, max_len, device=dev, dtype=torch.int32) if frames else None
     tm = _lib.BeamTiming(_addr(fr), None) if frames else None
@@ -2016,7 +2039,7 @@ def _beam_search_sync_run(enc_tm, fc_w, fc_b, emb_w, rnn_weights, cell, out_w, o
     fs = fusion_struct(fusion, fused) if fusion is not None else None
     if mu > 0.0:
         entry, ngram = "rnnt_hip_beam_sync_search_ilm", isinstance(fs, _lib.BeamNgram)
-        ilm = _lib.BeamIlm(_addr(fc_b), mu)
+        ilm = ilm_struct(fc_b, mu)
         check(L.rnnt_hip_beam_sync_search_ilm(C.byref(d), None if ngram else C.byref(fs), C.byref(fs) if ngram else None, C.byref(ilm),
                                               C.byref(tm) if tm is not None else None, _stream()), entry)
     else:
@@ -2389,8 +2412,7 @@ def beam_sync_stream_desc(B: int, fc_w, emb_w, rnn_weights, cell: int, out_w, ou
     caller's to fill.  -> (descriptor, tensors to keep alive)."""
     what = "streaming frame-synchronous beam search"
     check_beam_sync_args(beam, max_symbols, token_min_logp, what)
-    if isinstance(step_group, bool) or not isinstance(step_group, int) or step_group < 0:
-        raise ValueError(f"{what}: step_group must be an integer >= 0, got {step_group!r}")
+    _check_step_group(step_group, what)
     if B < 1:
         raise ValueError(f"{what}: {B} streams")
     _need_gpu(fc_w, emb_w)
